@@ -13,13 +13,22 @@ One "step" = one full training iteration on one synthetic batch already resident
   mp_former_amd.dist.FlatGradSync; MPF_GRAD_SYNC=ddp = torch DDP; N > 1)  ->  full-model grad-norm clip 0.01  ->  AdamW.
 Per-GPU batch is fixed at 2 images (IMS_PER_BATCH 16 on 8 GPUs): weak scaling.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line: metric, value (images/sec), unit, higher_is_better, dtype, ms_per_step (one timed step), ...
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs DIR) and prints that line; nothing else.
+
+--full adds, after the timed region, everything else the line has carried (each outside every timed region):
   "roofline":     achieved-vs-peak of the time-dominant native kernel family (gemm3: the encoder's / pixel decoder's fp32
                   GEMMs as split-bf16 MFMA products, ~40 % of the step) with the HBM-bound deformable-attention kernels,
                   the attention tiles and the fused mask kernels under "also" — all from HIP events recorded on the launch
                   stream around every launch of a few extra steps AFTER the timed region (which runs with the log off);
   "cpu_baseline": the oracle's CPU restatement of the hot path (pixel decoder + decoder +
-                  criterion, forward + backward) timed on this box's host cores on a bounded sample.
+                  criterion, forward + backward) timed on this box's host cores on a bounded sample;
+  config.head_only, config.trained_like_offsets (second timed legs), config.grad_sync and config.param_sync_spread
+  (N > 1: exchange diagnostics, replicas check).  Without --full, "roofline" and "cpu_baseline" are null.
+
+--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy (float32 / float64, see dump_outputs).  The batches,
+the initial parameters and the sampled positions are seeded, and the last timed step starts from the initial parameters with
+zeroed AdamW moments, so its inputs are the same on every run and two builds run with the same arguments can be compared.
 """
 import argparse
 import hashlib
@@ -34,6 +43,10 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 # kernel arguments in device memory (this runtime's default; spelled out because the step is ~1 200 launches of mostly 3-10 us
 # kernels: with HIP_FORCE_DEV_KERNARG=0 the same step takes 24.6 instead of 22.7 ms — tools/experiments/README.md)
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
+# the backbone's forward convolutions without MIOpen's split-K assembly solver: its partial sums meet in an order that changes
+# from run to run, so the same inputs gave different features, losses and, through the matcher, different gradients.  The
+# next solvers in the shipped find-db are deterministic (~0.06 ms per step by the db's own timings)
+os.environ.setdefault("MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_ASM_FWD_GTC_XDLOPS_NHWC", "0")
 
 import torch
 import torch.distributed as dist
@@ -227,6 +240,54 @@ def cpu_baseline(size, threads=None):
                                  "sample": f"same path at 256x256, N=1, 1 warm-up + {n_a} timed steps, median {med_a:.3f} s/step"}}
 
 
+def trained_like_offsets(model, dev):
+    """sampling offsets of a mid-training model: per-query scatter of sigma ~ 3 px (weights N(0, 0.18) on the O(1) query
+    features) around the initial pattern moved by N(0, 1 px) (biases).  A freshly built MSDeformAttn has zero offset weights,
+    i.e. every query of a head looks the same way: the regime in which bounding-box designs are at their best."""
+    g_ = torch.Generator(device="cpu").manual_seed(1234)          # the same on every rank: replicas stay identical
+    with torch.no_grad():
+        for n_, p_ in model.head.pixel_decoder.named_parameters():
+            if n_.endswith("sampling_offsets.bias"):
+                p_.add_(torch.randn(p_.shape, generator=g_).to(dev))
+            elif n_.endswith("sampling_offsets.weight"):
+                p_.copy_((torch.randn(p_.shape, generator=g_) * 0.18).to(dev))
+
+
+DUMP_SAMPLE = 1 << 21          # elements of the seeded parameter / gradient samples (8 MB each in float32)
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step receives after its last call, written as out_dir/<name>.npy (~16 MB in all):
+      loss.npy              float64 [1]      the summed weighted loss the step returned
+      params_sample.npy     float32 [2^21]   the updated parameters (clip + AdamW applied), sampled (all, if fewer)
+      grads_sample.npy      float32 [2^21]   the gradients of that step at the same positions (zero for a parameter without one)
+      param_sums.npy        float64 [n]      sum of every parameter tensor (all elements, named_parameters order)
+      grad_sums.npy         float64 [n]      sum of every gradient tensor
+    The samples are the same positions of the flattened parameter vector (named_parameters order, logical element order,
+    so independent of the memory format) on every run: a private generator with a fixed seed picks them."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        gen = torch.Generator().manual_seed(20240)
+        if flat_p.numel() <= DUMP_SAMPLE:
+            idx = torch.arange(flat_p.numel(), device=flat_p.device)
+        else:
+            idx = torch.randint(0, flat_p.numel(), (DUMP_SAMPLE,), generator=gen).sort().values.to(flat_p.device)
+        arrays = {
+            "loss": np.array([float(loss.detach())], dtype=np.float64),
+            "params_sample": flat_p.index_select(0, idx).cpu().numpy(),
+            "grads_sample": flat_g.index_select(0, idx).cpu().numpy(),
+            "param_sums": torch.stack([p.detach().double().sum() for p in params]).cpu().numpy(),
+            "grad_sums": torch.stack([p.grad.detach().double().sum() if p.grad is not None else p.new_zeros((), dtype=torch.float64)
+                                      for p in params]).cpu().numpy(),
+        }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def _sha256(path):
     with open(path, "rb") as f:
         return hashlib.sha256(f.read()).hexdigest()
@@ -282,7 +343,15 @@ def main():
                     help="N = 1, full step only: timed HEAD-ONLY steps after everything else (config.head_only; 0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-size", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the roofline steps, the head-only and trained-offsets legs, the N > 1 "
+                         "exchange diagnostics and replicas check, and the CPU baseline (the options above that select them "
+                         "only act with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.workload != "B" and not a.head_only:
         raise SystemExit("--workload C / D / E are head-only workloads (their backbones are outside the path): add --head-only")
     wl = WORKLOADS[a.workload]
@@ -316,20 +385,8 @@ def main():
         model = TrainModel().to(dev).train()
         model.backbone.to(memory_format=torch.channels_last)
 
-    def trained_like_offsets():
-        """sampling offsets of a mid-training model: per-query scatter of sigma ~ 3 px (weights N(0, 0.18) on the O(1) query
-        features) around the initial pattern moved by N(0, 1 px) (biases).  A freshly built MSDeformAttn has zero offset weights,
-        i.e. every query of a head looks the same way: the regime in which bounding-box designs are at their best."""
-        g_ = torch.Generator(device="cpu").manual_seed(1234)          # the same on every rank: replicas stay identical
-        with torch.no_grad():
-            for n_, p_ in model.head.pixel_decoder.named_parameters():
-                if n_.endswith("sampling_offsets.bias"):
-                    p_.add_(torch.randn(p_.shape, generator=g_).to(dev))
-                elif n_.endswith("sampling_offsets.weight"):
-                    p_.copy_((torch.randn(p_.shape, generator=g_) * 0.18).to(dev))
-
     if a.msda_offsets == "trained":
-        trained_like_offsets()
+        trained_like_offsets(model, dev)
     # gradient exchange: three flat buckets (head | res5 + res4 | rest of the backbone), the first two launched from two
     # tensor hooks while the backbone back-propagates (mp_former_amd.dist.FlatGradSync); MPF_GRAD_SYNC=ddp selects torch's
     # DistributedDataParallel (per-parameter hooks, 25 MB buckets)
@@ -364,17 +421,90 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # the seeded initial parameters: the LAST timed step starts from them again, with zeroed moments, so that the step whose
+    # results --dump-outputs writes has the same inputs on every run (the state after W + K - 1 steps carries the run-to-run
+    # rounding of float atomics in backward passes, which the matcher and the point sampling turn into large differences)
+    params = [p for p in model.parameters()]
+    init_params = [p.detach().clone() for p in params]
+
+    def restart_from_init():
+        with torch.no_grad():
+            torch._foreach_copy_(params, init_params)
+            moments = [t for st in opt.state.values() for k, t in st.items() if k in ("exp_avg", "exp_avg_sq")]
+            if moments:
+                torch._foreach_zero_(moments)
+
     for i in range(a.warmup):
         step(i)
     barrier()
     # ---- the metric: K steps, launch profiler OFF (no event records inside the timed region) -------------------------
     t0 = time.perf_counter()
     for i in range(a.steps):
+        if i == a.steps - 1:
+            restart_from_init()             # (two multi-tensor launches on the device, no synchronisation)
         loss = step(a.warmup + i)
     barrier()
     dt = time.perf_counter() - t0
     dt = mdist.max_over_ranks(dt, dev)
     final_loss = float(loss.detach())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, loss)
+
+    S_tok = sum((hw[0] // s) * (hw[1] // s) for s in (8, 16, 32))
+    # what the process group actually was (a SCALE line then proves RCCL saw N ranks): backend, ranks, RCCL's version
+    pg_info = None
+    if mdist.distributed():
+        pg_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "grad_sync": os.environ.get("MPF_GRAD_SYNC", "flat")}
+        if pg_info["backend"] == "nccl":
+            pg_info["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
+    full = run_full(a, model, step, barrier, sync, world, rank, dev, hw, S_tok, batches, opt) if a.full else None
+
+    if rank == 0:
+        ips = a.batch * world * a.steps / dt
+        if a.head_only:
+            metric = "training images/sec, segmentation head only (synthetic backbone features), %s %dx%d" % (wl["name"], hw[0], hw[1])
+            workload = ("%s, %d queries, %d classes, %dx%d, HEAD ONLY: MSDeformAttn pixel decoder (6 layers) + MP masked decoder (9 layers, "
+                        "NUM_DN 1) + Hungarian matching + 60 losses + backward + clip + AdamW of the head, on synthetic bf16 backbone "
+                        "features with channels %s" % (wl["name"], wl["queries"], wl["classes"], hw[0], hw[1], list(wl["chans"])))
+        else:
+            metric = "training images/sec COCO-instance R50 1024x1024"
+            workload = ("COCO-instance R50, 100 queries, 80 classes, %dx%d: full train step = R50 backbone "
+                        "+ MSDeformAttn pixel decoder (6 layers) + MP masked decoder (9 layers, NUM_DN 1) "
+                        "+ Hungarian matching + 60 losses + backward + grad all-reduce + clip + AdamW" % (a.size, a.size))
+        out = {
+            "metric": metric,
+            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(dt / a.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "bf16 (backbone, decoder) + f32 (pixel decoder, losses), as the reference's AMP",
+            "data": "synthetic",
+            "config": {"workload": workload, "baseline_config": a.workload, "head_only_workload": bool(a.head_only),
+                       "global_batch": a.batch * world, "per_gpu_batch": a.batch, "parallelism": f"dp{world}",
+                       "tokens_per_image_S": S_tok, "final_loss": round(final_loss, 4),
+                       "msda_offsets": a.msda_offsets, "full": bool(a.full),
+                       "autograd_threads": "backward on the launch thread",
+                       "process_group": pg_info},
+            "roofline": None,
+            "cpu_baseline": None,
+        }
+        out["config"]["fp32_gemm"] = ("fp16 x 2 split: two pieces per operand, three MFMA products, power-of-two scale from the operand's "
+                                      "largest magnitude; error vs fp64 <= the library fp32 GEMM's (tests/test_gemm3_gpu.py)")
+        out["config"]["miopen_find_db"] = "mismatch (MIOpen ignored the shipped db)" if _miopen.db_mismatch() else "shipped"
+        if full is not None:
+            out["config"].update(full["config"])
+            out["roofline"] = full["roofline"]
+            if world == 1 and not a.no_cpu_baseline and not a.head_only:      # (the oracle's step is the config-B / config-A head)
+                out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_size)
+        print(json.dumps(out), flush=True)
+    if mdist.distributed():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def run_full(a, model, step, barrier, sync, world, rank, dev, hw, S_tok, batches, opt):
+    """--full: the measurements and checks beyond the headline, all after its timed region.  Returns {"config": extra config
+    keys, "roofline": the roofline object (rank 0) or None}."""
+    from mp_former_amd import _lib
+    from mp_former_amd import dist as mdist
 
     # ---- roofline block: a few MORE steps with the in-library launch log on (HIP events recorded on the launch stream
     # around every native kernel; outside the timed region, so the headline does not pay for the event records) --------
@@ -436,7 +566,6 @@ def main():
                           "what": "allreduce_ms = each bucket's collective alone (median of 5, idle device); exposed_wait_ms = compute-stream time "
                                   "from finish()'s first wait to its last unpack on a step; in_flight_ms = bucket launch -> wait satisfied (includes "
                                   "the backbone backward it ran under)"}
-    S_tok = sum((hw[0] // s) * (hw[1] // s) for s in (8, 16, 32))
     n_b = n_pull                                   # one bin + one tile launch per MSDA backward call
     ms_b = ms_push + ms_pull
     by_b = 1344.0 * 4 * S_tok * a.batch * n_b      # algorithmic bytes: SURVEY.md §8(d), fp32, per call
@@ -498,7 +627,7 @@ def main():
     # freshly initialised model); 3 warm-up + 10 timed steps, launch log off
     trained_ms = None
     if a.msda_offsets == "init" and a.trained_steps > 0:
-        trained_like_offsets()
+        trained_like_offsets(model, dev)
         for i in range(3):
             step(i)
         barrier()
@@ -520,14 +649,19 @@ def main():
         allcs = torch.stack(allcs)
         sync_spread = float(((allcs.max(0).values - allcs.min(0).values) / scale).max())
 
-    # what the process group actually was (a SCALE line then proves RCCL saw N ranks): backend, ranks, RCCL's version
-    pg_info = None
-    if mdist.distributed():
-        pg_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "grad_sync": os.environ.get("MPF_GRAD_SYNC", "flat")}
-        if pg_info["backend"] == "nccl":
-            pg_info["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
+    extra = {"roofline_steps": P}
+    if trained_ms is not None:
+        extra["trained_like_offsets"] = {"ms_per_step": round(trained_ms, 2), "images_per_sec": round(a.batch * world / trained_ms * 1e3, 2),
+                                         "steps": a.trained_steps,
+                                         "what": "same step, sampling offsets scattered per query (sigma ~ 3 px): offset weights N(0, 0.18), biases + N(0, 1 px)"}
+    if sync_spread is not None:
+        extra["param_sync_spread"] = sync_spread
+    if grad_sync_info is not None:
+        extra["grad_sync"] = grad_sync_info
+    if head_leg is not None:
+        extra["head_only"] = head_leg
+    roofline = None
     if rank == 0:
-        ips = a.batch * world * a.steps / dt
         achieved = by_b / (ms_b * 1e-3) / 1e9 if ms_b > 0 else 0.0
 
         def attn_entry(name):
@@ -592,95 +726,53 @@ def main():
             return e
 
         fwd_alg = 800.0 * 4 * S_tok * a.batch * n_f            # the forward's own algorithmic bytes
-        if a.head_only:
-            metric = "training images/sec, segmentation head only (synthetic backbone features), %s %dx%d" % (wl["name"], hw[0], hw[1])
-            workload = ("%s, %d queries, %d classes, %dx%d, HEAD ONLY: MSDeformAttn pixel decoder (6 layers) + MP masked decoder (9 layers, "
-                        "NUM_DN 1) + Hungarian matching + 60 losses + backward + clip + AdamW of the head, on synthetic bf16 backbone "
-                        "features with channels %s" % (wl["name"], wl["queries"], wl["classes"], hw[0], hw[1], list(wl["chans"])))
-        else:
-            metric = "training images/sec COCO-instance R50 1024x1024"
-            workload = ("COCO-instance R50, 100 queries, 80 classes, %dx%d: full train step = R50 backbone "
-                        "+ MSDeformAttn pixel decoder (6 layers) + MP masked decoder (9 layers, NUM_DN 1) "
-                        "+ Hungarian matching + 60 losses + backward + grad all-reduce + clip + AdamW" % (a.size, a.size))
-        out = {
-            "metric": metric,
-            "value": round(ips, 3), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16 (backbone, decoder) + f32 (pixel decoder, losses), as the reference's AMP",
-            "data": "synthetic",
-            "config": {"workload": workload, "baseline_config": a.workload, "head_only_workload": bool(a.head_only),
-                       "global_batch": a.batch * world, "per_gpu_batch": a.batch, "parallelism": f"dp{world}",
-                       "tokens_per_image_S": S_tok, "final_loss": round(final_loss, 4),
-                       "roofline_steps": P, "msda_offsets": a.msda_offsets,
-                       "autograd_threads": "backward on the launch thread",
-                       "process_group": pg_info},
-            # the time-dominant native kernel family: the fp32 GEMMs of the pixel decoder as SIX bf16 MFMA products per fp32
-            # product (three 8-bit-mantissa planes per operand, terms >= 2^-16 kept).  achieved = bf16 MFMA flops actually
-            # issued per second; peak = the dense bf16 MFMA peak
-            "roofline": {"kernel": "gemm3 family (gemm3_tn / gemm3_nt / gemm3_nt_group: the fp32 Linear layers of the pixel decoder and their gradients as fp16 x 2 (three) or bf16 x 3 (six) MFMA products; the MFMA-bound 3 x 3 convolution groups are listed under also)",
-                         # ALGORITHMIC fraction: the family's shapes are HBM-bound on algorithmic terms (64-115 fp32 flop/B,
-                         # ridge 312), so achieved = algorithmic bytes / time against 8 TB/s; the MFMA products issued are separate keys
-                         "bound": "hbm", "achieved": round(g_by / g_sec / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(g_hf, 4), "traffic": None,
-                         "traffic_note": "algorithmic bytes = 4 (M K + M N) + 4 | 6 N K per launch (activations in, result out, weight planes); a family of "
-                                         "~90 launches of different shapes has no per-launch PMC figure — the calibrated FETCH_SIZE / WRITE_SIZE of its TN "
-                                         "kernel on the three encoder shapes (tools/pmc_gemm3_traffic.sh) is in tn_traffic_over_algorithmic",
-                         "tn_traffic_over_algorithmic": _gemm3_traffic_ratios(),
-                         "launches_per_step": g_n / max(P, 1), "ms_per_step": round(g_ms / max(P, 1), 3),
-                         "ms_per_step_incl_conv3x3": round(g_ms_all / max(P, 1), 3),
-                         "avg_us": round(g_ms * 1e3 / max(g_n, 1), 1),
-                         "issued_mfma_tflops": round(g_issued / g_sec / 1e12, 1), "issued_mfma_frac": round(g_mf, 4),
-                         "algorithmic_tflops_fp32": round(g_fl / g_sec / 1e12, 1),
-                         "algorithmic_mfma_frac": round(g_fl / g_sec / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-                         "x_native_fp32_mfma_peak_157": round(g_fl / g_sec / 1e12 / FP32_MFMA_PEAK_TFLOPS, 3),
-                         "amax_passes": {"launches_per_step": n_am / max(P, 1), "ms_per_step": round(ms_am / max(P, 1), 3)},
-                         "also": [
-                             gemm_entry("gemm3_tn_kernel", g_tn), gemm_entry("gemm3_nt_kernel", g_nt),
-                             gemm_entry("gemm3_nt_group_kernel", g_ng), gemm_entry("gemm3_conv_kernel", g_cv),
-                             gemm_entry("gemm3_nt_kernel<conv3x3>", g_cw),
-                             # the deformable-sampling kernels against the HBM roofline (north-star)
-                             {"kernel": "MSDA backward (msda_bwd_bin_kernel + msda_bwd_tile_kernel: destination-side, atomics-free, no bounding boxes)",
-                              "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                              "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_note": traffic_note,
-                              "launches": n_b, "avg_us": round(ms_b * 1e3 / max(n_b, 1), 1),
-                              "avg_us_bin": round(ms_push * 1e3 / max(n_push, 1), 1), "avg_us_tile": round(ms_pull * 1e3 / max(n_pull, 1), 1),
-                              "algorithmic_bytes_per_launch": round(by_b / max(n_b, 1))},
-                             {"kernel": "msda_fwd_block_kernel", "launches": n_f, "avg_us": round(ms_f * 1e3 / max(n_f, 1), 1),
-                              "bound": "hbm", "achieved": round(fwd_alg / (ms_f * 1e-3) / 1e9 if ms_f > 0 else 0.0, 1), "unit": "GB/s",
-                              "frac": round(fwd_alg / (ms_f * 1e-3) / 1e9 / HBM_PEAK_GBPS if ms_f > 0 else 0.0, 4),
-                              "algorithmic_bytes_per_launch": round(fwd_alg / max(n_f, 1)),
-                              "frac_incl_loc_attn_written": round(by_f / (ms_f * 1e-3) / 1e9 / HBM_PEAK_GBPS if ms_f > 0 else 0.0, 4),
-                              "note": "frac = SURVEY 8(d)'s 800*e*S*N bytes; frac_incl_loc_attn_written adds the 288*e*Lq*N bytes of sampling "
-                                      "locations / attention weights this launch also writes for the backward (the msda_prep pass fused in)"},
-                             # masked cross- / self-attention on bf16 MFMA tiles: MFMA rate against the gfx950 peak AND the
-                             # K / V / mask stream rate (bound by the latter at ~120 queries: 4 MFMAs per 32 keys)
-                             attn_entry("attn_fwd_kernel"), attn_entry("attn_bwd_kv_kernel"), attn_entry("attn_bwd_q_kernel"),
-                             # the mask predictions from their factors (csrc/mask_fused.hip): no [N, 10 Qtot, H/4, W/4] tensor
-                             fused_entry("match_cost_fused_kernel", "corner rows gathered: 2048 B per point and (output, image) + target samples"),
-                             fused_entry("pair_planes_fwd_kernel", "features read once per image"),
-                             fused_entry("pair_planes_dfeat_kernel", "features-gradient written + gradient planes read"),
-                             fused_entry("pair_planes_dembed_kernel", "features + gradient planes read")]},
-            "cpu_baseline": None,
-        }
-        if trained_ms is not None:
-            out["config"]["trained_like_offsets"] = {"ms_per_step": round(trained_ms, 2), "images_per_sec": round(a.batch * world / trained_ms * 1e3, 2),
-                                                     "steps": a.trained_steps,
-                                                     "what": "same step, sampling offsets scattered per query (sigma ~ 3 px): offset weights N(0, 0.18), biases + N(0, 1 px)"}
-        if sync_spread is not None:
-            out["config"]["param_sync_spread"] = sync_spread
-        if grad_sync_info is not None:
-            out["config"]["grad_sync"] = grad_sync_info
-        if head_leg is not None:
-            out["config"]["head_only"] = head_leg
-        out["config"]["fp32_gemm"] = ("fp16 x 2 split: two pieces per operand, three MFMA products, power-of-two scale from the operand's "
-                                      "largest magnitude; error vs fp64 <= the library fp32 GEMM's (tests/test_gemm3_gpu.py)")
-        out["config"]["miopen_find_db"] = "mismatch (MIOpen ignored the shipped db)" if _miopen.db_mismatch() else "shipped"
-        if world == 1 and not a.no_cpu_baseline and not a.head_only:      # (the oracle's step is the config-B / config-A head)
-            out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_size)
-        print(json.dumps(out), flush=True)
-    if mdist.distributed():
-        dist.barrier()
-        dist.destroy_process_group()
+        # the time-dominant native kernel family: the fp32 GEMMs of the pixel decoder as SIX bf16 MFMA products per fp32
+        # product (three 8-bit-mantissa planes per operand, terms >= 2^-16 kept).  achieved = bf16 MFMA flops actually
+        # issued per second; peak = the dense bf16 MFMA peak
+        roofline = {"kernel": "gemm3 family (gemm3_tn / gemm3_nt / gemm3_nt_group: the fp32 Linear layers of the pixel decoder and their gradients as fp16 x 2 (three) or bf16 x 3 (six) MFMA products; the MFMA-bound 3 x 3 convolution groups are listed under also)",
+                    # ALGORITHMIC fraction: the family's shapes are HBM-bound on algorithmic terms (64-115 fp32 flop/B,
+                    # ridge 312), so achieved = algorithmic bytes / time against 8 TB/s; the MFMA products issued are separate keys
+                    "bound": "hbm", "achieved": round(g_by / g_sec / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(g_hf, 4), "traffic": None,
+                    "traffic_note": "algorithmic bytes = 4 (M K + M N) + 4 | 6 N K per launch (activations in, result out, weight planes); a family of "
+                                    "~90 launches of different shapes has no per-launch PMC figure — the calibrated FETCH_SIZE / WRITE_SIZE of its TN "
+                                    "kernel on the three encoder shapes (tools/pmc_gemm3_traffic.sh) is in tn_traffic_over_algorithmic",
+                    "tn_traffic_over_algorithmic": _gemm3_traffic_ratios(),
+                    "launches_per_step": g_n / max(P, 1), "ms_per_step": round(g_ms / max(P, 1), 3),
+                    "ms_per_step_incl_conv3x3": round(g_ms_all / max(P, 1), 3),
+                    "avg_us": round(g_ms * 1e3 / max(g_n, 1), 1),
+                    "issued_mfma_tflops": round(g_issued / g_sec / 1e12, 1), "issued_mfma_frac": round(g_mf, 4),
+                    "algorithmic_tflops_fp32": round(g_fl / g_sec / 1e12, 1),
+                    "algorithmic_mfma_frac": round(g_fl / g_sec / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+                    "x_native_fp32_mfma_peak_157": round(g_fl / g_sec / 1e12 / FP32_MFMA_PEAK_TFLOPS, 3),
+                    "amax_passes": {"launches_per_step": n_am / max(P, 1), "ms_per_step": round(ms_am / max(P, 1), 3)},
+                    "also": [
+                        gemm_entry("gemm3_tn_kernel", g_tn), gemm_entry("gemm3_nt_kernel", g_nt),
+                        gemm_entry("gemm3_nt_group_kernel", g_ng), gemm_entry("gemm3_conv_kernel", g_cv),
+                        gemm_entry("gemm3_nt_kernel<conv3x3>", g_cw),
+                        # the deformable-sampling kernels against the HBM roofline (north-star)
+                        {"kernel": "MSDA backward (msda_bwd_bin_kernel + msda_bwd_tile_kernel: destination-side, atomics-free, no bounding boxes)",
+                         "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_note": traffic_note,
+                         "launches": n_b, "avg_us": round(ms_b * 1e3 / max(n_b, 1), 1),
+                         "avg_us_bin": round(ms_push * 1e3 / max(n_push, 1), 1), "avg_us_tile": round(ms_pull * 1e3 / max(n_pull, 1), 1),
+                         "algorithmic_bytes_per_launch": round(by_b / max(n_b, 1))},
+                        {"kernel": "msda_fwd_block_kernel", "launches": n_f, "avg_us": round(ms_f * 1e3 / max(n_f, 1), 1),
+                         "bound": "hbm", "achieved": round(fwd_alg / (ms_f * 1e-3) / 1e9 if ms_f > 0 else 0.0, 1), "unit": "GB/s",
+                         "frac": round(fwd_alg / (ms_f * 1e-3) / 1e9 / HBM_PEAK_GBPS if ms_f > 0 else 0.0, 4),
+                         "algorithmic_bytes_per_launch": round(fwd_alg / max(n_f, 1)),
+                         "frac_incl_loc_attn_written": round(by_f / (ms_f * 1e-3) / 1e9 / HBM_PEAK_GBPS if ms_f > 0 else 0.0, 4),
+                         "note": "frac = SURVEY 8(d)'s 800*e*S*N bytes; frac_incl_loc_attn_written adds the 288*e*Lq*N bytes of sampling "
+                                 "locations / attention weights this launch also writes for the backward (the msda_prep pass fused in)"},
+                        # masked cross- / self-attention on bf16 MFMA tiles: MFMA rate against the gfx950 peak AND the
+                        # K / V / mask stream rate (bound by the latter at ~120 queries: 4 MFMAs per 32 keys)
+                        attn_entry("attn_fwd_kernel"), attn_entry("attn_bwd_kv_kernel"), attn_entry("attn_bwd_q_kernel"),
+                        # the mask predictions from their factors (csrc/mask_fused.hip): no [N, 10 Qtot, H/4, W/4] tensor
+                        fused_entry("match_cost_fused_kernel", "corner rows gathered: 2048 B per point and (output, image) + target samples"),
+                        fused_entry("pair_planes_fwd_kernel", "features read once per image"),
+                        fused_entry("pair_planes_dfeat_kernel", "features-gradient written + gradient planes read"),
+                        fused_entry("pair_planes_dembed_kernel", "features + gradient planes read")]}
+    return {"config": extra, "roofline": roofline}
 
 
 if __name__ == "__main__":

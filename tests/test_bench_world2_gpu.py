@@ -32,7 +32,7 @@ def _run_two_ranks(grad_sync, extra_args=(), **extra_env):
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MPF_CHECK_SYNC="1", MPF_GRAD_SYNC=grad_sync, **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_bench_world2_child.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--profile-steps", "1", "--trained-steps", "1", "--size", "512", "--no-cpu-baseline"] + list(extra_args)
+           "--profile-steps", "1", "--trained-steps", "1", "--size", "512", "--no-cpu-baseline", "--full"] + list(extra_args)
     return subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1400)
 
 
@@ -102,7 +102,7 @@ def test_bench_starts_its_own_ranks():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MPF_CHECK_SYNC="1", MPF_GRAD_SYNC="flat",
                MPF_BENCH_LAUNCH_SCRIPT=os.path.join(ROOT, "tests", "_bench_world2_child.py"))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--profile-steps", "1",
-           "--trained-steps", "0", "--size", "512", "--no-cpu-baseline"]
+           "--trained-steps", "0", "--size", "512", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1400)
     assert r.returncode == 0, f"self-launched bench.py --gpus 2 failed:\n{r.stdout[-2000:]}\n{r.stderr[-6000:]}"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

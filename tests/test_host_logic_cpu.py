@@ -230,6 +230,42 @@ def test_bench_self_launch_starts_one_fresh_process_per_rank(tmp_path):
     assert r.returncode != 0
 
 
+def test_bench_dump_outputs_is_the_same_on_every_run(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): the loss, the sampled parameters and gradients and the per-tensor sums come out
+    as float32 / float64 .npy files, bit-identical for the same model from one process to the next (the sampled positions
+    come from a private seeded generator, whatever the global RNG did).  Run in child processes: importing bench sets its
+    runtime environment variables.  An invalid --steps is refused before anything touches a GPU."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = ("import sys, torch, bench\n"
+              "torch.manual_seed(0)\n"
+              "m = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.Flatten(), torch.nn.Linear(288, 4), torch.nn.LayerNorm(4))\n"
+              "m[0].to(memory_format=torch.channels_last)\n"
+              "loss = m(torch.randn(2, 3, 8, 8)).square().sum()\n"
+              "loss.backward()\n"
+              "m[3].weight.grad = None\n"
+              "torch.manual_seed(int(sys.argv[2]))\n"
+              "bench.DUMP_SAMPLE = 1000\n"
+              "bench.dump_outputs(sys.argv[1], m, loss)\n")
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d, seed in zip(dirs, (1, 2)):
+        r = subprocess.run([sys.executable, "-c", script, str(d), str(seed)], cwd=root, env=dict(os.environ, PYTHONPATH=root),
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["grad_sums.npy", "grads_sample.npy", "loss.npy", "param_sums.npy", "params_sample.npy"]
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, n
+        assert np.array_equal(a, b), n
+    assert np.load(dirs[0] / "params_sample.npy").shape == (1000,)            # 1388 parameters, a 1000-element sample
+    assert np.load(dirs[0] / "param_sums.npy").shape == (6,) and np.load(dirs[0] / "grad_sums.npy")[4] == 0.0
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
 def test_registry_plugin_builds_both_decoders_by_name():
     """mp_former_amd.d2_plugin against stub registries of detectron2's interface (this image has no detectron2): the reference's
     build functions (pixel_decoder/fpn.py:21-34, transformer_decoder/maskformer_transformer_decoder.py:21-28) look a class up
