@@ -106,7 +106,8 @@ int mpf_msda_backward(const void* value, const int64_t* spatial_shapes,
  * Shapes the prologue cannot serve (a side > 16384 or <= 0, a level outside value, overlapping levels) leave every output
  * element NaN — there is no host-visible error without a synchronisation; mpf_msda_dev_geometry reads the record back.
  *   workspace: mpf_msda_dev_workspace_bytes(..., backward) bytes, 256-byte aligned, owned by the caller for the duration of the
- *              kernels (forward: 1 KB; backward: tile counters, entry runs and the spill list, ~60 MB at 1024 x 1024, batch 2).
+ *              kernels (forward: the 1 KB header and the tile counters; backward: those, the entry runs and the spill list, ~60 MB
+ *              at 1024 x 1024, batch 2).
  * Other dtypes / head widths / point counts / more than 4 levels: mpf_msda_forward / mpf_msda_backward (which read the same two
  * device arrays themselves), also without a copy.
  */

@@ -265,30 +265,25 @@ def profile_get(name_substr):
     return n.value, ms.value, by.value
 
 
-# ---- workspace scopes -------------------------------------------------------------------------------------------------------
-# The python mirrors keep grow-on-demand scratch buffers per device (MSDA entry runs, GroupNorm / LayerNorm partials, decoder
-# scratch).  A HIP graph bakes the address of the buffer it was captured with: if eager code later asks the same cache for more
-# bytes, the old buffer is freed and every replay writes through a dangling pointer (measured: memory fault in the first
-# step after capturing the pixel decoder).  Code that is being captured therefore runs inside ``workspace_scope(name)``, which
-# is part of every cache key: buffers baked into a graph are private to it and never resized by anyone else.
-_WS_SCOPE = [""]
+# ---- native scratch ---------------------------------------------------------------------------------------------------------
+_scratch = {}
 
 
-def ws_scope():
-    return _WS_SCOPE[-1]
+def scratch(owner, device, stream, nbytes, zeroed=False):
+    """Grow-on-demand device scratch of the native ops -> uint8 tensor of at least ``nbytes`` (pass its ``numel()`` on).
 
-
-class workspace_scope:
-    def __init__(self, name):
-        self.name = str(name)
-
-    def __enter__(self):
-        _WS_SCOPE.append(self.name)
-        return self
-
-    def __exit__(self, *exc):
-        _WS_SCOPE.pop()
-        return False
+    One buffer per (owner, device, stream).  ``owner`` is a literal naming ONE buffer layout: a layout may keep state between
+    calls (the MSDA geometry record, the res-LN ticket, the mask-head flags) that another layout would overwrite.  ``stream`` is
+    the raw stream of the native call (`stream_ptr`): ops running at once on two streams never share scratch.  ``zeroed``: a new
+    or grown buffer starts zero, for layouts whose kernels leave it zero between calls (ticket, flags) or that must not find a
+    stale geometry key in fresh memory.  A buffer whose address a HIP graph has baked in must never be resized: if graph capture
+    returns, put the capture in the key here."""
+    key = (owner, device, stream)
+    w = _scratch.get(key)
+    if w is None or w.numel() < nbytes:
+        n = int(nbytes * 1.25) + 1024
+        w = _scratch[key] = (torch.zeros if zeroed else torch.empty)(n, dtype=torch.uint8, device=device)
+    return w
 
 
 def stream_ptr(device):

@@ -11,18 +11,6 @@ from torch.autograd import Function
 
 from . import _lib
 
-_ws = {}
-
-
-def _workspace(device, nbytes):
-    key = (device, _lib.ws_scope())          # (a graph capture has its own buffers: _lib.workspace_scope)
-    w = _ws.get(key)
-    if w is None or w.numel() < nbytes:
-        w = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _ws[key] = w
-    return w
-
-
 class _AttnCore(Function):
     """q [Lq,N,E], k, v [Lk,N,E] (sequence-first, as nn.MultiheadAttention projects them), mask bool
     [N,Lq,Lk] / [Lq,Lk] / None -> [Lq,N,E].  Forward and backward on the native MFMA kernels; the
@@ -51,7 +39,7 @@ class _AttnCore(Function):
             assert m.dtype == torch.bool and m.shape[-2:] == (Lq, Lk)
         out = torch.empty((Lq, N, E), dtype=torch.bfloat16, device=q.device)
         lse = torch.empty((N, nheads, Lq), dtype=torch.float32, device=q.device)
-        ws = _workspace(q.device, lib.mpf_attn_workspace_bytes(Lq, Lk, N, nheads))
+        ws = _lib.scratch("attn", q.device, stream, lib.mpf_attn_workspace_bytes(Lq, Lk, N, nheads))
         with _lib.device_guard(q.device):
             code = lib.mpf_attn_forward(qb.data_ptr(), kb.data_ptr(), vt.data_ptr(), m.data_ptr() if m is not None else None,
                                         1 if (m is not None and m.dim() == 3) else 0, out.data_ptr(), lse.data_ptr(),
@@ -80,7 +68,7 @@ class _AttnCore(Function):
         dq = torch.empty_like(qb)
         dk = torch.empty_like(kb)
         dv = torch.empty_like(vb)
-        ws = _workspace(dev, lib.mpf_attn_workspace_bytes(Lq, Lk, N, H))
+        ws = _lib.scratch("attn", dev, stream, lib.mpf_attn_workspace_bytes(Lq, Lk, N, H))
         with _lib.device_guard(dev):
             _lib.check(lib.mpf_attn_bwd_prep(qb.data_ptr(), gob.data_ptr(), out.data_ptr(), qT.data_ptr(), doT.data_ptr(),
                                              delta.data_ptr(), Lq, LqP, N, H, stream), "mpf_attn_bwd_prep")      # Q^T, dO^T, delta

@@ -13,7 +13,6 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
-from .attention import _workspace as _attn_workspace
 
 _vp, _u64, _i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32
 
@@ -42,7 +41,6 @@ class MpfDecoderLayerGrad(ctypes.Structure):
 
 
 _checked = False
-_scratch = {}
 _PARAM_DTYPES = tuple(torch.float32 if n in _LN else torch.bfloat16 for n in PARAM_NAMES)
 _layouts = {}
 
@@ -91,15 +89,6 @@ def _lib_checked():
             raise RuntimeError("MpfDecoderLayer layout differs between decoder_layer.py and libmpformer_hip.so")
         _checked = True
     return lib
-
-
-def _scratch_buf(device, nbytes):
-    key = (device, _lib.ws_scope())
-    w = _scratch.get(key)
-    if w is None or w.numel() < nbytes:
-        w = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _scratch[key] = w
-    return w
 
 
 def _al(n):
@@ -231,10 +220,10 @@ class DecoderLayerFn(Function):
         if not k_c.is_contiguous():
             L.kv_row_stride, L.kv_img_stride = k_c.stride(0), k_c.stride(1)
         sc_bytes, ws_bytes = _scratch_bytes(lib, Qt, N, nheads, S, F_)
-        sc = _scratch_buf(dev, sc_bytes)
-        ws = _attn_workspace(dev, ws_bytes)
-        L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
         stream = _lib.stream_ptr(dev)
+        sc = _lib.scratch("decoder_scratch", dev, stream, sc_bytes)
+        ws = _lib.scratch("attn", dev, stream, ws_bytes)
+        L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
         with _lib.device_guard(dev):
             code = lib.mpf_decoder_layer_forward(ctypes.byref(L), stream)
         _lib.check(code, "mpf_decoder_layer_forward")
@@ -291,10 +280,10 @@ class DecoderLayerFn(Function):
             setattr(G, n, wbase + 2 * o)
         G.d_ln = d_ln.data_ptr()
         sc_bytes, ws_bytes = _scratch_bytes(lib, Qt, N, H, S, F_)
-        sc = _scratch_buf(dev, sc_bytes)
-        ws = _attn_workspace(dev, ws_bytes)
-        L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
         stream = _lib.stream_ptr(dev)
+        sc = _lib.scratch("decoder_scratch", dev, stream, sc_bytes)
+        ws = _lib.scratch("attn", dev, stream, ws_bytes)
+        L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
         with _lib.device_guard(dev):
             code = lib.mpf_decoder_layer_backward(ctypes.byref(L), ctypes.byref(G), stream)
         _lib.check(code, "mpf_decoder_layer_backward")

@@ -342,7 +342,6 @@ def _native_backward(gout, params, saved, planes_t, meta, nl, dims, F, rps, spli
     """The backward of all layers as ONE native call (csrc/encoder_layer.hip, mpf_encoder_backward): same launches, same
     arguments as the python-sequenced loop below.  -> (d input [R, C], out arena [nl, per], (o_dw288, o_lvl, o_db288, group stride),
     dgb [2 nl, 2, 256])"""
-    from .msda import _workspace
     N, S, C = dims
     R = N * S
     M, L, P = meta["n_heads"], meta["n_levels"], meta["n_points"]
@@ -374,7 +373,8 @@ def _native_backward(gout, params, saved, planes_t, meta, nl, dims, F, rps, spli
     need = lib.mpf_msda_backward_workspace_bytes(N, M, L, S, P, host_shapes.data_ptr())
     if need == 0:
         raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
-    ws = _workspace(dev, need)
+    stream = _lib.stream_ptr(dev)
+    ws = _lib.scratch("msda_host", dev, stream, need)
     dgb = torch.empty((2 * nl, 2, 256), dtype=torch.float32, device=dev)
     am = amax_slots(5 * nl, dev)                     # per layer: ds2, dh, ds1, draw, gv
     tab = np.zeros((nl, len(_ENCB_FIELDS)), dtype=np.uint64)
@@ -391,7 +391,7 @@ def _native_backward(gout, params, saved, planes_t, meta, nl, dims, F, rps, spli
                              ds2, dh, dx1, ds1, dao, gv, draw, (ctypes.c_void_p * 2)(dq0, dq1), (ctypes.c_void_p * 2)(g0, g1_), cpart, cs, pgroup,
                              ln_parts.data_ptr(), ln_stride, ws.data_ptr(), ws.numel(), dgb.data_ptr(), tab.ctypes.data)
     with _lib.device_guard(dev):
-        code = lib.mpf_encoder_backward(ctypes.byref(call), _lib.stream_ptr(dev))
+        code = lib.mpf_encoder_backward(ctypes.byref(call), stream)
     _lib.check(code, "mpf_encoder_backward")
     o0 = (g0 - tmp.data_ptr()) // 4
     g = tmp[o0:o0 + R * C].view(R, C)              # g[0]: what layer 0 hands down

@@ -14,18 +14,6 @@ from torch.autograd import Function
 
 from . import _lib
 
-_ws = {}
-
-
-def _workspace(device, nbytes):
-    key = (device, _lib.ws_scope())          # (a graph capture has its own buffers: _lib.workspace_scope)
-    w = _ws.get(key)
-    if w is None or w.numel() < nbytes:
-        w = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=device)
-        _ws[key] = w
-    return w
-
-
 def _transpose(src, B, R, C, in_bs=None):
     out = torch.empty(B * R * C, dtype=torch.float32, device=src.device)
     with _lib.device_guard(src.device):
@@ -71,10 +59,11 @@ class _GroupNormFn(Function):
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
         lib = _lib.lib()
-        ws = _workspace(x.device, lib.mpf_group_stats_workspace_bytes(rows, row_len))
+        stream = _lib.stream_ptr(x.device)
+        ws = _lib.scratch("gn", x.device, stream, lib.mpf_group_stats_workspace_bytes(rows, row_len))
         with _lib.device_guard(x.device):
             code = lib.mpf_group_stats(x.data_ptr(), rows, row_len, float(eps), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), _lib.stream_ptr(x.device))
+                                       ws.numel(), stream)
         _lib.check(code, "mpf_group_stats")
         # y = x * a + b with a[n, c] = rstd[n, g] * gamma[c], b[n, c] = beta[c] - mean[n, g] * a[n, c]
         a = (rstd.view(N, groups, 1) * weight.view(1, groups, C // groups)).view(N, C)
@@ -118,12 +107,13 @@ class _GroupNormCLFn(Function):
         mean = torch.empty(N * groups, dtype=torch.float32, device=x.device)
         rstd = torch.empty(N * groups, dtype=torch.float32, device=x.device)
         y = _cl_empty(N, C, H, W, x.device)
-        ws = _workspace(x.device, lib.mpf_gn_cl_workspace_bytes(N, H * W, C, groups))
+        stream = _lib.stream_ptr(x.device)
+        ws = _lib.scratch("gn", x.device, stream, lib.mpf_gn_cl_workspace_bytes(N, H * W, C, groups))
         with _lib.device_guard(x.device):
             code = lib.mpf_gn_cl_forward(x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(), N, H * W, C, groups, float(eps),
                                          1 if relu else 0, top.data_ptr() if top is not None else None,
                                          top.stride(0) if top is not None else 0, W, y.data_ptr(), y.stride(0), mean.data_ptr(),
-                                         rstd.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device))
+                                         rstd.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         _lib.check(code, "mpf_gn_cl_forward")
         ctx.save_for_backward(x, weight, bias, mean, rstd)
         ctx.groups, ctx.relu, ctx.has_top = groups, bool(relu), top is not None
@@ -141,8 +131,8 @@ class _GroupNormCLFn(Function):
         dx = _cl_empty(N, C, H, W, x.device)
         dg = torch.empty(C, dtype=torch.float32, device=x.device)
         db = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = _workspace(x.device, lib.mpf_gn_cl_workspace_bytes(N, H * W, C, ctx.groups))
         stream = _lib.stream_ptr(x.device)
+        ws = _lib.scratch("gn", x.device, stream, lib.mpf_gn_cl_workspace_bytes(N, H * W, C, ctx.groups))
         dtop = None
         with _lib.device_guard(x.device):
             code = lib.mpf_gn_cl_backward(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(),
@@ -178,7 +168,7 @@ class _GroupNormFlattenFn(Function):
             for x, w, b, hw in zip(xs, ws, bs, sizes):
                 mean = torch.empty(N * groups, dtype=torch.float32, device=dev)
                 rstd = torch.empty(N * groups, dtype=torch.float32, device=dev)
-                wsb = _workspace(dev, lib.mpf_gn_cl_workspace_bytes(N, hw, C, groups))
+                wsb = _lib.scratch("gn", dev, stream, lib.mpf_gn_cl_workspace_bytes(N, hw, C, groups))
                 code = lib.mpf_gn_cl_forward(x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), N, hw, C, groups, float(eps), 0,
                                              None, 0, int(x.shape[3]), out.data_ptr() + off * C * 4, S * C, mean.data_ptr(),
                                              rstd.data_ptr(), wsb.data_ptr(), wsb.numel(), stream)
@@ -207,7 +197,7 @@ class _GroupNormFlattenFn(Function):
                 dx = _cl_empty(N, C, H, W, dev)
                 dg = torch.empty(C, dtype=torch.float32, device=dev)
                 db = torch.empty(C, dtype=torch.float32, device=dev)
-                wsb = _workspace(dev, lib.mpf_gn_cl_workspace_bytes(N, hw, C, ctx.groups))
+                wsb = _lib.scratch("gn", dev, stream, lib.mpf_gn_cl_workspace_bytes(N, hw, C, ctx.groups))
                 code = lib.mpf_gn_cl_backward(g.data_ptr() + off * C * 4, S * C, x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(),
                                               stats[2 * l].data_ptr(), stats[2 * l + 1].data_ptr(), N, hw, C, ctx.groups, 0,
                                               dx.data_ptr(), dx.stride(0), dg.data_ptr(), db.data_ptr(), wsb.data_ptr(), wsb.numel(),

@@ -75,20 +75,21 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     hs = host_shapes if host_shapes is not None else _attached_host_shapes(spatial_shapes, level_start_index)
     lib = _lib.lib()
+    stream = _stream(value)
     with _lib.device_guard(value.device):
         if hs is None and _dev_applicable(value, D, L, P):
             # the reference's call (func.py:36): device tensors only -> geometry derived on the device, same blocked kernel
-            ws = _workspace(value.device, lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 0))
+            ws = _lib.scratch("msda_dev", value.device, stream, lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 0), zeroed=True)
             code = lib.mpf_msda_forward_dev(
                 value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
                 attn_weight.data_ptr(), out.data_ptr(), N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(),
-                _stream(value))
+                stream)
         else:
             code = lib.mpf_msda_forward_hs(
                 value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
                 hs.data_ptr() if hs is not None else None,
                 sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], _stream(value))
+                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], stream)
     _lib.check(code, "mpf_msda_forward")
     return out
 
@@ -96,8 +97,6 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
 # backward formulation: "auto" = atomics-free binned kernels when applicable, else the atomic kernels;
 # "atomic" forces the reference-style scatter with hardware fp32 atomics; "binned" requires the binned path.
 BWD_MODE = "auto"
-
-_workspaces = {}
 
 
 def _contiguous_starts(hs):
@@ -146,13 +145,10 @@ def _dev_applicable(value, D, L, P):
     return value.dtype == torch.float32 and D == 32 and P == 4 and 1 <= L <= 4
 
 
-def _workspace(device, nbytes):
-    key = (device, _lib.ws_scope())          # (a graph capture has its own buffers: _lib.workspace_scope)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
+def _workspace(device, nbytes=0):
+    """The "msda_dev" buffer of the current stream, at least ``nbytes``: the workspace of the *_dev routes, whose first KB holds
+    the geometry record (tests read it back)."""
+    return _lib.scratch("msda_dev", device, _lib.stream_ptr(device), nbytes, zeroed=True)
 
 
 def _binned_applicable(value, D, L, P):
@@ -179,12 +175,13 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         lib = _lib.lib()
         need = lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 1)
         if need:
-            ws = _workspace(value.device, need)
+            stream = _stream(value)
+            ws = _lib.scratch("msda_dev", value.device, stream, need, zeroed=True)
             with _lib.device_guard(value.device):
                 code = lib.mpf_msda_backward_dev(
                     value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
                     attn_weight.data_ptr(), grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-                    N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), _stream(value))
+                    N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), stream)
             _lib.check(code, "mpf_msda_backward_dev")
             return [gv, gl, ga]
     if BWD_MODE == "binned" and hs is None:
@@ -194,12 +191,13 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         need = lib.mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, hs.data_ptr())
         if need == 0:
             raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
-        ws = _workspace(value.device, need)
+        stream = _stream(value)
+        ws = _lib.scratch("msda_host", value.device, stream, need)
         with _lib.device_guard(value.device):
             code = lib.mpf_msda_backward_ws(
                 value.data_ptr(), hs.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
                 grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), _stream(value))
+                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), stream)
         _lib.check(code, "mpf_msda_backward_ws")
         return [gv, gl, ga]
     with _lib.device_guard(value.device):
@@ -246,7 +244,8 @@ def ms_deform_attn_backward_raw(value, host_shapes, sampling_loc, attn_weight, g
     need = lib.mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, host_shapes.data_ptr())
     if need == 0:
         raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
-    ws = _workspace(value.device, need)
+    stream = _stream(value)
+    ws = _lib.scratch("msda_host", value.device, stream, need)
     with _lib.device_guard(value.device):
         if output is not None:
             assert output.is_contiguous() and output.numel() == N * Lq * M * D and output.dtype == value.dtype
@@ -255,12 +254,12 @@ def ms_deform_attn_backward_raw(value, host_shapes, sampling_loc, attn_weight, g
                 grad_output.data_ptr(), output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
                 N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(),
                 graw_amax.data_ptr() if graw_amax is not None else None, gv_amax.data_ptr() if gv_amax is not None else None,
-                _stream(value))
+                stream)
         else:
             code = lib.mpf_msda_backward_ws_raw(
                 value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
                 grad_output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), _stream(value))
+                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), stream)
     _lib.check(code, "mpf_msda_backward_ws_raw")
     return gv, graw
 

@@ -52,19 +52,21 @@ class _ResLN(Function):
         if g16 is not None:
             g16 = g16.contiguous()
         lib = _lib.lib()
+        stream = _stream(s)
         args = (s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
                 g32.data_ptr() if g32 is not None else None, g16.data_ptr() if g16 is not None else None, None,
                 ds32.data_ptr() if ds32 is not None else None, ds16.data_ptr() if ds16 is not None else None)
         with _lib.device_guard(s.device):
             # parameter gradients without float atomics (bit-reproducible): per-workgroup partials summed in a fixed order —
             # by the workgroup that arrives last (one launch) for a few hundred rows, by a parallel second launch beyond
+            # (the ticket word at the head of the "ln_det" buffer is zero between calls: zero-initialised, reset by every launch)
             if ctx.rows <= 1024:
-                ws = _det_ws(s.device, lib.mpf_res_ln256_backward_det_workspace_bytes(ctx.rows))
-                code = lib.mpf_res_ln256_backward_det(*args, dgb.data_ptr(), ctx.rows, ws.data_ptr(), ws.numel(), _stream(s))
+                ws = _lib.scratch("ln_det", s.device, stream, lib.mpf_res_ln256_backward_det_workspace_bytes(ctx.rows), zeroed=True)
+                code = lib.mpf_res_ln256_backward_det(*args, dgb.data_ptr(), ctx.rows, ws.data_ptr(), ws.numel(), stream)
             else:
-                ws = _det_ws(s.device, lib.mpf_res_ln256_backward_workspace_bytes(ctx.rows) + 256)
+                ws = _lib.scratch("ln_det", s.device, stream, lib.mpf_res_ln256_backward_workspace_bytes(ctx.rows) + 256, zeroed=True)
                 code = lib.mpf_res_ln256_backward_ws(*args, dgb[0].data_ptr(), dgb[1].data_ptr(), ctx.rows, ws.data_ptr() + 256,
-                                                     ws.numel() - 256, _stream(s))
+                                                     ws.numel() - 256, stream)
         _lib.check(code, "mpf_res_ln256_backward")
         dt = None
         if need_t:
@@ -114,21 +116,17 @@ def ln256_backward(s, mean, rstd, gamma, gy, gy_plus=None, ds_amax=None):
     ds = torch.empty_like(s)
     dgb = torch.empty((2, 256), dtype=torch.float32, device=s.device)
     lib = _lib.lib()
-    nbytes = lib.mpf_res_ln256_backward_workspace_bytes(s.shape[0])
-    wkey = (s.device, _lib.ws_scope())          # (a graph capture has its own buffers: _lib.workspace_scope)
-    ws = _ln_ws.get(wkey)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=s.device)
-        _ln_ws[wkey] = ws
+    stream = _stream(s)
+    ws = _lib.scratch("ln_bwd", s.device, stream, lib.mpf_res_ln256_backward_workspace_bytes(s.shape[0]))
     with _lib.device_guard(s.device):
         # parameter gradients through per-workgroup partials, fixed order (no atomics, no zero-fill)
         args = (s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), gy.data_ptr(), None,
                 gy_plus.data_ptr() if gy_plus is not None else None, ds.data_ptr(), None, dgb[0].data_ptr(), dgb[1].data_ptr(),
                 s.shape[0], ws.data_ptr(), ws.numel())
         if ds_amax is not None:
-            code = lib.mpf_res_ln256_backward_ws_amax(*args, ds_amax.data_ptr(), _stream(s))
+            code = lib.mpf_res_ln256_backward_ws_amax(*args, ds_amax.data_ptr(), stream)
         else:
-            code = lib.mpf_res_ln256_backward_ws(*args, _stream(s))
+            code = lib.mpf_res_ln256_backward_ws(*args, stream)
     _lib.check(code, "mpf_res_ln256_backward_ws")
     return ds, dgb[0], dgb[1]
 
@@ -163,18 +161,3 @@ class LnGradGroup:
             code = _lib.lib().mpf_ln_partial_reduce(self.parts.data_ptr(), self.stride, self.rows, self.used, out.data_ptr(), _stream(out))
         _lib.check(code, "mpf_ln_partial_reduce")
         return out
-
-
-_ln_ws = {}
-_det_ws_cache = {}
-
-
-def _det_ws(dev, nbytes):
-    """workspace of mpf_res_ln256_backward_det per (device, stream): its ticket word is zero between calls (zero-initialised
-    here, reset by every launch), so it is shared by all LayerNorms that run on that stream"""
-    key = (dev, _lib.stream_ptr(dev), _lib.ws_scope())
-    ws = _det_ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.zeros(int(nbytes) + 4096, dtype=torch.uint8, device=dev)
-        _det_ws_cache[key] = ws
-    return ws

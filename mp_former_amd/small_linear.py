@@ -119,15 +119,6 @@ def small_linear(x, w, b=None, relu=False):
 # gradient dW = dY^T x — a 256x256 output contracted over thousands of rows, 57-66 us in the library plus a separate bias
 # reduction — on the split-over-rows MFMA kernel of gemm3.hip in its one-product bf16 form (mpf_gemm_nt_bf16), bias gradient
 # included.
-_nt_ws = {}
-
-
-def _nt_workspace(device, nbytes):
-    w = _nt_ws.get(device)
-    if w is None or w.numel() < nbytes:
-        w = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _nt_ws[device] = w
-    return w
 
 
 def gemm_nt_bf16(a, b, want_csum=True):
@@ -137,12 +128,13 @@ def gemm_nt_bf16(a, b, want_csum=True):
     N = b.shape[1]
     rps = pick_rows_per_split(R, ((M + 127) // 128) * ((N + 127) // 128))
     lib = _lib.lib()
-    ws = _nt_workspace(a.device, lib.mpf_gemm_nt_bf16_workspace_bytes(R, M, N, rps))
+    stream = _stream(a)
+    ws = _lib.scratch("nt_bf16", a.device, stream, lib.mpf_gemm_nt_bf16_workspace_bytes(R, M, N, rps))
     c = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     cs = torch.empty((M,), dtype=torch.bfloat16, device=a.device) if want_csum else None
     with _lib.device_guard(a.device):
         code = lib.mpf_gemm_nt_bf16(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), c.data_ptr(),
-                                    cs.data_ptr() if want_csum else None, R, M, N, rps, ws.data_ptr(), ws.numel(), _stream(a))
+                                    cs.data_ptr() if want_csum else None, R, M, N, rps, ws.data_ptr(), ws.numel(), stream)
     _lib.check(code, "mpf_gemm_nt_bf16")
     return c, cs
 

@@ -274,18 +274,12 @@ def mask_product(me, mask_features):
     return torch.einsum("bqc,bchw->bqhw", me, mask_features)
 
 
-_mask_flags = {}
-
-
 class MpfNextMask(ctypes.Structure):
     """include/mpformer_hip.h MpfNextMask"""
     _fields_ = [(n, ctypes.c_void_p) for n in ("x", "ln_gamma", "ln_beta", "w0", "b0", "w1", "b1", "w2", "b2", "pooled", "mp_rows",
                                                 "out", "flags", "scratch")] + \
                [("scratch_bytes", ctypes.c_size_t), ("N", ctypes.c_int), ("Q", ctypes.c_int), ("HW", ctypes.c_int),
                 ("pad", ctypes.c_int), ("eps", ctypes.c_float)]
-
-
-_next_mask_scratch = {}
 
 
 def next_attn_mask_native(x, norm, mlp, pooled, mp_rows=None):
@@ -298,15 +292,10 @@ def next_attn_mask_native(x, norm, mlp, pooled, mp_rows=None):
     pad = 0 if mp_rows is None else mp_rows.shape[1]
     if pad:
         mp_rows = mp_rows.contiguous()
-    flags = _mask_flags.get((dev, N * Q))
-    if flags is None:
-        flags = torch.zeros(N * Q, dtype=torch.int32, device=dev)          # zero on entry, zeroed again by the kernel
-        _mask_flags[(dev, N * Q)] = flags
     lib = _lib.lib()
-    key = (dev, N, Q)
-    sc = _next_mask_scratch.get(key)
-    if sc is None:
-        sc = _next_mask_scratch[key] = torch.empty(lib.mpf_next_attn_mask_scratch_bytes(N, Q), dtype=torch.uint8, device=dev)
+    stream = _lib.stream_ptr(dev)
+    flags = _lib.scratch("next_mask_flags", dev, stream, 4 * N * Q, zeroed=True)       # zero on entry, zeroed again by the kernel
+    sc = _lib.scratch("next_mask", dev, stream, lib.mpf_next_attn_mask_scratch_bytes(N, Q))
     out = torch.empty((N, Q, HW), dtype=torch.bool, device=dev)
     m = MpfNextMask()
     m.x, m.ln_gamma, m.ln_beta, m.eps = x.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps)
@@ -316,7 +305,7 @@ def next_attn_mask_native(x, norm, mlp, pooled, mp_rows=None):
     m.scratch, m.scratch_bytes = sc.data_ptr(), sc.numel()
     m.N, m.Q, m.HW, m.pad = N, Q, HW, pad
     with _lib.device_guard(dev):
-        code = lib.mpf_next_attn_mask(ctypes.byref(m), _lib.stream_ptr(dev))
+        code = lib.mpf_next_attn_mask(ctypes.byref(m), stream)
     _lib.check(code, "mpf_next_attn_mask")
     return out
 
@@ -332,15 +321,13 @@ def mask_head_bits(mask_embed, pooled, mp_rows=None):
     if pad:
         mp_rows = mp_rows.contiguous()
     dev = mask_embed.device
-    flags = _mask_flags.get((dev, N * Q))
-    if flags is None:
-        flags = torch.zeros(N * Q, dtype=torch.int32, device=dev)          # zero on entry, zeroed again by the kernel
-        _mask_flags[(dev, N * Q)] = flags
+    stream = _lib.stream_ptr(dev)
+    flags = _lib.scratch("next_mask_flags", dev, stream, 4 * N * Q, zeroed=True)       # zero on entry, zeroed again by the kernel
     out = torch.empty((N, Q, HW), dtype=torch.bool, device=dev)
     with _lib.device_guard(dev):
         code = _lib.lib().mpf_mask_head_bits(mask_embed.data_ptr(), mask_embed.stride(1), mask_embed.stride(0), pooled.data_ptr(),
                                              mp_rows.data_ptr() if pad else None, pad, out.data_ptr(), flags.data_ptr(), N, Q, HW,
-                                             _lib.stream_ptr(dev))
+                                             stream)
     _lib.check(code, "mpf_mask_head_bits")
     return out
 

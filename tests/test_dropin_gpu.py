@@ -219,3 +219,41 @@ def test_device_geometry_full_size_config_B_properties():
     assert _lib.lib().mpf_msda_dev_geometry(msda_mod._workspace(dev, need).data_ptr(), rec, 10) == 0
     assert rec[0] == 1 and rec[1] == 1
     assert rec[2] == N * M * (256 + 64 + 16) and rec[3] == N * M * 448, list(rec)
+
+
+def test_device_geometry_record_survives_the_host_shapes_backward():
+    """The *_dev routes keep their geometry record (bytes 0..556) and its key (from byte 768) at the head of their workspace; the
+    host-shapes backward lays its tile counters out from byte 0.  At N = 1, M = 8, one 8 x 8 level, Lq = 64 it zeroes bytes
+    0..132 (32 counters + the spill count) and writes entry runs from byte 256: a shared buffer would keep the key of a record it
+    had overwritten.  With one buffer per layout and stream, a dev call after a host-shapes backward reproduces the first one."""
+    import ctypes
+    from mp_former_amd import _lib, ms_deform_attn_backward, ms_deform_attn_forward
+    from mp_former_amd import msda as msda_mod
+    dev = torch.device("cuda:0")
+    lv = [(8, 8)]
+    value, shapes, lsi, loc, attn, go = _problem(lv, 1, 64, 13)
+    dv = [t.to(dev) for t in (value, shapes, lsi, loc, attn, go)]
+    o1 = ms_deform_attn_forward(dv[0], dv[1], dv[2], dv[3], dv[4], 128)
+    assert _lib.last_kernel() == "msda_fwd_block_kernel<dev>", _lib.last_kernel()
+    g1 = ms_deform_attn_backward(dv[0], dv[1], dv[2], dv[3], dv[4], dv[5], 128)
+    assert _lib.last_kernel() == "msda_bwd_block(bin+tile)<dev>", _lib.last_kernel()
+    hs = msda_mod.attach_host_shapes(dv[1].clone(), lv, dv[2])
+    ms_deform_attn_backward(dv[0], hs, dv[2], dv[3], dv[4], dv[5], 128)
+    assert _lib.last_kernel() == "msda_bwd_block(bin+tile)", _lib.last_kernel()
+    o2 = ms_deform_attn_forward(dv[0], dv[1], dv[2], dv[3], dv[4], 128)
+    g2 = ms_deform_attn_backward(dv[0], dv[1], dv[2], dv[3], dv[4], dv[5], 128)
+    assert torch.equal(o1, o2) and torch.equal(g1[1], g2[1]) and torch.equal(g1[2], g2[2])
+    torch.testing.assert_close(g1[0], g2[0], rtol=1e-5, atol=1e-5)
+    rec = (ctypes.c_int * 10)()
+    assert _lib.lib().mpf_msda_dev_geometry(msda_mod._workspace(dev).data_ptr(), rec, 10) == 0 and rec[0] == 1
+    stream = _lib.stream_ptr(dev)
+    assert _lib.scratch("msda_dev", dev, stream, 0).data_ptr() != _lib.scratch("msda_host", dev, stream, 0).data_ptr()
+    # an op on another stream gets its own buffer
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        o3 = ms_deform_attn_forward(dv[0], dv[1], dv[2], dv[3], dv[4], 128)
+        side_ws = msda_mod._workspace(dev).data_ptr()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    assert side_ws != msda_mod._workspace(dev).data_ptr()
+    assert torch.equal(o1, o3)

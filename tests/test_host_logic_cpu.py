@@ -334,3 +334,22 @@ def test_encoder_arena_layout_is_aligned_and_disjoint():
         for (o, n), (o2, _) in zip(spans, spans[1:] + [(tot, 0)]):
             assert o % 4 == 0 and o + n <= o2
         assert offs["hbits"][1] * 32 >= R * F and offs["loc"][1] == R * M * L * P * 2 and offs["x2"][1] == R * 256
+
+
+def test_scratch_is_one_buffer_per_owner_device_and_stream():
+    """_lib.scratch: grows on demand, serves a smaller later request from the same buffer, keeps owners and streams apart, and a
+    zeroed owner's buffer starts zero again when it grows, whatever the old buffer held."""
+    from mp_former_amd import _lib
+    cpu = torch.device("cpu")
+    a = _lib.scratch("test_a", cpu, 0, 100)
+    assert a.dtype == torch.uint8 and a.numel() >= 100
+    big = _lib.scratch("test_a", cpu, 0, a.numel() + 1)
+    assert big.numel() > a.numel()
+    assert _lib.scratch("test_a", cpu, 0, 10).data_ptr() == big.data_ptr()
+    assert _lib.scratch("test_b", cpu, 0, 10).data_ptr() != big.data_ptr()
+    assert _lib.scratch("test_a", cpu, 1, 10).data_ptr() != big.data_ptr()
+    z = _lib.scratch("test_z", cpu, 0, 64, zeroed=True)
+    assert not z.any()
+    z.fill_(7)
+    z2 = _lib.scratch("test_z", cpu, 0, z.numel() + 1, zeroed=True)
+    assert z2.numel() > z.numel() and not z2.any()
