@@ -1174,6 +1174,44 @@ typedef struct MpfEncoderBwdCall {
 int mpf_encoder_bwd_fields(void);
 int mpf_encoder_backward(const MpfEncoderBwdCall* call, void* stream);
 
+/*
+ * Inference post-processing (csrc/seg_infer.hip): the eval branch of MaskFormer.forward
+ * (mask2former/maskformer_model.py:236-279) and its semantic / panoptic / instance inference (:301-401), per image,
+ * straight from the low-resolution mask logits.  Replaces F.interpolate to the padded size (:241-246), detectron2's
+ * sem_seg_postprocess (crop + resize, :260-262 / :268), the sigmoid / threshold / einsum passes over [Q, H, W], and the
+ * per-query .item() syncs of panoptic_inference (:333-340).  Every output pixel is computed from the 4 x 4 logits behind
+ * it (both bilinear resamples composed, torch's align_corners=False index rule); [Q, Hp, Wp] is never formed.
+ *
+ * Mask logits: query q's contiguous [h, w] plane at masks + q * stride_q elements, dtype MPF_F32 or MPF_BF16 (a slice of
+ * the decoder's [N, L*Q, h, w] output is accepted as is).  Geometry: low-res (h, w) -> padded batch (Hp, Wp), crop to the
+ * image (hi, wi) <= (Hp, Wp), resampled to the output (H, W).  Output (H, W) == (hi, wi) gives the cropped padded grid.
+ *   mpf_seg_softmax:          cls fp32 [Q, K1] (K1 = K + 1) -> probs [Q, K] (softmax without the no-object column),
+ *                             max_score / max_label [Q] (torch max(-1)), kept int32 [1 + 2Q] = {count, query[Q], label[Q]}
+ *                             of the panoptic keep rule (label != K and score > threshold, :310), kept_score [Q].  Q <= 1024.
+ *   mpf_seg_semantic:         out fp32 [K, H, W] = sum_q probs[q, c] * sigmoid(m_q) (:302-306).
+ *   mpf_seg_instance_scores:  scores[t] = cls_score[t] * sum sigmoid(m)[m > 0] / (sum [m > 0] + 1e-6) for the selected
+ *                             queries sel_q int64 [T] (:394-396); fixed-order reduction, bitwise deterministic.  workspace of
+ *                             mpf_seg_instance_workspace_bytes(T, H, W) bytes.
+ *   mpf_seg_instance_masks:   masks_out fp32 [T, H, W] = (m_{sel_q[t]} > 0) (:388).
+ *   mpf_seg_panoptic_areas:   code int32 [H, W] = 2 * winner + (sigmoid >= 0.5) over the kept list (argmax of
+ *                             kept_score * sigmoid, first index on ties, :329); areas int32 [3][Q] = mask_area,
+ *                             original_area, intersection per kept entry (:333-336), zeroed by the call.
+ *   mpf_seg_panoptic_paint:   out int32 [H, W] = lut[winner] where the bit is set, else 0 (:342-360, lut built on the host).
+ */
+int mpf_seg_softmax(const float* cls, int Q, int K1, float object_mask_threshold, float* probs, float* max_score, int* max_label,
+                    int* kept, float* kept_score, void* stream);
+int mpf_seg_semantic(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H, int W,
+                     const float* probs, int K, float* out, void* stream);
+size_t mpf_seg_instance_workspace_bytes(int T, int H, int W);
+int mpf_seg_instance_scores(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                            int W, const int64_t* sel_q, const float* cls_score, int T, float* scores, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int mpf_seg_instance_masks(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                           int W, const int64_t* sel_q, int T, float* masks_out, void* stream);
+int mpf_seg_panoptic_areas(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                           int W, const int* kept, const float* kept_score, int* code, int* areas, void* stream);
+int mpf_seg_panoptic_paint(const int* code, int H, int W, const int* lut, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

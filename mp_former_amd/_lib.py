@@ -180,6 +180,14 @@ SIGNATURES = {
     "mpf_msda_backward_ws_raw_o": (_c_int, [_c_vp] * 8 + [_c_int] * 8 + [_c_vp, ctypes.c_size_t, _c_vp, _c_vp, _c_vp]),
     "mpf_msda_backward_workspace_bytes": (ctypes.c_size_t, [_c_int] * 5 + [_c_vp]),
     "mpf_msda_backward_ws": (_c_int, [_c_vp] * 8 + [_c_int] * 8 + [_c_vp, ctypes.c_size_t, _c_vp]),
+    "mpf_seg_softmax": (_c_int, [_c_vp, _c_int, _c_int, ctypes.c_float] + [_c_vp] * 6),
+    "mpf_seg_semantic": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_instance_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "mpf_seg_instance_scores": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_vp, _c_int, _c_vp, _c_vp, ctypes.c_size_t,
+                                                                                   _c_vp]),
+    "mpf_seg_instance_masks": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_panoptic_areas": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp] * 5),
+    "mpf_seg_panoptic_paint": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
 }
 
 

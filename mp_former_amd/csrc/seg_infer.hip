@@ -1,0 +1,524 @@
+// Inference post-processing of the mask predictions for MI355X: semantic, instance and panoptic results straight from the
+// low-resolution mask logits.
+//
+// Reference (mask2former/maskformer_model.py:236-279 and the three *_inference functions, :301-401): the eval branch
+//     masks = F.interpolate(pred_masks, (Hp, Wp), bilinear)                    fp32 [Q, Hp, Wp]   (~390 MB per COCO image)
+//     masks = sem_seg_postprocess(masks, (hi, wi), H, W)   = crop + bilinear   fp32 [Q, H, W]
+//     then sigmoid / "> 0" / products over whole [Q, H, W] tensors, and four .item() syncs per kept query (panoptic).
+// Here every output pixel is computed from the 4 x 4 low-resolution neighbourhood behind its 2 x 2 intermediate pixels
+// (both resamples composed, torch's upsample_bilinear2d index rule and weight order at each stage), so each kernel reads
+// the [Q, h, w] logits once and writes only its final result.  The [Q, Hp, Wp] and [Q, H, W] intermediates never exist.
+//
+//   seg_softmax_kernel      softmax of the [Q, K+1] class logits -> probs [Q, K] (no-object column dropped) and the
+//                           panoptic keep list (label != K and score > threshold), compacted in query order.
+//   seg_semantic_kernel     sem_seg[c, p] = sum_q probs[q, c] * sigmoid(m_q(p)), fp32: a tile of 128 pixels x <= 192
+//                           classes per workgroup, the sigmoids of 32 queries at a time staged in LDS.
+//   seg_instance_kernel     per (selected entry, 1024-pixel tile): either the partial sums of sigmoid(m) * [m > 0] and
+//                           [m > 0] (workspace, no atomics) or the 0/1 mask of the entry.
+//   seg_instance_reduce     the partials of one entry summed in a fixed order: bitwise deterministic scores.
+//   seg_panoptic_kernel     per pixel: the winning kept query (first index on ties), its sigmoid >= 0.5 bit, and the three
+//                           integer areas per kept query (LDS histogram, then integer global atomics: order-independent).
+//   seg_paint_kernel        int32 id map from the winner code and the host's segment lookup table.
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "mpf_common.h"
+
+namespace {
+
+constexpr int kT = 256;            // threads per workgroup, every kernel
+constexpr int kSemPix = 128;       // semantic: output pixels per workgroup
+constexpr int kSemQ = 32;          // semantic: queries staged per LDS round
+constexpr int kInstPix = 1024;     // instance: output pixels per workgroup
+constexpr int kMaxQ = 1024;        // panoptic LDS histogram bound
+
+__device__ __forceinline__ float ldm(const float* p, int64_t i) { return p[i]; }
+__device__ __forceinline__ float ldm(const __hip_bfloat16* p, int64_t i) { return __bfloat162float(p[i]); }
+
+// torch upsample_bilinear2d, align_corners=False, no explicit scale: scale = in / out in fp32,
+// src = max(scale * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1.
+// (__fmul_rn / __fadd_rn: no contraction into an FMA, the same roundings as the reference's separate operations)
+struct Tap {
+    int i0, i1;
+    float l0, l1;
+};
+__device__ __forceinline__ Tap tap(int dst, int in, int out)
+{
+    const float scale = (float)in / (float)out;
+    float src = __fsub_rn(__fmul_rn(scale, __fadd_rn((float)dst, 0.5f)), 0.5f);
+    src = src < 0.f ? 0.f : src;
+    Tap t;
+    t.i0 = (int)src;
+    t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
+    t.l1 = __fsub_rn(src, (float)t.i0);
+    t.l0 = __fsub_rn(1.f, t.l1);
+    return t;
+}
+
+// The composed geometry of one output pixel: stage 2 (crop [hi, wi] of the padded grid -> [H, W]) picks 2 x 2 intermediate
+// pixels, stage 1 ([h, w] -> [Hp, Wp]) resamples each of them from a 2 x 2 low-resolution neighbourhood.
+struct PixGeom {
+    int64_t off[2][2][4];          // [intermediate row a][intermediate col b][low-res tap r*2+c]
+    float w1[2][2][4];
+    float w2y[2], w2x[2];
+};
+__device__ __forceinline__ void pix_geom(PixGeom& g, int y, int x, int h, int w, int Hp, int Wp, int hi, int wi, int H, int W)
+{
+    const Tap ty = tap(y, hi, H), tx = tap(x, wi, W);
+    g.w2y[0] = ty.l0; g.w2y[1] = ty.l1;
+    g.w2x[0] = tx.l0; g.w2x[1] = tx.l1;
+    const int ya[2] = {ty.i0, ty.i1}, xa[2] = {tx.i0, tx.i1};
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const Tap sy = tap(ya[a], h, Hp);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const Tap sx = tap(xa[b], w, Wp);
+            g.off[a][b][0] = (int64_t)sy.i0 * w + sx.i0;
+            g.off[a][b][1] = (int64_t)sy.i0 * w + sx.i1;
+            g.off[a][b][2] = (int64_t)sy.i1 * w + sx.i0;
+            g.off[a][b][3] = (int64_t)sy.i1 * w + sx.i1;
+            g.w1[a][b][0] = sy.l0; g.w1[a][b][1] = sy.l1;    // row weights (h0lambda, h1lambda)
+            g.w1[a][b][2] = sx.l0; g.w1[a][b][3] = sx.l1;    // column weights (w0lambda, w1lambda)
+        }
+    }
+}
+
+// torch's weight order at each stage: h0l * (w0l * x00 + w1l * x01) + h1l * (w0l * x10 + w1l * x11)
+__device__ __forceinline__ float lerp2(float h0, float h1, float w0, float w1, float x00, float x01, float x10, float x11)
+{
+    return __fadd_rn(__fmul_rn(h0, __fadd_rn(__fmul_rn(w0, x00), __fmul_rn(w1, x01))),
+                     __fmul_rn(h1, __fadd_rn(__fmul_rn(w0, x10), __fmul_rn(w1, x11))));
+}
+
+template <typename T>
+__device__ __forceinline__ float resample(const T* m, const PixGeom& g)
+{
+    float v[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const float* wt = g.w1[a][b];
+            v[a][b] = lerp2(wt[0], wt[1], wt[2], wt[3], ldm(m, g.off[a][b][0]), ldm(m, g.off[a][b][1]), ldm(m, g.off[a][b][2]),
+                            ldm(m, g.off[a][b][3]));
+        }
+    return lerp2(g.w2y[0], g.w2y[1], g.w2x[0], g.w2x[1], v[0][0], v[0][1], v[1][0], v[1][1]);
+}
+
+__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ----------------------------------------------------------------------------------------------------------------
+// class softmax + panoptic keep list; one workgroup, one wave per query row
+// kept: [0] count, [1 .. Q] query of kept entry n, [1+Q .. 2Q] its label; kept_score [Q]
+// ----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kT) void seg_softmax_kernel(const float* __restrict__ cls, int Q, int K1, float thr,
+                                                         float* __restrict__ probs, float* __restrict__ max_score,
+                                                         int* __restrict__ max_label, int* __restrict__ kept,
+                                                         float* __restrict__ kept_score)
+{
+    __shared__ float s_score[kMaxQ];
+    __shared__ int s_label[kMaxQ];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = K1 - 1;
+    for (int q = wave; q < Q; q += kT / 64) {
+        const float* row = cls + (int64_t)q * K1;
+        float mx = -INFINITY;
+        for (int c = lane; c < K1; c += 64) mx = fmaxf(mx, row[c]);
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        float s = 0.f;
+        for (int c = lane; c < K1; c += 64) s += expf(row[c] - mx);
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        // max over the K+1 probabilities, first index on ties (torch max(-1))
+        float best = -1.f;
+        int bi = 0;
+        for (int c = lane; c < K1; c += 64) {
+            const float p = expf(row[c] - mx) / s;
+            if (c < K) probs[(int64_t)q * K + c] = p;
+            if (p > best) { best = p; bi = c; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        if (lane == 0) {
+            max_score[q] = s_score[q] = best;
+            max_label[q] = s_label[q] = bi;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {           // Q <= 1024: a serial compaction in query order, from LDS
+        int n = 0;
+        for (int q = 0; q < Q; ++q) {
+            const int lab = s_label[q];
+            const float sc = s_score[q];
+            if (lab != K && sc > thr) {
+                kept[1 + n] = q;
+                kept[1 + Q + n] = lab;
+                kept_score[n] = sc;
+                ++n;
+            }
+        }
+        kept[0] = n;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// semantic: out[c, p] = sum_q probs[q, c] * sigmoid(m_q(p)) for a tile of kSemPix pixels and 8 * CPT classes
+// thread (pg = tid & 31, cg = tid >> 5): pixels pg*4 .. +3, classes cbase + cg*CPT .. +CPT-1
+// ----------------------------------------------------------------------------------------------------------------
+template <typename T, int CPT>
+__global__ __launch_bounds__(kT) void seg_semantic_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
+                                                          int Wp, int hi, int wi, int H, int W, const float* __restrict__ probs, int K,
+                                                          float* __restrict__ out)
+{
+    constexpr int KC = 8 * CPT;
+    __shared__ float4 sig4[kSemQ][kSemPix / 4];
+    __shared__ float4 pr4[kSemQ][KC / 4];
+    const int tid = threadIdx.x;
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p0 = (int64_t)blockIdx.x * kSemPix;
+    const int cbase = blockIdx.y * KC;
+    // geometry of the staging pixel of this thread (pixel tid & 127, queries tid >> 7 + 2 i)
+    const int sp = tid & (kSemPix - 1), sq = tid >> 7;
+    const int64_t pix = p0 + sp;
+    const bool live = pix < HW;
+    PixGeom g;
+    pix_geom(g, live ? (int)(pix / W) : 0, live ? (int)(pix % W) : 0, h, w, Hp, Wp, hi, wi, H, W);
+    float* sig = (float*)sig4;
+    float* pr = (float*)pr4;
+    const int pg = tid & 31, cg = tid >> 5;
+    float acc[CPT][4];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+    for (int q0 = 0; q0 < Q; q0 += kSemQ) {
+        const int nq = min(kSemQ, Q - q0);
+        __syncthreads();
+        for (int i = sq; i < kSemQ; i += kT / kSemPix) {
+            float s = 0.f;                                     // padding queries contribute 0 (their probs are 0 too)
+            if (i < nq && live) s = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
+            sig[i * kSemPix + sp] = s;
+        }
+        for (int e = tid; e < kSemQ * KC; e += kT) {
+            const int i = e / KC, c = e % KC;
+            pr[e] = (i < nq && cbase + c < K) ? probs[(int64_t)(q0 + i) * K + cbase + c] : 0.f;
+        }
+        __syncthreads();
+        for (int i = 0; i < nq; ++i) {
+            const float4 s = sig4[i][pg];
+#pragma unroll
+            for (int j4 = 0; j4 < CPT / 4; ++j4) {
+                const float4 pv = pr4[i][cg * (CPT / 4) + j4];
+                const float pj[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    float* a = acc[j4 * 4 + u];
+                    a[0] = fmaf(pj[u], s.x, a[0]);
+                    a[1] = fmaf(pj[u], s.y, a[1]);
+                    a[2] = fmaf(pj[u], s.z, a[2]);
+                    a[3] = fmaf(pj[u], s.w, a[3]);
+                }
+            }
+        }
+    }
+    const int64_t px = p0 + pg * 4;
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+        const int c = cbase + cg * CPT + j;
+        if (c >= K) break;
+        float* o = out + (int64_t)c * HW + px;
+        if (px + 3 < HW && ((HW & 3) == 0)) {
+            *(float4*)o = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (px + i < HW) o[i] = acc[j][i];
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// instance: entry t = blockIdx.y (query sel_q[t]), pixels blockIdx.x * kInstPix + tid + kT * i
+//   masks_out == NULL: partial[t][tile] = {sum sigmoid(m) * [m > 0], count [m > 0]}
+//   else:              masks_out[t][p] = m > 0 ? 1 : 0
+// ----------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kT) void seg_instance_kernel(const T* __restrict__ masks, int64_t stride_q, int h, int w, int Hp, int Wp,
+                                                          int hi, int wi, int H, int W, const int64_t* __restrict__ sel_q,
+                                                          float* __restrict__ masks_out, float2* __restrict__ partial)
+{
+    const int t = blockIdx.y;
+    const int64_t HW = (int64_t)H * W;
+    const T* m = masks + sel_q[t] * stride_q;
+    float s = 0.f, n = 0.f;
+#pragma unroll
+    for (int i = 0; i < kInstPix / kT; ++i) {
+        const int64_t p = (int64_t)blockIdx.x * kInstPix + threadIdx.x + kT * i;
+        if (p >= HW) break;
+        PixGeom g;
+        pix_geom(g, (int)(p / W), (int)(p % W), h, w, Hp, Wp, hi, wi, H, W);
+        const float v = resample(m, g);
+        const bool on = v > 0.f;
+        if (masks_out) {
+            masks_out[t * HW + p] = on ? 1.f : 0.f;
+        } else if (on) {
+            s += sigm(v);
+            n += 1.f;
+        }
+    }
+    if (masks_out) return;
+    // fixed-order workgroup reduction: wave shuffles, then wave 0 over the 4 wave sums
+    __shared__ float ws[2][kT / 64];
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        n += __shfl_xor(n, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { ws[0][wave] = s; ws[1][wave] = n; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a = 0.f, b = 0.f;
+        for (int i = 0; i < kT / 64; ++i) { a += ws[0][i]; b += ws[1][i]; }
+        partial[(int64_t)t * gridDim.x + blockIdx.x] = make_float2(a, b);
+    }
+}
+
+// one wave per entry: lane l sums tiles l, l + 64, ... in order, then a fixed shuffle tree (no atomics: bitwise deterministic);
+// scores[t] = cls_score[t] * sum / (count + 1e-6)
+__global__ __launch_bounds__(kT) void seg_instance_reduce_kernel(const float2* __restrict__ partial, int tiles, int T,
+                                                                 const float* __restrict__ cls_score, float* __restrict__ scores)
+{
+    const int t = blockIdx.x * (kT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= T) return;                                    // whole waves leave together
+    float a = 0.f, b = 0.f;
+    for (int i = lane; i < tiles; i += 64) {
+        const float2 v = partial[(int64_t)t * tiles + i];
+        a += v.x;
+        b += v.y;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o);
+        b += __shfl_xor(b, o);
+    }
+    if (lane == 0) scores[t] = cls_score[t] * (a / (b + 1e-6f));
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// panoptic kernel 1: one thread per pixel over the kept list (count read from the device)
+//   code[p] = 2 * winner + (sigmoid(m_winner) >= 0.5);  areas [3][Q]: mask_area, original_area, intersection
+// ----------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kT) void seg_panoptic_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
+                                                          int Wp, int hi, int wi, int H, int W, const int* __restrict__ kept,
+                                                          const float* __restrict__ kept_score, int* __restrict__ code,
+                                                          int* __restrict__ areas)
+{
+    __shared__ int hist[3][kMaxQ];
+    __shared__ int kq[kMaxQ];
+    __shared__ float ks[kMaxQ];
+    const int count = kept[0];
+    for (int i = threadIdx.x; i < count; i += kT) {
+        hist[0][i] = hist[1][i] = hist[2][i] = 0;
+        kq[i] = kept[1 + i];
+        ks[i] = kept_score[i];
+    }
+    __syncthreads();
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (p < HW) {
+        PixGeom g;
+        pix_geom(g, (int)(p / W), (int)(p % W), h, w, Hp, Wp, hi, wi, H, W);
+        float best = -1.f;
+        int win = 0, bit = 0;
+        for (int n = 0; n < count; ++n) {
+            const float sg = sigm(resample(masks + (int64_t)kq[n] * stride_q, g));
+            const float pr = ks[n] * sg;
+            const int on = sg >= 0.5f;
+            const unsigned long long b = __ballot(on);         // n is wave-uniform: one LDS atomic per wave, not per lane
+            if ((threadIdx.x & 63) == 0 && b) atomicAdd(&hist[1][n], __popcll(b));
+            if (pr > best) { best = pr; win = n; bit = on; }
+        }
+        if (count > 0) {
+            atomicAdd(&hist[0][win], 1);
+            if (bit) atomicAdd(&hist[2][win], 1);
+        }
+        code[p] = 2 * win + bit;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < count; i += kT)
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            if (hist[a][i]) atomicAdd(&areas[a * Q + i], hist[a][i]);
+}
+
+// kernel 2: id map; lut[n] = segment id of kept entry n (0 = dropped)
+__global__ __launch_bounds__(kT) void seg_paint_kernel(const int* __restrict__ code, int64_t HW, const int* __restrict__ lut,
+                                                       int* __restrict__ out)
+{
+    const int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (p >= HW) return;
+    const int c = code[p];
+    out[p] = (c & 1) ? lut[c >> 1] : 0;
+}
+
+// shared argument checks of the per-pixel entry points
+int check_geom(const char* who, const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
+               int H, int W)
+{
+    static thread_local char msg[160];
+    if (!masks) { snprintf(msg, sizeof msg, "%s: NULL mask logits", who); return mpf::fail(MPF_E_NULL, msg); }
+    if (dtype != MPF_F32 && dtype != MPF_BF16) { snprintf(msg, sizeof msg, "%s: mask logits must be f32 or bf16 (dtype)", who); return mpf::fail(MPF_E_DTYPE, msg); }
+    if (Q <= 0 || h <= 0 || w <= 0 || Hp <= 0 || Wp <= 0 || hi <= 0 || wi <= 0 || H <= 0 || W <= 0 || hi > Hp || wi > Wp ||
+        stride_q < (int64_t)h * w) {
+        snprintf(msg, sizeof msg, "%s: bad sizes (Q %d, low-res %dx%d, padded %dx%d, image %dx%d, output %dx%d, stride_q %lld)", who, Q, h,
+                 w, Hp, Wp, hi, wi, H, W, (long long)stride_q);
+        return mpf::fail(MPF_E_SHAPE, msg);
+    }
+    if ((int64_t)H * W >= (1ll << 31) || (int64_t)Q * stride_q >= (1ll << 40)) {
+        snprintf(msg, sizeof msg, "%s: output too large", who);
+        return mpf::fail(MPF_E_TOO_LARGE, msg);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mpf_seg_softmax(const float* cls, int Q, int K1, float object_mask_threshold, float* probs, float* max_score,
+                               int* max_label, int* kept, float* kept_score, void* stream)
+{
+    if (!cls || !probs || !max_score || !max_label || !kept || !kept_score) return mpf::fail(MPF_E_NULL, "seg_softmax: NULL buffer");
+    if (Q <= 0 || Q > kMaxQ || K1 < 2) return mpf::fail(MPF_E_SHAPE, "seg_softmax: need 1 <= Q <= 1024 queries and K + 1 >= 2 columns");
+    hipStream_t st = (hipStream_t)stream;
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_softmax_kernel");
+    hipLaunchKernelGGL(seg_softmax_kernel, dim3(1), dim3(kT), 0, st, cls, Q, K1, object_mask_threshold, probs, max_score, max_label, kept,
+                       kept_score);
+    mpf::prof_end("seg_softmax_kernel", st, 8.0 * Q * K1);
+    return mpf::check(hipGetLastError(), "mpf_seg_softmax");
+}
+
+extern "C" int mpf_seg_semantic(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
+                                int H, int W, const float* probs, int K, float* out, void* stream)
+{
+    if (int e = check_geom("seg_semantic", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!probs || !out) return mpf::fail(MPF_E_NULL, "seg_semantic: NULL buffer");
+    if (K <= 0) return mpf::fail(MPF_E_SHAPE, "seg_semantic: K must be positive");
+    if ((int64_t)K * H * W >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "seg_semantic: output too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    const int cpt = K <= 32 ? 4 : K <= 64 ? 8 : K <= 96 ? 12 : 24;
+    const dim3 grid((unsigned)((HW + kSemPix - 1) / kSemPix), (unsigned)((K + 8 * cpt - 1) / (8 * cpt)));
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_semantic_kernel");
+#define MPF_SEM(T, C)                                                                                                                \
+    hipLaunchKernelGGL((seg_semantic_kernel<T, C>), grid, dim3(kT), 0, st, (const T*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H, W, \
+                       probs, K, out)
+#define MPF_SEM_T(T)                   \
+    do {                               \
+        if (cpt == 4) MPF_SEM(T, 4);   \
+        else if (cpt == 8) MPF_SEM(T, 8);   \
+        else if (cpt == 12) MPF_SEM(T, 12); \
+        else MPF_SEM(T, 24);           \
+    } while (0)
+    if (dtype == MPF_F32) MPF_SEM_T(float);
+    else MPF_SEM_T(__hip_bfloat16);
+#undef MPF_SEM_T
+#undef MPF_SEM
+    mpf::prof_end("seg_semantic_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * K * HW, 2.0 * K * Q * (double)HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_semantic");
+}
+
+extern "C" size_t mpf_seg_instance_workspace_bytes(int T, int H, int W)
+{
+    if (T <= 0 || H <= 0 || W <= 0) return 0;
+    const int64_t tiles = ((int64_t)H * W + kInstPix - 1) / kInstPix;
+    return (size_t)(T * tiles) * sizeof(float2);
+}
+
+extern "C" int mpf_seg_instance_scores(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi,
+                                       int wi, int H, int W, const int64_t* sel_q, const float* cls_score, int T, float* scores,
+                                       void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (int e = check_geom("seg_instance_scores", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!sel_q || !cls_score || !scores || !workspace) return mpf::fail(MPF_E_NULL, "seg_instance_scores: NULL buffer");
+    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_scores: need 1 <= T <= 65535 entries");
+    if (workspace_bytes < mpf_seg_instance_workspace_bytes(T, H, W)) return mpf::fail(MPF_E_SHAPE, "seg_instance_scores: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    const int tiles = (int)((HW + kInstPix - 1) / kInstPix);
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_instance_kernel+seg_instance_reduce_kernel");
+    if (dtype == MPF_F32)
+        hipLaunchKernelGGL(seg_instance_kernel<float>, dim3(tiles, T), dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi,
+                           H, W, sel_q, (float*)nullptr, (float2*)workspace);
+    else
+        hipLaunchKernelGGL(seg_instance_kernel<__hip_bfloat16>, dim3(tiles, T), dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h,
+                           w, Hp, Wp, hi, wi, H, W, sel_q, (float*)nullptr, (float2*)workspace);
+    hipLaunchKernelGGL(seg_instance_reduce_kernel, dim3((T + kT / 64 - 1) / (kT / 64)), dim3(kT), 0, st, (const float2*)workspace, tiles, T, cls_score,
+                       scores);
+    mpf::prof_end("seg_instance_scores", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + 8.0 * T * tiles);
+    return mpf::check(hipGetLastError(), "mpf_seg_instance_scores");
+}
+
+extern "C" int mpf_seg_instance_masks(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi,
+                                      int wi, int H, int W, const int64_t* sel_q, int T, float* masks_out, void* stream)
+{
+    if (int e = check_geom("seg_instance_masks", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!sel_q || !masks_out) return mpf::fail(MPF_E_NULL, "seg_instance_masks: NULL buffer");
+    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_masks: need 1 <= T <= 65535 entries");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    const int tiles = (int)((HW + kInstPix - 1) / kInstPix);
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_instance_kernel");
+    if (dtype == MPF_F32)
+        hipLaunchKernelGGL(seg_instance_kernel<float>, dim3(tiles, T), dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi,
+                           H, W, sel_q, masks_out, (float2*)nullptr);
+    else
+        hipLaunchKernelGGL(seg_instance_kernel<__hip_bfloat16>, dim3(tiles, T), dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h,
+                           w, Hp, Wp, hi, wi, H, W, sel_q, masks_out, (float2*)nullptr);
+    mpf::prof_end("seg_instance_kernel", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * T * HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_instance_masks");
+}
+
+extern "C" int mpf_seg_panoptic_areas(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi,
+                                      int wi, int H, int W, const int* kept, const float* kept_score, int* code, int* areas,
+                                      void* stream)
+{
+    if (int e = check_geom("seg_panoptic_areas", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!kept || !kept_score || !code || !areas) return mpf::fail(MPF_E_NULL, "seg_panoptic_areas: NULL buffer");
+    if (Q > kMaxQ) return mpf::fail(MPF_E_SHAPE, "seg_panoptic_areas: at most 1024 queries");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    if (int e = mpf::check(hipMemsetAsync(areas, 0, 3 * (size_t)Q * sizeof(int), st), "seg_panoptic_areas: memset")) return e;
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_panoptic_kernel");
+    const unsigned grid = (unsigned)((HW + kT - 1) / kT);
+    if (dtype == MPF_F32)
+        hipLaunchKernelGGL(seg_panoptic_kernel<float>, dim3(grid), dim3(kT), 0, st, (const float*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H,
+                           W, kept, kept_score, code, areas);
+    else
+        hipLaunchKernelGGL(seg_panoptic_kernel<__hip_bfloat16>, dim3(grid), dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, Q, h, w,
+                           Hp, Wp, hi, wi, H, W, kept, kept_score, code, areas);
+    mpf::prof_end("seg_panoptic_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_panoptic_areas");
+}
+
+extern "C" int mpf_seg_panoptic_paint(const int* code, int H, int W, const int* lut, int* out, void* stream)
+{
+    if (!code || !lut || !out) return mpf::fail(MPF_E_NULL, "seg_panoptic_paint: NULL buffer");
+    if (H <= 0 || W <= 0) return mpf::fail(MPF_E_SHAPE, "seg_panoptic_paint: bad sizes");
+    if ((int64_t)H * W >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "seg_panoptic_paint: output too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_paint_kernel");
+    hipLaunchKernelGGL(seg_paint_kernel, dim3((unsigned)((HW + kT - 1) / kT)), dim3(kT), 0, st, code, HW, lut, out);
+    mpf::prof_end("seg_paint_kernel", st, 8.0 * HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_panoptic_paint");
+}

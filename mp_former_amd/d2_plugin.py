@@ -101,3 +101,34 @@ def registered():
 
 
 register()
+
+
+def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None):
+    """The eval branch of a reference ``MaskFormer`` (mask2former/maskformer_model.py:199-203 + 233-279) with the native
+    post-processing (inference.postprocess) in place of its F.interpolate / sem_seg_postprocess / *_inference body."""
+    from .inference import postprocess
+    if image_list_cls is None:
+        from detectron2.structures import ImageList as image_list_cls
+    images = [x["image"].to(model.device) for x in batched_inputs]
+    images = [(x - model.pixel_mean) / model.pixel_std for x in images]
+    images = image_list_cls.from_tensors(images, model.size_divisibility)
+    outputs = model.sem_seg_head(model.backbone(images.tensor))
+    out_sizes = [(x.get("height", s[0]), x.get("width", s[1])) for x, s in zip(batched_inputs, images.image_sizes)]
+    return postprocess(outputs["pred_logits"], outputs["pred_masks"], images.image_sizes, tuple(images.tensor.shape[-2:]), out_sizes,
+                       cfg)
+
+
+def install_native_inference(model, image_list_cls=None):
+    """Route the eval branch of a reference ``MaskFormer`` instance through ``native_eval_forward``; training is unchanged.
+    Returns the inference.InferenceConfig read from the model."""
+    from .inference import InferenceConfig
+    cfg = InferenceConfig.from_maskformer(model)
+    train_forward = model.forward
+
+    def forward(batched_inputs):
+        if model.training:
+            return train_forward(batched_inputs)
+        return native_eval_forward(model, batched_inputs, cfg, image_list_cls)
+
+    model.forward = forward
+    return cfg

@@ -87,6 +87,16 @@ class MPFormerHead(nn.Module):
         wd = self.criterion.weight_dict
         return {k: v * wd[k] for k, v in losses.items() if k in wd}, outputs
 
+    @torch.no_grad()
+    def inference(self, features, image_sizes, padded_hw, output_sizes, cfg):
+        """The eval branch of MaskFormer.forward (maskformer_model.py:233-279): pixel decoder and predictor without targets
+        (dn_args=None: the learnable queries only), then the native post-processing (inference.postprocess) of the last
+        layer's predictions.  ``cfg``: inference.InferenceConfig."""
+        from .inference import postprocess
+        mask_features, _, multi_scale = self.pixel_decoder.forward_features(features)
+        outputs = self.predictor(multi_scale, mask_features, None, None)
+        return postprocess(outputs["pred_logits"], outputs["pred_masks"], image_sizes, padded_hw, output_sizes, cfg)
+
     def total_loss(self, features, targets):
         """Sum of the weighted losses without materialising the weighted dict (2 kernels instead of 120)."""
         mask_features, _, multi_scale = self.pixel_decoder.forward_features(features)
