@@ -170,8 +170,7 @@ class _Conv1x1Fn(Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .encoder_fused import _balanced_rps
-        from .gemm3 import gemm3, gemm3_ex, gemm3_nt, gemm3_nt_ex, nt_reduce
+        from .gemm3 import balanced_rps, gemm3, gemm3_ex, gemm3_nt, gemm3_nt_ex, nt_reduce
         x2, pb = ctx.saved_tensors
         N, Cin, Cout, H, W = ctx.dims
         g2 = gy.permute(0, 2, 3, 1).reshape(N * H * W, Cout)
@@ -187,7 +186,7 @@ class _Conv1x1Fn(Function):
                 dx2 = gemm3_ex(g2, pb, out_dtype=x2.dtype)                       # bf16 input -> bf16 gradient, no cast pass
             dx = dx2.view(N, H, W, Cin).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            rps = _balanced_rps(g2.shape[0], Cout, Cin, g2.device)
+            rps = balanced_rps(g2.shape[0], Cout, Cin, g2.device)
             mixed = g2.dtype != x2.dtype
             if mixed and Cin % 128 == 0:
                 c, ca = gemm3_nt_ex(g2, x2, rps, want_csum_a=True)

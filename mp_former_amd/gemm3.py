@@ -4,6 +4,8 @@
 (``transpose=True``: planes of W^T, the operand of dX = dY . W); ``gemm3`` runs
 C = (A + A2) . B^T + bias + Cin + Cin2, optional ReLU / ReLU-backward gate.  GPU only, fp32 only.
 """
+import functools
+
 import torch
 
 from . import _lib
@@ -212,6 +214,25 @@ def pick_rows_per_split(R, out_tiles, align=None):
         if align % rps != 0:
             return None
     return rps
+
+
+@functools.lru_cache(None)
+def workgroup_slots(device):
+    """2 x the number of CUs: the workgroups of a split-K weight-gradient kernel that run at once (one round of the chip)"""
+    return 2 * torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def balanced_rps(R, M, N, device, base=1 << 30):
+    """Rows per split of a weight-gradient GEMM such that its (tile, split) workgroups fill ONE whole round of the chip's
+    2 x CU workgroup slots (more rounds only if the output alone has more tiles than slots): with round 1's 512-row
+    splits a 256 x 256 gradient at R = 43 008 was 336 workgroups (0.66 of a round) and a 256 x 1024 one 1 344 (2.6
+    rounds, run as 3) with 84 partial results to sum; now 492 / 512 workgroups and 123 / 32 partials.  Same tiles, same
+    products — only the split boundaries move."""
+    slots = workgroup_slots(device)
+    tiles = ((M + 127) // 128) * ((N + 127) // 128)
+    rounds = max(1, -(-tiles * max(1, R // base) // slots))          # rounds that `base`-row splits would take
+    ns = max(1, rounds * slots // tiles)
+    return max(128, ((-(-R // ns)) + 31) // 32 * 32)
 
 
 def gemm3_nt(a, b, rows_per_split, b2=None, want_csum_a=False, want_csum_b=False, transpose_out=False, amax_ab=None):

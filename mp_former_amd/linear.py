@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from .gemm3 import gemm3, gemm3_nt, nt_reduce, split_weights_grouped
+from .gemm3 import balanced_rps, gemm3, gemm3_nt, nt_reduce, split_weights_grouped
 
 
 class _LinearFn(Function):
@@ -23,14 +23,13 @@ class _LinearFn(Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .encoder_fused import _balanced_rps
         x2, pb = ctx.saved_tensors
         g2 = gy if (gy.stride(1) == 1 and gy.stride(0) % 4 == 0) else gy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = gemm3(g2, pb)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            rps = _balanced_rps(g2.shape[0], g2.shape[1], x2.shape[1], g2.device)
+            rps = balanced_rps(g2.shape[0], g2.shape[1], x2.shape[1], g2.device)
             c, ca, _ = gemm3_nt(g2, x2, rps, want_csum_a=True)
             dw, db = nt_reduce(c, ca)
             if not ctx.has_bias:

@@ -124,8 +124,10 @@ def test_shipped_miopen_find_db_is_wired(monkeypatch, tmp_path):
 
 def test_encoder_call_structs_match_the_header(tmp_path):
     """The ctypes mirrors of MpfEncoderCall / MpfEncoderBwdCall (mp_former_amd/encoder_fused.py) against the C declarations of
-    include/mpformer_hip.h compiled by gcc: same size, same offset of every member, same number of table fields — the two structs
-    carry ~30 pointers each, a drift between the two sides would be a silent corruption on the GPU."""
+    include/mpformer_hip.h compiled by gcc: same size, same offset of every member, same number of table fields, and every table
+    field at the position its MPF_ENC_* / MPF_ENCB_* enumerator names (the tables are filled by name on the python side: two
+    swapped names keep the count) — the two structs carry ~30 pointers each and the tables 40 more per layer, a drift between the
+    two sides would be a silent corruption on the GPU."""
     import ctypes
     import subprocess
     from mp_former_amd import encoder_fused as EF
@@ -136,19 +138,27 @@ def test_encoder_call_structs_match_the_header(tmp_path):
         src.append(f'  printf("{st} size %zu\\n", sizeof({st}));')
         for n in names:
             src.append(f'  printf("{st} {n} %zu\\n", offsetof({st}, {n}));')
-    src += ['  printf("fields %d %d\\n", (int)MPF_ENC_FIELDS, (int)MPF_ENCB_FIELDS);', '  return 0;', '}']
+    src += ['  printf("fields %d %d\\n", (int)MPF_ENC_FIELDS, (int)MPF_ENCB_FIELDS);']
+    tables = {"MPF_ENC": EF._ENC_FIELDS, "MPF_ENCB": EF._ENCB_FIELDS}
+    for prefix, names in tables.items():
+        src += [f'  printf("field {prefix} {n} %d\\n", (int){prefix}_{n.upper()});' for n in names]
+    src += ['  return 0;', '}']
     c = tmp_path / "layout.c"
     c.write_text("\n".join(src))
     exe = tmp_path / "layout"
     subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(c), "-o", str(exe)])
     out = subprocess.check_output([str(exe)], text=True).split("\n")
-    seen = 0
+    seen = placed = 0
     for line in out:
         t = line.split()
         if not t:
             continue
         if t[0] == "fields":
             assert (int(t[1]), int(t[2])) == (len(EF._ENC_FIELDS), len(EF._ENCB_FIELDS))
+            continue
+        if t[0] == "field":
+            assert tables[t[1]].index(t[2]) == int(t[3]), t
+            placed += 1
             continue
         cls = getattr(EF, t[0])
         if t[1] == "size":
@@ -157,6 +167,7 @@ def test_encoder_call_structs_match_the_header(tmp_path):
             assert getattr(cls, t[1]).offset == int(t[2]), t
         seen += 1
     assert seen == sum(len(v) for v in members.values()) + 2
+    assert placed == len(EF._ENC_FIELDS) + len(EF._ENCB_FIELDS) and all(len(set(v)) == len(v) for v in tables.values())
 
 
 def test_item_table_rows_match_the_header(tmp_path):
