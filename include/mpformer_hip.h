@@ -439,6 +439,40 @@ int mpf_small_gemm_bf16(const void* a, int64_t a_rs, int64_t a_ks, const void* g
 int mpf_mask_block_empty(const uint8_t* masks, uint8_t* out, int T, int H, int W, int h, int w, void* stream);
 
 /*
+ * Point noise of the mask-piloted rows (prepare_for_dn_v5 and gen_mask_dn, mask2former_transformer_decoder.py:985-998 and
+ * :1599-1620): every attention mask of a forward shows the ground-truth rows of its level with each position flipped with
+ * probability  areas * noise_scale / (h w),  areas = open (attended) positions of the row, and all-1 rows in the slots no
+ * instance occupies (padding_mask = ones, :985, :1599).  The reference draws the flips with torch.rand_like; here they are
+ * a pure function of (seed, draw, r, j), so a test can restate a row and the result cannot depend on the launch.
+ *
+ * mpf_mp_open_counts:  base [R, HW] bytes (0 = attend, 1 = do not attend; the rows mpf_mask_block_empty returns, after the
+ *   repeat over the `scalar` copies) -> counts [R] int32, the number of 0 bytes of each row (`areas`, :995, :1610).  The rows
+ *   do not change within a forward: one call per level and forward.
+ *
+ * mpf_mp_noise_rows:  writes every byte of out [N, pad, HW] exactly once, in one launch.
+ *   src_of [N * pad] int32: for each output row the row of `base` it shows; a value outside [0, R) (-1 by convention) marks a
+ *     slot no instance occupies, whose row is all 1 and for which `base` is not read.
+ *   For 0 <= r = src_of[n * pad + q] < R:
+ *       out[n, q, j] = base[r, j] ^ (u(r, j) < ratio[r])                         (base bytes must be 0 or 1)
+ *       ratio[r]     = (float)counts[r] * (float)(noise_scale / (double)HW)      one fp32 multiply, round to nearest; this is
+ *                      what torch computes for  (~b).sum(1) * (noise_scale / b.shape[1])  (int64 tensor times python scalar)
+ *   u(r, j): Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; multipliers 0xD2511F53 and
+ *     0xCD9E8D57, Weyl key increments 0x9E3779B9 and 0xBB67AE85, ten rounds) with
+ *       key     = (lo32, hi32) of  seed ^ MPF_MP_NOISE_KEY      (domain separation: torch's own Philox streams use `seed`
+ *                                                                unchanged as their key, and the callers pass torch's seed)
+ *       counter = (j >> 2, r, lo32(draw), hi32(draw))
+ *     position j takes output word  j & 3  of that block, and  u = (float)(word >> 8) * 2^-24  (exact in fp32, 0 <= u < 1).
+ *   `draw` names one mask: callers advance it between masks.  The result depends on (seed, draw, r, j) alone: not on the
+ *   grid, not on N, pad or the order of src_of, not on the stream.
+ * Argument errors are reported before any GPU call: NULL buffer -3; R, HW, N or pad <= 0, or noise_scale < 0 / NaN -2; R * HW
+ * or N * pad * HW >= 2^31 -4.
+ */
+#define MPF_MP_NOISE_KEY 0x4D50466F726D6572ULL /* "MPFormer" in ASCII */
+int mpf_mp_open_counts(const uint8_t* base, int R, int HW, int* counts, void* stream);
+int mpf_mp_noise_rows(const uint8_t* base, const int* counts, const int* src_of, int R, int HW, int N, int pad,
+                      double noise_scale, uint64_t seed, uint64_t draw, uint8_t* out, void* stream);
+
+/*
  * Decoder inputs of one feature level (mask2former_transformer_decoder.py:1756-1764: input_proj +
  * level_embed, flatten, permute; the key input adds the sine position embedding, :100-112):
  *   src[s, n, c] = x(n, c, s) + level_embed[c]        kin[s, n, c] = src[s, n, c] + pos[s, c]

@@ -112,6 +112,8 @@ SIGNATURES = {
     "mpf_lsa_assign": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, ctypes.c_int64] + [_c_vp] * 7),
     "mpf_lsa_assign_status": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, ctypes.c_int64] + [_c_vp] * 8),
     "mpf_mask_block_empty": (_c_int, [_c_vp, _c_vp] + [_c_int] * 5 + [_c_vp]),
+    "mpf_mp_open_counts": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_mp_noise_rows": (_c_int, [_c_vp] * 3 + [_c_int] * 4 + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_vp, _c_vp]),
     "mpf_gemm_nt_bf16_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),
     "mpf_gemm_nt_bf16": (_c_int, [_c_vp, ctypes.c_int64, _c_vp, ctypes.c_int64, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp,
                                   ctypes.c_size_t, _c_vp]),

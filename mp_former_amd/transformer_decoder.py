@@ -15,13 +15,18 @@ Differences that do not change results:
   * ground-truth masks are OR-reduced to the 3 level sizes once per forward (A.5: area <= 1e-8 is
     "no GT pixel in the block") instead of 10 area-interpolations;
   * hard-coded .cuda() / 8 heads of the reference become the module's device / num_heads.
-Only dn_mode "points" with NOISE_SCALE 0 (the shipped run script) is implemented; other modes raise.
+Only dn_mode "points" is implemented (other modes and HEAD_DN raise), with or without point noise on the MP rows:
+NOISE_SCALE 0 (the shipped run script) builds the rows once per forward; NOISE_SCALE > 0 (the DN_query configs) makes each
+mask's rows with one native launch (``mp_noise_rows``, csrc/mp_noise.hip), the flips drawn by a counter-based generator keyed by
+the device generator's seed and offset.  The torch ops of the reference remain as ``noisy_rows`` for the tests, which feed them
+recorded draws through ``_rng.install_replay``.
 """
 import math
 import ctypes
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
@@ -464,6 +469,55 @@ def gt_block_or(masks: Tensor, size):
     return out
 
 
+def mp_open_counts(base: Tensor) -> Tensor:
+    """``areas`` of :995 / :1610: base [R, HW] bool (True = do not attend) -> the number of open positions per row, int32 [R]."""
+    if not base.is_cuda:
+        raise RuntimeError("mp_former_amd decoder runs on the GPU only (no CPU fallback)")
+    base = base.contiguous()
+    R, HW = base.shape
+    counts = torch.empty(R, dtype=torch.int32, device=base.device)
+    with _lib.device_guard(base.device):
+        code = _lib.lib().mpf_mp_open_counts(base.data_ptr(), R, HW, counts.data_ptr(), _lib.stream_ptr(base.device))
+    _lib.check(code, "mpf_mp_open_counts")
+    return counts
+
+
+def mp_noise_rows(base: Tensor, src_of: Tensor, N: int, pad: int, noise_scale: float, seed: int, draw: int,
+                  counts: Optional[Tensor] = None) -> Tensor:
+    """One attention mask's worth of mask-piloted rows with point noise (:985-998, :1599-1620), one native launch.
+    base [R, HW] bool (the GT rows of the level, True = do not attend), src_of [N * pad] int32 (for each output row the row of
+    ``base`` it shows, -1 = empty slot -> all True) -> [N, pad, HW] bool.  Each position of row r flips with probability
+    counts[r] * noise_scale / HW; the flips are the function of (seed, draw, r, position) that include/mpformer_hip.h defines.
+    ``counts``: mp_open_counts(base) if the caller already has it (it does not change within a forward)."""
+    if not base.is_cuda:
+        raise RuntimeError("mp_former_amd decoder runs on the GPU only (no CPU fallback)")
+    base = base.contiguous()
+    R, HW = base.shape
+    if counts is None:
+        counts = mp_open_counts(base)
+    assert base.dtype == torch.bool and counts.dtype == torch.int32 and counts.numel() == R and counts.is_contiguous()
+    assert src_of.dtype == torch.int32 and src_of.numel() == N * pad and src_of.is_contiguous()
+    assert src_of.device == base.device and counts.device == base.device
+    out = torch.empty((N, pad, HW), dtype=torch.bool, device=base.device)
+    mask64 = (1 << 64) - 1
+    with _lib.device_guard(base.device):
+        code = _lib.lib().mpf_mp_noise_rows(base.data_ptr(), counts.data_ptr(), src_of.data_ptr(), R, HW, N, pad, float(noise_scale),
+                                            int(seed) & mask64, int(draw) & mask64, out.data_ptr(), _lib.stream_ptr(base.device))
+    _lib.check(code, "mpf_mp_noise_rows")
+    return out
+
+
+def _next_noise_draw(device):
+    """(seed, draw) of the next noised mask, from the CUDA generator of ``device``: its seed, and its Philox offset as the draw
+    number, advanced by 4 (the generator's own granularity) per mask.  ``torch.manual_seed`` and a saved / restored generator
+    state therefore reproduce the masks.  Host-side state only: no device synchronisation."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    gen = torch.cuda.default_generators[idx]
+    draw = gen.get_offset()
+    gen.set_offset(draw + 4)
+    return gen.initial_seed(), draw
+
+
 class MultiScaleMaskedTransformerDecoderMaskDN(nn.Module):
     _version = 2
 
@@ -588,8 +642,24 @@ class MultiScaleMaskedTransformerDecoderMaskDN(nn.Module):
             pm[(bid, slot)] = torch.logical_xor(b, _rng.rand("mp_noise", tuple(b.shape), device) < ratio[:, None])
             return pm
 
-        if noise_scale != 0:
-            rows = noisy_rows
+        if noise_scale != 0 and _rng.replaying():
+            rows = noisy_rows          # the tests' reference: the reference's ops, fed with the reference's recorded draws
+        elif noise_scale != 0:
+            # production: one native launch per mask (mp_noise.hip).  What does not change within the forward is made once:
+            # the open counts of every level, and the inverse of (bid, slot) — for each output row the base row it shows
+            counts = [mp_open_counts(b) for b in base]
+            total = sum(num)
+            src_of = np.full((bs, pad), -1, dtype=np.int32)
+            first = 0
+            for b, n in enumerate(num):
+                for s in range(scalar):
+                    src_of[b, s * max_num:s * max_num + n] = np.arange(s * total + first, s * total + first + n, dtype=np.int32)
+                first += n
+            src_of = upload(src_of.reshape(-1), device)
+
+            def rows(level):
+                seed, draw = _next_noise_draw(device)
+                return mp_noise_rows(base[level], src_of, bs, pad, noise_scale, seed, draw, counts[level])
         tgt_size = pad + self.num_queries
         tgt_mask = torch.zeros(tgt_size, tgt_size, dtype=torch.bool, device=device)
         tgt_mask[pad:, :pad] = True
@@ -874,8 +944,11 @@ class MultiScaleMaskedTransformerDecoderMaskDN(nn.Module):
             streams.append(out_heads)
             if i + 1 < self.num_layers:
                 attn_mask = self._next_attn_mask(W, output, mask_features, size_list[nxt], rows(nxt, i), pooled[nxt])
-            elif mp is not None and callable(mp["rows"]) and _rng.replaying() and (self.all_lys or i < 3):
-                rows(nxt, i)        # the reference draws the noise of the mask after the last layer too (unused): keep the FIFO aligned
+            elif mp is not None and callable(mp["rows"]) and (self.all_lys or i < 3):
+                # the reference makes the mask after the last layer too (unused): dec_layers + 1 noised masks per forward.  Under
+                # replay this keeps the FIFO aligned; the native route follows the same schedule, so the generator offset a
+                # forward consumes is the reference's count of draws (one launch at this level's size)
+                rows(nxt, i)
         predictions_class, predictions_mask = self._heads_batched(W, streams, mask_features)
 
         nq = self.num_queries
