@@ -249,6 +249,9 @@ _ENC_FIELDS = ("pv", "pv_am", "po", "po_am", "p1", "p1_am", "p2", "p2_am", "p288
 _ENC_AT = {k: i for i, k in enumerate(_ENC_FIELDS)}
 _NATIVE_FWD = os.environ.get("MPF_ENCODER_NATIVE", "1") != "0"        # (0: the python-sequenced forward / backward the tests compare with)
 _NATIVE_BWD = _NATIVE_FWD
+# calls of EncoderFn by the route they took (the two routes launch the same kernels, so nothing in the kernel log tells them apart;
+# the tests that compare the routes assert on these)
+ROUTE_CALLS = {"native_fwd": 0, "python_fwd": 0, "native_bwd": 0, "python_bwd": 0}
 
 
 class MpfEncoderCall(ctypes.Structure):
@@ -532,7 +535,8 @@ class EncoderFn(Function):
         amax(pos_full, pos_am)
         ctx.guarded = guarded = _guard_begin()
         native = _native_forward_applies(guarded, meta, C, prm)
-        _guard["active"] = guarded                   # (the operands of this call go through mpf_h2_range_stats in _audit)
+        ROUTE_CALLS["native_fwd" if native else "python_fwd"] += 1
+        _guard["active"] = guarded                  # (the operands of this call go through mpf_h2_range_stats in _audit)
         try:
             saved, x = (_native_forward if native else _python_forward)(x, x_am, q_am, pos_full, pos_am, prm, [f for f, _ in planes], b288_all,
                                                                         ams, meta, (N, S, C))
@@ -562,7 +566,9 @@ class EncoderFn(Function):
                 split_level = meta["level_idx"][::rps].repeat(N)          # level of every split's rows
                 meta[key] = split_level
         guarded = bool(getattr(ctx, "guarded", False))
-        if _native_backward_applies(guarded, meta, aligned, C, prm, saved):
+        native = _native_backward_applies(guarded, meta, aligned, C, prm, saved)
+        ROUTE_CALLS["native_bwd" if native else "python_bwd"] += 1
+        if native:
             g, dprm, dgb, lvls_all = _native_backward(g, prm, saved, ctx.planes_t, meta, (N, S, C), rps, split_level)
         else:
             _guard["active"] = guarded

@@ -202,18 +202,33 @@ def test_native_encoder_calls_match_the_python_sequenced_ones(shapes, batch, lay
     pos = [pe(s) for s in srcs]
     go = torch.randn(batch, sum(h * w for h, w in shapes), 256, device=dev)
     res = {}
+    # the one-call backward takes level-aligned weight-gradient splits only: the (5, 7) pyramid has none, its backward is sequenced
+    # in python on every leg (what that case pins is the native forward and the python backward on its arena views)
+    bwd_applies = encoder_fused.rows_per_split([h * w for h, w in shapes])[1]
+    every = encoder_fused.RANGE_GUARD_EVERY
+    # (the range guard sends the 3rd encoder call of a process, and every 64th after it, down the python-sequenced route: with it
+    # on, which leg is native depends on how many encoder calls came before this test)
+    encoder_fused.RANGE_GUARD_EVERY = 0
     _lib.set_option("msda_bwd_sorted", 1)              # (the MSDA backward's grad_value depends on the arrival order of the tile entries otherwise)
-    for native in ((False, False), (True, False), (True, True)):
-        encoder_fused._NATIVE_FWD, encoder_fused._NATIVE_BWD = native
-        try:
-            _lib.profile_enable(True)
-            res[native] = _run(enc, srcs, pos, go, fused=True)
-            n_calls = _lib.profile_get("gemm3_tn_kernel")[0]
-            _lib.profile_enable(False)
-            assert n_calls > 0
-        finally:
-            encoder_fused._NATIVE_FWD = encoder_fused._NATIVE_BWD = True
-    _lib.set_option("msda_bwd_sorted", 0)
+    try:
+        for native in ((False, False), (True, False), (True, True)):
+            encoder_fused._NATIVE_FWD, encoder_fused._NATIVE_BWD = native
+            before = dict(encoder_fused.ROUTE_CALLS)
+            try:
+                _lib.profile_enable(True)
+                res[native] = _run(enc, srcs, pos, go, fused=True)
+                n_calls = _lib.profile_get("gemm3_tn_kernel")[0]
+                _lib.profile_enable(False)
+                assert n_calls > 0
+            finally:
+                encoder_fused._NATIVE_FWD = encoder_fused._NATIVE_BWD = True
+            took = {k: v - before[k] for k, v in encoder_fused.ROUTE_CALLS.items() if v != before[k]}
+            assert took == {"native_fwd" if native[0] else "python_fwd": 1,
+                            "native_bwd" if native[1] and bwd_applies else "python_bwd": 1}, (native, took)
+    finally:
+        encoder_fused.RANGE_GUARD_EVERY = every
+        _lib.set_option("msda_bwd_sorted", 0)
+    assert bwd_applies == (shapes[0] != (5, 7))
     (m0, gx0, gp0) = res[(False, False)]
     for key in ((True, False), (True, True)):
         m1, gx1, gp1 = res[key]
