@@ -30,9 +30,7 @@ def upload(data, device, dtype=None):
             from . import _lib
             a = data if data.flags.c_contiguous else np.ascontiguousarray(data)
             out = torch.empty(a.shape, dtype=_NP2T[a.dtype], device=device)
-            with _lib.device_guard(device):
-                code = _lib.lib().mpf_upload_small(a.__array_interface__["data"][0], out.data_ptr(), nbytes, _lib.stream_ptr(device))
-            _lib.check(code, "mpf_upload_small")
+            _lib.call("mpf_upload_small", device, a.__array_interface__["data"][0], out.data_ptr(), nbytes, _lib.stream_ptr(device))
             return out
     t = torch.from_numpy(data) if isinstance(data, np.ndarray) else torch.as_tensor(data)
     if dtype is not None and t.dtype != dtype:
@@ -47,8 +45,6 @@ def upload(data, device, dtype=None):
         from . import _lib
         t = t.contiguous()
         out = torch.empty(t.shape, dtype=t.dtype, device=device)
-        with _lib.device_guard(device):
-            code = _lib.lib().mpf_upload_small(t.data_ptr(), out.data_ptr(), nbytes, _lib.stream_ptr(device))
-        _lib.check(code, "mpf_upload_small")
+        _lib.call("mpf_upload_small", device, t.data_ptr(), out.data_ptr(), nbytes, _lib.stream_ptr(device))
         return out
     return t.pin_memory().to(device, non_blocking=True)

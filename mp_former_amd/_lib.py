@@ -2,6 +2,12 @@
 
 The library is built in-tree by ``__graft_entry__.build()`` / ``make -C mp_former_amd/csrc`` and is
 loaded lazily on first use.  A missing library is a hard error: there is no fallback path.
+
+How a host wrapper reaches it:
+  ``call(name, device, *args)``  every entry point that returns a status: makes ``device`` current, runs it, raises on failure
+  ``lib().mpf_*_bytes(...)``     size queries (and the other calls that return a value, not a status): they launch nothing
+  ``stream_ptr(device)``         the stream argument, passed by the caller where the signature wants it
+  ``scratch(...)``               workspace; ``ptr(t)`` for an optional tensor; ``DTYPE[t.dtype]`` for the MPF_* dtype code
 """
 import ctypes
 
@@ -15,8 +21,11 @@ LIB_PATH = os.environ.get("MPF_LIB_PATH", LIB_PATH)
 ABI_VERSION = 1
 
 MPF_F32, MPF_F64, MPF_BF16, MPF_U8, MPF_BITS = 0, 1, 2, 3, 4
+# torch dtype -> MPF_* code (bool tensors are read as bytes)
+DTYPE = {torch.float32: MPF_F32, torch.float64: MPF_F64, torch.bfloat16: MPF_BF16, torch.uint8: MPF_U8, torch.bool: MPF_U8}
 
 _lib = None
+_status_fns = {}  # name -> bound function, for the symbols that return a status (restype c_int): what `call` may run
 
 _c_int = ctypes.c_int
 _c_vp = ctypes.c_void_p
@@ -213,6 +222,8 @@ def lib():
                 raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
             fn.restype = res
             fn.argtypes = args
+            if res is _c_int:
+                _status_fns[name] = fn
         v = l.mpf_abi_version()
         if v != ABI_VERSION:
             raise NativeLibraryError(f"ABI mismatch: library {v}, binding {ABI_VERSION}")
@@ -228,6 +239,33 @@ def check(code, what):
     if code != 0:
         msg = lib().mpf_last_error().decode()
         raise RuntimeError(f"{what} failed with code {code}: {msg}")
+
+
+def _status_fn(name):
+    lib()
+    fn = _status_fns.get(name)
+    if fn is None:
+        raise TypeError(f"{name} does not return a status: call() is for the int-returning entry points, sizes go through lib()")
+    return fn
+
+
+def call(name, device, *args):
+    """Run the int-returning entry point `name` with `device` current; raise RuntimeError naming `name` with mpf_last_error() if
+    it fails.  The stream is an argument like any other (it is not last in every signature): pass ``stream_ptr(device)``."""
+    fn = _status_fns.get(name) or _status_fn(name)
+    idx = device.index
+    if idx is None or idx == torch.cuda.current_device():  # as device_guard
+        code = fn(*args)
+    else:
+        with torch.cuda.device(device):
+            code = fn(*args)
+    if code != 0:
+        check(code, name)  # mpf_last_error is thread-local: read here, on the calling thread
+
+
+def ptr(t):
+    """data_ptr of an optional tensor (None -> NULL)"""
+    return None if t is None else t.data_ptr()
 
 
 _option_gen = 0

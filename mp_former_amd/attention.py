@@ -30,9 +30,7 @@ class _AttnCore(Function):
         stream = _lib.stream_ptr(q.device)
         kt = torch.empty((N, E, Lk), dtype=torch.bfloat16, device=q.device)      # K^T is for the backward
         vt = torch.empty((N, E, Lk), dtype=torch.bfloat16, device=q.device)
-        with _lib.device_guard(q.device):
-            _lib.check(lib.mpf_attn_transpose2(kb.data_ptr(), vb.data_ptr(), kt.data_ptr(), vt.data_ptr(), Lk, Lk, N, E, stream),
-                       "mpf_attn_transpose2")
+        _lib.call("mpf_attn_transpose2", q.device, kb.data_ptr(), vb.data_ptr(), kt.data_ptr(), vt.data_ptr(), Lk, Lk, N, E, stream)
         m = None
         if mask is not None:
             m = mask.contiguous()
@@ -40,11 +38,9 @@ class _AttnCore(Function):
         out = torch.empty((Lq, N, E), dtype=torch.bfloat16, device=q.device)
         lse = torch.empty((N, nheads, Lq), dtype=torch.float32, device=q.device)
         ws = _lib.scratch("attn", q.device, stream, lib.mpf_attn_workspace_bytes(Lq, Lk, N, nheads))
-        with _lib.device_guard(q.device):
-            code = lib.mpf_attn_forward(qb.data_ptr(), kb.data_ptr(), vt.data_ptr(), m.data_ptr() if m is not None else None,
-                                        1 if (m is not None and m.dim() == 3) else 0, out.data_ptr(), lse.data_ptr(),
-                                        Lq, Lk, N, nheads, hd, 1.0 / math.sqrt(hd), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(code, "mpf_attn_forward")
+        _lib.call("mpf_attn_forward", q.device, qb.data_ptr(), kb.data_ptr(), vt.data_ptr(), _lib.ptr(m),
+                  1 if (m is not None and m.dim() == 3) else 0, out.data_ptr(), lse.data_ptr(),
+                  Lq, Lk, N, nheads, hd, 1.0 / math.sqrt(hd), ws.data_ptr(), ws.numel(), stream)
         ctx.save_for_backward(qb, kb, vb, kt, m, out, lse)
         ctx.nheads = nheads
         ctx.in_dtypes = (q.dtype, k.dtype, v.dtype)
@@ -69,15 +65,13 @@ class _AttnCore(Function):
         dk = torch.empty_like(kb)
         dv = torch.empty_like(vb)
         ws = _lib.scratch("attn", dev, stream, lib.mpf_attn_workspace_bytes(Lq, Lk, N, H))
-        with _lib.device_guard(dev):
-            _lib.check(lib.mpf_attn_bwd_prep(qb.data_ptr(), gob.data_ptr(), out.data_ptr(), qT.data_ptr(), doT.data_ptr(),
-                                             delta.data_ptr(), Lq, LqP, N, H, stream), "mpf_attn_bwd_prep")      # Q^T, dO^T, delta
-            code = lib.mpf_attn_backward(qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), kT.data_ptr(), qT.data_ptr(),
-                                         gob.data_ptr(), doT.data_ptr(), m.data_ptr() if m is not None else None,
-                                         1 if (m is not None and m.dim() == 3) else 0, lse.data_ptr(), delta.data_ptr(),
-                                         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Lq, LqP, Lk, N, H, hd,
-                                         1.0 / math.sqrt(hd), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(code, "mpf_attn_backward")
+        _lib.call("mpf_attn_bwd_prep", dev, qb.data_ptr(), gob.data_ptr(), out.data_ptr(), qT.data_ptr(), doT.data_ptr(),
+                  delta.data_ptr(), Lq, LqP, N, H, stream)      # Q^T, dO^T, delta
+        _lib.call("mpf_attn_backward", dev, qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), kT.data_ptr(), qT.data_ptr(),
+                  gob.data_ptr(), doT.data_ptr(), _lib.ptr(m),
+                  1 if (m is not None and m.dim() == 3) else 0, lse.data_ptr(), delta.data_ptr(),
+                  dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Lq, LqP, Lk, N, H, hd,
+                  1.0 / math.sqrt(hd), ws.data_ptr(), ws.numel(), stream)
         tq, tk, tv = ctx.in_dtypes
         return dq.to(tq), dk.to(tk), dv.to(tv), None, None
 

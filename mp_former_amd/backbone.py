@@ -53,10 +53,8 @@ class _BiasAct(torch.autograd.Function):
     def forward(ctx, x, shift, res, relu):
         y = torch.empty_like(x)
         C = x.shape[1]
-        code = _lib.lib().mpf_bias_act(x.data_ptr(), shift.data_ptr(), res.data_ptr() if res is not None else None,
-                                       y.data_ptr(), x.numel(), C, _lib.MPF_BF16 if x.dtype == torch.bfloat16 else _lib.MPF_F32,
-                                       1 if relu else 0, _lib.stream_ptr(x.device))
-        _lib.check(code, "mpf_bias_act")
+        _lib.call("mpf_bias_act", x.device, x.data_ptr(), shift.data_ptr(), _lib.ptr(res), y.data_ptr(), x.numel(), C,
+                  _lib.DTYPE[x.dtype], 1 if relu else 0, _lib.stream_ptr(x.device))
         ctx.relu, ctx.has_res = relu, res is not None
         if relu:
             ctx.save_for_backward(y)
@@ -78,10 +76,8 @@ def _relu_bwd_add(ga, gb, y):
     if not (ga.is_cuda and same):
         return torch.ops.aten.threshold_backward(ga if gb is None else ga + gb, y, 0)
     out = torch.empty_like(y)
-    with _lib.device_guard(y.device):
-        code = _lib.lib().mpf_relu_bwd_add(ga.data_ptr(), gb.data_ptr() if gb is not None else None, y.data_ptr(), out.data_ptr(),
-                                           y.numel(), _lib.MPF_BF16, _lib.stream_ptr(y.device))
-    _lib.check(code, "mpf_relu_bwd_add")
+    _lib.call("mpf_relu_bwd_add", y.device, ga.data_ptr(), _lib.ptr(gb), y.data_ptr(), out.data_ptr(), y.numel(), _lib.MPF_BF16,
+              _lib.stream_ptr(y.device))
     return out
 
 
@@ -94,10 +90,8 @@ class _BiasActFork(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, shift, res):
         y = torch.empty_like(x)
-        code = _lib.lib().mpf_bias_act(x.data_ptr(), shift.data_ptr(), res.data_ptr(), y.data_ptr(), x.numel(), x.shape[1],
-                                       _lib.MPF_BF16 if x.dtype == torch.bfloat16 else _lib.MPF_F32, 1,
-                                       _lib.stream_ptr(x.device))
-        _lib.check(code, "mpf_bias_act")
+        _lib.call("mpf_bias_act", x.device, x.data_ptr(), shift.data_ptr(), res.data_ptr(), y.data_ptr(), x.numel(), x.shape[1],
+                  _lib.DTYPE[x.dtype], 1, _lib.stream_ptr(x.device))
         ctx.save_for_backward(y)
         ctx.set_materialize_grads(False)
         return y, y.view(y.shape)
@@ -149,10 +143,8 @@ class _MaxPool3x3s2(torch.autograd.Function):
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty((N, C, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         code = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=x.device)
-        with _lib.device_guard(x.device):
-            rc = _lib.lib().mpf_maxpool3x3s2_forward(x.data_ptr(), y.data_ptr(), code.data_ptr(), N, H, W, C,
-                                                     _lib.stream_ptr(x.device))
-        _lib.check(rc, "mpf_maxpool3x3s2_forward")
+        _lib.call("mpf_maxpool3x3s2_forward", x.device, x.data_ptr(), y.data_ptr(), code.data_ptr(), N, H, W, C,
+                  _lib.stream_ptr(x.device))
         ctx.save_for_backward(code)
         ctx.in_shape = (N, C, H, W)
         return y
@@ -164,10 +156,8 @@ class _MaxPool3x3s2(torch.autograd.Function):
         if gy.dtype != torch.bfloat16 or not gy.is_contiguous(memory_format=torch.channels_last):
             gy = gy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         gx = torch.empty((N, C, H, W), dtype=gy.dtype, device=gy.device, memory_format=torch.channels_last)
-        with _lib.device_guard(gy.device):
-            rc = _lib.lib().mpf_maxpool3x3s2_backward(gy.data_ptr(), code.data_ptr(), gx.data_ptr(), N, H, W, C,
-                                                      _lib.stream_ptr(gy.device))
-        _lib.check(rc, "mpf_maxpool3x3s2_backward")
+        _lib.call("mpf_maxpool3x3s2_backward", gy.device, gy.data_ptr(), code.data_ptr(), gx.data_ptr(), N, H, W, C,
+                  _lib.stream_ptr(gy.device))
         return gx
 
 
@@ -228,11 +218,8 @@ def _grouped_scale_cast(srcs, scales, out_dtype):
     table[:, 0] = [t.data_ptr() for t in srcs]
     table[:, 1] = offs_b + out.data_ptr()
     items = upload(table.reshape(-1), dev)
-    dt = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}
-    with _lib.device_guard(dev):
-        code = _lib.lib().mpf_grouped_scale_cast(items.data_ptr(), len(srcs), blk, dt[srcs[0].dtype], dt[out_dtype],
-                                                 _lib.stream_ptr(dev))
-    _lib.check(code, "mpf_grouped_scale_cast")
+    _lib.call("mpf_grouped_scale_cast", dev, items.data_ptr(), len(srcs), blk, _lib.DTYPE[srcs[0].dtype], _lib.DTYPE[out_dtype],
+              _lib.stream_ptr(dev))
     return [out[o:o + n].as_strided(shp, std) for o, n, shp, std in views]
 
 

@@ -44,18 +44,12 @@ class _Conv3x3Fn(Function):
         if h2:
             (pf, pf_am), (pb, pb_am) = split_weights_grouped_h2([([w2.contiguous()], False), ([w2t.contiguous()], False)])
             x_am = amax(x.permute(0, 2, 3, 1))           # (the planes are dense in this order)
-            with _lib.device_guard(x.device):
-                code = _lib.lib().mpf_gemm3_conv3x3_h2(x.data_ptr(), x_am.data_ptr(), pf.data_ptr(), pf_am.data_ptr(),
-                                                       bias.data_ptr() if bias is not None else None, y.data_ptr(), None,
-                                                       N, H, W, Cin, Cout, 0, st)
-            _lib.check(code, "mpf_gemm3_conv3x3_h2")
+            _lib.call("mpf_gemm3_conv3x3_h2", x.device, x.data_ptr(), x_am.data_ptr(), pf.data_ptr(), pf_am.data_ptr(), _lib.ptr(bias),
+                      y.data_ptr(), None, N, H, W, Cin, Cout, 0, st)
             ctx.save_for_backward(x, weight, pb, pb_am, x_am)
         else:
             pf, pb = split_weights_grouped([([w2.contiguous()], False), ([w2t.contiguous()], False)])
-            with _lib.device_guard(x.device):
-                code = _lib.lib().mpf_gemm3_conv3x3(x.data_ptr(), pf.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                                    N, H, W, Cin, Cout, 0, st)
-            _lib.check(code, "mpf_gemm3_conv3x3")
+            _lib.call("mpf_gemm3_conv3x3", x.device, x.data_ptr(), pf.data_ptr(), _lib.ptr(bias), y.data_ptr(), N, H, W, Cin, Cout, 0, st)
             ctx.save_for_backward(x, weight, pb)
         ctx.has_bias, ctx.h2 = bias is not None, h2
         return y
@@ -75,13 +69,11 @@ class _Conv3x3Fn(Function):
         gy_am = amax(gy.permute(0, 2, 3, 1)) if ctx.h2 else None
         if ctx.needs_input_grad[0]:
             dx = _planes(N, Cin, H, W, x.device)
-            with _lib.device_guard(x.device):
-                if ctx.h2:
-                    code = _lib.lib().mpf_gemm3_conv3x3_h2(gy.data_ptr(), gy_am.data_ptr(), pb.data_ptr(), pb_am.data_ptr(), None,
-                                                           dx.data_ptr(), None, N, H, W, Cout, Cin, 1, st)
-                else:
-                    code = _lib.lib().mpf_gemm3_conv3x3(gy.data_ptr(), pb.data_ptr(), None, dx.data_ptr(), N, H, W, Cout, Cin, 1, st)
-            _lib.check(code, "mpf_gemm3_conv3x3")
+            if ctx.h2:
+                _lib.call("mpf_gemm3_conv3x3_h2", x.device, gy.data_ptr(), gy_am.data_ptr(), pb.data_ptr(), pb_am.data_ptr(), None,
+                          dx.data_ptr(), None, N, H, W, Cout, Cin, 1, st)
+            else:
+                _lib.call("mpf_gemm3_conv3x3", x.device, gy.data_ptr(), pb.data_ptr(), None, dx.data_ptr(), N, H, W, Cout, Cin, 1, st)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             if W % 8 == 0 and Cin % 128 == 0:
                 dw, db = _wgrad_native(gy, x, N, H, W, Cin, Cout, ctx.has_bias, (gy_am, x_am) if ctx.h2 else None)
@@ -107,15 +99,12 @@ def _wgrad_native(gy, x, N, H, W, Cin, Cout, has_bias, amax_ab=None):
     ns = -(-R // rps)
     c = torch.empty((ns, Cout, 9 * Cin), dtype=torch.float32, device=x.device)
     ca = torch.empty((ns, Cout), dtype=torch.float32, device=x.device) if has_bias else None
-    with _lib.device_guard(x.device):
-        if amax_ab is not None:
-            code = _lib.lib().mpf_gemm3_conv3x3_wgrad_h2(gy.data_ptr(), amax_ab[0].data_ptr(), x.data_ptr(), amax_ab[1].data_ptr(), c.data_ptr(),
-                                                         ca.data_ptr() if has_bias else None, N, H, W, Cin, Cout, rps,
-                                                         _lib.stream_ptr(x.device))
-        else:
-            code = _lib.lib().mpf_gemm3_conv3x3_wgrad(gy.data_ptr(), x.data_ptr(), c.data_ptr(), ca.data_ptr() if has_bias else None, N, H, W,
-                                                      Cin, Cout, rps, _lib.stream_ptr(x.device))
-    _lib.check(code, "mpf_gemm3_conv3x3_wgrad")
+    if amax_ab is not None:
+        _lib.call("mpf_gemm3_conv3x3_wgrad_h2", x.device, gy.data_ptr(), amax_ab[0].data_ptr(), x.data_ptr(), amax_ab[1].data_ptr(),
+                  c.data_ptr(), _lib.ptr(ca), N, H, W, Cin, Cout, rps, _lib.stream_ptr(x.device))
+    else:
+        _lib.call("mpf_gemm3_conv3x3_wgrad", x.device, gy.data_ptr(), x.data_ptr(), c.data_ptr(), _lib.ptr(ca), N, H, W, Cin, Cout, rps,
+                  _lib.stream_ptr(x.device))
     dw2, db = nt_reduce(c, ca)
     return dw2.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2), db
 

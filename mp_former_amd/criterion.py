@@ -53,7 +53,7 @@ def strided_stack(ts):
     return base.as_strided((len(ts),) + tuple(shape), (delta,) + tuple(stride), so[0]), order
 
 
-_DT = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}
+_CLASS_LOSS_DTYPES = (torch.float32, torch.bfloat16)    # what the native class loss reads
 
 
 def _native_tail():
@@ -74,12 +74,10 @@ class _ClassLossFn(torch.autograd.Function):
         weight = weight.float().contiguous()
         lse = torch.empty((3, L, N * Q), dtype=torch.float32, device=dev)    # log-sum-exp of the rows + the kernel's row scratch
         out = torch.empty((2, L), dtype=torch.float32, device=dev)           # ce, wsum
-        with _lib.device_guard(dev):
-            code = _lib.lib().mpf_class_loss_forward(
-                logits.data_ptr(), _DT[logits.dtype], logits.stride(0), logits.stride(1), logits.stride(2), target.data_ptr(),
-                per_output, weight.data_ptr(), L, N, Q, C, lse.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
-                _lib.stream_ptr(dev))
-        _lib.check(code, "mpf_class_loss_forward")
+        _lib.call("mpf_class_loss_forward", dev,
+                  logits.data_ptr(), _lib.DTYPE[logits.dtype], logits.stride(0), logits.stride(1), logits.stride(2), target.data_ptr(),
+                  per_output, weight.data_ptr(), L, N, Q, C, lse.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                  _lib.stream_ptr(dev))
         ctx.save_for_backward(logits, target, weight, lse, out)
         ctx.per_output = per_output
         return out[0]
@@ -91,12 +89,10 @@ class _ClassLossFn(torch.autograd.Function):
         dev = logits.device
         g = g.float().contiguous()
         d = torch.empty((L, N, Q, C), dtype=logits.dtype, device=dev)
-        with _lib.device_guard(dev):
-            code = _lib.lib().mpf_class_loss_backward(
-                logits.data_ptr(), _DT[logits.dtype], logits.stride(0), logits.stride(1), logits.stride(2), target.data_ptr(),
-                ctx.per_output, weight.data_ptr(), L, N, Q, C, lse.data_ptr(), out[1].data_ptr(), g.data_ptr(), d.data_ptr(),
-                _lib.stream_ptr(dev))
-        _lib.check(code, "mpf_class_loss_backward")
+        _lib.call("mpf_class_loss_backward", dev,
+                  logits.data_ptr(), _lib.DTYPE[logits.dtype], logits.stride(0), logits.stride(1), logits.stride(2), target.data_ptr(),
+                  ctx.per_output, weight.data_ptr(), L, N, Q, C, lse.data_ptr(), out[1].data_ptr(), g.data_ptr(), d.data_ptr(),
+                  _lib.stream_ptr(dev))
         return d, None, None
 
 
@@ -109,10 +105,8 @@ class _MaskLossFinalizeFn(torch.autograd.Function):
         n, G = sums.shape[0], norm.shape[0]
         sums = sums.contiguous()
         out = torch.empty((2, G), dtype=torch.float32, device=sums.device)
-        with _lib.device_guard(sums.device):
-            code = _lib.lib().mpf_mask_loss_finalize(sums.data_ptr(), runs.data_ptr(), norm.data_ptr(), n, G, points, out.data_ptr(),
-                                                     _lib.stream_ptr(sums.device))
-        _lib.check(code, "mpf_mask_loss_finalize")
+        _lib.call("mpf_mask_loss_finalize", sums.device, sums.data_ptr(), runs.data_ptr(), norm.data_ptr(), n, G, points, out.data_ptr(),
+                  _lib.stream_ptr(sums.device))
         ctx.save_for_backward(sums, runs, norm)
         ctx.points = points
         return out
@@ -123,11 +117,8 @@ class _MaskLossFinalizeFn(torch.autograd.Function):
         n, G = sums.shape[0], norm.shape[0]
         g = g.float().contiguous()
         d = torch.empty_like(sums)
-        with _lib.device_guard(sums.device):
-            code = _lib.lib().mpf_mask_loss_finalize_backward(sums.data_ptr(), runs.data_ptr(), norm.data_ptr(), n, G, ctx.points,
-                                                              g.data_ptr(), d.data_ptr(),
-                                                              _lib.stream_ptr(sums.device))
-        _lib.check(code, "mpf_mask_loss_finalize_backward")
+        _lib.call("mpf_mask_loss_finalize_backward", sums.device, sums.data_ptr(), runs.data_ptr(), norm.data_ptr(), n, G, ctx.points,
+                  g.data_ptr(), d.data_ptr(), _lib.stream_ptr(sums.device))
         return d, None, None, None
 
 
@@ -164,7 +155,7 @@ class SetCriterion(nn.Module):
         """logits [L,N,Q,K+1], target_classes [L,N,Q] (or [N,Q], shared) -> per-output weighted CE [L]
         (F.cross_entropy with class weights = sum w_y nll / sum w_y, criterion.py:123-139)."""
         L = logits.shape[0]
-        if (_native_tail() and logits.is_cuda and logits.dim() == 4 and logits.stride(3) == 1 and logits.dtype in _DT
+        if (_native_tail() and logits.is_cuda and logits.dim() == 4 and logits.stride(3) == 1 and logits.dtype in _CLASS_LOSS_DTYPES
                 and logits.shape[3] <= 256):
             return _ClassLossFn.apply(logits, target_classes, self.empty_weight)
         if target_classes.dim() == 2:

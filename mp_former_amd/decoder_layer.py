@@ -224,9 +224,7 @@ class DecoderLayerFn(Function):
         sc = _lib.scratch("decoder_scratch", dev, stream, sc_bytes)
         ws = _lib.scratch("attn", dev, stream, ws_bytes)
         L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
-        with _lib.device_guard(dev):
-            code = lib.mpf_decoder_layer_forward(ctypes.byref(L), stream)
-        _lib.check(code, "mpf_decoder_layer_forward")
+        _lib.call("mpf_decoder_layer_forward", dev, ctypes.byref(L), stream)
         ctx.save_for_backward(xb0, k_c, v_c, mask_c, mask_s, arena, *params)
         ctx.layer = L
         ctx.kv_pack = kv_pack
@@ -284,9 +282,7 @@ class DecoderLayerFn(Function):
         sc = _lib.scratch("decoder_scratch", dev, stream, sc_bytes)
         ws = _lib.scratch("attn", dev, stream, ws_bytes)
         L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
-        with _lib.device_guard(dev):
-            code = lib.mpf_decoder_layer_backward(ctypes.byref(L), ctypes.byref(G), stream)
-        _lib.check(code, "mpf_decoder_layer_backward")
+        _lib.call("mpf_decoder_layer_backward", dev, ctypes.byref(L), ctypes.byref(G), stream)
         grads, wi, li = [], 0, 0
         lns = d_ln.unbind(0)
         for ln in _IS_LN:

@@ -122,10 +122,8 @@ def _audit(name, t, slot):
             _guard["counters"] = torch.zeros((_GUARD_SLOTS, 2), dtype=torch.int64, device=t.device)
         i = _guard["names"].setdefault(name, len(_guard["names"]))
         if i < _GUARD_SLOTS and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] % 4 == 0 and t.stride(0) % 4 == 0:
-            with _lib.device_guard(t.device):
-                code = _lib.lib().mpf_h2_range_stats(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0), slot.data_ptr(), RANGE_GUARD_LOG2,
-                                                     _guard["counters"][i].data_ptr(), _lib.stream_ptr(t.device))
-            _lib.check(code, "mpf_h2_range_stats")
+            _lib.call("mpf_h2_range_stats", t.device, t.data_ptr(), t.shape[0], t.shape[1], t.stride(0), slot.data_ptr(), RANGE_GUARD_LOG2,
+                      _guard["counters"][i].data_ptr(), _lib.stream_ptr(t.device))
     if RANGE_AUDIT is None:
         return
     from .gemm3 import amax_value
@@ -322,9 +320,7 @@ def _native_forward(x, x_am, q_am, pos_full, pos_am, prm, planes, b288_all, ams,
     call = MpfEncoderCall(N, S, M, L, P, nl, F, 0, _EPS, 0.0, host_shapes.data_ptr(), meta["shapes"].data_ptr(), meta["lsi"].data_ptr(),
                           meta["ref"].data_ptr(), pos_full.data_ptr(), pos_am.data_ptr(), x.data_ptr(), x_am.data_ptr(), q.data_ptr(),
                           q_am.data_ptr(), tab.ctypes.data)
-    with _lib.device_guard(x.device):
-        code = lib.mpf_encoder_forward(ctypes.byref(call), _lib.stream_ptr(x.device))
-    _lib.check(code, "mpf_encoder_forward")
+    _lib.call("mpf_encoder_forward", x.device, ctypes.byref(call), _lib.stream_ptr(x.device))
     saved, members = [], _arena_members((N, S), C, F, no3, M, L, P)
     for am, a in zip(ams, arena):
         t = {k: a[offs[k][0]:sum(offs[k])].view(dt).view(shape) for k, shape, dt in members}      # the layer's arena slice by member
@@ -443,9 +439,7 @@ def _native_backward(gout, prm, saved, planes_t, meta, dims, rps, split_level):
                              t["ds2"], t["dh"], t["dx1"], t["ds1"], t["dao"], t["gv"], t["draw"], (ctypes.c_void_p * 2)(t["dq0"], t["dq1"]),
                              (ctypes.c_void_p * 2)(t["g0"], t["g1"]), t["cpart"], t["cs"], t["pgroup"],
                              ln_parts.data_ptr(), ln_stride, ws.data_ptr(), ws.numel(), dgb.data_ptr(), tab.ctypes.data)
-    with _lib.device_guard(dev):
-        code = lib.mpf_encoder_backward(ctypes.byref(call), stream)
-    _lib.check(code, "mpf_encoder_backward")
+    _lib.call("mpf_encoder_backward", dev, ctypes.byref(call), stream)
     dprm = []
     for o_ in out:
         dw288, db288 = o_[oo["dw288"]:oo["lvl"]].view(no3, C), o_[oo["db288"]:]

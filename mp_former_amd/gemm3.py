@@ -11,16 +11,11 @@ import torch
 from . import _lib
 
 
-def _stream(t):
-    return _lib.stream_ptr(t.device)
-
-
 def split_weight(w, transpose=False):
     assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous()
     r, c = w.shape
     out = torch.empty((3, c, r) if transpose else (3, r, c), dtype=torch.bfloat16, device=w.device)
-    _lib.check(_lib.lib().mpf_gemm3_split(w.data_ptr(), r, c, 1 if transpose else 0, out.data_ptr(), _stream(w)),
-               "mpf_gemm3_split")
+    _lib.call("mpf_gemm3_split", w.device, w.data_ptr(), r, c, 1 if transpose else 0, out.data_ptr(), _lib.stream_ptr(w.device))
     return out
 
 
@@ -52,9 +47,7 @@ def split_weights_grouped(groups):
             r0 += t.shape[0]
         outs.append(buf[off:off + 3 * n].view((3, K, R) if tr else (3, R, K)))
     items = upload(np.asarray(rows_tab, dtype=np.int64).reshape(-1), dev)
-    with _lib.device_guard(dev):
-        code = _lib.lib().mpf_gemm3_split_grouped(items.data_ptr(), len(rows_tab), blk, _stream(buf))
-    _lib.check(code, "mpf_gemm3_split_grouped")
+    _lib.call("mpf_gemm3_split_grouped", dev, items.data_ptr(), len(rows_tab), blk, _lib.stream_ptr(dev))
     return outs
 
 
@@ -76,9 +69,7 @@ def amax(t, out=None):
     assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     if out is None:
         out = torch.zeros(AMAX_SLOT, dtype=torch.float32, device=t.device)
-    with _lib.device_guard(t.device):
-        code = _lib.lib().mpf_amax_f32(t.data_ptr(), t.numel(), out.data_ptr(), _stream(t))
-    _lib.check(code, "mpf_amax_f32")
+    _lib.call("mpf_amax_f32", t.device, t.data_ptr(), t.numel(), out.data_ptr(), _lib.stream_ptr(t.device))
     return out
 
 
@@ -121,11 +112,8 @@ def split_weights_grouped_h2(groups):
             r0 += t.shape[0]
         outs.append((buf[off:off + 2 * n].view((2, K, R) if tr else (2, R, K)), slots[slot_src]))
     both = upload(np.asarray([x for row in am_tab for x in row] + [x for row in sp_tab for x in row], dtype=np.int64), dev)
-    with _lib.device_guard(dev):
-        code = _lib.lib().mpf_amax_f32_grouped(both.data_ptr(), len(am_tab), ablk, _stream(buf))
-        _lib.check(code, "mpf_amax_f32_grouped")
-        code = _lib.lib().mpf_gemm3_split_grouped_h2(both.data_ptr() + 8 * 4 * len(am_tab), len(sp_tab), sblk, _stream(buf))
-    _lib.check(code, "mpf_gemm3_split_grouped_h2")
+    _lib.call("mpf_amax_f32_grouped", dev, both.data_ptr(), len(am_tab), ablk, _lib.stream_ptr(dev))
+    _lib.call("mpf_gemm3_split_grouped_h2", dev, both.data_ptr() + 8 * 4 * len(am_tab), len(sp_tab), sblk, _lib.stream_ptr(dev))
     return outs
 
 
@@ -138,13 +126,11 @@ def gemm3_h2(a, a_amax, planes, w_amax, bias=None, cin=None, cin2=None, gate=Non
     N = planes.shape[1]
     assert planes.shape[2] == K
     c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_gemm3_tn_h2(
-            a.data_ptr(), a.stride(0), a_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), _p(bias),
-            _p(cin), _rows(cin, N) if cin is not None else 0, _p(cin2), _rows(cin2, N) if cin2 is not None else 0,
-            _p(gate), _rows(gate, N) if gate is not None else 0, c.data_ptr(), c.stride(0), _p(out_amax), M, N, K, 1 if relu else 0,
-            _stream(a))
-    _lib.check(code, "mpf_gemm3_tn_h2")
+    _lib.call("mpf_gemm3_tn_h2", a.device,
+              a.data_ptr(), a.stride(0), a_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), _lib.ptr(bias),
+              _lib.ptr(cin), _rows(cin, N) if cin is not None else 0, _lib.ptr(cin2), _rows(cin2, N) if cin2 is not None else 0,
+              _lib.ptr(gate), _rows(gate, N) if gate is not None else 0, c.data_ptr(), c.stride(0), _lib.ptr(out_amax), M, N, K,
+              1 if relu else 0, _lib.stream_ptr(a.device))
     return c
 
 
@@ -162,17 +148,12 @@ def gemm3_h2_bits(a, a_amax, planes, w_amax, bias=None, cin=None, cin2=None, gat
         assert gate_bits.dtype == torch.uint8 and gate_bits.shape == (M, N // 8) and gate_bits.is_contiguous()
     c = torch.empty((M, N), dtype=torch.float32, device=a.device)
     bits = torch.empty((M, N // 8), dtype=torch.uint8, device=a.device) if want_bits else None
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_gemm3_tn_h2_bits(
-            a.data_ptr(), a.stride(0), a_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), _p(bias),
-            _p(cin), _rows(cin, N) if cin is not None else 0, _p(cin2), _rows(cin2, N) if cin2 is not None else 0,
-            _p(gate_bits), N // 8, c.data_ptr(), c.stride(0), _p(out_amax), _p(bits), N // 8, M, N, K, 1 if relu else 0, _stream(a))
-    _lib.check(code, "mpf_gemm3_tn_h2_bits")
+    _lib.call("mpf_gemm3_tn_h2_bits", a.device,
+              a.data_ptr(), a.stride(0), a_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), _lib.ptr(bias),
+              _lib.ptr(cin), _rows(cin, N) if cin is not None else 0, _lib.ptr(cin2), _rows(cin2, N) if cin2 is not None else 0,
+              _lib.ptr(gate_bits), N // 8, c.data_ptr(), c.stride(0), _lib.ptr(out_amax), _lib.ptr(bits), N // 8, M, N, K,
+              1 if relu else 0, _lib.stream_ptr(a.device))
     return (c, bits) if want_bits else c
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _rows(t, n):
@@ -192,13 +173,11 @@ def gemm3(a, planes, bias=None, a2=None, cin=None, cin2=None, gate=None, relu=Fa
         assert a2.dtype == torch.float32 and a2.dim() == 2 and a2.is_contiguous() and a2.shape[1] == K
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_gemm3_tn(
-            a.data_ptr(), a.stride(0), _p(a2), a2.shape[0] if a2 is not None else 0, planes.data_ptr(), _p(bias),
-            _p(cin), _rows(cin, N) if cin is not None else 0, _p(cin2), _rows(cin2, N) if cin2 is not None else 0,
-            _p(gate), _rows(gate, N) if gate is not None else 0, c.data_ptr(), c.stride(0), M, N, K,
-            1 if relu else 0, _stream(a))
-    _lib.check(code, "mpf_gemm3_tn")
+    _lib.call("mpf_gemm3_tn", a.device,
+              a.data_ptr(), a.stride(0), _lib.ptr(a2), a2.shape[0] if a2 is not None else 0, planes.data_ptr(), _lib.ptr(bias),
+              _lib.ptr(cin), _rows(cin, N) if cin is not None else 0, _lib.ptr(cin2), _rows(cin2, N) if cin2 is not None else 0,
+              _lib.ptr(gate), _rows(gate, N) if gate is not None else 0, c.data_ptr(), c.stride(0), M, N, K,
+              1 if relu else 0, _lib.stream_ptr(a.device))
     return c
 
 
@@ -248,18 +227,16 @@ def gemm3_nt(a, b, rows_per_split, b2=None, want_csum_a=False, want_csum_b=False
     cb = torch.empty((ns, N), dtype=torch.float32, device=a.device) if want_csum_b else None
     if b2 is not None:
         assert b2.dtype == torch.float32 and b2.dim() == 2 and b2.stride(1) == 1 and b2.shape[1] == N
-    with _lib.device_guard(a.device):
-        if amax_ab is not None:
-            assert b2 is None
-            code = _lib.lib().mpf_gemm3_nt_h2(
-                a.data_ptr(), a.stride(0), amax_ab[0].data_ptr(), b.data_ptr(), b.stride(0), amax_ab[1].data_ptr(), c.data_ptr(),
-                _p(ca), _p(cb), R, M, N, rows_per_split, 1 if transpose_out else 0, _stream(a))
-        else:
-            code = _lib.lib().mpf_gemm3_nt(
-                a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), _p(b2), b2.stride(0) if b2 is not None else 0,
-                b2.shape[0] if b2 is not None else 0, c.data_ptr(), _p(ca), _p(cb), R, M, N, rows_per_split,
-                1 if transpose_out else 0, _stream(a))
-    _lib.check(code, "mpf_gemm3_nt")
+    if amax_ab is not None:
+        assert b2 is None
+        _lib.call("mpf_gemm3_nt_h2", a.device,
+                  a.data_ptr(), a.stride(0), amax_ab[0].data_ptr(), b.data_ptr(), b.stride(0), amax_ab[1].data_ptr(), c.data_ptr(),
+                  _lib.ptr(ca), _lib.ptr(cb), R, M, N, rows_per_split, 1 if transpose_out else 0, _lib.stream_ptr(a.device))
+    else:
+        _lib.call("mpf_gemm3_nt", a.device,
+                  a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), _lib.ptr(b2), b2.stride(0) if b2 is not None else 0,
+                  b2.shape[0] if b2 is not None else 0, c.data_ptr(), _lib.ptr(ca), _lib.ptr(cb), R, M, N, rows_per_split,
+                  1 if transpose_out else 0, _lib.stream_ptr(a.device))
     return c, ca, cb
 
 
@@ -291,10 +268,8 @@ def gemm3_nt_grouped(pairs, rows_per_split, amax_pairs=None):
         else:
             items[i] = (g.data_ptr(), g.stride(0), amax_pairs[i][0].data_ptr(), x.data_ptr(), x.stride(0), amax_pairs[i][1].data_ptr(),
                         base + 4 * o, base + 4 * (o + M * N), M, N)
-    with _lib.device_guard(dev):
-        fn = _lib.lib().mpf_gemm3_nt_grouped if amax_pairs is None else _lib.lib().mpf_gemm3_nt_grouped_h2
-        code = fn(items.ctypes.data, len(pairs), R, rows_per_split, tot, _stream(part))
-    _lib.check(code, "mpf_gemm3_nt_grouped")
+    _lib.call("mpf_gemm3_nt_grouped" if amax_pairs is None else "mpf_gemm3_nt_grouped_h2", dev,
+              items.ctypes.data, len(pairs), R, rows_per_split, tot, _lib.stream_ptr(dev))
     out, _ = nt_reduce(part)
     res = []
     for (g, x), o in zip(pairs, offs):
@@ -310,10 +285,8 @@ def nt_reduce(c_part, s_part=None):
     s = torch.empty(s_part.shape[1:], dtype=torch.float32, device=c_part.device) if s_part is not None else None
     if c.numel() % 4 or (s is not None and s.numel() % 4):
         return c_part.sum(0), (s_part.sum(0) if s_part is not None else None)
-    with _lib.device_guard(c_part.device):
-        code = _lib.lib().mpf_gemm3_nt_reduce(c_part.data_ptr(), c.numel(), _p(s_part), s.numel() if s is not None else 0, ns,
-                                              c.data_ptr(), _p(s), _stream(c_part))
-    _lib.check(code, "mpf_gemm3_nt_reduce")
+    _lib.call("mpf_gemm3_nt_reduce", c_part.device, c_part.data_ptr(), c.numel(), _lib.ptr(s_part), s.numel() if s is not None else 0, ns,
+              c.data_ptr(), _lib.ptr(s), _lib.stream_ptr(c_part.device))
     return c, s
 
 
@@ -326,10 +299,8 @@ def nt_reduce_levels(c_part, s_part, level_of_split, n_levels):
     lvl = torch.empty((n_levels, n), dtype=torch.float32, device=c_part.device)
     s = torch.empty((n,), dtype=torch.float32, device=c_part.device)
     assert level_of_split.dtype == torch.int64 and level_of_split.numel() == ns and c.numel() % 4 == 0 and n % 4 == 0 and n_levels <= 4
-    with _lib.device_guard(c_part.device):
-        code = _lib.lib().mpf_gemm3_nt_reduce_levels(c_part.data_ptr(), c.numel(), s_part.data_ptr(), n, ns, level_of_split.data_ptr(),
-                                                     n_levels, c.data_ptr(), lvl.data_ptr(), s.data_ptr(), _stream(c_part))
-    _lib.check(code, "mpf_gemm3_nt_reduce_levels")
+    _lib.call("mpf_gemm3_nt_reduce_levels", c_part.device, c_part.data_ptr(), c.numel(), s_part.data_ptr(), n, ns,
+              level_of_split.data_ptr(), n_levels, c.data_ptr(), lvl.data_ptr(), s.data_ptr(), _lib.stream_ptr(c_part.device))
     return c, lvl, s
 
 
@@ -341,12 +312,9 @@ def gemm3_ex(a, planes, bias=None, cin=None, relu=False, out_dtype=torch.float32
     N = planes.shape[1]
     assert planes.shape[2] == K and planes.dtype == torch.bfloat16 and planes.is_contiguous()
     c = torch.empty((M, N), dtype=out_dtype, device=a.device)
-    dt = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_gemm3_tn_ex(a.data_ptr(), dt[a.dtype], a.stride(0), planes.data_ptr(), _p(bias), _p(cin),
-                                          _rows(cin, N) if cin is not None else 0, c.data_ptr(), dt[out_dtype], N, M, N, K,
-                                          1 if relu else 0, _stream(a))
-    _lib.check(code, "mpf_gemm3_tn_ex")
+    _lib.call("mpf_gemm3_tn_ex", a.device, a.data_ptr(), _lib.DTYPE[a.dtype], a.stride(0), planes.data_ptr(), _lib.ptr(bias), _lib.ptr(cin),
+              _rows(cin, N) if cin is not None else 0, c.data_ptr(), _lib.DTYPE[out_dtype], N, M, N, K,
+              1 if relu else 0, _lib.stream_ptr(a.device))
     return c
 
 
@@ -359,9 +327,6 @@ def gemm3_nt_ex(a, b, rows_per_split, want_csum_a=False):
     ns = (R + rows_per_split - 1) // rows_per_split
     c = torch.empty((ns, M, N), dtype=torch.float32, device=a.device)
     ca = torch.empty((ns, M), dtype=torch.float32, device=a.device) if want_csum_a else None
-    dt = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_gemm3_nt_ex(a.data_ptr(), dt[a.dtype], a.stride(0), b.data_ptr(), dt[b.dtype], b.stride(0), c.data_ptr(),
-                                          _p(ca), R, M, N, rows_per_split, _stream(a))
-    _lib.check(code, "mpf_gemm3_nt_ex")
+    _lib.call("mpf_gemm3_nt_ex", a.device, a.data_ptr(), _lib.DTYPE[a.dtype], a.stride(0), b.data_ptr(), _lib.DTYPE[b.dtype], b.stride(0),
+              c.data_ptr(), _lib.ptr(ca), R, M, N, rows_per_split, _lib.stream_ptr(a.device))
     return c, ca

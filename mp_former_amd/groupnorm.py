@@ -16,10 +16,8 @@ from . import _lib
 
 def _transpose(src, B, R, C, in_bs=None):
     out = torch.empty(B * R * C, dtype=torch.float32, device=src.device)
-    with _lib.device_guard(src.device):
-        code = _lib.lib().mpf_transpose_f32(src.data_ptr(), R * C if in_bs is None else in_bs, out.data_ptr(), R * C, B, R, C,
-                                            _lib.stream_ptr(src.device))
-    _lib.check(code, "mpf_transpose_f32")
+    _lib.call("mpf_transpose_f32", src.device, src.data_ptr(), R * C if in_bs is None else in_bs, out.data_ptr(), R * C, B, R, C,
+              _lib.stream_ptr(src.device))
     return out
 
 
@@ -61,10 +59,8 @@ class _GroupNormFn(Function):
         lib = _lib.lib()
         stream = _lib.stream_ptr(x.device)
         ws = _lib.scratch("gn", x.device, stream, lib.mpf_group_stats_workspace_bytes(rows, row_len))
-        with _lib.device_guard(x.device):
-            code = lib.mpf_group_stats(x.data_ptr(), rows, row_len, float(eps), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), stream)
-        _lib.check(code, "mpf_group_stats")
+        _lib.call("mpf_group_stats", x.device, x.data_ptr(), rows, row_len, float(eps), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
+                  ws.numel(), stream)
         # y = x * a + b with a[n, c] = rstd[n, g] * gamma[c], b[n, c] = beta[c] - mean[n, g] * a[n, c]
         a = (rstd.view(N, groups, 1) * weight.view(1, groups, C // groups)).view(N, C)
         b = (bias.view(1, groups, C // groups) - mean.view(N, groups, 1) * a.view(N, groups, C // groups)).view(N, C)
@@ -109,12 +105,9 @@ class _GroupNormCLFn(Function):
         y = _cl_empty(N, C, H, W, x.device)
         stream = _lib.stream_ptr(x.device)
         ws = _lib.scratch("gn", x.device, stream, lib.mpf_gn_cl_workspace_bytes(N, H * W, C, groups))
-        with _lib.device_guard(x.device):
-            code = lib.mpf_gn_cl_forward(x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(), N, H * W, C, groups, float(eps),
-                                         1 if relu else 0, top.data_ptr() if top is not None else None,
-                                         top.stride(0) if top is not None else 0, W, y.data_ptr(), y.stride(0), mean.data_ptr(),
-                                         rstd.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(code, "mpf_gn_cl_forward")
+        _lib.call("mpf_gn_cl_forward", x.device, x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(), N, H * W, C, groups,
+                  float(eps), 1 if relu else 0, _lib.ptr(top), top.stride(0) if top is not None else 0, W, y.data_ptr(), y.stride(0),
+                  mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         ctx.save_for_backward(x, weight, bias, mean, rstd)
         ctx.groups, ctx.relu, ctx.has_top = groups, bool(relu), top is not None
         return y
@@ -134,16 +127,13 @@ class _GroupNormCLFn(Function):
         stream = _lib.stream_ptr(x.device)
         ws = _lib.scratch("gn", x.device, stream, lib.mpf_gn_cl_workspace_bytes(N, H * W, C, ctx.groups))
         dtop = None
-        with _lib.device_guard(x.device):
-            code = lib.mpf_gn_cl_backward(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(),
-                                          mean.data_ptr(), rstd.data_ptr(), N, H * W, C, ctx.groups, 1 if ctx.relu else 0,
-                                          dx.data_ptr(), dx.stride(0), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-            _lib.check(code, "mpf_gn_cl_backward")
-            if ctx.has_top and ctx.needs_input_grad[6]:
-                dtop = _cl_empty(N, C, H // 2, W // 2, x.device)
-                code = lib.mpf_upsample2x_cl_backward(gy.data_ptr(), gy.stride(0), N, H // 2, W // 2, C, dtop.data_ptr(),
-                                                      dtop.stride(0), stream)
-                _lib.check(code, "mpf_upsample2x_cl_backward")
+        _lib.call("mpf_gn_cl_backward", x.device, gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(),
+                  mean.data_ptr(), rstd.data_ptr(), N, H * W, C, ctx.groups, 1 if ctx.relu else 0,
+                  dx.data_ptr(), dx.stride(0), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        if ctx.has_top and ctx.needs_input_grad[6]:
+            dtop = _cl_empty(N, C, H // 2, W // 2, x.device)
+            _lib.call("mpf_upsample2x_cl_backward", x.device, gy.data_ptr(), gy.stride(0), N, H // 2, W // 2, C, dtop.data_ptr(),
+                      dtop.stride(0), stream)
         return dx, dg, db, None, None, None, dtop
 
 
@@ -164,17 +154,15 @@ class _GroupNormFlattenFn(Function):
         stats = []
         stream = _lib.stream_ptr(dev)
         off = 0
-        with _lib.device_guard(dev):
-            for x, w, b, hw in zip(xs, ws, bs, sizes):
-                mean = torch.empty(N * groups, dtype=torch.float32, device=dev)
-                rstd = torch.empty(N * groups, dtype=torch.float32, device=dev)
-                wsb = _lib.scratch("gn", dev, stream, lib.mpf_gn_cl_workspace_bytes(N, hw, C, groups))
-                code = lib.mpf_gn_cl_forward(x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), N, hw, C, groups, float(eps), 0,
-                                             None, 0, int(x.shape[3]), out.data_ptr() + off * C * 4, S * C, mean.data_ptr(),
-                                             rstd.data_ptr(), wsb.data_ptr(), wsb.numel(), stream)
-                _lib.check(code, "mpf_gn_cl_forward")
-                stats += [mean, rstd]
-                off += hw
+        for x, w, b, hw in zip(xs, ws, bs, sizes):
+            mean = torch.empty(N * groups, dtype=torch.float32, device=dev)
+            rstd = torch.empty(N * groups, dtype=torch.float32, device=dev)
+            wsb = _lib.scratch("gn", dev, stream, lib.mpf_gn_cl_workspace_bytes(N, hw, C, groups))
+            _lib.call("mpf_gn_cl_forward", dev, x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(), N, hw, C, groups, float(eps), 0,
+                      None, 0, int(x.shape[3]), out.data_ptr() + off * C * 4, S * C, mean.data_ptr(),
+                      rstd.data_ptr(), wsb.data_ptr(), wsb.numel(), stream)
+            stats += [mean, rstd]
+            off += hw
         ctx.save_for_backward(*xs, *ws, *bs, *stats)
         ctx.groups, ctx.sizes, ctx.nl = groups, sizes, len(xs)
         return out
@@ -191,20 +179,17 @@ class _GroupNormFlattenFn(Function):
         stream = _lib.stream_ptr(dev)
         grads = []
         off = 0
-        with _lib.device_guard(dev):
-            for l, (x, w, b, hw) in enumerate(zip(xs, ws, bs, ctx.sizes)):
-                H, W = int(x.shape[2]), int(x.shape[3])
-                dx = _cl_empty(N, C, H, W, dev)
-                dg = torch.empty(C, dtype=torch.float32, device=dev)
-                db = torch.empty(C, dtype=torch.float32, device=dev)
-                wsb = _lib.scratch("gn", dev, stream, lib.mpf_gn_cl_workspace_bytes(N, hw, C, ctx.groups))
-                code = lib.mpf_gn_cl_backward(g.data_ptr() + off * C * 4, S * C, x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(),
-                                              stats[2 * l].data_ptr(), stats[2 * l + 1].data_ptr(), N, hw, C, ctx.groups, 0,
-                                              dx.data_ptr(), dx.stride(0), dg.data_ptr(), db.data_ptr(), wsb.data_ptr(), wsb.numel(),
-                                              stream)
-                _lib.check(code, "mpf_gn_cl_backward")
-                grads += [dx, dg, db]
-                off += hw
+        for l, (x, w, b, hw) in enumerate(zip(xs, ws, bs, ctx.sizes)):
+            H, W = int(x.shape[2]), int(x.shape[3])
+            dx = _cl_empty(N, C, H, W, dev)
+            dg = torch.empty(C, dtype=torch.float32, device=dev)
+            db = torch.empty(C, dtype=torch.float32, device=dev)
+            wsb = _lib.scratch("gn", dev, stream, lib.mpf_gn_cl_workspace_bytes(N, hw, C, ctx.groups))
+            _lib.call("mpf_gn_cl_backward", dev, g.data_ptr() + off * C * 4, S * C, x.data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(),
+                      stats[2 * l].data_ptr(), stats[2 * l + 1].data_ptr(), N, hw, C, ctx.groups, 0,
+                      dx.data_ptr(), dx.stride(0), dg.data_ptr(), db.data_ptr(), wsb.data_ptr(), wsb.numel(), stream)
+            grads += [dx, dg, db]
+            off += hw
         return (None, None) + tuple(grads)
 
 

@@ -12,16 +12,14 @@ Deviations from the reference, by design:
 * ``instances`` are sorted by score, descending (the reference's ``topk(sorted=False)`` order is unspecified);
 * all results are fp32 whatever the mask dtype (bf16 logits are widened on load; the reference would compute in bf16).
 """
-import ctypes
 from dataclasses import dataclass, field
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import MPF_BF16, MPF_F32
 
-_DTYPES = {torch.float32: MPF_F32, torch.bfloat16: MPF_BF16}
+_MASK_DTYPES = (torch.float32, torch.bfloat16)
 
 
 @dataclass
@@ -148,15 +146,11 @@ def _geom(masks_n, image_size, padded_hw, out_hw):
 
 def _masks_arg(pm):
     """(pointer of image 0, stride_q, dtype code) of [N, Q, h, w] logits whose [h, w] planes are contiguous."""
-    if pm.dtype not in _DTYPES:
+    if pm.dtype not in _MASK_DTYPES:
         raise TypeError(f"pred_masks must be float32 or bfloat16, got {pm.dtype}")
     if not (pm.stride(-1) == 1 and pm.stride(-2) == pm.shape[-1]):
         pm = pm.contiguous()
-    return pm, pm.stride(0), pm.stride(1), _DTYPES[pm.dtype]
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+    return pm, pm.stride(0), pm.stride(1), _lib.DTYPE[pm.dtype]
 
 
 class _Image:
@@ -164,7 +158,6 @@ class _Image:
 
     def __init__(self, cls, K, thr, dev, stream, slot):
         Q = cls.shape[0]
-        L = _lib.lib()
         self.Q, self.K = Q, K
         nbytes = 4 * (Q * K + 2 * Q + Q) + 4 * (1 + 2 * Q + 3 * Q)
         ws = _lib.scratch(("seg_infer.softmax", slot), dev, stream, nbytes)
@@ -174,18 +167,18 @@ class _Image:
         # {count, kept query [Q], kept label [Q], areas [3][Q]}: one device-to-host copy for the panoptic table
         self.ints = ws[4 * (Q * K + 3 * Q):4 * (Q * K + 3 * Q) + 4 * (1 + 5 * Q)].view(torch.int32)
         self.kept, self.areas = self.ints[:1 + 2 * Q], self.ints[1 + 2 * Q:]
-        _lib.check(L.mpf_seg_softmax(_ptr(cls), Q, K + 1, float(thr), _ptr(self.probs), _ptr(self.max_score), _ptr(self.max_label),
-                                     _ptr(self.kept), _ptr(self.kept_score), stream), "mpf_seg_softmax")
+        _lib.call("mpf_seg_softmax", dev, cls.data_ptr(), Q, K + 1, float(thr), self.probs.data_ptr(), self.max_score.data_ptr(),
+                  self.max_label.data_ptr(), self.kept.data_ptr(), self.kept_score.data_ptr(), stream)
 
 
-def _semantic(L, mptr, sq, dt, geom, probs, K, dev, stream):
+def _semantic(mptr, sq, dt, geom, probs, K, dev, stream):
     H, W = geom[-2:]
     out = torch.empty((K, H, W), dtype=torch.float32, device=dev)
-    _lib.check(L.mpf_seg_semantic(mptr, sq, dt, *geom, _ptr(probs), K, _ptr(out), stream), "mpf_seg_semantic")
+    _lib.call("mpf_seg_semantic", dev, mptr, sq, dt, *geom, probs.data_ptr(), K, out.data_ptr(), stream)
     return out
 
 
-def _instances(L, mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
+def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
     Q, K = img.Q, img.K
     H, W = geom[-2:]
     k = min(int(cfg.test_topk_per_image), Q * K)
@@ -206,14 +199,14 @@ def _instances(L, mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw
         return result
     query = query.contiguous()
     scores = torch.empty(T, dtype=torch.float32, device=dev)
-    nws = L.mpf_seg_instance_workspace_bytes(T, H, W)
+    nws = _lib.lib().mpf_seg_instance_workspace_bytes(T, H, W)
     ws = _lib.scratch("seg_infer.instance", dev, stream, nws)
-    _lib.check(L.mpf_seg_instance_scores(mptr, sq, dt, *geom, _ptr(query), _ptr(sc), T, _ptr(scores), _ptr(ws), ws.numel(), stream),
-               "mpf_seg_instance_scores")
+    _lib.call("mpf_seg_instance_scores", dev, mptr, sq, dt, *geom, query.data_ptr(), sc.data_ptr(), T, scores.data_ptr(), ws.data_ptr(),
+              ws.numel(), stream)
     scores, order = scores.sort(descending=True, stable=True)
     query, labels = query[order].contiguous(), labels[order]
     masks = torch.empty((T, H, W), dtype=torch.float32, device=dev)
-    _lib.check(L.mpf_seg_instance_masks(mptr, sq, dt, *geom, _ptr(query), T, _ptr(masks), stream), "mpf_seg_instance_masks")
+    _lib.call("mpf_seg_instance_masks", dev, mptr, sq, dt, *geom, query.data_ptr(), T, masks.data_ptr(), stream)
     result.pred_masks = masks
     result.pred_boxes = Boxes(torch.zeros(T, 4))
     result.scores = scores
@@ -221,12 +214,12 @@ def _instances(L, mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw
     return result
 
 
-def _panoptic(L, mptr, sq, dt, geom, img, cfg, dev, stream):
+def _panoptic(mptr, sq, dt, geom, img, cfg, dev, stream):
     Q = img.Q
     H, W = geom[-2:]
     code = torch.empty((H, W), dtype=torch.int32, device=dev)
-    _lib.check(L.mpf_seg_panoptic_areas(mptr, sq, dt, *geom, _ptr(img.kept), _ptr(img.kept_score), _ptr(code), _ptr(img.areas), stream),
-               "mpf_seg_panoptic_areas")
+    _lib.call("mpf_seg_panoptic_areas", dev, mptr, sq, dt, *geom, img.kept.data_ptr(), img.kept_score.data_ptr(), code.data_ptr(),
+              img.areas.data_ptr(), stream)
     host = img.ints.cpu()                                # the one device-to-host copy of panoptic inference
     n = int(host[0])
     labels = host[1 + Q:1 + Q + n].tolist()
@@ -235,7 +228,7 @@ def _panoptic(L, mptr, sq, dt, geom, img, cfg, dev, stream):
                                        cfg.overlap_threshold)
     ids = torch.empty((H, W), dtype=torch.int32, device=dev)
     lut_d = torch.tensor(lut + [0], dtype=torch.int32).to(dev)
-    _lib.check(L.mpf_seg_panoptic_paint(_ptr(code), H, W, _ptr(lut_d), _ptr(ids), stream), "mpf_seg_panoptic_paint")
+    _lib.call("mpf_seg_panoptic_paint", dev, code.data_ptr(), H, W, lut_d.data_ptr(), ids.data_ptr(), stream)
     return ids, segments_info
 
 
@@ -257,7 +250,6 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
         raise ValueError(f"pred_masks {tuple(pred_masks.shape)} does not match pred_logits {tuple(pred_logits.shape)}")
     pm, sn, sq, dt = _masks_arg(pred_masks)
     dev = pm.device
-    L = _lib.lib()
     out = []
     thing_lut = None
     if cfg.instance_on and cfg.panoptic_on:
@@ -266,25 +258,24 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
             if 0 <= i < K:
                 thing_lut[i] = True
         thing_lut = thing_lut.to(dev)
-    with _lib.device_guard(dev):
-        stream = _lib.stream_ptr(dev)
-        logits = pred_logits.detach().float()
-        for n in range(N):
-            mptr = ctypes.c_void_p(pm.data_ptr() + n * sn * pm.element_size())
-            hi, wi = int(image_sizes[n][0]), int(image_sizes[n][1])
-            H, W = int(output_sizes[n][0]), int(output_sizes[n][1])
-            img = _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n)
-            res = {}
-            if cfg.semantic_on:
-                if cfg.sem_seg_postprocess_before_inference:
-                    res["sem_seg"] = _semantic(L, mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img.probs, K, dev, stream)
-                else:   # inference on the cropped padded grid, then the reference's own resize of the K planes (:264-265)
-                    r = _semantic(L, mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (hi, wi)), img.probs, K, dev, stream)
-                    res["sem_seg"] = F.interpolate(r[None], size=(H, W), mode="bilinear", align_corners=False)[0]
-            if cfg.panoptic_on:
-                res["panoptic_seg"] = _panoptic(L, mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, dev, stream)
-            if cfg.instance_on:
-                res["instances"] = _instances(L, mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, thing_lut, dev,
-                                              stream, (H, W))
-            out.append(res)
+    stream = _lib.stream_ptr(dev)
+    logits = pred_logits.detach().float()
+    for n in range(N):
+        mptr = pm.data_ptr() + n * sn * pm.element_size()
+        hi, wi = int(image_sizes[n][0]), int(image_sizes[n][1])
+        H, W = int(output_sizes[n][0]), int(output_sizes[n][1])
+        img = _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n)
+        res = {}
+        if cfg.semantic_on:
+            if cfg.sem_seg_postprocess_before_inference:
+                res["sem_seg"] = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img.probs, K, dev, stream)
+            else:   # inference on the cropped padded grid, then the reference's own resize of the K planes (:264-265)
+                r = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (hi, wi)), img.probs, K, dev, stream)
+                res["sem_seg"] = F.interpolate(r[None], size=(H, W), mode="bilinear", align_corners=False)[0]
+        if cfg.panoptic_on:
+            res["panoptic_seg"] = _panoptic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, dev, stream)
+        if cfg.instance_on:
+            res["instances"] = _instances(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, thing_lut, dev, stream,
+                                          (H, W))
+        out.append(res)
     return out

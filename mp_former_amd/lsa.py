@@ -75,13 +75,9 @@ def lsa_assign(cost, problems, n_slots, want_rows=True, want_cols=True, want_a=F
     check_status(dev)                       # a failure of an earlier step surfaces here
     st = _status_of(dev)
     pd = upload(problems.reshape(-1), dev)
-    p = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
-    with _lib.device_guard(dev):
-        code = _lib.lib().mpf_lsa_assign_status(cost.data_ptr(), pd.data_ptr(), n, max_dim, max_entries, p("rows"), p("cols"), p("a"),
-                                                p("b"), scatter_dst.data_ptr() if scatter_dst is not None else None,
-                                                scatter_src.data_ptr() if scatter_src is not None else None,
-                                                st["dev"].data_ptr(), _lib.stream_ptr(dev))
-    _lib.check(code, "mpf_lsa_assign_status")
+    p = lambda k: _lib.ptr(out.get(k))  # noqa: E731
+    _lib.call("mpf_lsa_assign_status", dev, cost.data_ptr(), pd.data_ptr(), n, max_dim, max_entries, p("rows"), p("cols"), p("a"),
+              p("b"), _lib.ptr(scatter_dst), _lib.ptr(scatter_src), st["dev"].data_ptr(), _lib.stream_ptr(dev))
     if st["event"] is None:                 # one read-back in flight at a time (16 bytes, pinned, behind the kernel)
         st["host"].copy_(st["dev"], non_blocking=True)
         st["event"] = torch.cuda.Event()

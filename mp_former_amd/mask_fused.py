@@ -20,10 +20,6 @@ from . import _lib
 from ._h2d import upload
 
 
-def _stream(dev):
-    return _lib.stream_ptr(dev)
-
-
 def _is_planes(x):
     """[N, C, H, W] whose images are dense [H*W, C] planes (channels_last), 16-byte aligned."""
     return (x.dim() == 4 and x.stride(1) == 1 and x.stride(3) == x.shape[1] and x.stride(2) == x.shape[3] * x.shape[1]
@@ -52,12 +48,9 @@ class PairPlanes(Function):
         dev = me.device
         out = torch.empty((total_slots, HW), dtype=torch.bfloat16, device=dev)
         if total_slots and max_count:
-            with _lib.device_guard(dev):
-                code = _lib.lib().mpf_pair_planes_forward(me.data_ptr(), row_off.data_ptr(),
-                                                          pair_of_slot.data_ptr() if pair_of_slot is not None else None,
-                                                          slot_first.data_ptr(), slot_count.data_ptr(), mf.data_ptr(), mf.stride(0),
-                                                          out.data_ptr(), N, HW, C, _stream(dev))
-            _lib.check(code, "mpf_pair_planes_forward")
+            _lib.call("mpf_pair_planes_forward", dev, me.data_ptr(), row_off.data_ptr(), _lib.ptr(pair_of_slot),
+                      slot_first.data_ptr(), slot_count.data_ptr(), mf.data_ptr(), mf.stride(0),
+                      out.data_ptr(), N, HW, C, _lib.stream_ptr(dev))
         ctx.save_for_backward(me, mf, row_off, pair_of_slot if pair_of_slot is not None else row_off, slot_first, slot_count)
         ctx.identity = pair_of_slot is None
         ctx.sizes = (total_slots, max_count)
@@ -83,13 +76,11 @@ class PairPlanes(Function):
             g = g.contiguous()
             lib = _lib.lib()
             ws = torch.empty(lib.mpf_pair_planes_backward_workspace_bytes(N, HW, total_slots, max_count), dtype=torch.uint8, device=dev)
-            with _lib.device_guard(dev):
-                code = lib.mpf_pair_planes_backward(
-                    g.data_ptr(), me.data_ptr(), row_off.data_ptr(), pair_of_slot.data_ptr() if pair_of_slot is not None else None,
-                    slot_first.data_ptr(), slot_count.data_ptr(), mf.data_ptr(), mf.stride(0),
-                    d_mf.data_ptr() if d_mf is not None else None, HW * C, d_me.data_ptr() if d_me is not None else None,
-                    _lib.MPF_BF16, N, HW, C, total_slots, max_count, ws.data_ptr(), ws.numel(), _stream(dev))
-            _lib.check(code, "mpf_pair_planes_backward")
+            _lib.call("mpf_pair_planes_backward", dev,
+                      g.data_ptr(), me.data_ptr(), row_off.data_ptr(), _lib.ptr(pair_of_slot),
+                      slot_first.data_ptr(), slot_count.data_ptr(), mf.data_ptr(), mf.stride(0),
+                      _lib.ptr(d_mf), HW * C, _lib.ptr(d_me),
+                      _lib.MPF_BF16, N, HW, C, total_slots, max_count, ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
         g_mf = d_mf.view(N, H, W, C).permute(0, 3, 1, 2) if d_mf is not None else None
         return d_me, g_mf, None, None, None, None, None, None
 
@@ -188,10 +179,8 @@ def match_cost_fused(views, coords, tsamp, t_first, t_count, group_view, group_i
     cost = torch.zeros((G, Q, Tmax), dtype=torch.float32, device=dev)
     lib = _lib.lib()
     ws = torch.empty(lib.mpf_match_cost_fused_workspace_bytes(G, Q, Tmax, P, tsamp.shape[0]), dtype=torch.uint8, device=dev)
-    with _lib.device_guard(dev):
-        code = lib.mpf_match_cost_fused(me.data_ptr(), first_d.data_ptr(), me.stride(1), mf.data_ptr(), mf.stride(0), i32[:G].data_ptr(),
-                                        H, W, mf.shape[1], coords.data_ptr(), tsamp.data_ptr(), tsamp.shape[0], i32[G:2 * G].data_ptr(),
-                                        i32[2 * G:].data_ptr(), cost.data_ptr(), G, Q, Tmax, P, float(w_mask), float(w_dice),
-                                        ws.data_ptr(), ws.numel(), _stream(dev))
-    _lib.check(code, "mpf_match_cost_fused")
+    _lib.call("mpf_match_cost_fused", dev, me.data_ptr(), first_d.data_ptr(), me.stride(1), mf.data_ptr(), mf.stride(0), i32[:G].data_ptr(),
+              H, W, mf.shape[1], coords.data_ptr(), tsamp.data_ptr(), tsamp.shape[0], i32[G:2 * G].data_ptr(),
+              i32[2 * G:].data_ptr(), cost.data_ptr(), G, Q, Tmax, P, float(w_mask), float(w_dice),
+              ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
     return cost

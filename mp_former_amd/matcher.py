@@ -54,9 +54,7 @@ class GTMasks:
         self.bits = None
         if self.total and (self.H * self.W) % 32 == 0:
             self.bits = torch.empty((self.total, self.H * self.W // 32), dtype=torch.int32, device=dev)
-            with _lib.device_guard(dev):
-                _lib.check(_lib.lib().mpf_pack_mask_bits(self.u8.data_ptr(), self.bits.data_ptr(), self.u8.numel(),
-                                                         _lib.stream_ptr(dev)), "mpf_pack_mask_bits")
+            _lib.call("mpf_pack_mask_bits", dev, self.u8.data_ptr(), self.bits.data_ptr(), self.u8.numel(), _lib.stream_ptr(dev))
         self.image_of_row = np.concatenate([np.full(c, b, dtype=np.int64) for b, c in enumerate(self.counts)]) \
             if self.total else np.zeros(0, dtype=np.int64)
         self.device = dev

@@ -21,7 +21,7 @@ from torch.nn.init import constant_, xavier_uniform_
 from . import _lib
 from .linear import linear_tall
 
-_DTYPES = {torch.float32: _lib.MPF_F32, torch.float64: _lib.MPF_F64}
+_DTYPES = (torch.float32, torch.float64)      # AT_DISPATCH_FLOATING_TYPES of the reference
 
 
 def _check_inputs(named):
@@ -58,10 +58,6 @@ def _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, i
     return batch, spatial_size, num_heads, channels, num_levels, num_query, num_point
 
 
-def _stream(t):
-    return _lib.stream_ptr(t.device)
-
-
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
                            host_shapes=None):
     """-> output [N, Lq, M*D]; freshly allocated, computed on the current stream.  The spatially blocked production kernel runs
@@ -75,22 +71,19 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     hs = host_shapes if host_shapes is not None else _attached_host_shapes(spatial_shapes, level_start_index)
     lib = _lib.lib()
-    stream = _stream(value)
-    with _lib.device_guard(value.device):
-        if hs is None and _dev_applicable(value, D, L, P):
-            # the reference's call (func.py:36): device tensors only -> geometry derived on the device, same blocked kernel
-            ws = _lib.scratch("msda_dev", value.device, stream, lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 0), zeroed=True)
-            code = lib.mpf_msda_forward_dev(
-                value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                attn_weight.data_ptr(), out.data_ptr(), N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(),
-                stream)
-        else:
-            code = lib.mpf_msda_forward_hs(
-                value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                hs.data_ptr() if hs is not None else None,
-                sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], stream)
-    _lib.check(code, "mpf_msda_forward")
+    stream = _lib.stream_ptr(value.device)
+    if hs is None and _dev_applicable(value, D, L, P):
+        # the reference's call (func.py:36): device tensors only -> geometry derived on the device, same blocked kernel
+        ws = _lib.scratch("msda_dev", value.device, stream, lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 0), zeroed=True)
+        _lib.call("mpf_msda_forward_dev", value.device,
+                  value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+                  attn_weight.data_ptr(), out.data_ptr(), N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(),
+                  stream)
+    else:
+        _lib.call("mpf_msda_forward_hs", value.device,
+                  value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), _lib.ptr(hs),
+                  sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(),
+                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], stream)
     return out
 
 
@@ -175,14 +168,12 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         lib = _lib.lib()
         need = lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 1)
         if need:
-            stream = _stream(value)
+            stream = _lib.stream_ptr(value.device)
             ws = _lib.scratch("msda_dev", value.device, stream, need, zeroed=True)
-            with _lib.device_guard(value.device):
-                code = lib.mpf_msda_backward_dev(
-                    value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                    attn_weight.data_ptr(), grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-                    N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), stream)
-            _lib.check(code, "mpf_msda_backward_dev")
+            _lib.call("mpf_msda_backward_dev", value.device,
+                      value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+                      attn_weight.data_ptr(), grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
+                      N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(), stream)
             return [gv, gl, ga]
     if BWD_MODE == "binned" and hs is None:
         raise RuntimeError("MSDA binned backward requested but not applicable (needs fp32, D=32, L<=8, L*P<=32, host shapes)")
@@ -191,22 +182,18 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         need = lib.mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, hs.data_ptr())
         if need == 0:
             raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
-        stream = _stream(value)
+        stream = _lib.stream_ptr(value.device)
         ws = _lib.scratch("msda_host", value.device, stream, need)
-        with _lib.device_guard(value.device):
-            code = lib.mpf_msda_backward_ws(
-                value.data_ptr(), hs.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), stream)
-        _lib.check(code, "mpf_msda_backward_ws")
+        _lib.call("mpf_msda_backward_ws", value.device,
+                  value.data_ptr(), hs.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                  grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
+                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(), stream)
         return [gv, gl, ga]
-    with _lib.device_guard(value.device):
-        code = _lib.lib().mpf_msda_backward(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-            gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-            N, S, M, D, L, Lq, P, _DTYPES[value.dtype], _stream(value))
-    _lib.check(code, "mpf_msda_backward")
+    _lib.call("mpf_msda_backward", value.device,
+              value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+              sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
+              gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
+              N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], _lib.stream_ptr(value.device))
     return [gv, gl, ga]
 
 
@@ -222,13 +209,11 @@ def ms_deform_attn_forward_raw(value, spatial_shapes, level_start_index, raw, re
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     loc = torch.empty((N, Lq, M, L, P, 2), dtype=value.dtype, device=value.device)
     attn = torch.empty((N, Lq, M, L, P), dtype=value.dtype, device=value.device)
-    with _lib.device_guard(value.device):
-        code = _lib.lib().mpf_msda_forward_raw_hs(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            host_shapes.data_ptr() if host_shapes is not None else None, raw.data_ptr(), ref_points.data_ptr(),
-            loc.data_ptr(), attn.data_ptr(), out.data_ptr(),
-            N, S, M, D, L, Lq, P, _DTYPES[value.dtype], _stream(value))
-    _lib.check(code, "mpf_msda_forward_raw_hs")
+    _lib.call("mpf_msda_forward_raw_hs", value.device,
+              value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+              _lib.ptr(host_shapes), raw.data_ptr(), ref_points.data_ptr(),
+              loc.data_ptr(), attn.data_ptr(), out.data_ptr(),
+              N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], _lib.stream_ptr(value.device))
     return out, loc, attn
 
 
@@ -244,23 +229,20 @@ def ms_deform_attn_backward_raw(value, host_shapes, sampling_loc, attn_weight, g
     need = lib.mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, host_shapes.data_ptr())
     if need == 0:
         raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
-    stream = _stream(value)
+    stream = _lib.stream_ptr(value.device)
     ws = _lib.scratch("msda_host", value.device, stream, need)
-    with _lib.device_guard(value.device):
-        if output is not None:
-            assert output.is_contiguous() and output.numel() == N * Lq * M * D and output.dtype == value.dtype
-            code = lib.mpf_msda_backward_ws_raw_o(
-                value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                grad_output.data_ptr(), output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(),
-                graw_amax.data_ptr() if graw_amax is not None else None, gv_amax.data_ptr() if gv_amax is not None else None,
-                stream)
-        else:
-            code = lib.mpf_msda_backward_ws_raw(
-                value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                grad_output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
-                N, S, M, D, L, Lq, P, _DTYPES[value.dtype], ws.data_ptr(), ws.numel(), stream)
-    _lib.check(code, "mpf_msda_backward_ws_raw")
+    if output is not None:
+        assert output.is_contiguous() and output.numel() == N * Lq * M * D and output.dtype == value.dtype
+        _lib.call("mpf_msda_backward_ws_raw_o", value.device,
+                  value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                  grad_output.data_ptr(), output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
+                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(),
+                  _lib.ptr(graw_amax), _lib.ptr(gv_amax), stream)
+    else:
+        _lib.call("mpf_msda_backward_ws_raw", value.device,
+                  value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                  grad_output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
+                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(), stream)
     return gv, graw
 
 

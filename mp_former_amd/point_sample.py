@@ -17,13 +17,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-_DT = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16, torch.uint8: _lib.MPF_U8, torch.bool: _lib.MPF_U8,
-       "bits": _lib.MPF_BITS}
+_MAP_DTYPES = (torch.float32, torch.bfloat16, torch.uint8, torch.bool)
 _CHUNKS = 8
-
-
-def _stream(dev):
-    return _lib.stream_ptr(dev)
 
 
 def _row_slice_of(t):
@@ -67,7 +62,7 @@ class MapSet:
         self.h, self.w = t0.shape[-2:]
         self.dtype, self.device = t0.dtype, t0.device
         self.esize = t0.element_size()
-        if self.dtype not in _DT:
+        if self.dtype not in _MAP_DTYPES:
             raise RuntimeError(f"unsupported map dtype {self.dtype}")
         self.bases, self.base_of, self.q0 = [], [], []
         seen = {}
@@ -121,11 +116,8 @@ def point_sample_offsets(base_ptr, dtype, h, w, offs, coords, coord_rows, device
     out = torch.empty((n, P), dtype=torch.float32, device=device)
     if n == 0:
         return out
-    with _lib.device_guard(device):
-        code = _lib.lib().mpf_point_sample(base_ptr, _DT[dtype], h, w, offs.data_ptr(), coords.data_ptr(),
-                                           coord_rows.data_ptr() if coord_rows is not None else None,
-                                           out.data_ptr(), n, P, _stream(device))
-    _lib.check(code, "mpf_point_sample")
+    _lib.call("mpf_point_sample", device, base_ptr, _lib.MPF_BITS if dtype == "bits" else _lib.DTYPE[dtype], h, w, offs.data_ptr(),
+              coords.data_ptr(), _lib.ptr(coord_rows), out.data_ptr(), n, P, _lib.stream_ptr(device))
     return out
 
 
@@ -134,10 +126,8 @@ def select_uncertain(vals, coords_in, k, P_out):
     n, M = vals.shape
     out = torch.empty((n, P_out, 2), dtype=torch.float32, device=vals.device)
     if n and k:
-        with _lib.device_guard(vals.device):
-            code = _lib.lib().mpf_select_uncertain(vals.data_ptr(), coords_in.data_ptr(), out.data_ptr(), n, M, k, P_out,
-                                                   _stream(vals.device))
-        _lib.check(code, "mpf_select_uncertain")
+        _lib.call("mpf_select_uncertain", vals.device, vals.data_ptr(), coords_in.data_ptr(), out.data_ptr(), n, M, k, P_out,
+                  _lib.stream_ptr(vals.device))
     return out
 
 
@@ -148,10 +138,8 @@ def sample_select_uncertain(ms, offs, coords_in, k, P_out):
     n, M = coords_in.shape[0], coords_in.shape[1]
     if ms.dtype == torch.bfloat16 and ms.h * ms.w * 2 <= 128 * 1024 and (ms.h * ms.w * 2) % 16 == 0 and M <= 40960 and n and k:
         out = torch.empty((n, P_out, 2), dtype=torch.float32, device=coords_in.device)
-        with _lib.device_guard(ms.device):
-            code = _lib.lib().mpf_sample_select_uncertain(ms.base_ptr, _DT[ms.dtype], ms.h, ms.w, offs.data_ptr(), coords_in.data_ptr(),
-                                                          out.data_ptr(), n, M, k, P_out, _stream(ms.device))
-        _lib.check(code, "mpf_sample_select_uncertain")
+        _lib.call("mpf_sample_select_uncertain", ms.device, ms.base_ptr, _lib.DTYPE[ms.dtype], ms.h, ms.w, offs.data_ptr(),
+                  coords_in.data_ptr(), out.data_ptr(), n, M, k, P_out, _lib.stream_ptr(ms.device))
         return out
     logits = point_sample_offsets(ms.base_ptr, ms.dtype, ms.h, ms.w, offs, coords_in, None, ms.device)
     return select_uncertain(logits, coords_in, k, P_out)
@@ -162,12 +150,9 @@ def match_cost(ms, offs, coords, coord_rows, tsamp, t_first, t_count, Tmax, w_ma
     P = coords.shape[-2]
     cost = torch.zeros((n, Tmax), dtype=torch.float32, device=ms.device)
     if n:
-        with _lib.device_guard(ms.device):
-            code = _lib.lib().mpf_match_cost(ms.base_ptr, _DT[ms.dtype], ms.h, ms.w, offs.data_ptr(), coords.data_ptr(),
-                                             coord_rows.data_ptr(), tsamp.data_ptr(), t_first.data_ptr(),
-                                             t_count.data_ptr(), cost.data_ptr(), n, Tmax, P, float(w_mask),
-                                             float(w_dice), int(rows_per_group), _stream(ms.device))
-        _lib.check(code, "mpf_match_cost")
+        _lib.call("mpf_match_cost", ms.device, ms.base_ptr, _lib.DTYPE[ms.dtype], ms.h, ms.w, offs.data_ptr(), coords.data_ptr(),
+                  coord_rows.data_ptr(), tsamp.data_ptr(), t_first.data_ptr(), t_count.data_ptr(), cost.data_ptr(), n, Tmax, P,
+                  float(w_mask), float(w_dice), int(rows_per_group), _lib.stream_ptr(ms.device))
     return cost
 
 
@@ -181,11 +166,9 @@ def _mask_loss_sums_forward(ctx, ms, pred_offs, gt, gt_rows, coords):
     ctx.gt_hw, ctx.gdt, ctx.gt_u8 = (H, W), gdt, gt_u8
     partial = torch.empty((n, _CHUNKS, 4), dtype=torch.float32, device=ms.device)
     if n:
-        with _lib.device_guard(ms.device):
-            code = _lib.lib().mpf_mask_loss_forward(
-                ms.base_ptr, _DT[ms.dtype], ms.h, ms.w, pred_offs.data_ptr(), gt_u8.data_ptr(), gdt, H, W,
-                gt_rows.data_ptr(), coords.data_ptr(), partial.data_ptr(), n, P, _CHUNKS, _stream(ms.device))
-        _lib.check(code, "mpf_mask_loss_forward")
+        _lib.call("mpf_mask_loss_forward", ms.device,
+                  ms.base_ptr, _lib.DTYPE[ms.dtype], ms.h, ms.w, pred_offs.data_ptr(), gt_u8.data_ptr(), gdt, H, W,
+                  gt_rows.data_ptr(), coords.data_ptr(), partial.data_ptr(), n, P, _CHUNKS, _lib.stream_ptr(ms.device))
     ctx.ms = ms
     return partial.sum(1)
 
@@ -216,12 +199,11 @@ class MaskLossSums(Function):
         gbuf = torch.zeros(ms.g_total, dtype=ms.dtype, device=ms.device)
         if n:
             g = grad_sums.contiguous().float()
-            with _lib.device_guard(ms.device):
-                code = _lib.lib().mpf_mask_loss_backward_dense(
-                    ms.base_ptr, _DT[ms.dtype], ms.h, ms.w, pred_offs.data_ptr(), gt_u8.data_ptr(), ctx.gdt, H, W,
-                    gt_rows.data_ptr(), coords.data_ptr(), g.data_ptr(), gbuf.data_ptr(), _DT[ms.dtype], grad_offs.data_ptr(),
-                    n, P, _stream(ms.device))
-            _lib.check(code, "mpf_mask_loss_backward_dense")
+            dt = _lib.DTYPE[ms.dtype]
+            _lib.call("mpf_mask_loss_backward_dense", ms.device,
+                      ms.base_ptr, dt, ms.h, ms.w, pred_offs.data_ptr(), gt_u8.data_ptr(), ctx.gdt, H, W,
+                      gt_rows.data_ptr(), coords.data_ptr(), g.data_ptr(), gbuf.data_ptr(), dt, grad_offs.data_ptr(),
+                      n, P, _lib.stream_ptr(ms.device))
         grads = []
         for i, t in enumerate(ms.bases):
             s = int(ms.g_start[i])
@@ -251,10 +233,9 @@ class MaskLossSumsPlanes(Function):
         g_planes = torch.empty_like(planes)
         if n:
             g = grad_sums.contiguous().float()
-            with _lib.device_guard(ms.device):
-                code = _lib.lib().mpf_mask_loss_backward_dense(
-                    ms.base_ptr, _DT[ms.dtype], ms.h, ms.w, plane_offs.data_ptr(), gt_u8.data_ptr(), ctx.gdt, H, W,
-                    gt_rows.data_ptr(), coords.data_ptr(), g.data_ptr(), g_planes.data_ptr(), _DT[ms.dtype], plane_offs.data_ptr(),
-                    n, P, _stream(ms.device))
-            _lib.check(code, "mpf_mask_loss_backward_dense")
+            dt = _lib.DTYPE[ms.dtype]
+            _lib.call("mpf_mask_loss_backward_dense", ms.device,
+                      ms.base_ptr, dt, ms.h, ms.w, plane_offs.data_ptr(), gt_u8.data_ptr(), ctx.gdt, H, W,
+                      gt_rows.data_ptr(), coords.data_ptr(), g.data_ptr(), g_planes.data_ptr(), dt, plane_offs.data_ptr(),
+                      n, P, _lib.stream_ptr(ms.device))
         return None, None, None, None, None, g_planes

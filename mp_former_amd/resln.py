@@ -10,11 +10,7 @@ from torch.autograd import Function
 
 from . import _lib
 
-_DT = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}
-
-
-def _stream(t):
-    return _lib.stream_ptr(t.device)
+_BRANCH_DTYPES = (torch.float32, torch.bfloat16)     # what the kernel reads as the branch output t
 
 
 class _ResLN(Function):
@@ -26,13 +22,11 @@ class _ResLN(Function):
         y16 = torch.empty_like(x, dtype=torch.bfloat16) if want16 else None
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        with _lib.device_guard(x.device):
-            code = _lib.lib().mpf_res_ln256_forward(
-                x.data_ptr(), t.data_ptr() if t is not None else None, _DT[t.dtype] if t is not None else 0,
-                gamma.data_ptr(), beta.data_ptr(), s.data_ptr() if t is not None else None,
-                y32.data_ptr() if want32 else None, y16.data_ptr() if want16 else None, mean.data_ptr(), rstd.data_ptr(),
-                rows, float(eps), None, 0, None, _stream(x))
-        _lib.check(code, "mpf_res_ln256_forward")
+        _lib.call("mpf_res_ln256_forward", x.device,
+                  x.data_ptr(), _lib.ptr(t), _lib.DTYPE[t.dtype] if t is not None else 0,
+                  gamma.data_ptr(), beta.data_ptr(), s.data_ptr() if t is not None else None,
+                  _lib.ptr(y32), _lib.ptr(y16), mean.data_ptr(), rstd.data_ptr(),
+                  rows, float(eps), None, 0, None, _lib.stream_ptr(x.device))
         ctx.save_for_backward(s, mean, rstd, gamma)
         ctx.t_dtype = t.dtype if t is not None else None
         ctx.rows = rows
@@ -52,22 +46,19 @@ class _ResLN(Function):
         if g16 is not None:
             g16 = g16.contiguous()
         lib = _lib.lib()
-        stream = _stream(s)
-        args = (s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                g32.data_ptr() if g32 is not None else None, g16.data_ptr() if g16 is not None else None, None,
-                ds32.data_ptr() if ds32 is not None else None, ds16.data_ptr() if ds16 is not None else None)
-        with _lib.device_guard(s.device):
-            # parameter gradients without float atomics (bit-reproducible): per-workgroup partials summed in a fixed order —
-            # by the workgroup that arrives last (one launch) for a few hundred rows, by a parallel second launch beyond
-            # (the ticket word at the head of the "ln_det" buffer is zero between calls: zero-initialised, reset by every launch)
-            if ctx.rows <= 1024:
-                ws = _lib.scratch("ln_det", s.device, stream, lib.mpf_res_ln256_backward_det_workspace_bytes(ctx.rows), zeroed=True)
-                code = lib.mpf_res_ln256_backward_det(*args, dgb.data_ptr(), ctx.rows, ws.data_ptr(), ws.numel(), stream)
-            else:
-                ws = _lib.scratch("ln_det", s.device, stream, lib.mpf_res_ln256_backward_workspace_bytes(ctx.rows) + 256, zeroed=True)
-                code = lib.mpf_res_ln256_backward_ws(*args, dgb[0].data_ptr(), dgb[1].data_ptr(), ctx.rows, ws.data_ptr() + 256,
-                                                     ws.numel() - 256, stream)
-        _lib.check(code, "mpf_res_ln256_backward")
+        stream = _lib.stream_ptr(s.device)
+        args = (s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), _lib.ptr(g32), _lib.ptr(g16), None,
+                _lib.ptr(ds32), _lib.ptr(ds16))
+        # parameter gradients without float atomics (bit-reproducible): per-workgroup partials summed in a fixed order —
+        # by the workgroup that arrives last (one launch) for a few hundred rows, by a parallel second launch beyond
+        # (the ticket word at the head of the "ln_det" buffer is zero between calls: zero-initialised, reset by every launch)
+        if ctx.rows <= 1024:
+            ws = _lib.scratch("ln_det", s.device, stream, lib.mpf_res_ln256_backward_det_workspace_bytes(ctx.rows), zeroed=True)
+            _lib.call("mpf_res_ln256_backward_det", s.device, *args, dgb.data_ptr(), ctx.rows, ws.data_ptr(), ws.numel(), stream)
+        else:
+            ws = _lib.scratch("ln_det", s.device, stream, lib.mpf_res_ln256_backward_workspace_bytes(ctx.rows) + 256, zeroed=True)
+            _lib.call("mpf_res_ln256_backward_ws", s.device, *args, dgb[0].data_ptr(), dgb[1].data_ptr(), ctx.rows, ws.data_ptr() + 256,
+                      ws.numel() - 256, stream)
         dt = None
         if need_t:
             dt = ds16 if t16 else ds32
@@ -80,7 +71,7 @@ def res_ln(norm, x, t=None, want32=True, want16=False):
     requested."""
     C = x.shape[-1]
     ok = (x.is_cuda and C == 256 and x.dtype == torch.float32 and x.is_contiguous() and norm.elementwise_affine
-          and norm.bias is not None and (t is None or (t.shape == x.shape and t.dtype in _DT and t.is_contiguous())))
+          and norm.bias is not None and (t is None or (t.shape == x.shape and t.dtype in _BRANCH_DTYPES and t.is_contiguous())))
     if ok:
         return _ResLN.apply(x, t, norm.weight, norm.bias, norm.eps, want32, want16)
     s = x if t is None else x + t
@@ -96,18 +87,13 @@ def ln256_forward(x, gamma, beta, eps, padd=None, y_bound=None, padd_amax=None, 
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     yp = torch.empty_like(x) if padd is not None else None
-    p_ = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with _lib.device_guard(x.device):
-        if y_bound is not None:
-            code = _lib.lib().mpf_res_ln256_forward_b(
-                x.data_ptr(), None, 0, gamma.data_ptr(), beta.data_ptr(), None, y.data_ptr(), None, mean.data_ptr(), rstd.data_ptr(),
-                rows, float(eps), p_(padd), padd.shape[0] if padd is not None else 0, p_(yp), y_bound.data_ptr(), p_(padd_amax),
-                p_(yplus_bound) if yp is not None else None, _stream(x))
-        else:
-            code = _lib.lib().mpf_res_ln256_forward(
-                x.data_ptr(), None, 0, gamma.data_ptr(), beta.data_ptr(), None, y.data_ptr(), None, mean.data_ptr(), rstd.data_ptr(),
-                rows, float(eps), p_(padd), padd.shape[0] if padd is not None else 0, p_(yp), _stream(x))
-    _lib.check(code, "mpf_res_ln256_forward")
+    args = (x.data_ptr(), None, 0, gamma.data_ptr(), beta.data_ptr(), None, y.data_ptr(), None, mean.data_ptr(), rstd.data_ptr(),
+            rows, float(eps), _lib.ptr(padd), padd.shape[0] if padd is not None else 0, _lib.ptr(yp))
+    if y_bound is not None:
+        _lib.call("mpf_res_ln256_forward_b", x.device, *args, y_bound.data_ptr(), _lib.ptr(padd_amax),
+                  _lib.ptr(yplus_bound) if yp is not None else None, _lib.stream_ptr(x.device))
+    else:
+        _lib.call("mpf_res_ln256_forward", x.device, *args, _lib.stream_ptr(x.device))
     return y, mean, rstd, yp
 
 
@@ -116,18 +102,15 @@ def ln256_backward(s, mean, rstd, gamma, gy, gy_plus=None, ds_amax=None):
     ds = torch.empty_like(s)
     dgb = torch.empty((2, 256), dtype=torch.float32, device=s.device)
     lib = _lib.lib()
-    stream = _stream(s)
+    stream = _lib.stream_ptr(s.device)
     ws = _lib.scratch("ln_bwd", s.device, stream, lib.mpf_res_ln256_backward_workspace_bytes(s.shape[0]))
-    with _lib.device_guard(s.device):
-        # parameter gradients through per-workgroup partials, fixed order (no atomics, no zero-fill)
-        args = (s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), gy.data_ptr(), None,
-                gy_plus.data_ptr() if gy_plus is not None else None, ds.data_ptr(), None, dgb[0].data_ptr(), dgb[1].data_ptr(),
-                s.shape[0], ws.data_ptr(), ws.numel())
-        if ds_amax is not None:
-            code = lib.mpf_res_ln256_backward_ws_amax(*args, ds_amax.data_ptr(), stream)
-        else:
-            code = lib.mpf_res_ln256_backward_ws(*args, stream)
-    _lib.check(code, "mpf_res_ln256_backward_ws")
+    # parameter gradients through per-workgroup partials, fixed order (no atomics, no zero-fill)
+    args = (s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), gy.data_ptr(), None, _lib.ptr(gy_plus), ds.data_ptr(), None,
+            dgb[0].data_ptr(), dgb[1].data_ptr(), s.shape[0], ws.data_ptr(), ws.numel())
+    if ds_amax is not None:
+        _lib.call("mpf_res_ln256_backward_ws_amax", s.device, *args, ds_amax.data_ptr(), stream)
+    else:
+        _lib.call("mpf_res_ln256_backward_ws", s.device, *args, stream)
     return ds, dgb[0], dgb[1]
 
 
@@ -146,18 +129,15 @@ class LnGradGroup:
         """-> ds fp32 (the parameter gradients come from finish())"""
         assert self.used < self.n and s.shape[0] == self.rows
         ds = torch.empty_like(s)
-        with _lib.device_guard(s.device):
-            code = _lib.lib().mpf_res_ln256_backward_partial_amax(
-                s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), gy.data_ptr(), None,
-                gy_plus.data_ptr() if gy_plus is not None else None, ds.data_ptr(), None, self.rows,
-                self.parts.data_ptr() + self.used * self.stride, self.stride, ds_amax.data_ptr() if ds_amax is not None else None, _stream(s))
-        _lib.check(code, "mpf_res_ln256_backward_partial_amax")
+        _lib.call("mpf_res_ln256_backward_partial_amax", s.device,
+                  s.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), gy.data_ptr(), None, _lib.ptr(gy_plus), ds.data_ptr(),
+                  None, self.rows, self.parts.data_ptr() + self.used * self.stride, self.stride, _lib.ptr(ds_amax),
+                  _lib.stream_ptr(s.device))
         self.used += 1
         return ds
 
     def finish(self):
         out = torch.empty((self.used, 2, 256), dtype=torch.float32, device=self.parts.device)
-        with _lib.device_guard(out.device):
-            code = _lib.lib().mpf_ln_partial_reduce(self.parts.data_ptr(), self.stride, self.rows, self.used, out.data_ptr(), _stream(out))
-        _lib.check(code, "mpf_ln_partial_reduce")
+        _lib.call("mpf_ln_partial_reduce", out.device, self.parts.data_ptr(), self.stride, self.rows, self.used, out.data_ptr(),
+                  _lib.stream_ptr(out.device))
         return out

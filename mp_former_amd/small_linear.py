@@ -16,21 +16,14 @@ from . import _lib
 MAX_ROWS = 1024     # above this the library GEMMs have enough tiles to fill the chip
 
 
-def _stream(t):
-    return _lib.stream_ptr(t.device)
-
-
 def small_gemm(a, a_rs, a_ks, b, b_rs, b_ks, I, J, Kc, bias=None, gate=None, relu=False, rowsum=False, cin=None):
     """C[I, J] = sum_k A(i,k) B(j,k) (+bias) (ReLU) with explicit element strides; returns (C, rowsum_a or None)."""
     c = torch.empty((I, J), dtype=torch.bfloat16, device=a.device)
     rs = torch.empty((I,), dtype=torch.bfloat16, device=a.device) if rowsum else None
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_small_gemm_bf16(
-            a.data_ptr(), a_rs, a_ks, gate.data_ptr() if gate is not None else None, b.data_ptr(), b_rs, b_ks,
-            bias.data_ptr() if bias is not None else None, cin.data_ptr() if cin is not None else None,
-            cin.stride(0) if cin is not None else 0, c.data_ptr(), J, rs.data_ptr() if rowsum else None,
-            I, J, Kc, 1 if relu else 0, _stream(a))
-    _lib.check(code, "mpf_small_gemm_bf16")
+    _lib.call("mpf_small_gemm_bf16", a.device,
+              a.data_ptr(), a_rs, a_ks, _lib.ptr(gate), b.data_ptr(), b_rs, b_ks, _lib.ptr(bias), _lib.ptr(cin),
+              cin.stride(0) if cin is not None else 0, c.data_ptr(), J, _lib.ptr(rs),
+              I, J, Kc, 1 if relu else 0, _lib.stream_ptr(a.device))
     return c, rs
 
 
@@ -58,9 +51,7 @@ def weight_grads_grouped(problems):
         it.a_blk, it.I, it.J, it.Kc = 0, J, K, R
         outs.append((dw, db))
     dev = problems[0][0].device
-    with _lib.device_guard(dev):
-        code = _lib.lib().mpf_small_gemm_bf16_group(items, len(problems), _stream(problems[0][0]))
-    _lib.check(code, "mpf_small_gemm_bf16_group")
+    _lib.call("mpf_small_gemm_bf16_group", dev, items, len(problems), _lib.stream_ptr(dev))
     return outs
 
 
@@ -128,14 +119,12 @@ def gemm_nt_bf16(a, b, want_csum=True):
     N = b.shape[1]
     rps = pick_rows_per_split(R, ((M + 127) // 128) * ((N + 127) // 128))
     lib = _lib.lib()
-    stream = _stream(a)
+    stream = _lib.stream_ptr(a.device)
     ws = _lib.scratch("nt_bf16", a.device, stream, lib.mpf_gemm_nt_bf16_workspace_bytes(R, M, N, rps))
     c = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     cs = torch.empty((M,), dtype=torch.bfloat16, device=a.device) if want_csum else None
-    with _lib.device_guard(a.device):
-        code = lib.mpf_gemm_nt_bf16(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), c.data_ptr(),
-                                    cs.data_ptr() if want_csum else None, R, M, N, rps, ws.data_ptr(), ws.numel(), stream)
-    _lib.check(code, "mpf_gemm_nt_bf16")
+    _lib.call("mpf_gemm_nt_bf16", a.device, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), c.data_ptr(), _lib.ptr(cs),
+              R, M, N, rps, ws.data_ptr(), ws.numel(), stream)
     return c, cs
 
 
@@ -151,10 +140,8 @@ def tall_gemm(a, b, bias=None):
     M, K = a.shape
     N = b.shape[0]
     c = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    with _lib.device_guard(a.device):
-        code = _lib.lib().mpf_tall_gemm_bf16(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0),
-                                             bias.data_ptr() if bias is not None else None, c.data_ptr(), N, M, N, K, _stream(a))
-    _lib.check(code, "mpf_tall_gemm_bf16")
+    _lib.call("mpf_tall_gemm_bf16", a.device, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), _lib.ptr(bias), c.data_ptr(),
+              N, M, N, K, _lib.stream_ptr(a.device))
     return c
 
 

@@ -181,11 +181,8 @@ class _DecoderInputs(torch.autograd.Function):
         src = torch.empty((S, N, C), dtype=out_dtype, device=x.device)
         kin = torch.empty((S, N, C), dtype=out_dtype, device=x.device)
         dt = _lib.MPF_BF16 if out_dtype == torch.bfloat16 else _lib.MPF_F32
-        with _lib.device_guard(x.device):
-            code = _lib.lib().mpf_decoder_inputs_forward(x.data_ptr(), x.stride(0), x.stride(3), level_row.data_ptr(), pos_t.data_ptr(),
-                                                         src.data_ptr(), kin.data_ptr(), dt, S, N, C,
-                                                         _lib.stream_ptr(x.device))
-        _lib.check(code, "mpf_decoder_inputs_forward")
+        _lib.call("mpf_decoder_inputs_forward", x.device, x.data_ptr(), x.stride(0), x.stride(3), level_row.data_ptr(), pos_t.data_ptr(),
+                  src.data_ptr(), kin.data_ptr(), dt, S, N, C, _lib.stream_ptr(x.device))
         ctx.dims = (N, C, H, W)
         return src, kin
 
@@ -205,11 +202,8 @@ class _DecoderInputs(torch.autograd.Function):
         g_kin = g_kin.contiguous() if g_kin is not None else None
         mem = torch.empty((N, S, C), dtype=torch.float32, device=g.device)       # channel-last, like the input view
         dt = _lib.MPF_BF16 if g.dtype == torch.bfloat16 else _lib.MPF_F32
-        with _lib.device_guard(g.device):
-            code = _lib.lib().mpf_decoder_inputs_backward(g_src.data_ptr() if g_src is not None else None,
-                                                          g_kin.data_ptr() if g_kin is not None else None, dt, mem.data_ptr(),
-                                                          S * C, C, S, N, C, _lib.stream_ptr(g.device))
-        _lib.check(code, "mpf_decoder_inputs_backward")
+        _lib.call("mpf_decoder_inputs_backward", g.device, _lib.ptr(g_src), _lib.ptr(g_kin), dt, mem.data_ptr(),
+                  S * C, C, S, N, C, _lib.stream_ptr(g.device))
         dx = mem.permute(0, 2, 1).view(N, C, H, W)
         d_level = mem.sum((0, 1)) if ctx.needs_input_grad[1] else None
         return dx, d_level, None, None
@@ -225,18 +219,14 @@ def native_attn_mask(masks, size, mp_rows=None):
     hl, wl = size
     if masks.stride(3) != 1 or masks.stride(2) != w:
         masks = masks.contiguous()
-    dt = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}.get(masks.dtype)
-    if dt is None:
-        masks, dt = masks.float(), _lib.MPF_F32
+    if masks.dtype not in (torch.float32, torch.bfloat16):
+        masks = masks.float()
     pad = 0 if mp_rows is None else mp_rows.shape[1]
     if pad:
         mp_rows = mp_rows.contiguous()
     out = torch.empty((N, Q, hl * wl), dtype=torch.bool, device=masks.device)
-    with _lib.device_guard(masks.device):
-        code = _lib.lib().mpf_attn_mask(masks.data_ptr(), dt, masks.stride(0), masks.stride(1), h, w,
-                                        mp_rows.data_ptr() if pad else None, pad, out.data_ptr(), N, Q, hl, wl,
-                                        _lib.stream_ptr(masks.device))
-    _lib.check(code, "mpf_attn_mask")
+    _lib.call("mpf_attn_mask", masks.device, masks.data_ptr(), _lib.DTYPE[masks.dtype], masks.stride(0), masks.stride(1), h, w,
+              mp_rows.data_ptr() if pad else None, pad, out.data_ptr(), N, Q, hl, wl, _lib.stream_ptr(masks.device))
     return out
 
 
@@ -245,19 +235,16 @@ def pool_features(mask_features, size):
     matrix [N, hl*wl, 256] — the B operand of the fused mask head (csrc/mask_head.hip).  Once per step and level."""
     N, C, h, w = mask_features.shape
     hl, wl = size
-    dt = {torch.float32: _lib.MPF_F32, torch.bfloat16: _lib.MPF_BF16}[mask_features.dtype]
+    dt = _lib.DTYPE[mask_features.dtype]
     out = torch.empty((N, hl * wl, C), dtype=torch.bfloat16, device=mask_features.device)
     stream = _lib.stream_ptr(mask_features.device)
-    with _lib.device_guard(mask_features.device):
-        if _is_planes(mask_features) and not mask_features.is_contiguous():
-            # channel-last features (the pixel decoder's layout): no transpose needed
-            code = _lib.lib().mpf_pool_features_cl(mask_features.data_ptr(), mask_features.stride(0), dt, out.data_ptr(), N, C, h, w,
-                                                   hl, wl, stream)
-            _lib.check(code, "mpf_pool_features_cl")
-            return out
-        mf = mask_features if mask_features.is_contiguous() else mask_features.contiguous()
-        code = _lib.lib().mpf_pool_features(mf.data_ptr(), dt, out.data_ptr(), N, C, h, w, hl, wl, stream)
-    _lib.check(code, "mpf_pool_features")
+    if _is_planes(mask_features) and not mask_features.is_contiguous():
+        # channel-last features (the pixel decoder's layout): no transpose needed
+        _lib.call("mpf_pool_features_cl", mask_features.device, mask_features.data_ptr(), mask_features.stride(0), dt, out.data_ptr(),
+                  N, C, h, w, hl, wl, stream)
+        return out
+    mf = mask_features if mask_features.is_contiguous() else mask_features.contiguous()
+    _lib.call("mpf_pool_features", mf.device, mf.data_ptr(), dt, out.data_ptr(), N, C, h, w, hl, wl, stream)
     return out
 
 
@@ -297,10 +284,9 @@ def next_attn_mask_native(x, norm, mlp, pooled, mp_rows=None):
     pad = 0 if mp_rows is None else mp_rows.shape[1]
     if pad:
         mp_rows = mp_rows.contiguous()
-    lib = _lib.lib()
     stream = _lib.stream_ptr(dev)
     flags = _lib.scratch("next_mask_flags", dev, stream, 4 * N * Q, zeroed=True)       # zero on entry, zeroed again by the kernel
-    sc = _lib.scratch("next_mask", dev, stream, lib.mpf_next_attn_mask_scratch_bytes(N, Q))
+    sc = _lib.scratch("next_mask", dev, stream, _lib.lib().mpf_next_attn_mask_scratch_bytes(N, Q))
     out = torch.empty((N, Q, HW), dtype=torch.bool, device=dev)
     m = MpfNextMask()
     m.x, m.ln_gamma, m.ln_beta, m.eps = x.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps)
@@ -309,9 +295,7 @@ def next_attn_mask_native(x, norm, mlp, pooled, mp_rows=None):
     m.pooled, m.mp_rows, m.out, m.flags = pooled.data_ptr(), (mp_rows.data_ptr() if pad else None), out.data_ptr(), flags.data_ptr()
     m.scratch, m.scratch_bytes = sc.data_ptr(), sc.numel()
     m.N, m.Q, m.HW, m.pad = N, Q, HW, pad
-    with _lib.device_guard(dev):
-        code = lib.mpf_next_attn_mask(ctypes.byref(m), stream)
-    _lib.check(code, "mpf_next_attn_mask")
+    _lib.call("mpf_next_attn_mask", dev, ctypes.byref(m), stream)
     return out
 
 
@@ -329,11 +313,8 @@ def mask_head_bits(mask_embed, pooled, mp_rows=None):
     stream = _lib.stream_ptr(dev)
     flags = _lib.scratch("next_mask_flags", dev, stream, 4 * N * Q, zeroed=True)       # zero on entry, zeroed again by the kernel
     out = torch.empty((N, Q, HW), dtype=torch.bool, device=dev)
-    with _lib.device_guard(dev):
-        code = _lib.lib().mpf_mask_head_bits(mask_embed.data_ptr(), mask_embed.stride(1), mask_embed.stride(0), pooled.data_ptr(),
-                                             mp_rows.data_ptr() if pad else None, pad, out.data_ptr(), flags.data_ptr(), N, Q, HW,
-                                             stream)
-    _lib.check(code, "mpf_mask_head_bits")
+    _lib.call("mpf_mask_head_bits", dev, mask_embed.data_ptr(), mask_embed.stride(1), mask_embed.stride(0), pooled.data_ptr(),
+              mp_rows.data_ptr() if pad else None, pad, out.data_ptr(), flags.data_ptr(), N, Q, HW, stream)
     return out
 
 
@@ -462,10 +443,7 @@ def gt_block_or(masks: Tensor, size):
         raise RuntimeError("mp_former_amd decoder runs on the GPU only (no CPU fallback)")
     m = m.contiguous()
     out = torch.empty((T, h * w), dtype=torch.bool, device=m.device)
-    with _lib.device_guard(m.device):
-        code = _lib.lib().mpf_mask_block_empty(m.data_ptr(), out.data_ptr(), T, H, W, h, w,
-                                               _lib.stream_ptr(m.device))
-    _lib.check(code, "mpf_mask_block_empty")
+    _lib.call("mpf_mask_block_empty", m.device, m.data_ptr(), out.data_ptr(), T, H, W, h, w, _lib.stream_ptr(m.device))
     return out
 
 
@@ -476,9 +454,7 @@ def mp_open_counts(base: Tensor) -> Tensor:
     base = base.contiguous()
     R, HW = base.shape
     counts = torch.empty(R, dtype=torch.int32, device=base.device)
-    with _lib.device_guard(base.device):
-        code = _lib.lib().mpf_mp_open_counts(base.data_ptr(), R, HW, counts.data_ptr(), _lib.stream_ptr(base.device))
-    _lib.check(code, "mpf_mp_open_counts")
+    _lib.call("mpf_mp_open_counts", base.device, base.data_ptr(), R, HW, counts.data_ptr(), _lib.stream_ptr(base.device))
     return counts
 
 
@@ -500,10 +476,8 @@ def mp_noise_rows(base: Tensor, src_of: Tensor, N: int, pad: int, noise_scale: f
     assert src_of.device == base.device and counts.device == base.device
     out = torch.empty((N, pad, HW), dtype=torch.bool, device=base.device)
     mask64 = (1 << 64) - 1
-    with _lib.device_guard(base.device):
-        code = _lib.lib().mpf_mp_noise_rows(base.data_ptr(), counts.data_ptr(), src_of.data_ptr(), R, HW, N, pad, float(noise_scale),
-                                            int(seed) & mask64, int(draw) & mask64, out.data_ptr(), _lib.stream_ptr(base.device))
-    _lib.check(code, "mpf_mp_noise_rows")
+    _lib.call("mpf_mp_noise_rows", base.device, base.data_ptr(), counts.data_ptr(), src_of.data_ptr(), R, HW, N, pad, float(noise_scale),
+              int(seed) & mask64, int(draw) & mask64, out.data_ptr(), _lib.stream_ptr(base.device))
     return out
 
 

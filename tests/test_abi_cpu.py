@@ -185,3 +185,63 @@ def test_item_table_rows_match_the_header(tmp_path):
     subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(c), "-o", str(exe)])
     got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).strip().split("\n"))
     assert {k: int(v) for k, v in got.items()} == {k: 8 * n for k, n in want.items()}
+
+
+# ---- _lib.call: the one path to the status-returning entry points ---------------------------------------------------------------
+def _no_index_device():
+    import torch
+    return torch.device("cuda")      # index None: call() leaves the current device alone, so no GPU runtime is touched
+
+
+def test_call_raises_with_the_symbol_and_the_library_error(built):
+    with pytest.raises(RuntimeError) as e:
+        built.call("mpf_set_option", _no_index_device(), b"no_such_key", 1)
+    assert "mpf_set_option" in str(e.value)
+    text = built.lib().mpf_last_error().decode()        # thread-local on the C side: still that of the failed call
+    assert "unknown key" in text and str(e.value).endswith(text)
+
+
+def test_call_names_the_symbol_it_ran(built):
+    one = ctypes.c_void_p(16)  # never dereferenced: argument validation happens first
+    args = [one, 256, one, one, one, None, None, 0, None, 0, one, 16, one, 128, None, None, 16]
+    with pytest.raises(RuntimeError) as e:
+        built.call("mpf_gemm3_tn_h2_bits", _no_index_device(), *args, 128, 96, 256, 0, None)
+    assert re.search(r"\bmpf_gemm3_tn_h2_bits failed with code -2\b", str(e.value))
+    assert str(e.value).startswith("mpf_gemm3_tn_h2_bits failed")
+
+
+def test_call_returns_none_on_success(built):
+    # "msda_stats" is off by default; switching it off is a valid request that allocates nothing, and leaves the option as it was
+    try:
+        assert built.call("mpf_set_option", _no_index_device(), b"msda_stats", 0) is None
+    finally:
+        built.set_option("msda_stats", 0)
+
+
+def test_call_refuses_symbols_that_return_a_size(built):
+    with pytest.raises(TypeError):
+        built.call("mpf_next_attn_mask_scratch_bytes", _no_index_device(), 2, 100)
+    with pytest.raises(TypeError):
+        built.call("mpf_decoder_layer_struct_bytes", _no_index_device(), 0)
+
+
+def test_ptr_and_dtype_table(built):
+    import torch
+    assert built.ptr(None) is None
+    t = torch.zeros(4)
+    assert built.ptr(t) == t.data_ptr()
+    assert built.DTYPE == {torch.float32: built.MPF_F32, torch.float64: built.MPF_F64, torch.bfloat16: built.MPF_BF16,
+                           torch.uint8: built.MPF_U8, torch.bool: built.MPF_U8}
+
+
+def test_wrappers_reach_the_library_through_call_only():
+    """no module of the package other than _lib.py assembles guard + call + check by hand"""
+    pkg = os.path.join(ROOT, "mp_former_amd")
+    files = sorted(glob.glob(os.path.join(pkg, "*.py")))
+    assert len(files) > 20
+    for path in files:
+        if os.path.basename(path) == "_lib.py":
+            continue
+        src = open(path).read()
+        for needle in ("device_guard(", "_lib.check("):
+            assert needle not in src, f"{os.path.relpath(path, ROOT)} contains {needle!r}: use _lib.call"

@@ -7,6 +7,23 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices (skipped, not passed, with fewer): the "
+                                                          "tensor lives on device 1 while device 0 is current")
+def test_split_weight_runs_on_the_tensors_device_not_the_current_one():
+    from mp_former_amd.gemm3 import split_weight
+    torch.manual_seed(0)
+    w = torch.randn(32, 64)                          # the smallest shape the split kernel takes
+    with torch.cuda.device(0):
+        want = split_weight(w.to("cuda:0"))
+        got = split_weight(w.to("cuda:1"))
+        gott = split_weight(w.to("cuda:1"), transpose=True)
+        wantt = split_weight(w.to("cuda:0"), transpose=True)
+        assert torch.cuda.current_device() == 0
+    assert got.device == torch.device("cuda:1") and gott.device == torch.device("cuda:1")
+    assert torch.equal(got.cpu().view(torch.int16), want.cpu().view(torch.int16))
+    assert torch.equal(gott.cpu().view(torch.int16), wantt.cpu().view(torch.int16))
+
+
 def _ref_tn(a, a2, w, b, cin, cin2, relu, gate):
     x = a.double()
     if a2 is not None:
