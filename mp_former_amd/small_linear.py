@@ -35,6 +35,12 @@ class MpfSmallGemmItem(ctypes.Structure):
                 ("I", ctypes.c_int), ("J", ctypes.c_int), ("Kc", ctypes.c_int)]
 
 
+class MpfTransposeItem(ctypes.Structure):
+    """include/mpformer_hip.h MpfTransposeItem (mpf_transpose_group_bf16)."""
+    _fields_ = [("src", ctypes.c_void_p), ("gate", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("ld", ctypes.c_int64),
+                ("R", ctypes.c_int), ("C", ctypes.c_int)]
+
+
 def weight_grads_grouped(problems):
     """[(dy [R, J], x [R, K], gate or None)] -> [(dW [J, K], db [J])]: up to 8 weight-gradient problems
     dW = (dy gated)^T . x in ONE launch (mpf_small_gemm_bf16_group)."""

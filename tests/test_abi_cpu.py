@@ -187,6 +187,32 @@ def test_item_table_rows_match_the_header(tmp_path):
     assert {k: int(v) for k, v in got.items()} == {k: 8 * n for k, n in want.items()}
 
 
+def test_small_gemm_item_structs_match_the_header(tmp_path):
+    """The ctypes mirrors of MpfSmallGemmItem / MpfTransposeItem (mp_former_amd/small_linear.py) against the C declarations
+    (gcc on include/mpformer_hip.h): same size, same offset of every member."""
+    import ctypes
+    import subprocess
+    from mp_former_amd import small_linear as SL
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    mirrors = {"MpfSmallGemmItem": SL.MpfSmallGemmItem, "MpfTransposeItem": SL.MpfTransposeItem}
+    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "mpformer_hip.h"', 'int main(void) {']
+    for st, cls in mirrors.items():
+        src.append(f'  printf("{st} size %zu\\n", sizeof({st}));')
+        src += [f'  printf("{st} {n} %zu\\n", offsetof({st}, {n}));' for n, _ in cls._fields_]
+    src += ['  return 0;', '}']
+    c = tmp_path / "small_gemm_items.c"
+    c.write_text("\n".join(src))
+    exe = tmp_path / "small_gemm_items"
+    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(c), "-o", str(exe)])
+    lines = [line.split() for line in subprocess.check_output([str(exe)], text=True).strip().split("\n")]
+    assert len(lines) == sum(len(cls._fields_) + 1 for cls in mirrors.values())
+    for st, what, value in lines:
+        cls = mirrors[st]
+        assert (ctypes.sizeof(cls) if what == "size" else getattr(cls, what).offset) == int(value), (st, what)
+    # the members of the header's structs are all mirrored: no padding the mirror could hide a missing member in
+    assert ctypes.sizeof(SL.MpfSmallGemmItem) == 5 * 8 + 6 * 8 + 4 * 4 and ctypes.sizeof(SL.MpfTransposeItem) == 3 * 8 + 8 + 2 * 4
+
+
 # ---- _lib.call: the one path to the status-returning entry points ---------------------------------------------------------------
 def _no_index_device():
     import torch
