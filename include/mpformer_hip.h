@@ -1231,6 +1231,23 @@ int mpf_encoder_backward(const MpfEncoderBwdCall* call, void* stream);
  *                             kept_score * sigmoid, first index on ties, :329); areas int32 [3][Q] = mask_area,
  *                             original_area, intersection per kept entry (:333-336), zeroed by the call.
  *   mpf_seg_panoptic_paint:   out int32 [H, W] = lut[winner] where the bit is set, else 0 (:342-360, lut built on the host).
+ *
+ * Results in the form an evaluation loop consumes (the [K, H, W] scores and the [T, H, W] masks are not written):
+ *   mpf_seg_semantic_labels:  labels int32 [H, W] = argmax_c of what mpf_seg_semantic would write (:301-306 followed by the
+ *                             evaluator's argmax(0)), bit for bit: the same arithmetic in the same order, the lowest class on a
+ *                             tie.  One launch; every K that mpf_seg_semantic accepts.
+ *   mpf_seg_labels_resize:    labels int32 [H, W] = argmax_c of the bilinear resize (align_corners=False) of scores fp32
+ *                             [K, hi, wi] to [H, W] (:264-265: sem_seg_postprocess after the inference), plane by plane with a
+ *                             running argmax.  (H, W) == (hi, wi) gives the plain argmax of scores.
+ *   mpf_seg_confusion_add:    conf int64 [(K+1) * (K+1)] += bincount((K+1) * pred + gt) over n pixels (row = prediction, column =
+ *                             ground truth: detectron2's SemSegEvaluator).  gt == ignore_label, < 0 or >= K counts in column K,
+ *                             pred outside [0, K) in row K.  Integer arithmetic only; the caller zeroes conf once.
+ *   mpf_seg_instance_rle_*:   the masks of mpf_seg_instance_masks (:388) as uncompressed COCO run lengths: the mask flattened
+ *                             column-major, alternating runs starting with a (possibly empty) run of zeros.
+ *                             _count: packed bits (workspace of mpf_seg_instance_rle_workspace_bytes(T, H, W) bytes, 8-byte
+ *                             aligned) and offsets int64 [T + 1] of every entry's counts in the packed array, in a fixed order.
+ *                             _write: with total = offsets[T] read by the host, the counts uint32 [total] (pos uint32 [total] is
+ *                             scratch).  No atomics: the run order is deterministic.
  */
 int mpf_seg_softmax(const float* cls, int Q, int K1, float object_mask_threshold, float* probs, float* max_score, int* max_label,
                     int* kept, float* kept_score, void* stream);
@@ -1245,6 +1262,16 @@ int mpf_seg_instance_masks(const void* masks, int64_t stride_q, int dtype, int Q
 int mpf_seg_panoptic_areas(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
                            int W, const int* kept, const float* kept_score, int* code, int* areas, void* stream);
 int mpf_seg_panoptic_paint(const int* code, int H, int W, const int* lut, int* out, void* stream);
+int mpf_seg_semantic_labels(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                            int W, const float* probs, int K, int* labels, void* stream);
+int mpf_seg_labels_resize(const float* scores, int K, int hi, int wi, int H, int W, int* labels, void* stream);
+int mpf_seg_confusion_add(const int* pred, const int* gt, int64_t n, int K, int ignore_label, int64_t* conf, void* stream);
+size_t mpf_seg_instance_rle_workspace_bytes(int T, int H, int W);
+int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                               int W, const int64_t* sel_q, int T, int64_t* offsets, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int mpf_seg_instance_rle_write(const void* workspace, size_t workspace_bytes, int T, int H, int W, const int64_t* offsets, int64_t total,
+                               uint32_t* pos, uint32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

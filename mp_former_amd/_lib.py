@@ -199,6 +199,12 @@ SIGNATURES = {
     "mpf_seg_instance_masks": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp]),
     "mpf_seg_panoptic_areas": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp] * 5),
     "mpf_seg_panoptic_paint": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    "mpf_seg_semantic_labels": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_labels_resize": (_c_int, [_c_vp] + [_c_int] * 5 + [_c_vp, _c_vp]),
+    "mpf_seg_confusion_add": (_c_int, [_c_vp, _c_vp, ctypes.c_int64, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_instance_rle_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "mpf_seg_instance_rle_count": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "mpf_seg_instance_rle_write": (_c_int, [_c_vp, ctypes.c_size_t, _c_int, _c_int, _c_int, _c_vp, ctypes.c_int64, _c_vp, _c_vp, _c_vp]),
 }
 
 

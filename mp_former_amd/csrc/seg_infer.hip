@@ -19,10 +19,20 @@
 //   seg_panoptic_kernel     per pixel: the winning kept query (first index on ties), its sigmoid >= 0.5 bit, and the three
 //                           integer areas per kept query (LDS histogram, then integer global atomics: order-independent).
 //   seg_paint_kernel        int32 id map from the winner code and the host's segment lookup table.
+// The results an evaluation loop consumes, without the [K, H, W] scores or the [T, H, W] masks:
+//   seg_labels_kernel       int32 label map = argmax of seg_semantic_kernel's scores, bit for bit, in one launch: all classes of
+//                           a pixel tile in one workgroup, running (best, index) in registers, one LDS reduction at the end.
+//   seg_labels_resize       "after" mode: the [K, hi, wi] scores resized plane by plane with a running argmax per output pixel.
+//   seg_confusion_kernel    (K+1)^2 int64 confusion counts of prediction x ground truth: LDS histogram per workgroup where it
+//                           fits, integer global atomics otherwise.
+//   seg_rle_*               instance masks as uncompressed COCO run lengths: packed bits, boundaries per tile, a fixed-order
+//                           scan, scatter of the boundary positions, their differences.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stdio.h>
+
+#include <algorithm>
 
 #include "mpf_common.h"
 
@@ -366,6 +376,324 @@ __global__ __launch_bounds__(kT) void seg_paint_kernel(const int* __restrict__ c
     out[p] = (c & 1) ? lut[c >> 1] : 0;
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// semantic labels: argmax_c of the scores seg_semantic_kernel would write, without writing them.  One workgroup owns a tile of
+// kSemPix pixels and ALL classes: it walks the class chunks of 8 * CPT in a loop, with the same staging, the same q order and the
+// same fmaf chain per (class, pixel) as seg_semantic_kernel, so every score has the same bits.  Each thread keeps a running
+// (best, index) per pixel over its own classes (ascending, strict ">": the lowest index wins a tie); the 8 class groups of a pixel
+// meet once at the end through LDS.  The sigmoids are recomputed per chunk: K <= 192 (every shipped config) is one chunk.
+// ----------------------------------------------------------------------------------------------------------------
+// (waves per SIMD: the running (best, index) pairs must not cost the small tiles the occupancy seg_semantic_kernel has there)
+template <typename T, int CPT>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(CPT <= 4 ? 4 : CPT <= 12 ? 3 : 2))) void seg_labels_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
+                                                        int Wp, int hi, int wi, int H, int W, const float* __restrict__ probs, int K,
+                                                        int* __restrict__ labels)
+{
+    constexpr int KC = 8 * CPT;
+    __shared__ float4 sig4[kSemQ][kSemPix / 4];
+    __shared__ float4 pr4[kSemQ][KC / 4];
+    static_assert(2 * (kT / 32) <= kSemQ, "the final reduction reuses the sigmoid staging");
+    const int tid = threadIdx.x;
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p0 = (int64_t)blockIdx.x * kSemPix;
+    const int sp = tid & (kSemPix - 1), sq = tid >> 7;
+    const int64_t pix = p0 + sp;
+    const bool live = pix < HW;
+    PixGeom g;
+    pix_geom(g, live ? (int)(pix / W) : 0, live ? (int)(pix % W) : 0, h, w, Hp, Wp, hi, wi, H, W);
+    float* sig = (float*)sig4;
+    float* pr = (float*)pr4;
+    const int pg = tid & 31, cg = tid >> 5;
+    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int bidx[4] = {K, K, K, K};
+    for (int cbase = 0; cbase < K; cbase += KC) {
+        float acc[CPT][4];
+#pragma unroll
+        for (int j = 0; j < CPT; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+        for (int q0 = 0; q0 < Q; q0 += kSemQ) {
+            const int nq = min(kSemQ, Q - q0);
+            __syncthreads();
+            for (int i = sq; i < kSemQ; i += kT / kSemPix) {
+                float s = 0.f;
+                if (i < nq && live) s = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
+                sig[i * kSemPix + sp] = s;
+            }
+            for (int e = tid; e < kSemQ * KC; e += kT) {
+                const int i = e / KC, c = e % KC;
+                pr[e] = (i < nq && cbase + c < K) ? probs[(int64_t)(q0 + i) * K + cbase + c] : 0.f;
+            }
+            __syncthreads();
+            for (int i = 0; i < nq; ++i) {
+                const float4 s = sig4[i][pg];
+#pragma unroll
+                for (int j4 = 0; j4 < CPT / 4; ++j4) {
+                    const float4 pv = pr4[i][cg * (CPT / 4) + j4];
+                    const float pj[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        float* a = acc[j4 * 4 + u];
+                        a[0] = fmaf(pj[u], s.x, a[0]);
+                        a[1] = fmaf(pj[u], s.y, a[1]);
+                        a[2] = fmaf(pj[u], s.z, a[2]);
+                        a[3] = fmaf(pj[u], s.w, a[3]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) {
+            const int c = cbase + cg * CPT + j;
+            if (c < K) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (acc[j][i] > best[i]) { best[i] = acc[j][i]; bidx[i] = c; }
+            }
+        }
+    }
+    // the 8 class groups of a pixel meet in the staging buffer (same LDS as seg_semantic_kernel: same occupancy)
+    float (*red_v)[kSemPix] = (float (*)[kSemPix])sig;
+    int (*red_i)[kSemPix] = (int (*)[kSemPix])(sig + (kT / 32) * kSemPix);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        red_v[cg][pg * 4 + i] = best[i];
+        red_i[cg][pg * 4 + i] = bidx[i];
+    }
+    __syncthreads();
+    if (tid < kSemPix && p0 + tid < HW) {
+        float b = red_v[0][tid];
+        int bi = red_i[0][tid];
+#pragma unroll
+        for (int c = 1; c < kT / 32; ++c) {
+            const float v = red_v[c][tid];
+            const int vi = red_i[c][tid];
+            if (v > b || (v == b && vi < bi)) { b = v; bi = vi; }
+        }
+        labels[p0 + tid] = bi;
+    }
+}
+
+// labels of the "after" mode: scores fp32 [K, hi, wi] (mpf_seg_semantic on the cropped grid) resized to [H, W] plane by plane with
+// the tap() / lerp2 rule, running argmax per output pixel (first index on ties); the [K, H, W] map is never written
+__global__ __launch_bounds__(kT) void seg_labels_resize_kernel(const float* __restrict__ scores, int K, int hi, int wi, int H, int W,
+                                                               int* __restrict__ labels)
+{
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x;
+    if (p >= HW) return;
+    const Tap ty = tap((int)(p / W), hi, H), tx = tap((int)(p % W), wi, W);
+    const int64_t plane = (int64_t)hi * wi;
+    const int64_t o00 = (int64_t)ty.i0 * wi + tx.i0, o01 = (int64_t)ty.i0 * wi + tx.i1, o10 = (int64_t)ty.i1 * wi + tx.i0,
+                  o11 = (int64_t)ty.i1 * wi + tx.i1;
+    float best = -INFINITY;
+    int bi = 0;
+    for (int c = 0; c < K; ++c) {
+        const float* s = scores + c * plane;
+        const float v = lerp2(ty.l0, ty.l1, tx.l0, tx.l1, s[o00], s[o01], s[o10], s[o11]);
+        if (v > best) { best = v; bi = c; }
+    }
+    labels[p] = bi;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// confusion matrix: conf[(K+1) * pred + gt] += 1 over n pixels, integers only.  Each thread walks kConfRun consecutive pixels and
+// merges equal neighbours (label maps are piecewise constant) before it adds.  LDS form: a per-workgroup histogram of (K+1)^2
+// int32 counters in dynamic LDS, flushed with one 64-bit integer atomic per non-zero counter; global form: the merged runs go to
+// conf directly.
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int kConfT = 1024;       // threads per workgroup: 16 waves, the histogram is the only LDS user of its CU
+constexpr int kConfRun = 8;        // consecutive pixels per thread
+// LDS of a CU is 160 KiB (MI355X_MICROARCH.md, chip table).  One workgroup may take up to 128 KiB of it: 32 KiB stay free for a
+// workgroup of another kernel on the same CU (the semantic kernels of the next image hold 24-48 KiB).  (K+1)^2 * 4 B <= 128 KiB
+// is K <= 180: Cityscapes 19, COCO 133 and ADE20K 150 take the LDS form, larger class sets the global one.
+constexpr size_t kConfLdsMax = 128 * 1024;
+
+__device__ __forceinline__ int conf_cell(int pr, int g, int K, int ignore_label)
+{
+    const int r = (pr < 0 || pr >= K) ? K : pr;
+    const int c = (g == ignore_label || g < 0 || g >= K) ? K : g;
+    return r * (K + 1) + c;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kConfT) void seg_confusion_kernel(const int* __restrict__ pred, const int* __restrict__ gt, int64_t n, int K,
+                                                               int ignore_label, unsigned long long* __restrict__ conf)
+{
+    extern __shared__ int conf_hist[];
+    const int cells = (K + 1) * (K + 1);
+    if (LDS) {
+        for (int i = threadIdx.x; i < cells; i += kConfT) conf_hist[i] = 0;
+        __syncthreads();
+    }
+    const int64_t nruns = (n + kConfRun - 1) / kConfRun;
+    for (int64_t r = (int64_t)blockIdx.x * kConfT + threadIdx.x; r < nruns; r += (int64_t)gridDim.x * kConfT) {
+        const int64_t p0 = r * kConfRun;
+        const int m = (int)min((int64_t)kConfRun, n - p0);
+        int cur = conf_cell(pred[p0], gt[p0], K, ignore_label), cnt = 1;
+        for (int i = 1; i < m; ++i) {
+            const int c = conf_cell(pred[p0 + i], gt[p0 + i], K, ignore_label);
+            if (c == cur) { ++cnt; continue; }
+            if (LDS) atomicAdd(&conf_hist[cur], cnt);
+            else atomicAdd(&conf[cur], (unsigned long long)cnt);
+            cur = c;
+            cnt = 1;
+        }
+        if (LDS) atomicAdd(&conf_hist[cur], cnt);
+        else atomicAdd(&conf[cur], (unsigned long long)cnt);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < cells; i += kConfT) {
+            const int v = conf_hist[i];
+            if (v) atomicAdd(&conf[i], (unsigned long long)v);
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// instance masks as uncompressed COCO run lengths.  Position p = x * H + y (the mask flattened column-major); bit[p] = resample(m) > 0
+// exactly as seg_instance_kernel decides it.  A boundary is a position whose bit differs from its predecessor's, with bit[-1] = 0:
+// the counts of an instance are the differences of {0, boundaries ..., H * W}, so they start with a (possibly empty) run of zeros.
+//   seg_rle_bits_kernel     64 positions per wave ballot -> one packed word; entry t = blockIdx.y
+//   seg_rle_count_kernel    boundaries per tile of kRleWords words (one word per thread), from the packed bits
+//   seg_rle_scan_kernel     ONE workgroup: exclusive scan of the tile counts in (entry, tile) order, + 1 end mark per entry
+//                           -> first packed slot of every tile (int64) and the per-entry offsets [T + 1]
+//   seg_rle_scatter_kernel  the boundary positions (and H * W as the end mark) to their slots: rank = tile start + a fixed-order
+//                           scan inside the workgroup, no atomics
+//   seg_rle_diff_kernel     counts[i] = pos[i] - pos[i - 1] (0 before the first slot of an entry: the slot after an end mark)
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int kRleWords = kT;      // words (64 positions each) per tile of the count / scatter kernels
+
+template <typename T>
+__global__ __launch_bounds__(kT) void seg_rle_bits_kernel(const T* __restrict__ masks, int64_t stride_q, int h, int w, int Hp, int Wp,
+                                                          int hi, int wi, int H, int W, const int64_t* __restrict__ sel_q,
+                                                          int64_t nwords, unsigned long long* __restrict__ bits)
+{
+    const int t = blockIdx.y;
+    const int64_t HW = (int64_t)H * W;
+    const T* m = masks + sel_q[t] * stride_q;
+#pragma unroll
+    for (int i = 0; i < kInstPix / kT; ++i) {
+        const int64_t p = (int64_t)blockIdx.x * kInstPix + threadIdx.x + kT * i;    // wave-aligned: a wave covers one word
+        bool on = false;
+        if (p < HW) {
+            PixGeom g;
+            pix_geom(g, (int)(p % H), (int)(p / H), h, w, Hp, Wp, hi, wi, H, W);
+            on = resample(m, g) > 0.f;
+        }
+        const unsigned long long b = __ballot(on);
+        if ((threadIdx.x & 63) == 0 && (p >> 6) < nwords) bits[t * nwords + (p >> 6)] = b;
+    }
+}
+
+// the boundary mask of word j of one entry (bits beyond H * W are 0 in the packed words and are masked out here)
+__device__ __forceinline__ unsigned long long rle_boundaries(const unsigned long long* __restrict__ row, int64_t j, int64_t HW)
+{
+    const unsigned long long wd = row[j];
+    const unsigned long long prev = j > 0 ? row[j - 1] >> 63 : 0ull;
+    unsigned long long s = wd ^ ((wd << 1) | prev);
+    const int64_t left = HW - j * 64;
+    if (left < 64) s &= (1ull << left) - 1ull;
+    return s;
+}
+
+// inclusive scan of one int per thread over the workgroup, in thread order -> (exclusive prefix of this thread, workgroup total)
+__device__ __forceinline__ int block_excl_scan(int v, int& total)
+{
+    __shared__ int wsum[kT / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o);
+        if (lane >= o) inc += u;
+    }
+    __syncthreads();                                         // (wsum may still be read from an earlier call)
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < kT / 64; ++i) {
+        if (i < wave) base += wsum[i];
+        total += wsum[i];
+    }
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(kT) void seg_rle_count_kernel(const unsigned long long* __restrict__ bits, int64_t nwords, int64_t HW,
+                                                           int* __restrict__ tile_cnt)
+{
+    const int t = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * kRleWords + threadIdx.x;
+    int c = 0;
+    if (j < nwords) c = __popcll(rle_boundaries(bits + t * nwords, j, HW));
+    int total;
+    block_excl_scan(c, total);
+    if (threadIdx.x == 0) tile_cnt[(int64_t)t * gridDim.x + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kT) void seg_rle_scan_kernel(const int* __restrict__ tile_cnt, int tiles, int T, int64_t* __restrict__ tile_off,
+                                                          int64_t* __restrict__ offsets)
+{
+    __shared__ int64_t part[kT];
+    const int64_t n = (int64_t)T * tiles;
+    const int64_t per = (n + kT - 1) / kT;
+    const int64_t lo = min(n, per * threadIdx.x), hi = min(n, lo + per);
+    int64_t s = 0;
+    for (int64_t i = lo; i < hi; ++i) s += tile_cnt[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {                                   // 256 partial sums: serial, fixed order
+        int64_t run = 0;
+        for (int i = 0; i < kT; ++i) {
+            const int64_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        offsets[T] = run + T;
+    }
+    __syncthreads();
+    int64_t run = part[threadIdx.x];
+    for (int64_t i = lo; i < hi; ++i) {
+        const int64_t t = i / tiles;
+        const int64_t off = run + t;                          // + one end mark for every earlier entry
+        tile_off[i] = off;
+        if (i % tiles == 0) offsets[t] = off;
+        run += tile_cnt[i];
+    }
+}
+
+__global__ __launch_bounds__(kT) void seg_rle_scatter_kernel(const unsigned long long* __restrict__ bits, int64_t nwords, int64_t HW,
+                                                             const int64_t* __restrict__ tile_off, const int64_t* __restrict__ offsets,
+                                                             int64_t cap, unsigned* __restrict__ pos)
+{
+    const int t = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * kRleWords + threadIdx.x;
+    unsigned long long s = 0ull;
+    if (j < nwords) s = rle_boundaries(bits + t * nwords, j, HW);
+    int total;
+    int64_t slot = tile_off[(int64_t)t * gridDim.x + blockIdx.x] + block_excl_scan(__popcll(s), total);
+    while (s) {
+        const int k = __ffsll((long long)s) - 1;
+        if (slot < cap) pos[slot] = (unsigned)(j * 64 + k);      // (cap: the caller's total; never short when it read offsets[T])
+        ++slot;
+        s &= s - 1ull;
+    }
+    if (j == nwords - 1 && offsets[t + 1] <= cap) pos[offsets[t + 1] - 1] = (unsigned)HW;
+}
+
+__global__ __launch_bounds__(kT) void seg_rle_diff_kernel(const unsigned* __restrict__ pos, const int64_t* __restrict__ total_p, int64_t cap,
+                                                          unsigned HW, unsigned* __restrict__ counts)
+{
+    const int64_t total = min(*total_p, cap);
+    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
+        const unsigned before = i > 0 ? pos[i - 1] : HW;
+        counts[i] = pos[i] - (before == HW ? 0u : before);
+    }
+}
+
 // shared argument checks of the per-pixel entry points
 int check_geom(const char* who, const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
                int H, int W)
@@ -521,4 +849,153 @@ extern "C" int mpf_seg_panoptic_paint(const int* code, int H, int W, const int* 
     hipLaunchKernelGGL(seg_paint_kernel, dim3((unsigned)((HW + kT - 1) / kT)), dim3(kT), 0, st, code, HW, lut, out);
     mpf::prof_end("seg_paint_kernel", st, 8.0 * HW);
     return mpf::check(hipGetLastError(), "mpf_seg_panoptic_paint");
+}
+
+extern "C" int mpf_seg_semantic_labels(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
+                                       int H, int W, const float* probs, int K, int* labels, void* stream)
+{
+    if (int e = check_geom("seg_semantic_labels", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!probs || !labels) return mpf::fail(MPF_E_NULL, "seg_semantic_labels: NULL buffer");
+    if (K <= 0) return mpf::fail(MPF_E_SHAPE, "seg_semantic_labels: K must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    const int cpt = K <= 32 ? 4 : K <= 64 ? 8 : K <= 96 ? 12 : 24;      // as mpf_seg_semantic; K > 192: chunks of 192 in a loop
+    const dim3 grid((unsigned)((HW + kSemPix - 1) / kSemPix));
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_labels_kernel");
+#define MPF_LAB(T, C)                                                                                                              \
+    hipLaunchKernelGGL((seg_labels_kernel<T, C>), grid, dim3(kT), 0, st, (const T*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H, W, \
+                       probs, K, labels)
+#define MPF_LAB_T(T)                   \
+    do {                               \
+        if (cpt == 4) MPF_LAB(T, 4);   \
+        else if (cpt == 8) MPF_LAB(T, 8);   \
+        else if (cpt == 12) MPF_LAB(T, 12); \
+        else MPF_LAB(T, 24);           \
+    } while (0)
+    if (dtype == MPF_F32) MPF_LAB_T(float);
+    else MPF_LAB_T(__hip_bfloat16);
+#undef MPF_LAB_T
+#undef MPF_LAB
+    mpf::prof_end("seg_labels_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * HW, 2.0 * K * Q * (double)HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_semantic_labels");
+}
+
+extern "C" int mpf_seg_labels_resize(const float* scores, int K, int hi, int wi, int H, int W, int* labels, void* stream)
+{
+    if (!scores || !labels) return mpf::fail(MPF_E_NULL, "seg_labels_resize: NULL buffer");
+    if (K <= 0 || hi <= 0 || wi <= 0 || H <= 0 || W <= 0) return mpf::fail(MPF_E_SHAPE, "seg_labels_resize: bad sizes");
+    if ((int64_t)H * W >= (1ll << 31) || (int64_t)K * hi * wi >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "seg_labels_resize: too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_labels_resize_kernel");
+    hipLaunchKernelGGL(seg_labels_resize_kernel, dim3((unsigned)((HW + kT - 1) / kT)), dim3(kT), 0, st, scores, K, hi, wi, H, W, labels);
+    mpf::prof_end("seg_labels_resize_kernel", st, 4.0 * K * hi * wi + 4.0 * HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_labels_resize");
+}
+
+extern "C" int mpf_seg_confusion_add(const int* pred, const int* gt, int64_t n, int K, int ignore_label, int64_t* conf, void* stream)
+{
+    if (!pred || !gt || !conf) return mpf::fail(MPF_E_NULL, "seg_confusion_add: NULL buffer");
+    if (n <= 0 || K <= 0 || K > 32766) return mpf::fail(MPF_E_SHAPE, "seg_confusion_add: need n > 0 pixels and 1 <= K <= 32766 classes");
+    if (n >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "seg_confusion_add: too many pixels for one call");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)(K + 1) * (K + 1) * sizeof(int);
+    const int64_t nruns = (n + kConfRun - 1) / kConfRun;
+    const int64_t want = (nruns + kConfT - 1) / kConfT;
+    const bool use_lds = lds <= kConfLdsMax;
+    // LDS form: at most one workgroup per CU (every workgroup pays a zero and a flush pass over the histogram)
+    const unsigned grid = (unsigned)std::min<int64_t>(want, use_lds ? mpf::cu_count() : 4 * mpf::cu_count());
+    unsigned long long* out = (unsigned long long*)conf;
+    mpf::prof_begin(st);
+    mpf::set_kernel(use_lds ? "seg_confusion_kernel<lds>" : "seg_confusion_kernel<global>");
+    if (use_lds) {
+        static mpf::LdsAttr attr;
+        if (int e = mpf::ensure_dynamic_lds((const void*)seg_confusion_kernel<true>, kConfLdsMax, attr)) return e;
+        hipLaunchKernelGGL(seg_confusion_kernel<true>, dim3(grid), dim3(kConfT), lds, st, pred, gt, n, K, ignore_label, out);
+    } else {
+        hipLaunchKernelGGL(seg_confusion_kernel<false>, dim3(grid), dim3(kConfT), 0, st, pred, gt, n, K, ignore_label, out);
+    }
+    mpf::prof_end("seg_confusion_kernel", st, 8.0 * n);
+    return mpf::check(hipGetLastError(), "mpf_seg_confusion_add");
+}
+
+namespace {
+struct RleLayout {
+    int64_t nwords, tiles;
+    size_t bits, tile_off, tile_cnt, total;                  // byte offsets of the three parts, and the size
+};
+RleLayout rle_layout(int T, int H, int W)
+{
+    RleLayout l;
+    l.nwords = ((int64_t)H * W + 63) / 64;
+    l.tiles = (l.nwords + kRleWords - 1) / kRleWords;
+    l.bits = 0;
+    l.tile_off = (size_t)T * l.nwords * 8;
+    l.tile_cnt = l.tile_off + (size_t)T * l.tiles * 8;
+    l.total = l.tile_cnt + (((size_t)T * l.tiles * 4 + 7) & ~(size_t)7);
+    return l;
+}
+}  // namespace
+
+extern "C" size_t mpf_seg_instance_rle_workspace_bytes(int T, int H, int W)
+{
+    if (T <= 0 || H <= 0 || W <= 0) return 0;
+    return rle_layout(T, H, W).total;
+}
+
+extern "C" int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi,
+                                          int wi, int H, int W, const int64_t* sel_q, int T, int64_t* offsets, void* workspace,
+                                          size_t workspace_bytes, void* stream)
+{
+    if (int e = check_geom("seg_instance_rle_count", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!sel_q || !offsets || !workspace) return mpf::fail(MPF_E_NULL, "seg_instance_rle_count: NULL buffer");
+    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_count: need 1 <= T <= 65535 entries");
+    const RleLayout l = rle_layout(T, H, W);
+    if (workspace_bytes < l.total) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_count: workspace too small");
+    if (((uintptr_t)workspace & 7) != 0) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_count: workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    char* ws = (char*)workspace;
+    unsigned long long* bits = (unsigned long long*)(ws + l.bits);
+    int64_t* tile_off = (int64_t*)(ws + l.tile_off);
+    int* tile_cnt = (int*)(ws + l.tile_cnt);
+    const dim3 gbits((unsigned)((HW + kInstPix - 1) / kInstPix), (unsigned)T);
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_rle_bits_kernel+seg_rle_count_kernel+seg_rle_scan_kernel");
+    if (dtype == MPF_F32)
+        hipLaunchKernelGGL(seg_rle_bits_kernel<float>, gbits, dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi, H, W, sel_q,
+                           l.nwords, bits);
+    else
+        hipLaunchKernelGGL(seg_rle_bits_kernel<__hip_bfloat16>, gbits, dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h, w, Hp, Wp,
+                           hi, wi, H, W, sel_q, l.nwords, bits);
+    hipLaunchKernelGGL(seg_rle_count_kernel, dim3((unsigned)l.tiles, (unsigned)T), dim3(kT), 0, st, (const unsigned long long*)bits, l.nwords,
+                       HW, tile_cnt);
+    hipLaunchKernelGGL(seg_rle_scan_kernel, dim3(1), dim3(kT), 0, st, (const int*)tile_cnt, (int)l.tiles, T, tile_off, offsets);
+    mpf::prof_end("seg_rle_bits_kernel", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + (double)T * HW / 8);
+    return mpf::check(hipGetLastError(), "mpf_seg_instance_rle_count");
+}
+
+extern "C" int mpf_seg_instance_rle_write(const void* workspace, size_t workspace_bytes, int T, int H, int W, const int64_t* offsets,
+                                          int64_t total, uint32_t* pos, uint32_t* counts, void* stream)
+{
+    if (!workspace || !offsets || !pos || !counts) return mpf::fail(MPF_E_NULL, "seg_instance_rle_write: NULL buffer");
+    if (T <= 0 || T > 65535 || H <= 0 || W <= 0) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_write: bad sizes");
+    if ((int64_t)H * W >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "seg_instance_rle_write: output too large");
+    // every entry has at least its end mark and at most one boundary per position
+    if (total < T || total > (int64_t)T * ((int64_t)H * W + 1)) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_write: total is not offsets[T]");
+    const RleLayout l = rle_layout(T, H, W);
+    if (workspace_bytes < l.total) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_write: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    const char* ws = (const char*)workspace;
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_rle_scatter_kernel+seg_rle_diff_kernel");
+    hipLaunchKernelGGL(seg_rle_scatter_kernel, dim3((unsigned)l.tiles, (unsigned)T), dim3(kT), 0, st, (const unsigned long long*)(ws + l.bits),
+                       l.nwords, HW, (const int64_t*)(ws + l.tile_off), offsets, total, pos);
+    const unsigned gdiff = (unsigned)std::min<int64_t>((total + kT - 1) / kT, 8 * mpf::cu_count());
+    hipLaunchKernelGGL(seg_rle_diff_kernel, dim3(gdiff), dim3(kT), 0, st, (const unsigned*)pos, offsets + T, total, (unsigned)HW, counts);
+    mpf::prof_end("seg_rle_scatter_kernel", st, (double)T * HW / 8 + 12.0 * total);
+    return mpf::check(hipGetLastError(), "mpf_seg_instance_rle_write");
 }

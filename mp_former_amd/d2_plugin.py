@@ -118,11 +118,13 @@ def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None):
                        cfg)
 
 
-def install_native_inference(model, image_list_cls=None):
+def install_native_inference(model, image_list_cls=None, semantic_labels=False, instance_masks="dense"):
     """Route the eval branch of a reference ``MaskFormer`` instance through ``native_eval_forward``; training is unchanged.
-    Returns the inference.InferenceConfig read from the model."""
+    ``semantic_labels`` / ``instance_masks``: the evaluation-form results of inference.InferenceConfig (the model has no such
+    attributes; the defaults give the reference's own result dicts).  Returns the inference.InferenceConfig in use."""
+    import dataclasses
     from .inference import InferenceConfig
-    cfg = InferenceConfig.from_maskformer(model)
+    cfg = dataclasses.replace(InferenceConfig.from_maskformer(model), semantic_labels=semantic_labels, instance_masks=instance_masks)
     train_forward = model.forward
 
     def forward(batched_inputs):

@@ -8,12 +8,20 @@ The per-pixel work runs on the device; what stays on the host is the panoptic se
 entries), fed by ONE device-to-host copy of the per-query area counters.  CPU tensors and other dtypes raise: there is
 no torch fallback.
 
+For an evaluation loop the largest results can be had in the form their consumers use (both off by default):
+* ``InferenceConfig.semantic_labels``: ``"sem_seg_labels"`` int32 [H, W] (the argmax every evaluator takes) instead of the
+  fp32 [K, H, W] ``"sem_seg"``, which is then never written; ``SemSegConfusion`` accumulates the (K+1) x (K+1) counts of mIoU
+  from such label maps on the device.
+* ``InferenceConfig.instance_masks = "rle"``: ``pred_masks_rle`` (uncompressed COCO run lengths) instead of the fp32
+  [T, H, W] ``pred_masks``; only the run lengths cross to the host.
+
 Deviations from the reference, by design:
 * ``instances`` are sorted by score, descending (the reference's ``topk(sorted=False)`` order is unspecified);
 * all results are fp32 whatever the mask dtype (bf16 logits are widened on load; the reference would compute in bf16).
 """
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -35,9 +43,15 @@ class InferenceConfig:
     panoptic_on: bool = False
     sem_seg_postprocess_before_inference: bool = True
     thing_ids: frozenset = field(default_factory=frozenset)     # contiguous ids of the thing classes
+    semantic_labels: bool = False       # "sem_seg_labels" int32 [H, W] instead of "sem_seg" fp32 [K, H, W]
+    instance_masks: str = "dense"       # "dense": pred_masks fp32 [T, H, W]; "rle": pred_masks_rle (uncompressed COCO RLE)
 
     def __post_init__(self):
         self.thing_ids = frozenset(int(i) for i in self.thing_ids)
+        if self.semantic_labels and not self.semantic_on:
+            raise ValueError("semantic_labels needs semantic_on")
+        if self.instance_masks not in ("dense", "rle"):
+            raise ValueError(f"instance_masks must be 'dense' or 'rle', got {self.instance_masks!r}")
         if not self.semantic_on and not self.sem_seg_postprocess_before_inference:
             raise ValueError("sem_seg_postprocess_before_inference=False needs semantic_on (maskformer_model.py:97-98)")
         if (self.instance_on or self.panoptic_on) and not self.sem_seg_postprocess_before_inference:
@@ -178,6 +192,40 @@ def _semantic(mptr, sq, dt, geom, probs, K, dev, stream):
     return out
 
 
+def _semantic_labels(mptr, sq, dt, geom, probs, K, dev, stream):
+    """"before" mode: the label map straight from the logits, in one launch."""
+    H, W = geom[-2:]
+    out = torch.empty((H, W), dtype=torch.int32, device=dev)
+    _lib.call("mpf_seg_semantic_labels", dev, mptr, sq, dt, *geom, probs.data_ptr(), K, out.data_ptr(), stream)
+    return out
+
+
+def _labels_resize(scores, out_hw, dev, stream):
+    """"after" mode: scores [K, hi, wi] on the cropped grid -> labels [H, W] of their bilinear resize."""
+    K, hi, wi = scores.shape
+    out = torch.empty(out_hw, dtype=torch.int32, device=dev)
+    _lib.call("mpf_seg_labels_resize", dev, scores.data_ptr(), K, hi, wi, int(out_hw[0]), int(out_hw[1]), out.data_ptr(), stream)
+    return out
+
+
+def _instance_rle(mptr, sq, dt, geom, query, T, dev, stream):
+    """The masks of the sorted entries as uncompressed COCO RLE dicts; two device-to-host copies: offsets, then counts."""
+    H, W = geom[-2:]
+    nws = _lib.lib().mpf_seg_instance_rle_workspace_bytes(T, H, W)
+    ws = _lib.scratch("seg_infer.rle", dev, stream, nws)
+    offsets = torch.empty(T + 1, dtype=torch.int64, device=dev)
+    _lib.call("mpf_seg_instance_rle_count", dev, mptr, sq, dt, *geom, query.data_ptr(), T, offsets.data_ptr(), ws.data_ptr(), ws.numel(),
+              stream)
+    off = offsets.cpu().numpy()                          # copy 1: where every entry's counts lie
+    total = int(off[T])
+    pos = _lib.scratch("seg_infer.rle_pos", dev, stream, 4 * total)
+    counts = torch.empty(total, dtype=torch.int32, device=dev)
+    _lib.call("mpf_seg_instance_rle_write", dev, ws.data_ptr(), ws.numel(), T, H, W, offsets.data_ptr(), total, pos.data_ptr(),
+              counts.data_ptr(), stream)
+    host = counts.cpu().numpy().view(np.uint32)          # copy 2: the packed counts
+    return [{"size": [H, W], "counts": host[off[t]:off[t + 1]].tolist()} for t in range(T)]
+
+
 def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
     Q, K = img.Q, img.K
     H, W = geom[-2:]
@@ -191,8 +239,12 @@ def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
     T = int(sc.shape[0])
     Boxes, Instances = _structures()
     result = Instances(image_hw)
+    rle = cfg.instance_masks == "rle"
     if T == 0:
-        result.pred_masks = torch.zeros((0, H, W), dtype=torch.float32, device=dev)
+        if rle:
+            result.pred_masks_rle = []
+        else:
+            result.pred_masks = torch.zeros((0, H, W), dtype=torch.float32, device=dev)
         result.pred_boxes = Boxes(torch.zeros(0, 4))
         result.scores = sc
         result.pred_classes = labels
@@ -205,9 +257,12 @@ def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
               ws.numel(), stream)
     scores, order = scores.sort(descending=True, stable=True)
     query, labels = query[order].contiguous(), labels[order]
-    masks = torch.empty((T, H, W), dtype=torch.float32, device=dev)
-    _lib.call("mpf_seg_instance_masks", dev, mptr, sq, dt, *geom, query.data_ptr(), T, masks.data_ptr(), stream)
-    result.pred_masks = masks
+    if rle:
+        result.pred_masks_rle = _instance_rle(mptr, sq, dt, geom, query, T, dev, stream)
+    else:
+        masks = torch.empty((T, H, W), dtype=torch.float32, device=dev)
+        _lib.call("mpf_seg_instance_masks", dev, mptr, sq, dt, *geom, query.data_ptr(), T, masks.data_ptr(), stream)
+        result.pred_masks = masks
     result.pred_boxes = Boxes(torch.zeros(T, 4))
     result.scores = scores
     result.pred_classes = labels
@@ -239,7 +294,9 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
     planes (a slice of the decoder's [N, L*Q, h, w] tensor is used in place), image_sizes [(hi, wi)] per image,
     padded_hw = the padded batch size (images.tensor.shape[-2:]), output_sizes [(height, width)] per image.
     -> list of dicts with "sem_seg" [K, height, width], "panoptic_seg" (ids int32 [height, width], segments_info) and
-    "instances" (pred_masks [T, height, width] 0/1 fp32, pred_boxes zeros, scores, pred_classes), per the *_on flags."""
+    "instances" (pred_masks [T, height, width] 0/1 fp32, pred_boxes zeros, scores, pred_classes), per the *_on flags.
+    cfg.semantic_labels: "sem_seg_labels" int32 [height, width] in place of "sem_seg"; cfg.instance_masks == "rle":
+    instances.pred_masks_rle (list of T {"size", "counts"} dicts) in place of pred_masks."""
     if not (pred_masks.is_cuda and pred_logits.is_cuda):
         raise RuntimeError("postprocess: Not implemented on the CPU (device tensors only)")
     N, Q, K1 = pred_logits.shape
@@ -266,7 +323,14 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
         H, W = int(output_sizes[n][0]), int(output_sizes[n][1])
         img = _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n)
         res = {}
-        if cfg.semantic_on:
+        if cfg.semantic_on and cfg.semantic_labels:
+            if cfg.sem_seg_postprocess_before_inference:
+                res["sem_seg_labels"] = _semantic_labels(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img.probs, K, dev,
+                                                         stream)
+            else:   # the scores on the cropped padded grid (network resolution), then resize + argmax in one pass
+                r = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (hi, wi)), img.probs, K, dev, stream)
+                res["sem_seg_labels"] = _labels_resize(r, (H, W), dev, stream)
+        elif cfg.semantic_on:
             if cfg.sem_seg_postprocess_before_inference:
                 res["sem_seg"] = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img.probs, K, dev, stream)
             else:   # inference on the cropped padded grid, then the reference's own resize of the K planes (:264-265)
@@ -279,3 +343,90 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
                                           (H, W))
         out.append(res)
     return out
+
+
+# ---- semantic evaluation on the device ------------------------------------------------------------------------------------------
+class SemSegConfusion:
+    """The per-pixel part of detectron2's ``SemSegEvaluator``: the (K+1) x (K+1) confusion counts of predicted label against
+    ground truth (row = prediction, column = ground truth, index K = ignored / out of range), accumulated on the device by
+    ``mpf_seg_confusion_add``.  ``update`` launches and returns; only ``matrix`` copies to the host."""
+
+    def __init__(self, num_classes, ignore_label=255, device="cuda:0"):
+        self.num_classes = int(num_classes)
+        self.ignore_label = int(ignore_label)
+        self.device = torch.device(device)
+        if self.num_classes <= 0:
+            raise ValueError("num_classes must be positive")
+        self._conf = None
+
+    def _buffer(self):
+        if self._conf is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("SemSegConfusion: Not implemented on the CPU (device tensors only)")
+            self._conf = torch.zeros((self.num_classes + 1) ** 2, dtype=torch.int64, device=self.device)
+        return self._conf
+
+    def reset(self):
+        if self._conf is not None:
+            self._conf.zero_()
+
+    def update(self, labels, gt):
+        """labels: int32 [H, W] on the device ("sem_seg_labels"); gt: any integer dtype, [H, W]."""
+        if labels.dim() != 2 or tuple(labels.shape) != tuple(gt.shape):
+            raise ValueError(f"labels {tuple(labels.shape)} and gt {tuple(gt.shape)} must be the same [H, W]")
+        if labels.dtype != torch.int32:
+            raise TypeError(f"labels must be int32, got {labels.dtype}")
+        if gt.dtype.is_floating_point or gt.dtype.is_complex or gt.dtype == torch.bool:
+            raise TypeError(f"gt must be an integer tensor, got {gt.dtype}")
+        conf = self._buffer()
+        if labels.device != conf.device:
+            raise RuntimeError(f"labels are on {labels.device}, the counters on {conf.device}")
+        labels = labels.contiguous()
+        gt = gt.to(device=conf.device, dtype=torch.int32).contiguous()
+        _lib.call("mpf_seg_confusion_add", conf.device, labels.data_ptr(), gt.data_ptr(), labels.numel(), self.num_classes,
+                  self.ignore_label, conf.data_ptr(), _lib.stream_ptr(conf.device))
+
+    def matrix(self):
+        """-> int64 numpy [K+1, K+1] (one device-to-host copy)"""
+        k1 = self.num_classes + 1
+        if self._conf is None:
+            return np.zeros((k1, k1), dtype=np.int64)
+        return self._conf.cpu().numpy().reshape(k1, k1)
+
+    def results(self, class_names=None):
+        return confusion_results(self.matrix(), class_names)
+
+
+def confusion_results(conf, class_names=None):
+    """detectron2's ``SemSegEvaluator.evaluate`` on a [K+1, K+1] confusion matrix (row = prediction): mIoU, fwIoU, mACC, pACC and
+    the per-class IoU-{name} / ACC-{name} (x 100; names default to the class index)."""
+    conf = np.asarray(conf, dtype=np.int64)
+    k = conf.shape[0] - 1
+    if conf.shape != (k + 1, k + 1) or k <= 0:
+        raise ValueError(f"confusion matrix must be [K+1, K+1], got {conf.shape}")
+    if class_names is not None and len(class_names) != k:
+        raise ValueError(f"{len(class_names)} class names for {k} classes")
+    c = conf[:-1, :-1]
+    tp = np.diag(c).astype(np.float64)
+    pos_gt = c.sum(0).astype(np.float64)
+    pos_pred = c.sum(1).astype(np.float64)
+    acc = np.full(k, np.nan)
+    iou = np.full(k, np.nan)
+    acc_valid = pos_gt > 0
+    acc[acc_valid] = tp[acc_valid] / pos_gt[acc_valid]
+    union = pos_gt + pos_pred - tp
+    iou_valid = acc_valid & (union > 0)
+    iou[iou_valid] = tp[iou_valid] / union[iou_valid]
+    n_gt = pos_gt.sum()
+    class_weights = pos_gt / n_gt if n_gt > 0 else np.zeros(k)
+    res = {
+        "mIoU": 100 * (iou[iou_valid].sum() / iou_valid.sum()) if iou_valid.any() else float("nan"),
+        "fwIoU": 100 * float((iou[iou_valid] * class_weights[iou_valid]).sum()) if n_gt > 0 else float("nan"),
+        "mACC": 100 * (acc[acc_valid].sum() / acc_valid.sum()) if acc_valid.any() else float("nan"),
+        "pACC": 100 * tp.sum() / n_gt if n_gt > 0 else float("nan"),
+    }
+    names = [str(i) for i in range(k)] if class_names is None else list(class_names)
+    for i, name in enumerate(names):
+        res[f"IoU-{name}"] = 100 * float(iou[i])
+        res[f"ACC-{name}"] = 100 * float(acc[i])
+    return {key: float(v) for key, v in res.items()}

@@ -3,12 +3,18 @@ eval branch (tests/_infer_restate.py), per image on one GPU.  Prints one line pe
 inputs, the algorithmic bytes / FLOP of the native route and the fraction of the measured 6.3 TB/s copy rate or of the
 157 TF fp32 peak it reaches (whichever bound applies).
 
-    python tools/bench_infer.py [--iters 20]
+    python tools/bench_infer.py [--iters 20] [--rows base,eval]
+
+The ``eval`` rows measure the evaluation-form results (``semantic_labels``, ``SemSegConfusion``, ``instance_masks="rle"``) against
+the default route brought to the same end product: ``sem_seg`` + ``torch.argmax`` (+ ``.cpu()`` of the label map where the metric
+is wanted), and the dense masks + ``.cpu()``.  These rows are wall-clock medians between two device synchronisations, because
+their host copies and the host's list building are part of the product; peak MB above the inputs; bytes crossing to the host.
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 
@@ -16,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from _infer_restate import restate  # noqa: E402
-from mp_former_amd.inference import InferenceConfig, postprocess  # noqa: E402
+from mp_former_amd.inference import InferenceConfig, SemSegConfusion, postprocess  # noqa: E402
 
 CASES = {
     # name: (K, low-res hw, padded, image, output, config)
@@ -59,6 +65,80 @@ def timed(fn, iters):
     return ts[len(ts) // 2], peak
 
 
+def timed_wall(fn, iters):
+    """-> (median us between two synchronisations, peak MB above what was allocated before)"""
+    fn()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    peak = (torch.cuda.max_memory_allocated() - base) / 1e6
+    ts = []
+    for _ in range(iters):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e6)
+    ts.sort()
+    return ts[len(ts) // 2], peak
+
+
+def eval_rows(name, K, hw, padded, image, out, iters, dev):
+    """The evaluation-form rows of one case: labels in both modes, without and with the confusion counts, and rle masks."""
+    lg, mk = inputs(K, hw, dev)
+    H, W = out
+    gt = torch.randint(0, K, out, dtype=torch.int64, device=dev)
+    conf = SemSegConfusion(K, device=dev)
+    rows = []
+
+    def row(kind, native, parent, native_host_bytes, parent_host_bytes):
+        t_nat, m_nat = timed_wall(native, iters)
+        t_par, m_par = timed_wall(parent, iters)
+        rows.append({"case": name, "row": kind, "native_us": round(t_nat, 1), "parent_us": round(t_par, 1), "speedup": round(t_par / t_nat, 2),
+                     "native_peak_MB": round(m_nat, 1), "parent_peak_MB": round(m_par, 1), "native_host_bytes": int(native_host_bytes),
+                     "parent_host_bytes": int(parent_host_bytes)})
+        print(json.dumps(rows[-1]), flush=True)
+
+    for before in (True, False):
+        kw = dict(semantic_on=True, instance_on=False, sem_seg_postprocess_before_inference=before)
+        c_lab = InferenceConfig(num_classes=K, num_queries=100, semantic_labels=True, **kw)
+        c_par = InferenceConfig(num_classes=K, num_queries=100, **kw)
+        mode = "before" if before else "after"
+
+        def labels():
+            return postprocess(lg, mk, [image], padded, [out], c_lab)[0]["sem_seg_labels"]
+
+        def parent_labels():
+            return postprocess(lg, mk, [image], padded, [out], c_par)[0]["sem_seg"].argmax(0)
+
+        def labels_conf():
+            conf.update(labels(), gt)
+
+        def parent_conf():                               # the label map crosses; the host's bincount is not timed
+            return parent_labels().cpu()
+
+        row(f"labels_{mode}", labels, parent_labels, 0, 0)
+        row(f"labels_{mode}+confusion", labels_conf, parent_conf, 0, 8 * H * W)
+    c_rle = InferenceConfig(num_classes=K, num_queries=100, instance_masks="rle")
+    c_dense = InferenceConfig(num_classes=K, num_queries=100)
+    n_counts = []
+
+    def rle():
+        r = postprocess(lg, mk, [image], padded, [out], c_rle)[0]["instances"].pred_masks_rle
+        n_counts.append(sum(len(x["counts"]) for x in r))
+        return r
+
+    def dense():
+        return postprocess(lg, mk, [image], padded, [out], c_dense)[0]["instances"].pred_masks.cpu()
+
+    rle()
+    T = min(100, 100 * K)
+    row("instance_rle", rle, dense, 8 * (T + 1) + 4 * n_counts[0], 4 * T * H * W)
+    return rows
+
+
 def work(K, cfg, hw, out, Q=100, T=100):
     """(bytes, flop) the native route must move / compute: the logits once per kernel that reads them, the results once."""
     H, W = out
@@ -78,10 +158,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--rows", default="base,eval")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    kinds = args.rows.split(",")
     for name in args.cases.split(","):
         K, hw, padded, image, out, kw = CASES[name]
+        if "eval" in kinds:
+            eval_rows(name, K, hw, padded, image, out, args.iters, dev)
+        if "base" not in kinds:
+            continue
         cfg = InferenceConfig(num_classes=K, num_queries=100, **kw)
         lg, mk = inputs(K, hw, dev)
         t_nat, m_nat = timed(lambda: postprocess(lg, mk, [image], padded, [out], cfg), args.iters)
