@@ -1273,6 +1273,28 @@ int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, int dtype, i
 int mpf_seg_instance_rle_write(const void* workspace, size_t workspace_bytes, int T, int H, int W, const int64_t* offsets, int64_t total,
                                uint32_t* pos, uint32_t* counts, void* stream);
 
+/*
+ * Semantic test-time augmentation (mask2former/test_time_augmentation.py:71-98, SemanticSegmentorWithTTA._inference_one_image):
+ * sem_seg = (sum over the views v of flip_v(S_v)) / V, where S_v is the view's "sem_seg" at the output size (H, W)
+ * (maskformer_model.py:236-279, :301-306), flip_v mirrors the W axis of that OUTPUT when the view was flipped (:88-92), the sum
+ * runs in the order of the calls and the division is by (float)V in fp32 (:97).  acc fp32 [K, H, W] is the caller's accumulator.
+ * mode: bit 0 = add into acc (0 = store: the first view), bit 1 = hflip; any other bit is MPF_E_SHAPE.
+ *   mpf_seg_tta_accumulate:  one view with sem_seg_postprocess_before_inference: acc (=, +=) flip(sum_q probs[q, c] *
+ *                            sigmoid(m_q)) straight from the logits (arguments as mpf_seg_semantic).  The product runs on
+ *                            v_mfma_f32_16x16x4_f32, k ascending in query order.  In the other config mode it is called in store
+ *                            mode with (H, W) = (hi, wi) and a scratch acc, which is then the scores argument of
+ *   mpf_seg_tta_resize_add:  acc (=, +=) flip(bilinear resize of scores fp32 [K, hi, wi] to [H, W]) (:264-265, align_corners=False,
+ *                            the roundings of F.interpolate).
+ *   mpf_seg_tta_finish:      count = V > 0.  labels == NULL: acc /= (float)count in place, acc is then the "sem_seg".  Otherwise
+ *                            labels int32 [H, W] = argmax_c(acc[c] / (float)count), the lowest class on a tie, acc unchanged: the
+ *                            argmax(0) of what the other form writes, bit for bit.
+ * No atomics anywhere: every element of acc has one writer per call, so results are bitwise reproducible.
+ */
+int mpf_seg_tta_accumulate(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                           int W, const float* probs, int K, int mode, float* acc, void* stream);
+int mpf_seg_tta_resize_add(const float* scores, int K, int hi, int wi, int H, int W, int mode, float* acc, void* stream);
+int mpf_seg_tta_finish(float* acc, int K, int H, int W, int count, int* labels /* NULL: divide in place */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,9 @@ SIGNATURES = {
     "mpf_seg_instance_rle_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
     "mpf_seg_instance_rle_count": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_seg_instance_rle_write": (_c_int, [_c_vp, ctypes.c_size_t, _c_int, _c_int, _c_int, _c_vp, ctypes.c_int64, _c_vp, _c_vp, _c_vp]),
+    "mpf_seg_tta_accumulate": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_tta_resize_add": (_c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_vp]),
+    "mpf_seg_tta_finish": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
 }
 
 

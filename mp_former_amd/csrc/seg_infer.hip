@@ -27,6 +27,11 @@
 //                           fits, integer global atomics otherwise.
 //   seg_rle_*               instance masks as uncompressed COCO run lengths: packed bits, boundaries per tile, a fixed-order
 //                           scan, scatter of the boundary positions, their differences.
+// Semantic test-time augmentation (mask2former/test_time_augmentation.py): the mean over the views of an image, on the device:
+//   seg_tta_accumulate_kernel   the scores of one view from its logits on the fp32 MFMA, stored / added into acc [K, H, W], plain
+//                               or mirrored along W
+//   seg_tta_resize_add_kernel   "after" mode: [K, hi, wi] scores resized and stored / added, plain or mirrored
+//   seg_tta_finish_kernel       the division by the view count in place, or the label map of the divided sums
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
@@ -694,6 +699,208 @@ __global__ __launch_bounds__(kT) void seg_rle_diff_kernel(const unsigned* __rest
     }
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// semantic test-time augmentation (mask2former/test_time_augmentation.py:71-98): acc[K, H, W] = sum over the views of the view's
+// "sem_seg", flipped back along W where the view was flipped, then one division by the number of views.
+//   seg_tta_accumulate_kernel   one view straight from its logits: the product of seg_semantic_kernel on the fp32 matrix cores,
+//                               stored or added into acc, plain or mirrored
+//   seg_tta_resize_add_kernel   "after" mode: the view's [K, hi, wi] scores resized plane by plane, stored or added into acc
+//   seg_tta_finish_kernel       acc /= V in place, or labels = argmax_c(acc[c] / V) with acc left alone
+// mode: bit 0 = add (else store), bit 1 = hflip: output pixel (y, x) of the view lands on (y, W - 1 - x).  Every destination has
+// exactly one writer (the mirror is a bijection), so "add" is a plain read-add-write.
+// ----------------------------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTtaSigRow = kSemPix + 16;   // LDS row strides = an odd multiple of 16 floats (16 or 48 mod 64): the four k-rows of an MFMA
+constexpr int kTtaPad = 16;                // fragment (lanes 0-15, 16-31, ...) fall on four different groups of 16 banks (a stride of 128: on one)
+constexpr int kTtaOutRow = 36;             // epilogue staging row: 32 pixels + 4 (16-byte aligned rows, 4 row groups on 4 bank groups)
+
+// LDS written by one wave and read back by the same wave only: program order for the compiler, no workgroup barrier (the LDS
+// serves the requests of a wave in order)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// four consecutive pixels px .. px + 3 of one class plane.  vec: H * W (mirrored: W) is a multiple of 4 and the plane is 16-byte
+// aligned, so the four lie in one row and, mirrored, on one aligned float4 in reverse order; otherwise pixel by pixel (a run may
+// cross a row end, and the tail of the plane)
+__device__ __forceinline__ void tta_put4(float* __restrict__ plane, int64_t px, int64_t HW, int W, int mode, bool vec, float4 v)
+{
+    const bool add = mode & 1, flip = mode & 2;
+    if (vec) {
+        int64_t d = px;
+        if (flip) {
+            const int64_t y = px / W;
+            d = y * W + (W - 4 - (px - y * W));
+            v = make_float4(v.w, v.z, v.y, v.x);
+        }
+        float4* o = (float4*)(plane + d);
+        if (add) {
+            const float4 a = *o;
+            v = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+        }
+        *o = v;
+        return;
+    }
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t p = px + i;
+        if (p >= HW) break;
+        int64_t d = p;
+        if (flip) {
+            const int64_t y = p / W;
+            d = y * W + (W - 1 - (p - y * W));
+        }
+        plane[d] = add ? plane[d] + e[i] : e[i];
+    }
+}
+
+// A workgroup owns kSemPix pixels x 16 * MT classes (blockIdx.y: the class chunk).  The sigmoids of kSemQ queries are staged exactly
+// as in seg_semantic_kernel; the product probs^T [classes x Q] * sig [Q x pixels] runs on v_mfma_f32_16x16x4_f32 with the classes on
+// the A rows and the pixels on the B columns (lane l: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15]; C/D col = l & 15,
+// row = 4 * (l >> 4) + reg).  Wave wv owns pixels 32 wv .. + 31 (two column tiles) and every class tile: 2 * MT independent
+// accumulators, k ascending in query order, so each score is the fmaf chain of seg_semantic_kernel (queries past Q and classes
+// past K enter as zeros).  Epilogue: one class tile at a time through LDS, so that a lane leaves with four consecutive pixels of a
+// class and eight lanes cover the 128 bytes of the wave's pixels.
+template <typename T, int MT>
+__global__ __launch_bounds__(kT) void seg_tta_accumulate_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
+                                                                int Wp, int hi, int wi, int H, int W, const float* __restrict__ probs,
+                                                                int K, int mode, int vec, float* __restrict__ acc)
+{
+    constexpr int KC = 16 * MT;
+    constexpr int PR = KC + kTtaPad;
+    __shared__ float4 sig4[kSemQ * kTtaSigRow / 4];
+    __shared__ float pr[kSemQ * PR];
+    static_assert((kT / 64) * 16 * kTtaOutRow <= kSemQ * kTtaSigRow, "the epilogue staging reuses the sigmoid staging");
+    float* sig = (float*)sig4;
+    const int tid = threadIdx.x;
+    const int64_t HW = (int64_t)H * W;
+    const int64_t p0 = (int64_t)blockIdx.x * kSemPix;
+    const int cbase = blockIdx.y * KC;
+    const int sp = tid & (kSemPix - 1), sq = tid >> 7;
+    const int64_t pix = p0 + sp;
+    const bool live = pix < HW;
+    PixGeom g;
+    pix_geom(g, live ? (int)(pix / W) : 0, live ? (int)(pix % W) : 0, h, w, Hp, Wp, hi, wi, H, W);
+    const int lane = tid & 63, wv = tid >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    f32x4 c[MT][2];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) c[m][0] = c[m][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q0 = 0; q0 < Q; q0 += kSemQ) {
+        const int nq = min(kSemQ, Q - q0);
+        __syncthreads();
+        for (int i = sq; i < kSemQ; i += kT / kSemPix) {
+            float s = 0.f;
+            if (i < nq && live) s = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
+            sig[i * kTtaSigRow + sp] = s;
+        }
+        for (int e = tid; e < kSemQ * KC; e += kT) {
+            const int i = e / KC, cc = e % KC;
+            pr[i * PR + cc] = (i < nq && cbase + cc < K) ? probs[(int64_t)(q0 + i) * K + cbase + cc] : 0.f;
+        }
+        __syncthreads();
+        const int ksteps = (nq + 3) >> 2;                    // rows nq .. kSemQ - 1 are staged as zeros
+        for (int ks = 0; ks < ksteps; ++ks) {
+            const int kr = ks * 4 + lk;
+            const float b0 = sig[kr * kTtaSigRow + wv * 32 + lr];
+            const float b1 = sig[kr * kTtaSigRow + wv * 32 + 16 + lr];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const float a = pr[kr * PR + m * 16 + lr];
+                c[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, c[m][0], 0, 0, 0);
+                c[m][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1, c[m][1], 0, 0, 0);
+            }
+        }
+    }
+    float* stg = sig + wv * (16 * kTtaOutRow);               // one region per wave
+    __syncthreads();                                         // every wave has left the product: sig is free
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        wave_lds_sync();
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) stg[(4 * lk + r) * kTtaOutRow + n * 16 + lr] = c[m][n][r];
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int idx = lane + 64 * j;
+            const int cl = idx >> 3, pg = idx & 7;
+            const int cc = cbase + m * 16 + cl;
+            const int64_t px = p0 + wv * 32 + pg * 4;
+            if (cc < K && px < HW)
+                tta_put4(acc + (int64_t)cc * HW, px, HW, W, mode, vec != 0, *(const float4*)(stg + cl * kTtaOutRow + pg * 4));
+        }
+    }
+}
+
+// "after" mode: thread = four consecutive output pixels, blockIdx.y = a chunk of kTtaResC classes; the taps are computed once and
+// every plane of the chunk is resized with them (tap() / lerp2: the roundings of F.interpolate, no contraction)
+constexpr int kTtaResC = 16;
+__global__ __launch_bounds__(kT) void seg_tta_resize_add_kernel(const float* __restrict__ scores, int K, int hi, int wi, int H, int W,
+                                                                int mode, int vec, float* __restrict__ acc)
+{
+    const int64_t HW = (int64_t)H * W;
+    const int64_t px = ((int64_t)blockIdx.x * kT + threadIdx.x) * 4;
+    if (px >= HW) return;
+    int o[4][4];
+    float wy[4][2], wx[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t p = min(px + i, HW - 1);
+        const Tap ty = tap((int)(p / W), hi, H), tx = tap((int)(p % W), wi, W);
+        o[i][0] = ty.i0 * wi + tx.i0; o[i][1] = ty.i0 * wi + tx.i1;
+        o[i][2] = ty.i1 * wi + tx.i0; o[i][3] = ty.i1 * wi + tx.i1;
+        wy[i][0] = ty.l0; wy[i][1] = ty.l1;
+        wx[i][0] = tx.l0; wx[i][1] = tx.l1;
+    }
+    const int64_t plane = (int64_t)hi * wi;
+    const int c1 = min(K, ((int)blockIdx.y + 1) * kTtaResC);
+    for (int cc = blockIdx.y * kTtaResC; cc < c1; ++cc) {
+        const float* s = scores + cc * plane;
+        float e[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) e[i] = lerp2(wy[i][0], wy[i][1], wx[i][0], wx[i][1], s[o[i][0]], s[o[i][1]], s[o[i][2]], s[o[i][3]]);
+        tta_put4(acc + (int64_t)cc * HW, px, HW, W, mode, vec != 0, make_float4(e[0], e[1], e[2], e[3]));
+    }
+}
+
+// labels == NULL: acc[i] /= count over the n = K * H * W sums (vec: n is a multiple of 4 and acc 16-byte aligned).  Otherwise thread
+// = pixel: labels[p] = argmax_c(acc[c][p] / count), classes ascending with a strict ">" (the lowest class wins a tie): the argmax of
+// exactly the values the other form writes
+__global__ __launch_bounds__(kT) void seg_tta_finish_kernel(float* __restrict__ acc, int K, int64_t HW, float count, int vec,
+                                                            int* __restrict__ labels)
+{
+    const int64_t t0 = (int64_t)blockIdx.x * kT + threadIdx.x, step = (int64_t)gridDim.x * kT;
+    if (labels) {
+        for (int64_t p = t0; p < HW; p += step) {
+            float best = -INFINITY;
+            int bi = 0;
+            for (int cc = 0; cc < K; ++cc) {
+                const float v = __fdiv_rn(acc[cc * HW + p], count);
+                if (v > best) { best = v; bi = cc; }
+            }
+            labels[p] = bi;
+        }
+        return;
+    }
+    const int64_t n = (int64_t)K * HW;
+    if (vec) {
+        float4* a4 = (float4*)acc;
+        for (int64_t i = t0; i < n / 4; i += step) {
+            const float4 v = a4[i];
+            a4[i] = make_float4(__fdiv_rn(v.x, count), __fdiv_rn(v.y, count), __fdiv_rn(v.z, count), __fdiv_rn(v.w, count));
+        }
+    } else {
+        for (int64_t i = t0; i < n; i += step) acc[i] = __fdiv_rn(acc[i], count);
+    }
+}
+
 // shared argument checks of the per-pixel entry points
 int check_geom(const char* who, const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
                int H, int W)
@@ -893,6 +1100,93 @@ extern "C" int mpf_seg_labels_resize(const float* scores, int K, int hi, int wi,
     hipLaunchKernelGGL(seg_labels_resize_kernel, dim3((unsigned)((HW + kT - 1) / kT)), dim3(kT), 0, st, scores, K, hi, wi, H, W, labels);
     mpf::prof_end("seg_labels_resize_kernel", st, 4.0 * K * hi * wi + 4.0 * HW);
     return mpf::check(hipGetLastError(), "mpf_seg_labels_resize");
+}
+
+namespace {
+int check_tta_mode(const char* who, int mode)
+{
+    static thread_local char msg[96];
+    if (mode & ~3) { snprintf(msg, sizeof msg, "%s: mode has bit 0 (add) and bit 1 (hflip) only, got %d", who, mode); return mpf::fail(MPF_E_SHAPE, msg); }
+    return 0;
+}
+// the float4 form of tta_put4: whole rows of four (mirrored: W itself) and 16-byte aligned planes
+int tta_vec(const float* acc, int H, int W, int mode)
+{
+    const int64_t HW = (int64_t)H * W;
+    return ((uintptr_t)acc & 15) == 0 && (HW & 3) == 0 && (!(mode & 2) || (W & 3) == 0);
+}
+}  // namespace
+
+extern "C" int mpf_seg_tta_accumulate(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
+                                      int H, int W, const float* probs, int K, int mode, float* acc, void* stream)
+{
+    if (int e = check_geom("seg_tta_accumulate", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!probs || !acc) return mpf::fail(MPF_E_NULL, "seg_tta_accumulate: NULL buffer");
+    if (K <= 0) return mpf::fail(MPF_E_SHAPE, "seg_tta_accumulate: K must be positive");
+    if (int e = check_tta_mode("seg_tta_accumulate", mode)) return e;
+    if ((int64_t)K * H * W >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "seg_tta_accumulate: output too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    // class tiles of 16 per workgroup: ADE20K's 150 classes take 10 (160), larger sets chunks of 12 (192) on blockIdx.y
+    const int mt = K <= 32 ? 2 : K <= 64 ? 4 : K <= 128 ? 8 : K <= 160 ? 10 : 12;
+    const dim3 grid((unsigned)((HW + kSemPix - 1) / kSemPix), (unsigned)((K + 16 * mt - 1) / (16 * mt)));
+    const int vec = tta_vec(acc, H, W, mode);
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_tta_accumulate_kernel");
+#define MPF_TTA(T, M)                                                                                                                      \
+    hipLaunchKernelGGL((seg_tta_accumulate_kernel<T, M>), grid, dim3(kT), 0, st, (const T*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H, W, \
+                       probs, K, mode, vec, acc)
+#define MPF_TTA_T(T)                      \
+    do {                                  \
+        if (mt == 2) MPF_TTA(T, 2);       \
+        else if (mt == 4) MPF_TTA(T, 4);  \
+        else if (mt == 8) MPF_TTA(T, 8);  \
+        else if (mt == 10) MPF_TTA(T, 10); \
+        else MPF_TTA(T, 12);              \
+    } while (0)
+    if (dtype == MPF_F32) MPF_TTA_T(float);
+    else MPF_TTA_T(__hip_bfloat16);
+#undef MPF_TTA_T
+#undef MPF_TTA
+    mpf::prof_end("seg_tta_accumulate_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + ((mode & 1) ? 8.0 : 4.0) * K * HW,
+                  2.0 * K * Q * (double)HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_tta_accumulate");
+}
+
+extern "C" int mpf_seg_tta_resize_add(const float* scores, int K, int hi, int wi, int H, int W, int mode, float* acc, void* stream)
+{
+    if (!scores || !acc) return mpf::fail(MPF_E_NULL, "seg_tta_resize_add: NULL buffer");
+    if (K <= 0 || hi <= 0 || wi <= 0 || H <= 0 || W <= 0) return mpf::fail(MPF_E_SHAPE, "seg_tta_resize_add: bad sizes");
+    if (int e = check_tta_mode("seg_tta_resize_add", mode)) return e;
+    if ((int64_t)H * W >= (1ll << 31) || (int64_t)hi * wi >= (1ll << 31) || (int64_t)K * H * W >= (1ll << 40) ||
+        (int64_t)K * hi * wi >= (1ll << 40))
+        return mpf::fail(MPF_E_TOO_LARGE, "seg_tta_resize_add: too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    const dim3 grid((unsigned)(((HW + 3) / 4 + kT - 1) / kT), (unsigned)((K + kTtaResC - 1) / kTtaResC));
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_tta_resize_add_kernel");
+    hipLaunchKernelGGL(seg_tta_resize_add_kernel, grid, dim3(kT), 0, st, scores, K, hi, wi, H, W, mode, tta_vec(acc, H, W, mode), acc);
+    mpf::prof_end("seg_tta_resize_add_kernel", st, 4.0 * K * hi * wi + ((mode & 1) ? 8.0 : 4.0) * K * HW, 14.0 * K * (double)HW);
+    return mpf::check(hipGetLastError(), "mpf_seg_tta_resize_add");
+}
+
+extern "C" int mpf_seg_tta_finish(float* acc, int K, int H, int W, int count, int* labels, void* stream)
+{
+    if (!acc) return mpf::fail(MPF_E_NULL, "seg_tta_finish: NULL accumulator");
+    if (K <= 0 || H <= 0 || W <= 0) return mpf::fail(MPF_E_SHAPE, "seg_tta_finish: bad sizes");
+    if (count <= 0) return mpf::fail(MPF_E_SHAPE, "seg_tta_finish: count must be positive (no view was added)");
+    if ((int64_t)H * W >= (1ll << 31) || (int64_t)K * H * W >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "seg_tta_finish: too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W, n = (int64_t)K * HW;
+    const int vec = ((uintptr_t)acc & 15) == 0 && (n & 3) == 0;
+    const int64_t units = labels ? HW : vec ? n / 4 : n;
+    const unsigned grid = (unsigned)std::min<int64_t>((units + kT - 1) / kT, 64 * (int64_t)mpf::cu_count());
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_tta_finish_kernel");
+    hipLaunchKernelGGL(seg_tta_finish_kernel, dim3(grid), dim3(kT), 0, st, acc, K, HW, (float)count, vec, labels);
+    mpf::prof_end("seg_tta_finish_kernel", st, labels ? 4.0 * n + 4.0 * HW : 8.0 * n, (double)n);
+    return mpf::check(hipGetLastError(), "mpf_seg_tta_finish");
 }
 
 extern "C" int mpf_seg_confusion_add(const int* pred, const int* gt, int64_t n, int K, int ignore_label, int64_t* conf, void* stream)

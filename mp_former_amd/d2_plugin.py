@@ -134,3 +134,79 @@ def install_native_inference(model, image_list_cls=None, semantic_labels=False, 
 
     model.forward = forward
     return cfg
+
+
+def is_hflip(tfm):
+    """True when any transform of a ``TransformList`` (or a bare list of transforms) is an ``HFlipTransform``
+    (test_time_augmentation.py:87): by ``isinstance`` where fvcore is importable, else by class name."""
+    tfms = getattr(tfm, "transforms", tfm)
+    try:
+        from fvcore.transforms import HFlipTransform
+    except ImportError:
+        return any(type(t).__name__ == "HFlipTransform" for t in tfms)
+    return any(isinstance(t, HFlipTransform) for t in tfms)
+
+
+class SemanticSegmentorWithTTAHIP:
+    """The reference's ``SemanticSegmentorWithTTA`` (mask2former/test_time_augmentation.py:21-103) on inference.SemanticTTA:
+    ``__call__(batched_inputs)`` -> one ``{"sem_seg"}`` dict per input (``{"sem_seg_labels"}`` with ``semantic_labels``), the
+    mean over the augmented views of ``tta_mapper(input)``, flipped views mirrored back.  Each view runs through
+    ``model.backbone`` / ``model.sem_seg_head`` as in ``native_eval_forward``, one view at a time as in the reference
+    (``batch_size`` is accepted and unused there too).  With ``sem_seg_postprocess_before_inference`` no per-view scores exist;
+    in the other mode one view's ``[K, hi, wi]`` scores at a time live in native scratch, which is sized by the largest view
+    and kept between images."""
+
+    def __init__(self, cfg, model, tta_mapper=None, batch_size=1, *, image_list_cls=None, semantic_labels=False):
+        import dataclasses
+        from .inference import InferenceConfig
+        model = getattr(model, "module", model) if type(model).__name__ == "DistributedDataParallel" else model
+        if tta_mapper is None:
+            try:
+                from detectron2.modeling import DatasetMapperTTA
+            except ImportError as e:
+                raise ImportError("SemanticSegmentorWithTTAHIP: tta_mapper=None builds detectron2.modeling.DatasetMapperTTA(cfg), and "
+                                  "detectron2 is not importable; pass a tta_mapper (input dict -> list of augmented dicts with "
+                                  "'image' and 'transforms')") from e
+            tta_mapper = DatasetMapperTTA(cfg)
+        self.cfg = cfg.clone() if hasattr(cfg, "clone") else cfg
+        self.model = model
+        self.tta_mapper = tta_mapper
+        self.batch_size = batch_size
+        self.image_list_cls = image_list_cls
+        self.inference_cfg = dataclasses.replace(InferenceConfig.from_maskformer(model), semantic_labels=semantic_labels)
+        if not self.inference_cfg.semantic_on:
+            raise ValueError("SemanticSegmentorWithTTAHIP needs a model with semantic_on")
+
+    def _prepared(self, x):
+        """A copy of one input dict that has what a view needs: the "image" as a CHW tensor (decoded in the model's input format
+        where only "file_name" came) and the output size, which defaults to the image's own."""
+        x = dict(x)
+        if "image" not in x:
+            import torch
+            from detectron2.data.detection_utils import read_image
+            hwc = read_image(x.pop("file_name"), format=self.model.input_format)
+            x["image"] = torch.as_tensor(hwc.copy()).permute(2, 0, 1).contiguous()
+        x.setdefault("height", int(x["image"].shape[-2]))
+        x.setdefault("width", int(x["image"].shape[-1]))
+        return x
+
+    def __call__(self, batched_inputs):
+        return [self._inference_one_image(self._prepared(x)) for x in batched_inputs]
+
+    def _inference_one_image(self, inp):
+        import torch
+        from .inference import SemanticTTA
+        image_list_cls = self.image_list_cls
+        if image_list_cls is None:
+            from detectron2.structures import ImageList as image_list_cls
+        model = self.model
+        out_size = (int(inp["height"]), int(inp["width"]))
+        tta = SemanticTTA(self.inference_cfg)
+        with torch.no_grad():
+            for view in self.tta_mapper(inp):
+                image = (view["image"].to(model.device) - model.pixel_mean) / model.pixel_std
+                images = image_list_cls.from_tensors([image], model.size_divisibility)
+                outputs = model.sem_seg_head(model.backbone(images.tensor))
+                tta.add(outputs["pred_logits"], outputs["pred_masks"], images.image_sizes[0], tuple(images.tensor.shape[-2:]), out_size,
+                        is_hflip(view["transforms"]))
+            return tta.result()

@@ -97,6 +97,19 @@ class MPFormerHead(nn.Module):
         outputs = self.predictor(multi_scale, mask_features, None, None)
         return postprocess(outputs["pred_logits"], outputs["pred_masks"], image_sizes, padded_hw, output_sizes, cfg)
 
+    def inference_tta(self, views, output_size, cfg):
+        """Semantic test-time augmentation of ONE image (mask2former/test_time_augmentation.py:71-98): ``views`` is an iterable of
+        ``(features, image_size, padded_hw, hflip)``, the backbone features of one augmented view each.  Pixel decoder and
+        predictor run per view, one at a time as in the reference; the views meet in inference.SemanticTTA.
+        -> {"sem_seg"} or, with cfg.semantic_labels, {"sem_seg_labels"} at ``output_size``."""
+        from .inference import SemanticTTA
+        tta = SemanticTTA(cfg)
+        for features, image_size, padded_hw, hflip in views:
+            mask_features, _, multi_scale = self.pixel_decoder.forward_features(features)
+            outputs = self.predictor(multi_scale, mask_features, None, None)
+            tta.add(outputs["pred_logits"], outputs["pred_masks"], image_size, padded_hw, output_size, hflip)
+        return tta.result()
+
     def total_loss(self, features, targets):
         """Sum of the weighted losses without materialising the weighted dict (2 kernels instead of 120)."""
         mask_features, _, multi_scale = self.pixel_decoder.forward_features(features)

@@ -15,6 +15,9 @@ For an evaluation loop the largest results can be had in the form their consumer
 * ``InferenceConfig.instance_masks = "rle"``: ``pred_masks_rle`` (uncompressed COCO run lengths) instead of the fp32
   [T, H, W] ``pred_masks``; only the run lengths cross to the host.
 
+``SemanticTTA`` is the reference's semantic test-time augmentation (mask2former/test_time_augmentation.py): the mean of the
+views' "sem_seg", flipped views mirrored back, accumulated view by view in one [K, H, W] buffer on the device.
+
 Deviations from the reference, by design:
 * ``instances`` are sorted by score, descending (the reference's ``topk(sorted=False)`` order is unspecified);
 * all results are fp32 whatever the mask dtype (bf16 logits are widened on load; the reference would compute in bf16).
@@ -343,6 +346,89 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
                                           (H, W))
         out.append(res)
     return out
+
+
+# ---- semantic test-time augmentation --------------------------------------------------------------------------------------------
+TTA_ADD, TTA_HFLIP = 1, 2      # the mode bits of mpf_seg_tta_accumulate / mpf_seg_tta_resize_add
+
+
+class SemanticTTA:
+    """The accumulation of the reference's ``SemanticSegmentorWithTTA._inference_one_image`` (test_time_augmentation.py:71-98)
+    for ONE image: ``sem_seg = (sum_v flip_v(S_v)) / V`` over the views in the order they are added, S_v = the view's "sem_seg" at
+    the output size (``cfg.sem_seg_postprocess_before_inference`` as in ``postprocess``), flip_v = the W axis of that output
+    reversed where the view was flipped.  Every view goes from its logits into one fp32 [K, H, W] accumulator
+    (``seg_tta_accumulate_kernel``, in "after" mode through ``seg_tta_resize_add_kernel``): no per-view [K, H, W] tensor, no flip
+    copy.  "After" mode does hold one view's [K, hi, wi] scores at a time, in native scratch that grows to the largest view and
+    stays allocated between images.  With ``cfg.semantic_labels`` the accumulator is native scratch (one image at a time per stream) and ``result`` gives
+    the argmax of the mean, bit for bit that of the dense result.  ``add`` and ``result`` make no device-to-host copy."""
+
+    def __init__(self, cfg):
+        if not cfg.semantic_on:
+            raise ValueError("SemanticTTA needs semantic_on (the reference has test-time augmentation for sem_seg only)")
+        self.cfg = cfg
+        self.reset()
+
+    def reset(self):
+        self._acc, self._shape, self._count = None, None, 0
+
+    def add(self, pred_logits, pred_masks, image_size, padded_hw, output_size, hflip=False):
+        """One view: pred_logits [Q, K+1] or [1, Q, K+1], pred_masks [Q, h, w] or [1, Q, h, w] (fp32 / bf16), the view's image size
+        and padded size, the output size of the image (the same for every view), and whether the view was flipped."""
+        cfg = self.cfg
+        if pred_logits.dim() == 3 and pred_logits.shape[0] == 1:
+            pred_logits = pred_logits[0]
+        if pred_masks.dim() == 4 and pred_masks.shape[0] == 1:
+            pred_masks = pred_masks[0]
+        if pred_logits.dim() != 2 or pred_masks.dim() != 3 or pred_masks.shape[0] != pred_logits.shape[0]:
+            raise ValueError(f"one view at a time: pred_logits {tuple(pred_logits.shape)}, pred_masks {tuple(pred_masks.shape)}")
+        K = pred_logits.shape[1] - 1
+        H, W = int(output_size[0]), int(output_size[1])
+        if K != cfg.num_classes:
+            raise ValueError(f"pred_logits has {K} classes + no-object, config {cfg.num_classes}")
+        if self._count and (K, H, W) != self._shape:
+            raise ValueError(f"every view of an image has the same classes and output size: got {(K, H, W)}, first view {self._shape}")
+        if not (pred_masks.is_cuda and pred_logits.is_cuda):
+            raise RuntimeError("SemanticTTA.add: Not implemented on the CPU (device tensors only)")
+        pm, _, sq, dt = _masks_arg(pred_masks[None])
+        dev = pm.device
+        stream = _lib.stream_ptr(dev)
+        if not self._count:
+            self._shape = (K, H, W)
+            if cfg.semantic_labels:
+                self._acc = _lib.scratch("seg_infer.tta_acc", dev, stream, 4 * K * H * W)[:4 * K * H * W].view(torch.float32).view(K, H, W)
+            else:
+                self._acc = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+        elif dev != self._acc.device:
+            raise RuntimeError(f"view on {dev}, the accumulator on {self._acc.device}")
+        img = _Image(pred_logits.detach().float().contiguous(), K, cfg.object_mask_threshold, dev, stream, "tta")
+        mode = (TTA_ADD if self._count else 0) | (TTA_HFLIP if hflip else 0)
+        hi, wi = int(image_size[0]), int(image_size[1])
+        if cfg.sem_seg_postprocess_before_inference:
+            _lib.call("mpf_seg_tta_accumulate", dev, pm.data_ptr(), sq, dt, *_geom(pm[0], (hi, wi), padded_hw, (H, W)), img.probs.data_ptr(),
+                      K, mode, self._acc.data_ptr(), stream)
+        else:   # the scores on the cropped padded grid (store mode, never mirrored), then resize + flip + add in one pass
+            r = _lib.scratch("seg_infer.tta_scores", dev, stream, 4 * K * hi * wi)
+            _lib.call("mpf_seg_tta_accumulate", dev, pm.data_ptr(), sq, dt, *_geom(pm[0], (hi, wi), padded_hw, (hi, wi)),
+                      img.probs.data_ptr(), K, 0, r.data_ptr(), stream)
+            _lib.call("mpf_seg_tta_resize_add", dev, r.data_ptr(), K, hi, wi, H, W, mode, self._acc.data_ptr(), stream)
+        self._count += 1
+
+    def result(self):
+        """-> {"sem_seg": fp32 [K, H, W]} (the accumulator itself, divided in place) or, with cfg.semantic_labels,
+        {"sem_seg_labels": int32 [H, W]}; then ready for the next image."""
+        if not self._count:
+            raise RuntimeError("SemanticTTA.result: no view was added")
+        acc, (K, H, W), dev = self._acc, self._shape, self._acc.device
+        stream = _lib.stream_ptr(dev)
+        if self.cfg.semantic_labels:
+            labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+            _lib.call("mpf_seg_tta_finish", dev, acc.data_ptr(), K, H, W, self._count, labels.data_ptr(), stream)
+            res = {"sem_seg_labels": labels}
+        else:
+            _lib.call("mpf_seg_tta_finish", dev, acc.data_ptr(), K, H, W, self._count, None, stream)
+            res = {"sem_seg": acc}
+        self.reset()
+        return res
 
 
 # ---- semantic evaluation on the device ------------------------------------------------------------------------------------------

@@ -3,12 +3,19 @@ eval branch (tests/_infer_restate.py), per image on one GPU.  Prints one line pe
 inputs, the algorithmic bytes / FLOP of the native route and the fraction of the measured 6.3 TB/s copy rate or of the
 157 TF fp32 peak it reaches (whichever bound applies).
 
-    python tools/bench_infer.py [--iters 20] [--rows base,eval]
+    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta]
 
 The ``eval`` rows measure the evaluation-form results (``semantic_labels``, ``SemSegConfusion``, ``instance_masks="rle"``) against
 the default route brought to the same end product: ``sem_seg`` + ``torch.argmax`` (+ ``.cpu()`` of the label map where the metric
 is wanted), and the dense masks + ``.cpu()``.  These rows are wall-clock medians between two device synchronisations, because
 their host copies and the host's list building are part of the product; peak MB above the inputs; bytes crossing to the host.
+
+The ``tta`` rows (not in the default set) measure semantic test-time augmentation, 6 synthetic scales x {plain, flip} = 12 views per
+image in "after" mode with low-res = padded / 4 and Q = 100: ``SemanticTTA`` (dense and labels) against what the package offered
+before it, ``postprocess`` per view + ``flip`` + ``+=`` + one divide (+ ``argmax``).  One more line per case times
+``seg_tta_accumulate_kernel`` in store mode against ``seg_semantic_kernel`` on the same single view.  Wall-clock medians as above.
+The memory columns of these rows come from a call that starts without native scratch (``cold_memory``): the peak includes the scratch
+the route allocates, and "held" is what stays allocated for the next image after the result is dropped.
 """
 import argparse
 import json
@@ -22,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from _infer_restate import restate  # noqa: E402
-from mp_former_amd.inference import InferenceConfig, SemSegConfusion, postprocess  # noqa: E402
+from mp_former_amd import _lib  # noqa: E402
+from mp_former_amd.inference import InferenceConfig, SemanticTTA, SemSegConfusion, postprocess  # noqa: E402
 
 CASES = {
     # name: (K, low-res hw, padded, image, output, config)
@@ -36,8 +44,8 @@ CASES = {
 }
 
 
-def inputs(K, hw, dev, Q=100):
-    g = torch.Generator().manual_seed(0)
+def inputs(K, hw, dev, Q=100, seed=0):
+    g = torch.Generator().manual_seed(seed)
     logits = torch.randn(1, Q, K + 1, generator=g)
     logits[0, torch.randperm(Q, generator=g)[:20], torch.randint(0, K, (20,), generator=g)] = 9.0
     low = torch.randn(1, Q, hw[0] // 8, hw[1] // 8, generator=g) * 4
@@ -83,6 +91,21 @@ def timed_wall(fn, iters):
         ts.append((time.perf_counter() - t0) * 1e6)
     ts.sort()
     return ts[len(ts) // 2], peak
+
+
+def cold_memory(fn):
+    """-> (peak MB, MB still held after the result is dropped) of one call that starts without native scratch: what the route
+    costs a process, its persistent scratch included (timed_wall's baseline, taken after a warm call, leaves that out)."""
+    _lib._scratch.clear()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    r = fn()
+    torch.cuda.synchronize()
+    peak = (torch.cuda.max_memory_allocated() - base) / 1e6
+    del r
+    return peak, (torch.cuda.memory_allocated() - base) / 1e6
 
 
 def eval_rows(name, K, hw, padded, image, out, iters, dev):
@@ -139,6 +162,67 @@ def eval_rows(name, K, hw, padded, image, out, iters, dev):
     return rows
 
 
+TTA_CASES = {"ade20k_semantic_k150": (150, (640, 640)), "cityscapes_semantic_k19": (19, (1024, 2048))}
+TTA_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
+
+
+def tta_rows(name, iters, dev, Q=100):
+    """The test-time-augmentation rows of one case ("after" mode, the default of the semantic configs), and the single-view line
+    of the two product kernels."""
+    K, out = TTA_CASES[name]
+    views = []
+    for i, s in enumerate(TTA_SCALES):
+        image = (int(out[0] * s), int(out[1] * s))
+        padded = tuple((v + 31) // 32 * 32 for v in image)
+        lg, mk = inputs(K, (padded[0] // 4, padded[1] // 4), dev, Q, seed=i)
+        views += [(lg, mk, image, padded, False), (lg, mk, image, padded, True)]
+    kw = dict(num_classes=K, num_queries=Q, semantic_on=True, instance_on=False, sem_seg_postprocess_before_inference=False)
+    c_par = InferenceConfig(**kw)
+    ttas = {False: SemanticTTA(c_par), True: SemanticTTA(InferenceConfig(semantic_labels=True, **kw))}
+
+    def native(labels):
+        t = ttas[labels]
+        for lg, mk, image, padded, flip in views:
+            t.add(lg, mk, image, padded, out, flip)
+        return t.result()
+
+    def parent(labels):
+        final = None
+        for lg, mk, image, padded, flip in views:
+            s = postprocess(lg, mk, [image], padded, [out], c_par)[0]["sem_seg"]
+            s = s.flip(-1) if flip else s
+            if final is None:
+                final = s
+            else:
+                final += s
+        final = final / len(views)
+        return final.argmax(0) if labels else final
+
+    for labels in (False, True):
+        (m_nat, held_nat), (m_par, held_par) = cold_memory(lambda: native(labels)), cold_memory(lambda: parent(labels))
+        t_nat, _ = timed_wall(lambda: native(labels), iters)
+        t_par, _ = timed_wall(lambda: parent(labels), iters)
+        print(json.dumps({"case": name, "row": "tta_labels" if labels else "tta_dense", "views": len(views), "native_us": round(t_nat, 1),
+                          "parent_us": round(t_par, 1), "speedup": round(t_par / t_nat, 2), "native_peak_MB": round(m_nat, 1),
+                          "parent_peak_MB": round(m_par, 1), "native_held_MB": round(held_nat, 1),
+                          "parent_held_MB": round(held_par, 1)}), flush=True)
+    # one view (scale 1.0), scores on its own grid: the MFMA product in store mode against the VALU product
+    lg, mk, image, padded, _ = views[4]
+    stream = _lib.stream_ptr(dev)
+    probs = lg[0].softmax(-1)[:, :K].contiguous()
+    dst = torch.empty((K, *image), dtype=torch.float32, device=dev)
+    geom = [Q, mk.shape[-2], mk.shape[-1], *padded, *image, *image]
+    args = (mk.data_ptr(), mk.stride(1), _lib.MPF_F32, *geom, probs.data_ptr(), K)
+    t_mfma, _ = timed_wall(lambda: _lib.call("mpf_seg_tta_accumulate", dev, *args, 0, dst.data_ptr(), stream), iters)
+    a = dst.clone()
+    t_valu, _ = timed_wall(lambda: _lib.call("mpf_seg_semantic", dev, *args, dst.data_ptr(), stream), iters)
+    fl = 2.0 * K * Q * image[0] * image[1]
+    print(json.dumps({"case": name, "row": "single_view_product", "seg_tta_accumulate_us": round(t_mfma, 1),
+                      "seg_semantic_us": round(t_valu, 1), "speedup": round(t_valu / t_mfma, 2), "bitwise_equal": bool(torch.equal(a, dst)),
+                      "alg_GFLOP": round(fl / 1e9, 2), "mfma_frac_157TF": round(fl / (t_mfma * 1e-6) / 157e12, 3),
+                      "valu_frac_157TF": round(fl / (t_valu * 1e-6) / 157e12, 3)}), flush=True)
+
+
 def work(K, cfg, hw, out, Q=100, T=100):
     """(bytes, flop) the native route must move / compute: the logits once per kernel that reads them, the results once."""
     H, W = out
@@ -164,6 +248,8 @@ def main():
     kinds = args.rows.split(",")
     for name in args.cases.split(","):
         K, hw, padded, image, out, kw = CASES[name]
+        if "tta" in kinds and name in TTA_CASES:
+            tta_rows(name, args.iters, dev)
         if "eval" in kinds:
             eval_rows(name, K, hw, padded, image, out, args.iters, dev)
         if "base" not in kinds:
