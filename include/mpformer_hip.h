@@ -1295,6 +1295,35 @@ int mpf_seg_tta_accumulate(const void* masks, int64_t stride_q, int dtype, int Q
 int mpf_seg_tta_resize_add(const float* scores, int K, int hi, int wi, int H, int W, int mode, float* acc, void* stream);
 int mpf_seg_tta_finish(float* acc, int K, int H, int W, int count, int* labels /* NULL: divide in place */, void* stream);
 
+/*
+ * Panoptic quality on the device (csrc/seg_pq.hip): the per-image arithmetic of panopticapi's pq_compute_single_core, as the
+ * reference carries it in tools/evaluate_pq_for_semantic_segmentation.py (pq_compute_single_image, :41-136), on the int32 id map
+ * that mpf_seg_panoptic_paint wrote, without a copy to the host.
+ * Slots: 0 = VOID (id == void_id, on both sides), 1..G (ground truth) / 1..S (prediction) = the listed segments in ascending id
+ * order, G+1 / S+1 = an id that is neither.  The listed ids of a side are ids int32 [count] ascending, or with ids == NULL the
+ * range base .. base + count - 1.  table int32 [(G+2) * (S+2)], row = ground truth, holds mpf_seg_pq_workspace_bytes(G, S) bytes
+ * and is ZERO between calls: the caller zeroes it once, _pairs adds, _match reads it and writes it back to zero.
+ *   mpf_seg_pq_pairs:  table[gt slot][pred slot] += 1 over n pixels (:81-87).  pred int32 [n].  gt_format 0: gt int32 [n];
+ *                      gt_format 1: gt uint8 [n][3], R G B as a PNG reader delivers them, id = R + 256 G + 65536 B (panopticapi's
+ *                      rgb2id).  Integer arithmetic only.
+ *   mpf_seg_pq_match:  tp / fp / fn int64 [K] and iou float64 [K] += the image's counts (:89-134), one workgroup.  Per listed
+ *                      segment: gt_cat / pred_cat int32 = category in [0, K); gt_flags int32, bit 0 = iscrowd, bit 1 = the crowd
+ *                      segment of its category that comes last in the annotation (:118; at most one per category).  gt_flags may
+ *                      be NULL (no crowd).  Areas are the column (prediction) and row (ground truth) sums of the table.  A pair
+ *                      matches when inter / (area_p + area_g - inter - table[VOID][p]) > 0.5 in float64.  iou: the image's matches
+ *                      summed per category from 0.0 in ascending (gt id, pred id) order, then added to iou[]: bit for bit the
+ *                      reference's pq_stat += single.  err int64 [1] += what the reference raises KeyError for: pixels of an
+ *                      unlisted prediction id, listed predictions without a pixel.
+ *                      implicit = 1 (the reference tool's semantic form, :50-60): G == S == K, no tables, segment = class, a class
+ *                      exists on a side where it has pixels there; prediction pixels equal to void_id count in err.
+ * Calls on one stream run in order, so the running totals have one writer at a time.
+ */
+size_t mpf_seg_pq_workspace_bytes(int G, int S);
+int mpf_seg_pq_pairs(const int* pred, const void* gt, int gt_format, int64_t n, const int* gt_ids, int G, int gt_base,
+                     const int* pred_ids, int S, int pred_base, int void_id, int* table, size_t table_bytes, void* stream);
+int mpf_seg_pq_match(int* table, size_t table_bytes, int G, int S, int K, const int* gt_cat, const int* gt_flags, const int* pred_cat,
+                     int implicit, int64_t* tp, int64_t* fp, int64_t* fn, double* iou, int64_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

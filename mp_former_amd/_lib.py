@@ -208,6 +208,10 @@ SIGNATURES = {
     "mpf_seg_tta_accumulate": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_int, _c_vp, _c_vp]),
     "mpf_seg_tta_resize_add": (_c_int, [_c_vp] + [_c_int] * 6 + [_c_vp, _c_vp]),
     "mpf_seg_tta_finish": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp, _c_vp]),
+    "mpf_seg_pq_workspace_bytes": (ctypes.c_size_t, [_c_int] * 2),
+    "mpf_seg_pq_pairs": (_c_int, [_c_vp, _c_vp, _c_int, ctypes.c_int64, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp,
+                                  ctypes.c_size_t, _c_vp]),
+    "mpf_seg_pq_match": (_c_int, [_c_vp, ctypes.c_size_t, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_int] + [_c_vp] * 6),
 }
 
 

@@ -210,3 +210,51 @@ class SemanticSegmentorWithTTAHIP:
                 tta.add(outputs["pred_logits"], outputs["pred_masks"], images.image_sizes[0], tuple(images.tensor.shape[-2:]), out_size,
                         is_hflip(view["transforms"]))
             return tta.result()
+
+
+def _read_png_rgb(path):
+    """The panoptic PNG as uint8 [H, W, 3] (R, G, B), through PIL."""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+class PanopticQualityEvaluator:
+    """detectron2's evaluator protocol (``reset`` / ``process(inputs, outputs)`` / ``evaluate``) on inference.PanopticQuality, in
+    place of ``COCOPanopticEvaluator``: the predicted id map stays on the device, the ground-truth PNG goes up as its RGB bytes
+    (3 bytes per pixel) and is decoded by the kernel.  Writes no file and needs neither detectron2 nor panopticapi.
+
+    ``dataset_id_to_contiguous_id``: the union of the metadata's thing_ and stuff_dataset_id_to_contiguous_id, applied to the
+    ground truth's category ids (the model's are contiguous already).  ``read_png``: path -> uint8 [H, W, 3]."""
+
+    def __init__(self, num_classes, thing_ids, dataset_id_to_contiguous_id, read_png=None, void_id=0, device="cuda:0"):
+        from .inference import PanopticQuality
+        self.id_map = {int(k): int(v) for k, v in dict(dataset_id_to_contiguous_id).items()}
+        self.read_png = read_png or _read_png_rgb
+        self.pq = PanopticQuality(num_classes, thing_ids, void_id=void_id, device=device)
+
+    def reset(self):
+        self.pq.reset()
+
+    def gt_segments(self, segments_info):
+        """The annotation's segments with contiguous category ids, in the annotation's order."""
+        out = []
+        for s in segments_info:
+            c = int(s["category_id"])
+            if c not in self.id_map:
+                raise ValueError(f"ground-truth segment {s['id']} has category_id {c}, which the dataset mapping does not list")
+            out.append({"id": int(s["id"]), "category_id": self.id_map[c], "iscrowd": int(s.get("iscrowd", 0))})
+        return out
+
+    def process(self, inputs, outputs):
+        import numpy as np
+        from . import _h2d
+        for inp, out in zip(inputs, outputs):
+            ids, segments_info = out["panoptic_seg"]
+            rgb = np.ascontiguousarray(self.read_png(inp["pan_seg_file_name"]), dtype=np.uint8)
+            gt = _h2d.upload(rgb, self.pq.device)
+            self.pq.update(ids, segments_info, gt, self.gt_segments(inp["segments_info"]))
+
+    def evaluate(self):
+        return {"panoptic_seg": self.pq.results()}

@@ -516,3 +516,202 @@ def confusion_results(conf, class_names=None):
         res[f"IoU-{name}"] = 100 * float(iou[i])
         res[f"ACC-{name}"] = 100 * float(acc[i])
     return {key: float(v) for key, v in res.items()}
+
+
+# ---- panoptic evaluation on the device ------------------------------------------------------------------------------------------
+PQ_CROWD, PQ_CROWD_WINS = 1, 2      # the gt_flags bits of mpf_seg_pq_match
+
+
+def _pq_side(segments, K, void_id, what, crowd=False):
+    """One side's listed segments -> (ids ascending, categories, flags) as int32 arrays; ValueError on what the host can see."""
+    ids, cats, flags = [], [], []
+    winner = {}                                         # category -> position of the crowd segment that comes last (line 118)
+    for n, s in enumerate(segments):
+        i, c = int(s["id"]), int(s["category_id"])
+        if not 0 <= c < K:
+            raise ValueError(f"{what}: category_id {c} of segment {i} is outside [0, {K})")
+        if i < 0 or i >= 1 << 31 or i == void_id:
+            raise ValueError(f"{what}: segment id {i} is negative, too large or the void id")
+        ids.append(i)
+        cats.append(c)
+        flags.append(PQ_CROWD if crowd and int(s.get("iscrowd", 0)) == 1 else 0)
+        if flags[-1]:
+            winner[c] = n
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"{what}: duplicate segment ids")
+    for n in winner.values():
+        flags[n] |= PQ_CROWD_WINS
+    order = np.argsort(np.asarray(ids, dtype=np.int64), kind="stable")
+    pick = lambda v: np.asarray(v, dtype=np.int32)[order]      # noqa: E731
+    return pick(ids), pick(cats), pick(flags)
+
+
+class PanopticQuality:
+    """The per-image part of panopticapi's ``pq_compute`` (``pq_compute_single_core``; the reference carries the same body as
+    ``pq_compute_single_image`` in tools/evaluate_pq_for_semantic_segmentation.py:41-136): tp / fp / fn and the summed IoU per
+    category, accumulated on the device by ``mpf_seg_pq_pairs`` + ``mpf_seg_pq_match`` from the id map ``postprocess`` returns.
+    ``update`` / ``update_semantic`` launch and return; only ``stats`` copies to the host.  The counters are integers and the IoU
+    sum is float64 in the single-process reference's order, so ``stats`` is that reference's ``PQStat`` bit for bit.
+
+    Deviation: a ground-truth segment's area is its pixel count in ``gt`` (panopticapi reads the annotation's "area", which is the
+    same number for a consistent annotation)."""
+
+    def __init__(self, num_classes, thing_ids, void_id=0, device="cuda:0"):
+        self.num_classes = int(num_classes)
+        self.thing_ids = frozenset(int(i) for i in thing_ids)
+        self.void_id = int(void_id)
+        self.device = torch.device(device)
+        if self.num_classes <= 0:
+            raise ValueError("num_classes must be positive")
+        self._state = None          # int64 [4K + 1]: tp, fp, fn, iou (float64 bits), error count
+
+    def _buffers(self):
+        if self._state is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("PanopticQuality: Not implemented on the CPU (device tensors only)")
+            self._state = torch.zeros(4 * self.num_classes + 1, dtype=torch.int64, device=self.device)
+        p, K = self._state.data_ptr(), self.num_classes
+        return [p + 8 * K * i for i in range(5)]           # tp, fp, fn, iou, err
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    def _check_maps(self, pred, gt, rgb_ok):
+        if self.device.type != "cuda" or not (pred.is_cuda and gt.is_cuda):
+            raise RuntimeError("PanopticQuality: Not implemented on the CPU (device tensors only)")
+        if pred.dim() != 2 or pred.dtype != torch.int32:
+            raise ValueError(f"the prediction must be int32 [H, W], got {pred.dtype} {tuple(pred.shape)}")
+        rgb = rgb_ok and gt.dim() == 3
+        if rgb and (gt.dtype != torch.uint8 or gt.shape[2] != 3):
+            raise ValueError(f"an RGB ground truth must be uint8 [H, W, 3], got {gt.dtype} {tuple(gt.shape)}")
+        if tuple(gt.shape[:2]) != tuple(pred.shape) or gt.dim() != (3 if rgb else 2):
+            raise ValueError(f"prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} must be the same [H, W]")
+        if pred.numel() == 0:
+            raise ValueError("empty image")
+        if pred.device != self.device or gt.device != self.device:
+            raise RuntimeError(f"maps on {pred.device} / {gt.device}, the counters on {self.device}")
+        return rgb
+
+    def _run(self, pred, gt, fmt, G, S, gt_ids, gt_base, pred_ids, pred_base, gt_cat, gt_flags, pred_cat, implicit):
+        dev = self.device
+        stream = _lib.stream_ptr(dev)
+        tp, fp, fn, iou, err = self._buffers()
+        nbytes = _lib.lib().mpf_seg_pq_workspace_bytes(G, S)
+        table = _lib.scratch("seg_pq.table", dev, stream, nbytes, zeroed=True)     # zero between calls: the match kernel clears it
+        _lib.call("mpf_seg_pq_pairs", dev, pred.data_ptr(), gt.data_ptr(), fmt, pred.numel(), gt_ids, G, gt_base, pred_ids, S, pred_base,
+                  self.void_id, table.data_ptr(), table.numel(), stream)
+        _lib.call("mpf_seg_pq_match", dev, table.data_ptr(), table.numel(), G, S, self.num_classes, gt_cat, gt_flags, pred_cat, implicit,
+                  tp, fp, fn, iou, err, stream)
+
+    def update(self, pred_ids, segments_info, gt, gt_segments):
+        """pred_ids int32 [H, W] and segments_info ({"id", "category_id"}) as ``postprocess`` returns them; gt int32 [H, W] ids or
+        uint8 [H, W, 3] RGB (id = R + 256 G + 65536 B) on the device; gt_segments: {"id", "category_id", "iscrowd"} with contiguous
+        category ids, in the annotation's order."""
+        from . import _h2d
+        K = self.num_classes
+        rgb = self._check_maps(pred_ids, gt, True)
+        if not rgb and gt.dtype != torch.int32:
+            raise ValueError(f"a ground-truth id map must be int32, got {gt.dtype}")
+        g_ids, g_cat, g_flags = _pq_side(gt_segments, K, self.void_id, "gt_segments", crowd=True)
+        p_ids, p_cat, _ = _pq_side(segments_info, K, self.void_id, "segments_info")
+        G, S = len(g_ids), len(p_ids)
+        ptrs = [None] * 5
+        if G + S:
+            meta = _h2d.upload(np.concatenate([g_ids, p_ids, g_cat, g_flags, p_cat]), self.device)
+            self._meta = meta                               # (the caching allocator keeps it valid on this stream anyway)
+            off = np.cumsum([0, G, S, G, G])
+            ptrs = [meta.data_ptr() + 4 * int(o) for o in off]
+
+        def side(ids, n, ptr):
+            """-> (table pointer or None, base): a contiguous id range needs no table"""
+            if n == 0:
+                return None, 0
+            if int(ids[-1]) - int(ids[0]) == n - 1:
+                return None, int(ids[0])
+            return ptr, 0
+        gp, gbase = side(g_ids, G, ptrs[0])
+        pp, pbase = side(p_ids, S, ptrs[1])
+        self._run(pred_ids.contiguous(), gt.contiguous(), 1 if rgb else 0, G, S, gp, gbase, pp, pbase,
+                  ptrs[2] if G else None, ptrs[3] if G else None, ptrs[4] if S else None, 0)
+
+    def update_semantic(self, pred_labels, gt_labels):
+        """The route of the reference tool (:50-60): pred_labels int32 [H, W], gt_labels any integer dtype [H, W]; every class with
+        a pixel is one segment of its side, ``void_id`` is the ignore label.  A prediction outside [0, K) is an error at ``stats``."""
+        self._check_maps(pred_labels, gt_labels, False)
+        if gt_labels.dtype.is_floating_point or gt_labels.dtype.is_complex or gt_labels.dtype == torch.bool:
+            raise ValueError(f"gt_labels must be an integer tensor, got {gt_labels.dtype}")
+        K = self.num_classes
+        gt = gt_labels.to(dtype=torch.int32).contiguous()
+        self._run(pred_labels.contiguous(), gt, 0, K, K, None, 0, None, 0, None, None, None, 1)
+
+    def stats(self):
+        """-> {"tp", "fp", "fn"} int64 [K] and "iou" float64 [K] (one device-to-host copy); ValueError where the reference raises
+        KeyError: a predicted id that segments_info does not list, or a listed prediction without a pixel."""
+        K = self.num_classes
+        if self._state is None:
+            host = np.zeros(4 * K + 1, dtype=np.int64)
+        else:
+            host = self._state.cpu().numpy()
+        if host[4 * K]:
+            raise ValueError(f"PanopticQuality: {int(host[4 * K])} prediction pixels / segments disagree with their segments_info "
+                             "(an id that is not listed, or a listed segment without a pixel)")
+        return {"tp": host[:K].copy(), "fp": host[K:2 * K].copy(), "fn": host[2 * K:3 * K].copy(),
+                "iou": host[3 * K:4 * K].copy().view(np.float64)}
+
+    @staticmethod
+    def combine(list_of_stats):
+        """The sum over ranks or shards, in list order."""
+        out = None
+        for s in list_of_stats:
+            if out is None:
+                out = {k: np.array(s[k], dtype=np.float64 if k == "iou" else np.int64) for k in ("tp", "fp", "fn", "iou")}
+            else:
+                for k in out:
+                    out[k] = out[k] + np.asarray(s[k], dtype=out[k].dtype)
+        if out is None:
+            raise ValueError("combine: no stats")
+        return out
+
+    def results(self):
+        """The nine keys of detectron2's ``COCOPanopticEvaluator`` (x 100)."""
+        r = pq_results(self.stats(), self.thing_ids)
+        out = {}
+        for name, suffix in (("All", ""), ("Things", "_th"), ("Stuff", "_st")):
+            for m in ("pq", "sq", "rq"):
+                out[m.upper() + suffix] = 100 * r[name][m]
+        return out
+
+
+def pq_results(stats, thing_ids):
+    """panopticapi's ``PQStat.pq_average`` for all / thing / stuff categories -> {"All", "Things", "Stuff": {pq, sq, rq, n},
+    "per_class": {category: {pq, sq, rq}}}.  A category without entries is left out of n; a group with n == 0 gives nan (the
+    reference divides by zero there)."""
+    tp, fp, fn = (np.asarray(stats[k], dtype=np.int64) for k in ("tp", "fp", "fn"))
+    iou = np.asarray(stats["iou"], dtype=np.float64)
+    K = tp.shape[0]
+    things = frozenset(int(i) for i in thing_ids)
+    per_class = {}
+    for c in range(K):
+        t, p, n = int(tp[c]), int(fp[c]), int(fn[c])
+        if t + p + n == 0:
+            per_class[c] = {"pq": 0.0, "sq": 0.0, "rq": 0.0}
+            continue
+        den = t + 0.5 * p + 0.5 * n
+        per_class[c] = {"pq": float(iou[c]) / den, "sq": float(iou[c]) / t if t != 0 else 0.0, "rq": t / den}
+    out = {"per_class": per_class}
+    for name, want in (("All", None), ("Things", True), ("Stuff", False)):
+        pq = sq = rq = 0.0
+        n = 0
+        for c in range(K):
+            if want is not None and (c in things) != want:
+                continue
+            if int(tp[c]) + int(fp[c]) + int(fn[c]) == 0:
+                continue
+            n += 1
+            pq += per_class[c]["pq"]
+            sq += per_class[c]["sq"]
+            rq += per_class[c]["rq"]
+        nan = float("nan")
+        out[name] = {"pq": pq / n if n else nan, "sq": sq / n if n else nan, "rq": rq / n if n else nan, "n": n}
+    return out

@@ -3,7 +3,7 @@ eval branch (tests/_infer_restate.py), per image on one GPU.  Prints one line pe
 inputs, the algorithmic bytes / FLOP of the native route and the fraction of the measured 6.3 TB/s copy rate or of the
 157 TF fp32 peak it reaches (whichever bound applies).
 
-    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta]
+    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta,pq]
 
 The ``eval`` rows measure the evaluation-form results (``semantic_labels``, ``SemSegConfusion``, ``instance_masks="rle"``) against
 the default route brought to the same end product: ``sem_seg`` + ``torch.argmax`` (+ ``.cpu()`` of the label map where the metric
@@ -16,6 +16,11 @@ before it, ``postprocess`` per view + ``flip`` + ``+=`` + one divide (+ ``argmax
 ``seg_tta_accumulate_kernel`` in store mode against ``seg_semantic_kernel`` on the same single view.  Wall-clock medians as above.
 The memory columns of these rows come from a call that starts without native scratch (``cold_memory``): the peak includes the scratch
 the route allocates, and "held" is what stays allocated for the next image after the result is dropped.
+
+The ``pq`` row (not in the default set; COCO panoptic case only) measures panoptic quality: ``postprocess`` with ``panoptic_on``
+followed by ``PanopticQuality.update`` against ``postprocess``, ``ids.cpu()`` and the numpy restatement of panopticapi's per-image
+arithmetic (tests/_pq_restate.py).  The ground truth is in place on both sides before the clock starts (RGB bytes on the device,
+an id map on the host).  Wall-clock medians as above; the id map's 4 H W bytes cross to the host on the parent side only.
 """
 import argparse
 import json
@@ -30,7 +35,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from _infer_restate import restate  # noqa: E402
 from mp_former_amd import _lib  # noqa: E402
-from mp_former_amd.inference import InferenceConfig, SemanticTTA, SemSegConfusion, postprocess  # noqa: E402
+from mp_former_amd.inference import InferenceConfig, PanopticQuality, SemanticTTA, SemSegConfusion, postprocess  # noqa: E402
 
 CASES = {
     # name: (K, low-res hw, padded, image, output, config)
@@ -223,6 +228,62 @@ def tta_rows(name, iters, dev, Q=100):
                       "valu_frac_157TF": round(fl / (t_valu * 1e-6) / 157e12, 3)}), flush=True)
 
 
+def pq_rows(name, K, hw, padded, image, out, iters, dev):
+    """Panoptic quality of one image: the device route against the id map's copy to the host + the numpy restatement."""
+    import numpy as np
+    import _pq_restate as R
+    things = frozenset(range(80))
+    cfg = InferenceConfig(num_classes=K, num_queries=100, instance_on=False, panoptic_on=True, thing_ids=things)
+    # 20 confident queries that each own one block of a 4 x 5 grid (the random masks of inputs() keep no segment at all)
+    g = torch.Generator().manual_seed(0)
+    Q = 100
+    lg = torch.randn(1, Q, K + 1, generator=g)
+    strong = torch.randperm(Q, generator=g)[:20]
+    lg[0, strong, torch.randint(0, K, (20,), generator=g)] = 9.0
+    low = torch.randn(1, Q, hw[0] // 8, hw[1] // 8, generator=g) - 6.0
+    bh, bw = low.shape[-2] // 4, low.shape[-1] // 5
+    for j, q in enumerate(strong.tolist()):
+        low[0, q, j // 5 * bh:(j // 5 + 1) * bh, j % 5 * bw:(j % 5 + 1) * bw] += 14.0
+    lg, mk = lg.to(dev), torch.nn.functional.interpolate(low, size=hw, mode="bilinear", align_corners=False).to(dev)
+    H, W = out
+    ids0, info0 = postprocess(lg, mk, [image], padded, [out], cfg)[0]["panoptic_seg"]
+    assert len(info0) >= 10, f"the synthetic image keeps {len(info0)} segments"
+    # ground truth: the predicted partition moved by (5, 9) pixels under panoptic-PNG ids, a VOID band, one crowd segment
+    g = np.random.default_rng(0)
+    new_id = np.concatenate(([0], np.sort(g.choice(np.arange(1, 1 << 24), size=len(info0), replace=False))))
+    gt = new_id[np.roll(ids0.cpu().numpy().astype(np.int64), (5, 9), axis=(0, 1))]
+    gt[:16] = 0
+    gts = [{"id": int(new_id[s["id"]]), "category_id": s["category_id"], "iscrowd": int(n == 1)} for n, s in enumerate(info0)]
+    gt_dev = torch.from_numpy(R.id2rgb(gt)).to(dev)
+    pq = PanopticQuality(K, things, device=dev)
+    host_total = [R.zero_stats(K)]
+
+    def native():
+        ids, info = postprocess(lg, mk, [image], padded, [out], cfg)[0]["panoptic_seg"]
+        pq.update(ids, info, gt_dev, gts)
+
+    def parent():
+        ids, info = postprocess(lg, mk, [image], padded, [out], cfg)[0]["panoptic_seg"]
+        host_total[0] = R.add_stats(host_total[0], R.pq_single(gt, ids.cpu().numpy(), gts, info, K, 0))
+
+    def post_only():
+        return postprocess(lg, mk, [image], padded, [out], cfg)[0]["panoptic_seg"]
+
+    t_nat, m_nat = timed_wall(native, iters)
+    t_par, m_par = timed_wall(parent, iters)
+    t_post, _ = timed_wall(post_only, iters)
+    t_upd, _ = timed_wall(lambda: pq.update(ids0, info0, gt_dev, gts), iters)
+    pq.reset()
+    pq.update(ids0, info0, gt_dev, gts)
+    got, want = pq.stats(), R.pq_single(gt, ids0.cpu().numpy(), gts, info0, K, 0)
+    same = all(np.array_equal(got[k], want[k]) for k in ("tp", "fp", "fn")) and got["iou"].tobytes() == want["iou"].tobytes()
+    print(json.dumps({"case": name, "row": "pq", "segments": len(info0), "native_us": round(t_nat, 1), "parent_us": round(t_par, 1),
+                      "speedup": round(t_par / t_nat, 2), "native_slower": bool(t_nat > t_par), "postprocess_us": round(t_post, 1),
+                      "pq_update_us": round(t_upd, 1), "native_peak_MB": round(m_nat, 1), "parent_peak_MB": round(m_par, 1),
+                      "native_host_bytes": 0, "parent_host_bytes": 4 * H * W, "equal_to_restatement": bool(same),
+                      "tp_fp_fn": [int(want[k].sum()) for k in ("tp", "fp", "fn")]}), flush=True)
+
+
 def work(K, cfg, hw, out, Q=100, T=100):
     """(bytes, flop) the native route must move / compute: the logits once per kernel that reads them, the results once."""
     H, W = out
@@ -250,6 +311,8 @@ def main():
         K, hw, padded, image, out, kw = CASES[name]
         if "tta" in kinds and name in TTA_CASES:
             tta_rows(name, args.iters, dev)
+        if "pq" in kinds and name == "coco_panoptic_k133":
+            pq_rows(name, K, hw, padded, image, out, args.iters, dev)
         if "eval" in kinds:
             eval_rows(name, K, hw, padded, image, out, args.iters, dev)
         if "base" not in kinds:
