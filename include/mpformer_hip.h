@@ -1324,6 +1324,38 @@ int mpf_seg_pq_pairs(const int* pred, const void* gt, int gt_format, int64_t n, 
 int mpf_seg_pq_match(int* table, size_t table_bytes, int G, int S, int K, const int* gt_cat, const int* gt_flags, const int* pred_cat,
                      int implicit, int64_t* tp, int64_t* fp, int64_t* fn, double* iou, int64_t* err, void* stream);
 
+/*
+ * Instance mask AP on the device (csrc/seg_ap.hip): mask IoU and the per-image matching of the COCO evaluation as the reference
+ * carries it in mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py (evaluateVid, :267-345; an image is a one-frame video).
+ * Masks are packed bits: position p = x * H + y (column-major), 64 positions per uint64 word, bit b of word j = position 64 j + b,
+ * bits at or past H * W zero; nwords = (H * W + 63) / 64.
+ *   mpf_seg_instance_bits:  the masks of the selected entries as mpf_seg_instance_rle_count decides them (arguments as there, up to
+ *                           sel_q and T), as packed words bits uint64 [T, nwords].
+ *   mpf_seg_pack_masks:     dense masks [M, H, W] row-major, MPF_U8 (bool bytes too) or MPF_F32, non-zero = set -> bits [M, nwords].
+ *                           M == 0 launches nothing.
+ *   mpf_seg_mask_pairs:     inter int32 [T, G] = popcount(a_t & b_g), area_a int32 [T], area_b int32 [G]; the three are zeroed by the
+ *                           call.  T == 0 or G == 0 is valid (the other side's areas are still counted).
+ *   mpf_seg_ap_match:       ONE image.  Detections [D] in score-descending order: area_d (pixel counts), dt_score f32, dt_cat int32.
+ *                           Ground truths [G] in the annotation's order: area_g (pixel counts, the IoU's), gt_cat, gt_crowd int32,
+ *                           gt_area f64 (the area the ranges test).  iou_thrs f64 [Tn] and area_rngs f64 [A, 2] are used as uploaded.
+ *                           Only the first max_det detections of a category take part.  crowd_rule 0 = "coco" (a crowd ground truth's
+ *                           IoU is inter / area_d, pycocotools' rleIou), 1 = "union" (the reference file's computeIoU).
+ *                           records int64 [D, 4], fully overwritten: {score bits | category << 32, rank in (image, category) |
+ *                           image << 32, matched bits, ignored bits}, bit a * Tn + t per setting (A * Tn <= 64, else MPF_E_SHAPE).
+ *                           npig int64 [K, A] += the non-ignored ground truths.  workspace: mpf_seg_ap_workspace_bytes(G, A, Tn)
+ *                           bytes (the ground truths' matched marks), any content.
+ */
+int mpf_seg_instance_bits(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int H,
+                          int W, const int64_t* sel_q, int T, uint64_t* bits, void* stream);
+int mpf_seg_pack_masks(const void* masks, int dtype, int M, int H, int W, uint64_t* bits, void* stream);
+int mpf_seg_mask_pairs(const uint64_t* a_bits, int T, const uint64_t* b_bits, int G, int64_t nwords, int* inter, int* area_a,
+                       int* area_b, void* stream);
+size_t mpf_seg_ap_workspace_bytes(int G, int A, int Tn);
+int mpf_seg_ap_match(const int* inter, const int* area_d, const int* area_g, int D, int G, const float* dt_score, const int* dt_cat,
+                     const int* gt_cat, const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn,
+                     const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

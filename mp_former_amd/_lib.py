@@ -212,6 +212,12 @@ SIGNATURES = {
     "mpf_seg_pq_pairs": (_c_int, [_c_vp, _c_vp, _c_int, ctypes.c_int64, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp,
                                   ctypes.c_size_t, _c_vp]),
     "mpf_seg_pq_match": (_c_int, [_c_vp, ctypes.c_size_t, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_int] + [_c_vp] * 6),
+    "mpf_seg_instance_bits": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 10 + [_c_vp, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_pack_masks": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_mask_pairs": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, ctypes.c_int64, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "mpf_seg_ap_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "mpf_seg_ap_match": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp] + [_c_int] * 5
+                         + [_c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
 }
 
 

@@ -1271,6 +1271,29 @@ extern "C" int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, i
     return mpf::check(hipGetLastError(), "mpf_seg_instance_rle_count");
 }
 
+// the packed words of seg_rle_bits_kernel alone, into the caller's [T, nwords] buffer (the prediction side of csrc/seg_ap.hip)
+extern "C" int mpf_seg_instance_bits(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
+                                     int H, int W, const int64_t* sel_q, int T, uint64_t* bits, void* stream)
+{
+    if (int e = check_geom("seg_instance_bits", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    if (!sel_q || !bits) return mpf::fail(MPF_E_NULL, "seg_instance_bits: NULL buffer");
+    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_bits: need 1 <= T <= 65535 entries");
+    if (((uintptr_t)bits & 7) != 0) return mpf::fail(MPF_E_SHAPE, "seg_instance_bits: bits must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W, nwords = (HW + 63) / 64;
+    const dim3 gbits((unsigned)((HW + kInstPix - 1) / kInstPix), (unsigned)T);
+    mpf::prof_begin(st);
+    mpf::set_kernel("seg_rle_bits_kernel");
+    if (dtype == MPF_F32)
+        hipLaunchKernelGGL(seg_rle_bits_kernel<float>, gbits, dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi, H, W, sel_q,
+                           nwords, (unsigned long long*)bits);
+    else
+        hipLaunchKernelGGL(seg_rle_bits_kernel<__hip_bfloat16>, gbits, dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h, w, Hp, Wp,
+                           hi, wi, H, W, sel_q, nwords, (unsigned long long*)bits);
+    mpf::prof_end("seg_rle_bits_kernel", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + (double)T * HW / 8);
+    return mpf::check(hipGetLastError(), "mpf_seg_instance_bits");
+}
+
 extern "C" int mpf_seg_instance_rle_write(const void* workspace, size_t workspace_bytes, int T, int H, int W, const int64_t* offsets,
                                           int64_t total, uint32_t* pos, uint32_t* counts, void* stream)
 {

@@ -103,9 +103,11 @@ def registered():
 register()
 
 
-def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None):
+def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None, instance_bits=False):
     """The eval branch of a reference ``MaskFormer`` (mask2former/maskformer_model.py:199-203 + 233-279) with the native
-    post-processing (inference.postprocess) in place of its F.interpolate / sem_seg_postprocess / *_inference body."""
+    post-processing (inference.postprocess) in place of its F.interpolate / sem_seg_postprocess / *_inference body.
+    ``instance_bits``: ``[{"instances": d}]`` with d the per-image dict of inference.instance_bits (packed masks, for
+    ``InstanceAPEvaluator``) instead of the ``postprocess`` results."""
     from .inference import postprocess
     if image_list_cls is None:
         from detectron2.structures import ImageList as image_list_cls
@@ -114,14 +116,20 @@ def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None):
     images = image_list_cls.from_tensors(images, model.size_divisibility)
     outputs = model.sem_seg_head(model.backbone(images.tensor))
     out_sizes = [(x.get("height", s[0]), x.get("width", s[1])) for x, s in zip(batched_inputs, images.image_sizes)]
+    if instance_bits:
+        from .inference import instance_bits as bits_route
+        return [{"instances": d} for d in bits_route(outputs["pred_logits"], outputs["pred_masks"], images.image_sizes,
+                                                     tuple(images.tensor.shape[-2:]), out_sizes, cfg)]
     return postprocess(outputs["pred_logits"], outputs["pred_masks"], images.image_sizes, tuple(images.tensor.shape[-2:]), out_sizes,
                        cfg)
 
 
-def install_native_inference(model, image_list_cls=None, semantic_labels=False, instance_masks="dense"):
+def install_native_inference(model, image_list_cls=None, semantic_labels=False, instance_masks="dense", instance_bits=False):
     """Route the eval branch of a reference ``MaskFormer`` instance through ``native_eval_forward``; training is unchanged.
     ``semantic_labels`` / ``instance_masks``: the evaluation-form results of inference.InferenceConfig (the model has no such
-    attributes; the defaults give the reference's own result dicts).  Returns the inference.InferenceConfig in use."""
+    attributes; the defaults give the reference's own result dicts).  ``instance_bits``: the model returns only "instances", as
+    packed masks (inference.instance_bits), the form ``InstanceAPEvaluator`` consumes without a dense mask.  Returns the
+    inference.InferenceConfig in use."""
     import dataclasses
     from .inference import InferenceConfig
     cfg = dataclasses.replace(InferenceConfig.from_maskformer(model), semantic_labels=semantic_labels, instance_masks=instance_masks)
@@ -130,7 +138,7 @@ def install_native_inference(model, image_list_cls=None, semantic_labels=False, 
     def forward(batched_inputs):
         if model.training:
             return train_forward(batched_inputs)
-        return native_eval_forward(model, batched_inputs, cfg, image_list_cls)
+        return native_eval_forward(model, batched_inputs, cfg, image_list_cls, instance_bits)
 
     model.forward = forward
     return cfg
@@ -258,3 +266,58 @@ class PanopticQualityEvaluator:
 
     def evaluate(self):
         return {"panoptic_seg": self.pq.results()}
+
+
+class InstanceAPEvaluator:
+    """detectron2's evaluator protocol (``reset`` / ``process(inputs, outputs)`` / ``evaluate``) on inference.InstanceAP, in place
+    of ``COCOEvaluator`` for "segm": masks are packed and matched on the device, one record per detection crosses to the host at
+    ``evaluate``.  Writes no file and needs neither detectron2 nor pycocotools.
+
+    Predictions: ``outputs[i]["instances"]`` with dense ``pred_masks`` [T, H, W], ``scores`` and ``pred_classes`` (packed here), or
+    the dict of inference.instance_bits where the model was installed with ``install_native_inference(..., instance_bits=True)``.
+    Ground truth: ``inputs[i]["instances"]`` with ``gt_masks`` (a [G, H, W] tensor or an object with ``.tensor``) and ``gt_classes``
+    at the prediction's size; optional ``gt_iscrowd`` and ``gt_areas`` (missing: no crowd, the pixel counts)."""
+
+    def __init__(self, num_classes, class_names=None, device="cuda:0", **ap_options):
+        from .inference import InstanceAP
+        self.ap = InstanceAP(num_classes, device=device, **ap_options)
+        if class_names is not None and len(class_names) != self.ap.num_classes:
+            raise ValueError(f"{len(class_names)} class names for {self.ap.num_classes} classes")
+        self.class_names = class_names
+
+    def reset(self):
+        self.ap.reset()
+
+    @staticmethod
+    def _field(inst, name, default=None):
+        if isinstance(inst, dict):
+            return inst.get(name, default)
+        if hasattr(inst, "has") and not inst.has(name):
+            return default
+        return getattr(inst, name, default)
+
+    def process(self, inputs, outputs):
+        import torch
+        from .inference import pack_masks
+        dev = self.ap.device
+        for inp, out in zip(inputs, outputs):
+            pred, gt = out["instances"], inp["instances"]
+            if isinstance(pred, dict) and "bits" in pred:
+                dt_bits, size = pred["bits"], tuple(pred["size"])
+            else:
+                masks = self._field(pred, "pred_masks")
+                dt_bits, size = pack_masks(masks.to(dev)), tuple(masks.shape[-2:])
+            gm = self._field(gt, "gt_masks")
+            gm = getattr(gm, "tensor", gm)
+            if gm.shape[0] == 0:                             # an image without annotations, whatever shape its empty tensor has
+                gm = gm.new_zeros((0,) + size)
+            elif gm.dim() != 3 or tuple(gm.shape[-2:]) != size:
+                raise ValueError(f"gt_masks {tuple(gm.shape)} do not have the prediction's size {size}")
+            G = gm.shape[0]
+            crowd = self._field(gt, "gt_iscrowd")
+            self.ap.update(dt_bits, self._field(pred, "scores"), self._field(pred, "pred_classes"), pack_masks(gm.to(dev)),
+                           self._field(gt, "gt_classes"), torch.zeros(G, dtype=torch.int32) if crowd is None else crowd,
+                           self._field(gt, "gt_areas"))
+
+    def evaluate(self):
+        return {"segm": self.ap.results(self.class_names)}

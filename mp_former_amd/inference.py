@@ -229,7 +229,9 @@ def _instance_rle(mptr, sq, dt, geom, query, T, dev, stream):
     return [{"size": [H, W], "counts": host[off[t]:off[t + 1]].tolist()} for t in range(T)]
 
 
-def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
+def _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream):
+    """The entries of instance_inference (maskformer_model.py:362-401), sorted by their final score, descending and stable
+    -> (scores fp32 [T], labels int64 [T], query int64 [T] contiguous).  Shared by ``postprocess`` and ``instance_bits``."""
     Q, K = img.Q, img.K
     H, W = geom[-2:]
     k = min(int(cfg.test_topk_per_image), Q * K)
@@ -240,6 +242,22 @@ def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
         keep = thing_lut[labels]
         sc, labels, query = sc[keep], labels[keep], query[keep]
     T = int(sc.shape[0])
+    if T == 0:
+        return sc, labels, query
+    query = query.contiguous()
+    scores = torch.empty(T, dtype=torch.float32, device=dev)
+    nws = _lib.lib().mpf_seg_instance_workspace_bytes(T, H, W)
+    ws = _lib.scratch("seg_infer.instance", dev, stream, nws)
+    _lib.call("mpf_seg_instance_scores", dev, mptr, sq, dt, *geom, query.data_ptr(), sc.data_ptr(), T, scores.data_ptr(), ws.data_ptr(),
+              ws.numel(), stream)
+    scores, order = scores.sort(descending=True, stable=True)
+    return scores, labels[order], query[order].contiguous()
+
+
+def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
+    H, W = geom[-2:]
+    scores, labels, query = _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream)
+    T = int(scores.shape[0])
     Boxes, Instances = _structures()
     result = Instances(image_hw)
     rle = cfg.instance_masks == "rle"
@@ -249,17 +267,9 @@ def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
         else:
             result.pred_masks = torch.zeros((0, H, W), dtype=torch.float32, device=dev)
         result.pred_boxes = Boxes(torch.zeros(0, 4))
-        result.scores = sc
+        result.scores = scores
         result.pred_classes = labels
         return result
-    query = query.contiguous()
-    scores = torch.empty(T, dtype=torch.float32, device=dev)
-    nws = _lib.lib().mpf_seg_instance_workspace_bytes(T, H, W)
-    ws = _lib.scratch("seg_infer.instance", dev, stream, nws)
-    _lib.call("mpf_seg_instance_scores", dev, mptr, sq, dt, *geom, query.data_ptr(), sc.data_ptr(), T, scores.data_ptr(), ws.data_ptr(),
-              ws.numel(), stream)
-    scores, order = scores.sort(descending=True, stable=True)
-    query, labels = query[order].contiguous(), labels[order]
     if rle:
         result.pred_masks_rle = _instance_rle(mptr, sq, dt, geom, query, T, dev, stream)
     else:
@@ -290,6 +300,28 @@ def _panoptic(mptr, sq, dt, geom, img, cfg, dev, stream):
     return ids, segments_info
 
 
+def _head_outputs(who, pred_logits, pred_masks, cfg):
+    """The checks and per-batch launch state that ``postprocess`` and ``instance_bits`` share."""
+    if not (pred_masks.is_cuda and pred_logits.is_cuda):
+        raise RuntimeError(f"{who}: Not implemented on the CPU (device tensors only)")
+    N, Q, K1 = pred_logits.shape
+    K = K1 - 1
+    if K != cfg.num_classes:
+        raise ValueError(f"pred_logits has {K} classes + no-object, config {cfg.num_classes}")
+    if pred_masks.dim() != 4 or pred_masks.shape[:2] != (N, Q):
+        raise ValueError(f"pred_masks {tuple(pred_masks.shape)} does not match pred_logits {tuple(pred_logits.shape)}")
+    pm, sn, sq, dt = _masks_arg(pred_masks)
+    dev = pm.device
+    thing_lut = None
+    if cfg.instance_on and cfg.panoptic_on:
+        thing_lut = torch.zeros(K, dtype=torch.bool)
+        for i in cfg.thing_ids:
+            if 0 <= i < K:
+                thing_lut[i] = True
+        thing_lut = thing_lut.to(dev)
+    return N, K, pm, sn, sq, dt, dev, thing_lut, _lib.stream_ptr(dev), pred_logits.detach().float()
+
+
 def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
     """The reference's eval branch after the head (maskformer_model.py:236-279).
 
@@ -300,26 +332,8 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
     "instances" (pred_masks [T, height, width] 0/1 fp32, pred_boxes zeros, scores, pred_classes), per the *_on flags.
     cfg.semantic_labels: "sem_seg_labels" int32 [height, width] in place of "sem_seg"; cfg.instance_masks == "rle":
     instances.pred_masks_rle (list of T {"size", "counts"} dicts) in place of pred_masks."""
-    if not (pred_masks.is_cuda and pred_logits.is_cuda):
-        raise RuntimeError("postprocess: Not implemented on the CPU (device tensors only)")
-    N, Q, K1 = pred_logits.shape
-    K = K1 - 1
-    if K != cfg.num_classes:
-        raise ValueError(f"pred_logits has {K} classes + no-object, config {cfg.num_classes}")
-    if pred_masks.dim() != 4 or pred_masks.shape[:2] != (N, Q):
-        raise ValueError(f"pred_masks {tuple(pred_masks.shape)} does not match pred_logits {tuple(pred_logits.shape)}")
-    pm, sn, sq, dt = _masks_arg(pred_masks)
-    dev = pm.device
+    N, K, pm, sn, sq, dt, dev, thing_lut, stream, logits = _head_outputs("postprocess", pred_logits, pred_masks, cfg)
     out = []
-    thing_lut = None
-    if cfg.instance_on and cfg.panoptic_on:
-        thing_lut = torch.zeros(K, dtype=torch.bool)
-        for i in cfg.thing_ids:
-            if 0 <= i < K:
-                thing_lut[i] = True
-        thing_lut = thing_lut.to(dev)
-    stream = _lib.stream_ptr(dev)
-    logits = pred_logits.detach().float()
     for n in range(N):
         mptr = pm.data_ptr() + n * sn * pm.element_size()
         hi, wi = int(image_sizes[n][0]), int(image_sizes[n][1])
@@ -345,6 +359,30 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
             res["instances"] = _instances(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, thing_lut, dev, stream,
                                           (H, W))
         out.append(res)
+    return out
+
+
+def instance_bits(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
+    """The "instances" of ``postprocess`` (same arguments) with their masks as packed bits, for ``InstanceAP``: per image a dict
+    with "bits" int64 [T, nwords] on the device (position p = x * H + y, 64 per word, bit b of word j = position 64 j + b, zero at
+    and past H * W), "size" (H, W), "scores" and "pred_classes".  Selection, scores and order are those of ``postprocess``; the
+    dense [T, H, W] masks are never written."""
+    if not cfg.instance_on:
+        raise ValueError("instance_bits needs instance_on")
+    N, K, pm, sn, sq, dt, dev, thing_lut, stream, logits = _head_outputs("instance_bits", pred_logits, pred_masks, cfg)
+    out = []
+    for n in range(N):
+        mptr = pm.data_ptr() + n * sn * pm.element_size()
+        hi, wi = int(image_sizes[n][0]), int(image_sizes[n][1])
+        H, W = int(output_sizes[n][0]), int(output_sizes[n][1])
+        geom = _geom(pm[n], (hi, wi), padded_hw, (H, W))
+        img = _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n)
+        scores, labels, query = _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream)
+        T = int(scores.shape[0])
+        bits = torch.empty((T, (H * W + 63) // 64), dtype=torch.int64, device=dev)
+        if T:
+            _lib.call("mpf_seg_instance_bits", dev, mptr, sq, dt, *geom, query.data_ptr(), T, bits.data_ptr(), stream)
+        out.append({"bits": bits, "size": (H, W), "scores": scores, "pred_classes": labels})
     return out
 
 
@@ -715,3 +753,302 @@ def pq_results(stats, thing_ids):
         nan = float("nan")
         out[name] = {"pq": pq / n if n else nan, "sq": sq / n if n else nan, "rq": rq / n if n else nan, "n": n}
     return out
+
+
+# ---- instance mask AP on the device ---------------------------------------------------------------------------------------------
+AP_CROWD_RULES = {"coco": 0, "union": 1}      # the crowd_rule argument of mpf_seg_ap_match
+COCO_AREA_RNGS = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))     # all, small, medium, large
+_AP_REC = 4                                   # int64 words of a detection's record
+
+
+def _bits_arg(bits, what):
+    if not bits.is_cuda:
+        raise RuntimeError(f"{what}: Not implemented on the CPU (device tensors only)")
+    if bits.dim() != 2 or bits.dtype != torch.int64:
+        raise ValueError(f"{what} must be packed bits int64 [M, nwords], got {bits.dtype} {tuple(bits.shape)}")
+    return bits.contiguous()
+
+
+def pack_masks(masks):
+    """Dense masks [M, H, W] on the device (uint8, bool or float32; non-zero = set) -> packed bits int64 [M, nwords], in the layout
+    of ``instance_bits``: position p = x * H + y, 64 positions per word, bit b of word j = position 64 j + b, zero past H * W."""
+    if not masks.is_cuda:
+        raise RuntimeError("pack_masks: Not implemented on the CPU (device tensors only)")
+    if masks.dim() != 3 or masks.shape[1] == 0 or masks.shape[2] == 0:
+        raise ValueError(f"masks must be [M, H, W] with H, W > 0, got {tuple(masks.shape)}")
+    if masks.dtype not in (torch.uint8, torch.bool, torch.float32):
+        raise TypeError(f"masks must be uint8, bool or float32, got {masks.dtype}")
+    masks = masks.contiguous()
+    M, H, W = masks.shape
+    dev = masks.device
+    bits = torch.empty((M, (H * W + 63) // 64), dtype=torch.int64, device=dev)
+    if M:
+        _lib.call("mpf_seg_pack_masks", dev, masks.data_ptr(), _lib.DTYPE[masks.dtype], M, H, W, bits.data_ptr(), _lib.stream_ptr(dev))
+    return bits
+
+
+def mask_pair_counts(a_bits, b_bits):
+    """Two sets of packed masks of one image, A [T, nwords] and B [G, nwords] -> (inter int32 [T, G] = the pixels a_t and b_g share,
+    area_a int32 [T], area_b int32 [G]), on the device."""
+    a, b = _bits_arg(a_bits, "a_bits"), _bits_arg(b_bits, "b_bits")
+    if a.device != b.device:
+        raise RuntimeError(f"a_bits on {a.device}, b_bits on {b.device}")
+    if a.shape[1] != b.shape[1] or a.shape[1] == 0:
+        raise ValueError(f"both sides need the same nwords > 0, got {a.shape[1]} and {b.shape[1]}")
+    T, G, nwords = a.shape[0], b.shape[0], a.shape[1]
+    dev = a.device
+    inter = torch.empty((T, G), dtype=torch.int32, device=dev)
+    area_a = torch.empty(T, dtype=torch.int32, device=dev)
+    area_b = torch.empty(G, dtype=torch.int32, device=dev)
+    if T or G:
+        _lib.call("mpf_seg_mask_pairs", dev, a.data_ptr() if T else None, T, b.data_ptr() if G else None, G, nwords,
+                  inter.data_ptr() if T and G else None, area_a.data_ptr() if T else None, area_b.data_ptr() if G else None,
+                  _lib.stream_ptr(dev))
+    return inter, area_a, area_b
+
+
+class InstanceAP:
+    """The per-image part of the COCO mask evaluation (``COCOeval.evaluateImg``; the reference carries the same body as
+    ``evaluateVid`` in mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py:267-345) on the device, and its ``accumulate`` /
+    ``summarize`` (:347-525) on the host.  ``update`` counts the pair intersections of packed masks (``mpf_seg_mask_pairs``) and runs
+    the greedy matching for every (category, area range, IoU threshold) (``mpf_seg_ap_match``); it launches and returns.  One record
+    per detection accumulates in a device buffer; only ``stats`` copies to the host.  IoUs are correctly rounded float64 quotients of
+    integer counts and the thresholds are uploaded as the host computed them, so the records are the reference's
+    dtMatches / dtIgnore / gtIgnore bit for bit.
+
+    crowd_rule: "coco" = pycocotools' rleIou (a crowd ground truth's IoU is inter / detection area); "union" = the reference file's
+    own computeIoU (the plain union for every pair).
+
+    Deviation: with ``gt_areas=None`` a ground truth's area is its pixel count (COCO reads the annotation's "area")."""
+
+    def __init__(self, num_classes, iou_thrs=None, area_rngs=None, max_dets=(1, 10, 100), crowd_rule="coco", device="cuda:0"):
+        self.num_classes = int(num_classes)
+        if self.num_classes <= 0:
+            raise ValueError("num_classes must be positive")
+        self.iou_thrs = np.linspace(.5, 0.95, 10) if iou_thrs is None else np.array(iou_thrs, dtype=np.float64)
+        self.area_rngs = np.array(COCO_AREA_RNGS if area_rngs is None else area_rngs, dtype=np.float64)
+        self.rec_thrs = np.linspace(.0, 1.00, 101)
+        if self.iou_thrs.ndim != 1 or self.iou_thrs.size == 0:
+            raise ValueError("iou_thrs must be a non-empty list of thresholds")
+        if self.area_rngs.ndim != 2 or self.area_rngs.shape[1] != 2 or self.area_rngs.shape[0] == 0:
+            raise ValueError("area_rngs must be [A, 2] (low, high) pairs")
+        if self.area_rngs.shape[0] * self.iou_thrs.size > 64:
+            raise ValueError(f"{self.area_rngs.shape[0]} area ranges x {self.iou_thrs.size} thresholds do not fit the 64 bits of a record")
+        self.max_dets = tuple(sorted(int(m) for m in max_dets))        # evaluate() sorts them (:148)
+        if not self.max_dets or self.max_dets[0] <= 0:
+            raise ValueError("max_dets must be a non-empty list of positive counts")
+        if crowd_rule not in AP_CROWD_RULES:
+            raise ValueError(f"crowd_rule must be 'coco' or 'union', got {crowd_rule!r}")
+        self.crowd_rule = crowd_rule
+        self.device = torch.device(device)
+        self._rec = self._npig = self._settings = None
+        self._n = self._images = 0
+
+    # ---- device side ----
+    def _buffers(self):
+        if self._npig is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("InstanceAP: Not implemented on the CPU (device tensors only)")
+            self._npig = torch.zeros(self.num_classes * self.area_rngs.shape[0], dtype=torch.int64, device=self.device)
+            self._rec = torch.empty((256, _AP_REC), dtype=torch.int64, device=self.device)
+            # the float64 values as the host holds them: a kernel that rebuilt 0.5 + 0.05 i would differ in the last bit
+            self._settings = torch.from_numpy(np.concatenate([self.iou_thrs, self.area_rngs.reshape(-1)])).to(self.device)
+
+    def reset(self):
+        self._n = self._images = 0
+        if self._npig is not None:
+            self._npig.zero_()
+
+    def _small(self, v, n, dtype, what):
+        from . import _h2d
+        if torch.is_tensor(v) and v.is_cuda:
+            t = v.to(device=self.device, dtype=dtype)
+        elif len(v) == 0:
+            t = torch.empty(0, dtype=dtype, device=self.device)
+        else:
+            t = _h2d.upload(v, self.device, dtype)          # host data goes up without stalling the launch thread
+        t = t.reshape(-1).contiguous()
+        if t.numel() != n:
+            raise ValueError(f"{what} has {t.numel()} entries for {n} masks")
+        return t
+
+    def update(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas=None):
+        """One image.  dt_bits int64 [D, nwords] and gt_bits int64 [G, nwords] packed masks on the device (``instance_bits`` /
+        ``pack_masks``), scores [D], classes [D], gt_classes [G], gt_crowd [G] (0 / 1), gt_areas [G] or None (= the pixel counts).
+        The detections may come in any order: they are sorted by score, descending and stable (the reference's mergesort of -score).
+        No device-to-host copy."""
+        if self.device.type != "cuda":
+            raise RuntimeError("InstanceAP: Not implemented on the CPU (device tensors only)")
+        dt_bits, gt_bits = _bits_arg(dt_bits, "dt_bits"), _bits_arg(gt_bits, "gt_bits")
+        if dt_bits.device != self.device or gt_bits.device != self.device:
+            raise RuntimeError(f"masks on {dt_bits.device} / {gt_bits.device}, the records on {self.device}")
+        D, G = dt_bits.shape[0], gt_bits.shape[0]
+        if D and G and dt_bits.shape[1] != gt_bits.shape[1]:
+            raise ValueError(f"detections have {dt_bits.shape[1]} words per mask, ground truths {gt_bits.shape[1]}: not one image")
+        self._buffers()
+        dev = self.device
+        scores = self._small(scores, D, torch.float32, "scores")
+        classes = self._small(classes, D, torch.int32, "classes")
+        gt_cat = self._small(gt_classes, G, torch.int32, "gt_classes")
+        crowd = self._small(gt_crowd, G, torch.int32, "gt_crowd")
+        image = self._images
+        self._images += 1
+        if D == 0 and G == 0:
+            return
+        nwords = dt_bits.shape[1] if D else gt_bits.shape[1]
+        inter, area_d, area_g = mask_pair_counts(dt_bits if D else dt_bits.new_empty((0, nwords)),
+                                                 gt_bits if G else gt_bits.new_empty((0, nwords)))
+        scores, order = scores.sort(descending=True, stable=True)
+        classes, area_d, inter = classes[order].contiguous(), area_d[order].contiguous(), inter[order].contiguous()
+        gt_area = area_g.double() if gt_areas is None else self._small(gt_areas, G, torch.float64, "gt_areas")
+        if self._n + D > self._rec.shape[0]:                # grow by doubling; the old buffer stays valid for the queued launches
+            grown = torch.empty((max(2 * self._rec.shape[0], self._n + D), _AP_REC), dtype=torch.int64, device=dev)
+            grown[:self._n] = self._rec[:self._n]
+            self._rec = grown
+        stream = _lib.stream_ptr(dev)
+        Tn, A = self.iou_thrs.size, self.area_rngs.shape[0]
+        ws = _lib.scratch("seg_ap.gt_marks", dev, stream, max(1, _lib.lib().mpf_seg_ap_workspace_bytes(G, A, Tn)))
+        sp = self._settings.data_ptr()
+        _lib.call("mpf_seg_ap_match", dev, _lib.ptr(inter) if D and G else None, area_d.data_ptr() if D else None,
+                  area_g.data_ptr() if G else None, D, G, scores.data_ptr() if D else None, classes.data_ptr() if D else None,
+                  gt_cat.data_ptr() if G else None, crowd.data_ptr() if G else None, gt_area.data_ptr() if G else None, sp, Tn, sp + 8 * Tn,
+                  A, self.num_classes, self.max_dets[-1], AP_CROWD_RULES[self.crowd_rule], image,
+                  self._rec.data_ptr() + 8 * _AP_REC * self._n, self._npig.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        self._n += D
+
+    # ---- host side ----
+    def stats(self):
+        """-> for the N recorded detections, in update order and score order inside an image: "scores" float32 [N], "category",
+        "rank" (inside its image and category), "image" int64 [N], "matched" and "ignored" bool [N, A, Tn], and "npig" int64 [K, A]
+        (the non-ignored ground truths).  One device-to-host copy."""
+        K, A, Tn, n = self.num_classes, self.area_rngs.shape[0], self.iou_thrs.size, self._n
+        if self._npig is None:
+            host = np.zeros(K * A, dtype=np.int64)
+        else:
+            host = torch.cat([self._rec[:n].reshape(-1), self._npig]).cpu().numpy()
+        rec = host[:_AP_REC * n].reshape(n, _AP_REC).view(np.uint64)
+        shifts = np.arange(A * Tn, dtype=np.uint64)
+        unpack = lambda w: ((w[:, None] >> shifts[None, :]) & np.uint64(1)).astype(bool).reshape(n, A, Tn)      # noqa: E731
+        return {"scores": (rec[:, 0] & np.uint64(0xffffffff)).astype(np.uint32).view(np.float32),
+                "category": (rec[:, 0] >> np.uint64(32)).astype(np.int64), "rank": (rec[:, 1] & np.uint64(0xffffffff)).astype(np.int64),
+                "image": (rec[:, 1] >> np.uint64(32)).astype(np.int64), "matched": unpack(rec[:, 2]), "ignored": unpack(rec[:, 3]),
+                "npig": host[_AP_REC * n:].reshape(K, A).copy()}
+
+    @staticmethod
+    def combine(list_of_stats):
+        """Ranks or shards: the records concatenated in list order, npig summed."""
+        if not list_of_stats:
+            raise ValueError("combine: no stats")
+        keys = ("scores", "category", "rank", "image", "matched", "ignored")
+        out = {k: np.concatenate([np.asarray(s[k]) for s in list_of_stats]) for k in keys}
+        out["npig"] = np.sum([np.asarray(s["npig"], dtype=np.int64) for s in list_of_stats], axis=0)
+        return out
+
+    def accumulate(self, stats=None):
+        """``accumulate`` of the reference (:385-442) from the records -> {"precision" [Tn, R, K, A, M], "recall" [Tn, K, A, M],
+        "scores" [Tn, R, K, A, M]} float64, -1 where a (category, range) has no non-ignored ground truth; R = the 101 recall points."""
+        s = self.stats() if stats is None else stats
+        return ap_accumulate(s, self.num_classes, self.iou_thrs, self.rec_thrs, self.area_rngs.shape[0], self.max_dets)
+
+    def summarize(self, stats=None):
+        """The 12 statistics of the reference's ``_summarizeDets`` (:490-504)."""
+        return ap_summarize(self.accumulate(stats), self.iou_thrs, self.max_dets)
+
+    def results(self, class_names=None, stats=None):
+        """detectron2's ``COCOEvaluator`` keys for "segm": AP, AP50, AP75, APs, APm, APl (x 100, nan where the statistic is -1) and
+        one AP-{name} per category (names default to the class index)."""
+        K = self.num_classes
+        if class_names is not None and len(class_names) != K:
+            raise ValueError(f"{len(class_names)} class names for {K} classes")
+        acc = self.accumulate(stats)
+        st = ap_summarize(acc, self.iou_thrs, self.max_dets)
+        out = {name: float(st[i] * 100 if st[i] >= 0 else "nan") for i, name in enumerate(("AP", "AP50", "AP75", "APs", "APm", "APl"))}
+        names = [str(i) for i in range(K)] if class_names is None else list(class_names)
+        for k, name in enumerate(names):
+            p = acc["precision"][:, :, k, 0, -1]
+            p = p[p > -1]
+            out[f"AP-{name}"] = float(np.mean(p) * 100) if p.size else float("nan")
+        return out
+
+
+def ap_accumulate(stats, K, iou_thrs, rec_thrs, A, max_dets):
+    """The reference's ``accumulate`` (ytvoseval.py:385-442) from detection records (``InstanceAP.stats``).  The records of a category
+    in their stored order are the reference's concatenation of the images' evalImgs (image order, score order inside an image)."""
+    Tn, R, M = len(iou_thrs), len(rec_thrs), len(max_dets)
+    precision = -np.ones((Tn, R, K, A, M))
+    recall = -np.ones((Tn, K, A, M))
+    scores = -np.ones((Tn, R, K, A, M))
+    cat, rank = np.asarray(stats["category"]), np.asarray(stats["rank"])
+    sc = np.asarray(stats["scores"], dtype=np.float32).astype(np.float64)
+    matched, ignored, npig_all = np.asarray(stats["matched"]), np.asarray(stats["ignored"]), np.asarray(stats["npig"])
+    if npig_all.shape != (K, A) or matched.shape[1:] != (A, Tn) or ignored.shape != matched.shape:
+        raise ValueError(f"stats do not fit {K} classes, {A} ranges, {Tn} thresholds")
+    for k in range(K):
+        of_k = cat == k
+        for a in range(A):
+            npig = int(npig_all[k, a])
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(max_dets):
+                sel = np.nonzero(of_k & (rank < max_det))[0]
+                dt_scores = sc[sel]
+                inds = np.argsort(-dt_scores, kind="mergesort")
+                dt_sorted = dt_scores[inds]
+                dtm = matched[sel, a, :].T[:, inds]
+                dt_ig = ignored[sel, a, :].T[:, inds]
+                tps = np.logical_and(dtm, np.logical_not(dt_ig))
+                fps = np.logical_and(np.logical_not(dtm), np.logical_not(dt_ig))
+                tp_sum = np.cumsum(tps, axis=1).astype(dtype=np.float64)
+                fp_sum = np.cumsum(fps, axis=1).astype(dtype=np.float64)
+                for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                    nd = len(tp)
+                    rc = tp / npig
+                    pr = tp / (fp + tp + np.spacing(1))
+                    q = np.zeros((R,)).tolist()
+                    ss = np.zeros((R,))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    pr = pr.tolist()
+                    for i in range(nd - 1, 0, -1):
+                        if pr[i] > pr[i - 1]:
+                            pr[i - 1] = pr[i]
+                    pos = np.searchsorted(rc, rec_thrs, side="left")
+                    for ri, pi in enumerate(pos):
+                        if pi >= nd:                     # the reference's loop ends here in an IndexError: the rest stays 0
+                            break
+                        q[ri] = pr[pi]
+                        ss[ri] = dt_sorted[pi]
+                    precision[t, :, k, a, m] = np.array(q)
+                    scores[t, :, k, a, m] = np.array(ss)
+    return {"precision": precision, "recall": recall, "scores": scores}
+
+
+def ap_summarize(acc, iou_thrs, max_dets):
+    """The reference's ``_summarizeDets`` (ytvoseval.py:459-504) -> float64 [12].  As there, the area ranges are all / small / medium /
+    large in that order, and the first statistic asks for ``maxDets == 100``: it is -1 where max_dets does not list 100."""
+    precision, recall = acc["precision"], acc["recall"]
+    iou_thrs = np.asarray(iou_thrs)
+    if precision.shape[3] != 4 or len(max_dets) < 3:
+        raise ValueError("the 12 statistics need the four area ranges (all, small, medium, large) and three max_dets")
+
+    def one(ap=1, iou_thr=None, area=0, max_det=100):
+        aind = [area]
+        mind = [i for i, m in enumerate(max_dets) if m == max_det]
+        s = precision if ap == 1 else recall
+        if iou_thr is not None:
+            s = s[np.where(iou_thr == iou_thrs)[0]]
+        s = s[:, :, :, aind, mind] if ap == 1 else s[:, :, aind, mind]
+        return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+    st = np.zeros((12,))
+    st[0] = one(1)
+    st[1] = one(1, iou_thr=.5, max_det=max_dets[2])
+    st[2] = one(1, iou_thr=.75, max_det=max_dets[2])
+    st[3] = one(1, area=1, max_det=max_dets[2])
+    st[4] = one(1, area=2, max_det=max_dets[2])
+    st[5] = one(1, area=3, max_det=max_dets[2])
+    st[6] = one(0, max_det=max_dets[0])
+    st[7] = one(0, max_det=max_dets[1])
+    st[8] = one(0, max_det=max_dets[2])
+    st[9] = one(0, area=1, max_det=max_dets[2])
+    st[10] = one(0, area=2, max_det=max_dets[2])
+    st[11] = one(0, area=3, max_det=max_dets[2])
+    return st

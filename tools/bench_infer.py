@@ -3,7 +3,7 @@ eval branch (tests/_infer_restate.py), per image on one GPU.  Prints one line pe
 inputs, the algorithmic bytes / FLOP of the native route and the fraction of the measured 6.3 TB/s copy rate or of the
 157 TF fp32 peak it reaches (whichever bound applies).
 
-    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta,pq]
+    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta,pq,ap]
 
 The ``eval`` rows measure the evaluation-form results (``semantic_labels``, ``SemSegConfusion``, ``instance_masks="rle"``) against
 the default route brought to the same end product: ``sem_seg`` + ``torch.argmax`` (+ ``.cpu()`` of the label map where the metric
@@ -21,6 +21,11 @@ The ``pq`` row (not in the default set; COCO panoptic case only) measures panopt
 followed by ``PanopticQuality.update`` against ``postprocess``, ``ids.cpu()`` and the numpy restatement of panopticapi's per-image
 arithmetic (tests/_pq_restate.py).  The ground truth is in place on both sides before the clock starts (RGB bytes on the device,
 an id map on the host).  Wall-clock medians as above; the id map's 4 H W bytes cross to the host on the parent side only.
+
+The ``ap`` row (not in the default set; COCO instance case only) measures the per-image part of instance mask AP: ``instance_bits``
++ ``pack_masks`` of the ground truth + ``InstanceAP.update`` against ``postprocess`` with dense masks, ``pred_masks.cpu()`` and the
+numpy restatement of the COCO IoU and matching (tests/_ap_restate.py).  The ground truth (about 20 dense masks) is in place on
+both sides before the clock starts.  Wall-clock medians as above; the 4 T H W bytes of the masks cross on the parent side only.
 """
 import argparse
 import json
@@ -35,7 +40,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from _infer_restate import restate  # noqa: E402
 from mp_former_amd import _lib  # noqa: E402
-from mp_former_amd.inference import InferenceConfig, PanopticQuality, SemanticTTA, SemSegConfusion, postprocess  # noqa: E402
+from mp_former_amd.inference import (InferenceConfig, InstanceAP, PanopticQuality, SemanticTTA, SemSegConfusion,  # noqa: E402
+                                     instance_bits, pack_masks, postprocess)
 
 CASES = {
     # name: (K, low-res hw, padded, image, output, config)
@@ -284,6 +290,64 @@ def pq_rows(name, K, hw, padded, image, out, iters, dev):
                       "tp_fp_fn": [int(want[k].sum()) for k in ("tp", "fp", "fn")]}), flush=True)
 
 
+def ap_rows(name, K, hw, padded, image, out, iters, dev, n_gt=20):
+    """Instance mask AP of one image: the device route against the dense masks' copy to the host + the numpy restatement."""
+    import numpy as np
+    import _ap_restate as R
+    cfg = InferenceConfig(num_classes=K, num_queries=100)
+    lg, mk = inputs(K, hw, dev)
+    H, W = out
+    ins = postprocess(lg, mk, [image], padded, [out], cfg)[0]["instances"]
+    T = len(ins)
+    # ground truth: the first n_gt predictions moved by (5, 9) pixels (every third stays in place), their classes, one crowd
+    pm = ins.pred_masks[:n_gt] > 0.5
+    gt_dev = torch.stack([m if j % 3 == 0 else torch.roll(m, (5, 9), (0, 1)) for j, m in enumerate(pm)]).to(torch.uint8)
+    gt_cls = ins.pred_classes[:n_gt].clone()
+    crowd = torch.zeros(n_gt, dtype=torch.int32, device=dev)
+    crowd[1] = 1
+    gt_host, cls_host, crowd_host = gt_dev.cpu().numpy().astype(bool), gt_cls.cpu().tolist(), crowd.cpu().tolist()
+    gts = [{"id": j + 1, "category": int(cls_host[j]), "iscrowd": int(crowd_host[j]), "mask": gt_host[j], "area": float(gt_host[j].sum())}
+           for j in range(n_gt)]
+    ap = InstanceAP(K, device=dev)
+
+    def native():
+        b = instance_bits(lg, mk, [image], padded, [out], cfg)[0]
+        ap.update(b["bits"], b["scores"], b["pred_classes"], pack_masks(gt_dev), gt_cls, crowd)
+
+    def host_dets(i):
+        masks, sc, cl = i.pred_masks.cpu().numpy() > 0.5, i.scores.cpu().numpy(), i.pred_classes.cpu().numpy()
+        return [{"id": t + 1, "category": int(cl[t]), "score": float(sc[t]), "mask": masks[t], "area": float(masks[t].sum())}
+                for t in range(len(sc))]
+
+    def parent():
+        i = postprocess(lg, mk, [image], padded, [out], cfg)[0]["instances"]
+        return R.evaluate([(host_dets(i), gts)], K, R.COCO_AREA_RNGS, (1, 10, 100))
+
+    def bits_only():
+        return instance_bits(lg, mk, [image], padded, [out], cfg)
+
+    b0 = instance_bits(lg, mk, [image], padded, [out], cfg)[0]
+    g0 = pack_masks(gt_dev)
+    t_nat, m_nat = timed_wall(native, iters)
+    t_par, m_par = timed_wall(parent, max(3, iters // 4))
+    t_bits, _ = timed_wall(bits_only, iters)
+    t_pack, _ = timed_wall(lambda: pack_masks(gt_dev), iters)
+    t_upd, _ = timed_wall(lambda: ap.update(b0["bits"], b0["scores"], b0["pred_classes"], g0, gt_cls, crowd), iters)
+    ap.reset()
+    native()
+    got = ap.stats()
+    dts = host_dets(ins)
+    want = R.expected_stats([(dts, gts)], K, R.COCO_AREA_RNGS, (1, 10, 100))
+    same = got["scores"].tobytes() == want["scores"].tobytes() and all(np.array_equal(got[k], want[k])
+                                                                        for k in ("category", "rank", "matched", "ignored", "npig"))
+    print(json.dumps({"case": name, "row": "ap", "detections": T, "ground_truths": n_gt, "native_us": round(t_nat, 1),
+                      "parent_us": round(t_par, 1), "speedup": round(t_par / t_nat, 2), "native_slower": bool(t_nat > t_par),
+                      "instance_bits_us": round(t_bits, 1), "pack_masks_us": round(t_pack, 1), "ap_update_us": round(t_upd, 1),
+                      "native_peak_MB": round(m_nat, 1), "parent_peak_MB": round(m_par, 1), "native_host_bytes": 0,
+                      "parent_host_bytes": 4 * T * H * W, "records_equal_to_restatement": bool(same),
+                      "matched_at_0.5": int(want["matched"][:, 0, 0].sum())}), flush=True)
+
+
 def work(K, cfg, hw, out, Q=100, T=100):
     """(bytes, flop) the native route must move / compute: the logits once per kernel that reads them, the results once."""
     H, W = out
@@ -313,6 +377,8 @@ def main():
             tta_rows(name, args.iters, dev)
         if "pq" in kinds and name == "coco_panoptic_k133":
             pq_rows(name, K, hw, padded, image, out, args.iters, dev)
+        if "ap" in kinds and name == "coco_instance_k80":
+            ap_rows(name, K, hw, padded, image, out, args.iters, dev)
         if "eval" in kinds:
             eval_rows(name, K, hw, padded, image, out, args.iters, dev)
         if "base" not in kinds:
