@@ -11,8 +11,9 @@
 //
 //   seg_softmax_kernel      softmax of the [Q, K+1] class logits -> probs [Q, K] (no-object column dropped) and the
 //                           panoptic keep list (label != K and score > threshold), compacted in query order.
-//   seg_semantic_kernel     sem_seg[c, p] = sum_q probs[q, c] * sigmoid(m_q(p)), fp32: a tile of 128 pixels x <= 192
-//                           classes per workgroup, the sigmoids of 32 queries at a time staged in LDS.
+//   seg_product             sem_seg[c, p] = sum_q probs[q, c] * sigmoid(m_q(p)), fp32: a tile of 128 pixels x <= 192
+//                           classes per workgroup, the sigmoids of 32 queries at a time staged in LDS.  ONE body with two
+//                           epilogues: "put" (seg_semantic_kernel: the scores stored) and "argmax" (seg_labels_kernel, below).
 //   seg_instance_kernel     per (selected entry, 1024-pixel tile): either the partial sums of sigmoid(m) * [m > 0] and
 //                           [m > 0] (workspace, no atomics) or the 0/1 mask of the entry.
 //   seg_instance_reduce     the partials of one entry summed in a fixed order: bitwise deterministic scores.
@@ -38,6 +39,7 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "mpf_common.h"
 
@@ -79,9 +81,16 @@ struct PixGeom {
     float w1[2][2][4];
     float w2y[2], w2x[2];
 };
-__device__ __forceinline__ void pix_geom(PixGeom& g, int y, int x, int h, int w, int Hp, int Wp, int hi, int wi, int H, int W)
+// One view: Q logit planes [h, w] (stride_q elements apart) of a padded [Hp, Wp] grid whose [hi, wi] crop is the image, resized to
+// the [H, W] output.  check_geom fills it; every per-pixel kernel takes it by value.
+struct SegGeom {
+    int64_t stride_q;
+    int Q, h, w, Hp, Wp, hi, wi, H, W;
+};
+__device__ __forceinline__ void pix_geom(PixGeom& g, int y, int x, const SegGeom& s)
 {
-    const Tap ty = tap(y, hi, H), tx = tap(x, wi, W);
+    const int h = s.h, w = s.w, Hp = s.Hp, Wp = s.Wp;
+    const Tap ty = tap(y, s.hi, s.H), tx = tap(x, s.wi, s.W);
     g.w2y[0] = ty.l0; g.w2y[1] = ty.l1;
     g.w2x[0] = tx.l0; g.w2x[1] = tx.l1;
     const int ya[2] = {ty.i0, ty.i1}, xa[2] = {tx.i0, tx.i1};
@@ -181,80 +190,168 @@ __global__ __launch_bounds__(kT) void seg_softmax_kernel(const float* __restrict
     }
 }
 
+// ---- the staging of the semantic product, shared by seg_product and seg_tta_accumulate_kernel: per round of kSemQ queries the
+// sigmoids of the workgroup's kSemPix pixels and the probabilities of its class chunk go to LDS (ROW: the caller's row stride) ----
+// geometry of the staging pixel of this thread (pixel tid & 127 of the tile at p0) -> whether the pixel lies in the plane
+__device__ __forceinline__ bool stage_pixel(PixGeom& g, int64_t p0, const SegGeom& s)
+{
+    const int64_t pix = p0 + (threadIdx.x & (kSemPix - 1));
+    const bool live = pix < (int64_t)s.H * s.W;
+    pix_geom(g, live ? (int)(pix / s.W) : 0, live ? (int)(pix % s.W) : 0, s);
+    return live;
+}
+
+// sig[i * ROW + pixel] = sigmoid(m_{q0 + i}(pixel)), thread = (pixel tid & 127, queries tid >> 7 + 2 i); padding queries (i >= nq)
+// and pixels past the plane contribute 0 (their probabilities are 0 too)
+template <int ROW, typename T>
+__device__ __forceinline__ void stage_sigmoids(float* sig, const T* __restrict__ masks, int64_t stride_q, const PixGeom& g, bool live, int q0,
+                                               int nq)
+{
+    const int sp = threadIdx.x & (kSemPix - 1);
+    for (int i = threadIdx.x >> 7; i < kSemQ; i += kT / kSemPix) {
+        float v = 0.f;
+        if (i < nq && live) v = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
+        sig[i * ROW + sp] = v;
+    }
+}
+
+// pr[i * ROW + c] = probs[q0 + i][cbase + c] for the KC classes of the chunk, 0 past nq and past K (dense rows: the flat index,
+// which the compiler does not recover from i and c)
+template <int KC, int ROW>
+__device__ __forceinline__ void stage_probs(float* pr, const float* __restrict__ probs, int K, int cbase, int q0, int nq)
+{
+    for (int e = threadIdx.x; e < kSemQ * KC; e += kT) {
+        const int i = e / KC, c = e % KC;
+        pr[ROW == KC ? e : i * ROW + c] = (i < nq && cbase + c < K) ? probs[(int64_t)(q0 + i) * K + cbase + c] : 0.f;
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------
-// semantic: out[c, p] = sum_q probs[q, c] * sigmoid(m_q(p)) for a tile of kSemPix pixels and 8 * CPT classes
-// thread (pg = tid & 31, cg = tid >> 5): pixels pg*4 .. +3, classes cbase + cg*CPT .. +CPT-1
+// the semantic product: score[c, p] = sum_q probs[q, c] * sigmoid(m_q(p)) for a tile of kSemPix pixels and chunks of 8 * CPT classes
+// thread (pg = tid & 31, cg = tid >> 5): pixels pg*4 .. +3, classes cbase + cg*CPT .. +CPT-1.  Per chunk the sigmoids of kSemQ
+// queries at a time and their probabilities are staged in LDS, and every (class, pixel) is one fmaf chain in query order: the
+// scores have the same bits whatever becomes of them.  The whole body is one inlined function (a helper that took the accumulators
+// by reference cost registers and scratch); the two kernels below are its instantiations.
+//   put (Argmax false):  the chunk blockIdx.y is stored to out [K, H, W], four pixels of a class per thread
+//   argmax (Argmax true): one workgroup owns ALL classes of its pixels and walks the chunks in a loop (the sigmoids are recomputed
+//                        per chunk: K <= 192, every shipped config, is one chunk).  Each thread keeps a running (best, index) per
+//                        pixel over its own classes (ascending, strict ">": the lowest index wins a tie); the 8 class groups of a
+//                        pixel meet once at the end through LDS: labels[p] = argmax_c of the scores "put" would write
 // ----------------------------------------------------------------------------------------------------------------
-template <typename T, int CPT>
-__global__ __launch_bounds__(kT) void seg_semantic_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
-                                                          int Wp, int hi, int wi, int H, int W, const float* __restrict__ probs, int K,
-                                                          float* __restrict__ out)
+template <typename T, int CPT, bool Argmax>
+__device__ __forceinline__ void seg_product(const T* __restrict__ masks, const SegGeom s, const float* __restrict__ probs, int K,
+                                            float* __restrict__ out, int* __restrict__ labels)
 {
     constexpr int KC = 8 * CPT;
     __shared__ float4 sig4[kSemQ][kSemPix / 4];
     __shared__ float4 pr4[kSemQ][KC / 4];
+    static_assert(2 * (kT / 32) <= kSemQ, "the final reduction of the argmax reuses the sigmoid staging");
     const int tid = threadIdx.x;
-    const int64_t HW = (int64_t)H * W;
+    const int Q = s.Q;
+    const int64_t HW = (int64_t)s.H * s.W;
     const int64_t p0 = (int64_t)blockIdx.x * kSemPix;
-    const int cbase = blockIdx.y * KC;
-    // geometry of the staging pixel of this thread (pixel tid & 127, queries tid >> 7 + 2 i)
-    const int sp = tid & (kSemPix - 1), sq = tid >> 7;
-    const int64_t pix = p0 + sp;
-    const bool live = pix < HW;
     PixGeom g;
-    pix_geom(g, live ? (int)(pix / W) : 0, live ? (int)(pix % W) : 0, h, w, Hp, Wp, hi, wi, H, W);
+    const bool live = stage_pixel(g, p0, s);
     float* sig = (float*)sig4;
     float* pr = (float*)pr4;
     const int pg = tid & 31, cg = tid >> 5;
-    float acc[CPT][4];
+    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int bidx[4] = {K, K, K, K};
+    for (int cbase = Argmax ? 0 : blockIdx.y * KC; cbase < K; cbase += KC) {
+        float acc[CPT][4];
 #pragma unroll
-    for (int j = 0; j < CPT; ++j)
+        for (int j = 0; j < CPT; ++j)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
-    for (int q0 = 0; q0 < Q; q0 += kSemQ) {
-        const int nq = min(kSemQ, Q - q0);
-        __syncthreads();
-        for (int i = sq; i < kSemQ; i += kT / kSemPix) {
-            float s = 0.f;                                     // padding queries contribute 0 (their probs are 0 too)
-            if (i < nq && live) s = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
-            sig[i * kSemPix + sp] = s;
-        }
-        for (int e = tid; e < kSemQ * KC; e += kT) {
-            const int i = e / KC, c = e % KC;
-            pr[e] = (i < nq && cbase + c < K) ? probs[(int64_t)(q0 + i) * K + cbase + c] : 0.f;
-        }
-        __syncthreads();
-        for (int i = 0; i < nq; ++i) {
-            const float4 s = sig4[i][pg];
+            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+        for (int q0 = 0; q0 < Q; q0 += kSemQ) {
+            const int nq = min(kSemQ, Q - q0);
+            __syncthreads();
+            stage_sigmoids<kSemPix>(sig, masks, s.stride_q, g, live, q0, nq);
+            stage_probs<KC, KC>(pr, probs, K, cbase, q0, nq);
+            __syncthreads();
+            for (int i = 0; i < nq; ++i) {
+                const float4 sv = sig4[i][pg];
 #pragma unroll
-            for (int j4 = 0; j4 < CPT / 4; ++j4) {
-                const float4 pv = pr4[i][cg * (CPT / 4) + j4];
-                const float pj[4] = {pv.x, pv.y, pv.z, pv.w};
+                for (int j4 = 0; j4 < CPT / 4; ++j4) {
+                    const float4 pv = pr4[i][cg * (CPT / 4) + j4];
+                    const float pj[4] = {pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    float* a = acc[j4 * 4 + u];
-                    a[0] = fmaf(pj[u], s.x, a[0]);
-                    a[1] = fmaf(pj[u], s.y, a[1]);
-                    a[2] = fmaf(pj[u], s.z, a[2]);
-                    a[3] = fmaf(pj[u], s.w, a[3]);
+                    for (int u = 0; u < 4; ++u) {
+                        float* a = acc[j4 * 4 + u];
+                        a[0] = fmaf(pj[u], sv.x, a[0]);
+                        a[1] = fmaf(pj[u], sv.y, a[1]);
+                        a[2] = fmaf(pj[u], sv.z, a[2]);
+                        a[3] = fmaf(pj[u], sv.w, a[3]);
+                    }
                 }
             }
         }
-    }
-    const int64_t px = p0 + pg * 4;
+        if constexpr (Argmax) {
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-        const int c = cbase + cg * CPT + j;
-        if (c >= K) break;
-        float* o = out + (int64_t)c * HW + px;
-        if (px + 3 < HW && ((HW & 3) == 0)) {
-            *(float4*)o = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+            for (int j = 0; j < CPT; ++j) {
+                const int c = cbase + cg * CPT + j;
+                if (c < K) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (acc[j][i] > best[i]) { best[i] = acc[j][i]; bidx[i] = c; }
+                }
+            }
         } else {
+            const int64_t px = p0 + pg * 4;
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (px + i < HW) o[i] = acc[j][i];
+            for (int j = 0; j < CPT; ++j) {
+                const int c = cbase + cg * CPT + j;
+                if (c >= K) break;
+                float* o = out + (int64_t)c * HW + px;
+                if (px + 3 < HW && ((HW & 3) == 0)) {
+                    *(float4*)o = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (px + i < HW) o[i] = acc[j][i];
+                }
+            }
+            return;                                             // one chunk per workgroup
         }
     }
+    if constexpr (Argmax) {
+        // the 8 class groups of a pixel meet in the staging buffer (no LDS beyond the put form's: same occupancy)
+        float (*red_v)[kSemPix] = (float (*)[kSemPix])sig;
+        int (*red_i)[kSemPix] = (int (*)[kSemPix])(sig + (kT / 32) * kSemPix);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            red_v[cg][pg * 4 + i] = best[i];
+            red_i[cg][pg * 4 + i] = bidx[i];
+        }
+        __syncthreads();
+        if (tid < kSemPix && p0 + tid < HW) {
+            float b = red_v[0][tid];
+            int bi = red_i[0][tid];
+#pragma unroll
+            for (int c = 1; c < kT / 32; ++c) {
+                const float v = red_v[c][tid];
+                const int vi = red_i[c][tid];
+                if (v > b || (v == b && vi < bi)) { b = v; bi = vi; }
+            }
+            labels[p0 + tid] = bi;
+        }
+    }
+}
+
+template <typename T, int CPT>
+__global__ __launch_bounds__(kT) void seg_semantic_kernel(const T* __restrict__ masks, const SegGeom s, const float* __restrict__ probs,
+                                                          int K, float* __restrict__ out)
+{
+    seg_product<T, CPT, false>(masks, s, probs, K, out, nullptr);
+}
+
+// (waves per SIMD: the running (best, index) pairs must not cost the small tiles the occupancy seg_semantic_kernel has there)
+template <typename T, int CPT>
+__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(CPT <= 4 ? 4 : CPT <= 12 ? 3 : 2))) void seg_labels_kernel(
+    const T* __restrict__ masks, const SegGeom s, const float* __restrict__ probs, int K, int* __restrict__ labels)
+{
+    seg_product<T, CPT, true>(masks, s, probs, K, nullptr, labels);
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -263,20 +360,20 @@ __global__ __launch_bounds__(kT) void seg_semantic_kernel(const T* __restrict__ 
 //   else:              masks_out[t][p] = m > 0 ? 1 : 0
 // ----------------------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(kT) void seg_instance_kernel(const T* __restrict__ masks, int64_t stride_q, int h, int w, int Hp, int Wp,
-                                                          int hi, int wi, int H, int W, const int64_t* __restrict__ sel_q,
+__global__ __launch_bounds__(kT) void seg_instance_kernel(const T* __restrict__ masks, const SegGeom sg, const int64_t* __restrict__ sel_q,
                                                           float* __restrict__ masks_out, float2* __restrict__ partial)
 {
     const int t = blockIdx.y;
-    const int64_t HW = (int64_t)H * W;
-    const T* m = masks + sel_q[t] * stride_q;
+    const int W = sg.W;
+    const int64_t HW = (int64_t)sg.H * W;
+    const T* m = masks + sel_q[t] * sg.stride_q;
     float s = 0.f, n = 0.f;
 #pragma unroll
     for (int i = 0; i < kInstPix / kT; ++i) {
         const int64_t p = (int64_t)blockIdx.x * kInstPix + threadIdx.x + kT * i;
         if (p >= HW) break;
         PixGeom g;
-        pix_geom(g, (int)(p / W), (int)(p % W), h, w, Hp, Wp, hi, wi, H, W);
+        pix_geom(g, (int)(p / W), (int)(p % W), sg);
         const float v = resample(m, g);
         const bool on = v > 0.f;
         if (masks_out) {
@@ -328,8 +425,7 @@ __global__ __launch_bounds__(kT) void seg_instance_reduce_kernel(const float2* _
 //   code[p] = 2 * winner + (sigmoid(m_winner) >= 0.5);  areas [3][Q]: mask_area, original_area, intersection
 // ----------------------------------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(kT) void seg_panoptic_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
-                                                          int Wp, int hi, int wi, int H, int W, const int* __restrict__ kept,
+__global__ __launch_bounds__(kT) void seg_panoptic_kernel(const T* __restrict__ masks, const SegGeom s, const int* __restrict__ kept,
                                                           const float* __restrict__ kept_score, int* __restrict__ code,
                                                           int* __restrict__ areas)
 {
@@ -343,15 +439,16 @@ __global__ __launch_bounds__(kT) void seg_panoptic_kernel(const T* __restrict__ 
         ks[i] = kept_score[i];
     }
     __syncthreads();
-    const int64_t HW = (int64_t)H * W;
+    const int W = s.W;
+    const int64_t HW = (int64_t)s.H * W;
     const int64_t p = (int64_t)blockIdx.x * kT + threadIdx.x;
     if (p < HW) {
         PixGeom g;
-        pix_geom(g, (int)(p / W), (int)(p % W), h, w, Hp, Wp, hi, wi, H, W);
+        pix_geom(g, (int)(p / W), (int)(p % W), s);
         float best = -1.f;
         int win = 0, bit = 0;
         for (int n = 0; n < count; ++n) {
-            const float sg = sigm(resample(masks + (int64_t)kq[n] * stride_q, g));
+            const float sg = sigm(resample(masks + (int64_t)kq[n] * s.stride_q, g));
             const float pr = ks[n] * sg;
             const int on = sg >= 0.5f;
             const unsigned long long b = __ballot(on);         // n is wave-uniform: one LDS atomic per wave, not per lane
@@ -368,7 +465,7 @@ __global__ __launch_bounds__(kT) void seg_panoptic_kernel(const T* __restrict__ 
     for (int i = threadIdx.x; i < count; i += kT)
 #pragma unroll
         for (int a = 0; a < 3; ++a)
-            if (hist[a][i]) atomicAdd(&areas[a * Q + i], hist[a][i]);
+            if (hist[a][i]) atomicAdd(&areas[a * s.Q + i], hist[a][i]);
 }
 
 // kernel 2: id map; lut[n] = segment id of kept entry n (0 = dropped)
@@ -379,105 +476,6 @@ __global__ __launch_bounds__(kT) void seg_paint_kernel(const int* __restrict__ c
     if (p >= HW) return;
     const int c = code[p];
     out[p] = (c & 1) ? lut[c >> 1] : 0;
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// semantic labels: argmax_c of the scores seg_semantic_kernel would write, without writing them.  One workgroup owns a tile of
-// kSemPix pixels and ALL classes: it walks the class chunks of 8 * CPT in a loop, with the same staging, the same q order and the
-// same fmaf chain per (class, pixel) as seg_semantic_kernel, so every score has the same bits.  Each thread keeps a running
-// (best, index) per pixel over its own classes (ascending, strict ">": the lowest index wins a tie); the 8 class groups of a pixel
-// meet once at the end through LDS.  The sigmoids are recomputed per chunk: K <= 192 (every shipped config) is one chunk.
-// ----------------------------------------------------------------------------------------------------------------
-// (waves per SIMD: the running (best, index) pairs must not cost the small tiles the occupancy seg_semantic_kernel has there)
-template <typename T, int CPT>
-__global__ __launch_bounds__(kT) __attribute__((amdgpu_waves_per_eu(CPT <= 4 ? 4 : CPT <= 12 ? 3 : 2))) void seg_labels_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
-                                                        int Wp, int hi, int wi, int H, int W, const float* __restrict__ probs, int K,
-                                                        int* __restrict__ labels)
-{
-    constexpr int KC = 8 * CPT;
-    __shared__ float4 sig4[kSemQ][kSemPix / 4];
-    __shared__ float4 pr4[kSemQ][KC / 4];
-    static_assert(2 * (kT / 32) <= kSemQ, "the final reduction reuses the sigmoid staging");
-    const int tid = threadIdx.x;
-    const int64_t HW = (int64_t)H * W;
-    const int64_t p0 = (int64_t)blockIdx.x * kSemPix;
-    const int sp = tid & (kSemPix - 1), sq = tid >> 7;
-    const int64_t pix = p0 + sp;
-    const bool live = pix < HW;
-    PixGeom g;
-    pix_geom(g, live ? (int)(pix / W) : 0, live ? (int)(pix % W) : 0, h, w, Hp, Wp, hi, wi, H, W);
-    float* sig = (float*)sig4;
-    float* pr = (float*)pr4;
-    const int pg = tid & 31, cg = tid >> 5;
-    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int bidx[4] = {K, K, K, K};
-    for (int cbase = 0; cbase < K; cbase += KC) {
-        float acc[CPT][4];
-#pragma unroll
-        for (int j = 0; j < CPT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
-        for (int q0 = 0; q0 < Q; q0 += kSemQ) {
-            const int nq = min(kSemQ, Q - q0);
-            __syncthreads();
-            for (int i = sq; i < kSemQ; i += kT / kSemPix) {
-                float s = 0.f;
-                if (i < nq && live) s = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
-                sig[i * kSemPix + sp] = s;
-            }
-            for (int e = tid; e < kSemQ * KC; e += kT) {
-                const int i = e / KC, c = e % KC;
-                pr[e] = (i < nq && cbase + c < K) ? probs[(int64_t)(q0 + i) * K + cbase + c] : 0.f;
-            }
-            __syncthreads();
-            for (int i = 0; i < nq; ++i) {
-                const float4 s = sig4[i][pg];
-#pragma unroll
-                for (int j4 = 0; j4 < CPT / 4; ++j4) {
-                    const float4 pv = pr4[i][cg * (CPT / 4) + j4];
-                    const float pj[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        float* a = acc[j4 * 4 + u];
-                        a[0] = fmaf(pj[u], s.x, a[0]);
-                        a[1] = fmaf(pj[u], s.y, a[1]);
-                        a[2] = fmaf(pj[u], s.z, a[2]);
-                        a[3] = fmaf(pj[u], s.w, a[3]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < CPT; ++j) {
-            const int c = cbase + cg * CPT + j;
-            if (c < K) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (acc[j][i] > best[i]) { best[i] = acc[j][i]; bidx[i] = c; }
-            }
-        }
-    }
-    // the 8 class groups of a pixel meet in the staging buffer (same LDS as seg_semantic_kernel: same occupancy)
-    float (*red_v)[kSemPix] = (float (*)[kSemPix])sig;
-    int (*red_i)[kSemPix] = (int (*)[kSemPix])(sig + (kT / 32) * kSemPix);
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        red_v[cg][pg * 4 + i] = best[i];
-        red_i[cg][pg * 4 + i] = bidx[i];
-    }
-    __syncthreads();
-    if (tid < kSemPix && p0 + tid < HW) {
-        float b = red_v[0][tid];
-        int bi = red_i[0][tid];
-#pragma unroll
-        for (int c = 1; c < kT / 32; ++c) {
-            const float v = red_v[c][tid];
-            const int vi = red_i[c][tid];
-            if (v > b || (v == b && vi < bi)) { b = v; bi = vi; }
-        }
-        labels[p0 + tid] = bi;
-    }
 }
 
 // labels of the "after" mode: scores fp32 [K, hi, wi] (mpf_seg_semantic on the cropped grid) resized to [H, W] plane by plane with
@@ -572,20 +570,20 @@ __global__ __launch_bounds__(kConfT) void seg_confusion_kernel(const int* __rest
 constexpr int kRleWords = kT;      // words (64 positions each) per tile of the count / scatter kernels
 
 template <typename T>
-__global__ __launch_bounds__(kT) void seg_rle_bits_kernel(const T* __restrict__ masks, int64_t stride_q, int h, int w, int Hp, int Wp,
-                                                          int hi, int wi, int H, int W, const int64_t* __restrict__ sel_q,
+__global__ __launch_bounds__(kT) void seg_rle_bits_kernel(const T* __restrict__ masks, const SegGeom s, const int64_t* __restrict__ sel_q,
                                                           int64_t nwords, unsigned long long* __restrict__ bits)
 {
     const int t = blockIdx.y;
-    const int64_t HW = (int64_t)H * W;
-    const T* m = masks + sel_q[t] * stride_q;
+    const int H = s.H;
+    const int64_t HW = (int64_t)H * s.W;
+    const T* m = masks + sel_q[t] * s.stride_q;
 #pragma unroll
     for (int i = 0; i < kInstPix / kT; ++i) {
         const int64_t p = (int64_t)blockIdx.x * kInstPix + threadIdx.x + kT * i;    // wave-aligned: a wave covers one word
         bool on = false;
         if (p < HW) {
             PixGeom g;
-            pix_geom(g, (int)(p % H), (int)(p / H), h, w, Hp, Wp, hi, wi, H, W);
+            pix_geom(g, (int)(p % H), (int)(p / H), s);
             on = resample(m, g) > 0.f;
         }
         const unsigned long long b = __ballot(on);
@@ -702,7 +700,7 @@ __global__ __launch_bounds__(kT) void seg_rle_diff_kernel(const unsigned* __rest
 // ----------------------------------------------------------------------------------------------------------------
 // semantic test-time augmentation (mask2former/test_time_augmentation.py:71-98): acc[K, H, W] = sum over the views of the view's
 // "sem_seg", flipped back along W where the view was flipped, then one division by the number of views.
-//   seg_tta_accumulate_kernel   one view straight from its logits: the product of seg_semantic_kernel on the fp32 matrix cores,
+//   seg_tta_accumulate_kernel   one view straight from its logits: the product of seg_product on the fp32 matrix cores,
 //                               stored or added into acc, plain or mirrored
 //   seg_tta_resize_add_kernel   "after" mode: the view's [K, hi, wi] scores resized plane by plane, stored or added into acc
 //   seg_tta_finish_kernel       acc /= V in place, or labels = argmax_c(acc[c] / V) with acc left alone
@@ -759,18 +757,18 @@ __device__ __forceinline__ void tta_put4(float* __restrict__ plane, int64_t px, 
     }
 }
 
-// A workgroup owns kSemPix pixels x 16 * MT classes (blockIdx.y: the class chunk).  The sigmoids of kSemQ queries are staged exactly
-// as in seg_semantic_kernel; the product probs^T [classes x Q] * sig [Q x pixels] runs on v_mfma_f32_16x16x4_f32 with the classes on
+// A workgroup owns kSemPix pixels x 16 * MT classes (blockIdx.y: the class chunk).  The sigmoids of kSemQ queries are staged by
+// the helpers of seg_product; the product probs^T [classes x Q] * sig [Q x pixels] runs on v_mfma_f32_16x16x4_f32 with the classes on
 // the A rows and the pixels on the B columns (lane l: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15]; C/D col = l & 15,
 // row = 4 * (l >> 4) + reg).  Wave wv owns pixels 32 wv .. + 31 (two column tiles) and every class tile: 2 * MT independent
 // accumulators, k ascending in query order, so each score is the fmaf chain of seg_semantic_kernel (queries past Q and classes
 // past K enter as zeros).  Epilogue: one class tile at a time through LDS, so that a lane leaves with four consecutive pixels of a
 // class and eight lanes cover the 128 bytes of the wave's pixels.
 template <typename T, int MT>
-__global__ __launch_bounds__(kT) void seg_tta_accumulate_kernel(const T* __restrict__ masks, int64_t stride_q, int Q, int h, int w, int Hp,
-                                                                int Wp, int hi, int wi, int H, int W, const float* __restrict__ probs,
+__global__ __launch_bounds__(kT) void seg_tta_accumulate_kernel(const T* __restrict__ masks, const SegGeom s, const float* __restrict__ probs,
                                                                 int K, int mode, int vec, float* __restrict__ acc)
 {
+    const int Q = s.Q, W = s.W;
     constexpr int KC = 16 * MT;
     constexpr int PR = KC + kTtaPad;
     __shared__ float4 sig4[kSemQ * kTtaSigRow / 4];
@@ -778,14 +776,11 @@ __global__ __launch_bounds__(kT) void seg_tta_accumulate_kernel(const T* __restr
     static_assert((kT / 64) * 16 * kTtaOutRow <= kSemQ * kTtaSigRow, "the epilogue staging reuses the sigmoid staging");
     float* sig = (float*)sig4;
     const int tid = threadIdx.x;
-    const int64_t HW = (int64_t)H * W;
+    const int64_t HW = (int64_t)s.H * W;
     const int64_t p0 = (int64_t)blockIdx.x * kSemPix;
     const int cbase = blockIdx.y * KC;
-    const int sp = tid & (kSemPix - 1), sq = tid >> 7;
-    const int64_t pix = p0 + sp;
-    const bool live = pix < HW;
     PixGeom g;
-    pix_geom(g, live ? (int)(pix / W) : 0, live ? (int)(pix % W) : 0, h, w, Hp, Wp, hi, wi, H, W);
+    const bool live = stage_pixel(g, p0, s);
     const int lane = tid & 63, wv = tid >> 6;
     const int lr = lane & 15, lk = lane >> 4;
     f32x4 c[MT][2];
@@ -794,15 +789,8 @@ __global__ __launch_bounds__(kT) void seg_tta_accumulate_kernel(const T* __restr
     for (int q0 = 0; q0 < Q; q0 += kSemQ) {
         const int nq = min(kSemQ, Q - q0);
         __syncthreads();
-        for (int i = sq; i < kSemQ; i += kT / kSemPix) {
-            float s = 0.f;
-            if (i < nq && live) s = sigm(resample(masks + (int64_t)(q0 + i) * stride_q, g));
-            sig[i * kTtaSigRow + sp] = s;
-        }
-        for (int e = tid; e < kSemQ * KC; e += kT) {
-            const int i = e / KC, cc = e % KC;
-            pr[i * PR + cc] = (i < nq && cbase + cc < K) ? probs[(int64_t)(q0 + i) * K + cbase + cc] : 0.f;
-        }
+        stage_sigmoids<kTtaSigRow>(sig, masks, s.stride_q, g, live, q0, nq);
+        stage_probs<KC, PR>(pr, probs, K, cbase, q0, nq);
         __syncthreads();
         const int ksteps = (nq + 3) >> 2;                    // rows nq .. kSemQ - 1 are staged as zeros
         for (int ks = 0; ks < ksteps; ++ks) {
@@ -901,24 +889,111 @@ __global__ __launch_bounds__(kT) void seg_tta_finish_kernel(float* __restrict__ 
     }
 }
 
-// shared argument checks of the per-pixel entry points
-int check_geom(const char* who, const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
-               int H, int W)
+// ---- host side: argument checks and launches that several entry points share -------------------------------------------------------
+// records "<who>: <what>" as the error (who = the entry point without its mpf_ prefix, as in every message of this file)
+int fail_who(int code, const char* who, const char* what)
 {
-    static thread_local char msg[160];
-    if (!masks) { snprintf(msg, sizeof msg, "%s: NULL mask logits", who); return mpf::fail(MPF_E_NULL, msg); }
-    if (dtype != MPF_F32 && dtype != MPF_BF16) { snprintf(msg, sizeof msg, "%s: mask logits must be f32 or bf16 (dtype)", who); return mpf::fail(MPF_E_DTYPE, msg); }
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return mpf::fail(code, msg);
+}
+
+// the twelve leading arguments of the per-pixel entry points, checked and gathered into g
+int check_geom(const char* who, const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
+               int H, int W, SegGeom& g)
+{
+    if (!masks) return fail_who(MPF_E_NULL, who, "NULL mask logits");
+    if (dtype != MPF_F32 && dtype != MPF_BF16) return fail_who(MPF_E_DTYPE, who, "mask logits must be f32 or bf16 (dtype)");
     if (Q <= 0 || h <= 0 || w <= 0 || Hp <= 0 || Wp <= 0 || hi <= 0 || wi <= 0 || H <= 0 || W <= 0 || hi > Hp || wi > Wp ||
         stride_q < (int64_t)h * w) {
-        snprintf(msg, sizeof msg, "%s: bad sizes (Q %d, low-res %dx%d, padded %dx%d, image %dx%d, output %dx%d, stride_q %lld)", who, Q, h,
-                 w, Hp, Wp, hi, wi, H, W, (long long)stride_q);
-        return mpf::fail(MPF_E_SHAPE, msg);
+        char what[160];
+        snprintf(what, sizeof what, "bad sizes (Q %d, low-res %dx%d, padded %dx%d, image %dx%d, output %dx%d, stride_q %lld)", Q, h, w, Hp,
+                 Wp, hi, wi, H, W, (long long)stride_q);
+        return fail_who(MPF_E_SHAPE, who, what);
     }
-    if ((int64_t)H * W >= (1ll << 31) || (int64_t)Q * stride_q >= (1ll << 40)) {
-        snprintf(msg, sizeof msg, "%s: output too large", who);
-        return mpf::fail(MPF_E_TOO_LARGE, msg);
-    }
+    if ((int64_t)H * W >= (1ll << 31) || (int64_t)Q * stride_q >= (1ll << 40)) return fail_who(MPF_E_TOO_LARGE, who, "output too large");
+    g = SegGeom{stride_q, Q, h, w, Hp, Wp, hi, wi, H, W};
     return 0;
+}
+
+// the entries of an instance route are blockIdx.y of its kernels
+int check_entries(const char* who, int T)
+{
+    return T <= 0 || T > 65535 ? fail_who(MPF_E_SHAPE, who, "need 1 <= T <= 65535 entries") : 0;
+}
+
+int check_tta_mode(const char* who, int mode)
+{
+    if (!(mode & ~3)) return 0;
+    char what[96];
+    snprintf(what, sizeof what, "mode has bit 0 (add) and bit 1 (hflip) only, got %d", mode);
+    return fail_who(MPF_E_SHAPE, who, what);
+}
+
+// the float4 form of tta_put4: whole rows of four (mirrored: W itself) and 16-byte aligned planes
+int tta_vec(const float* acc, int H, int W, int mode)
+{
+    const int64_t HW = (int64_t)H * W;
+    return ((uintptr_t)acc & 15) == 0 && (HW & 3) == 0 && (!(mode & 2) || (W & 3) == 0);
+}
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// bytes of n [h, w] planes of mask logits: what a per-pixel kernel reads
+double logit_bytes(double n, const SegGeom& g, int dtype) { return n * g.h * g.w * (dtype == MPF_F32 ? 4 : 2); }
+
+// f(masks as const T*) with T = the type of the mask logits; elem_t<decltype(pointer)> names T inside f
+template <typename F>
+void with_mask_type(int dtype, const void* masks, F&& f)
+{
+    if (dtype == MPF_F32) f((const float*)masks);
+    else f((const __hip_bfloat16*)masks);
+}
+template <typename P>
+using elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: a run-time tile count to a template argument
+template <int... Vs, typename F>
+void with_int(int v, F&& f)
+{
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// seg_product: labels != NULL -> the argmax epilogue, else the scores stored to out
+void launch_product(const void* masks, int dtype, const SegGeom& g, const float* probs, int K, float* out, int* labels, hipStream_t st)
+{
+    const unsigned tiles = (unsigned)ceil_div((int64_t)g.H * g.W, kSemPix);
+    with_mask_type(dtype, masks, [&](auto* m) {
+        using T = elem_t<decltype(m)>;
+        // classes per thread: chunks of 8 * C = 32, 64, 96 or 192 classes (K > 192: several chunks, on blockIdx.y or in the argmax loop)
+        with_int<4, 8, 12, 24>(K <= 32 ? 4 : K <= 64 ? 8 : K <= 96 ? 12 : 24, [&](auto cpt) {
+            constexpr int C = decltype(cpt)::value;
+            if (labels)
+                hipLaunchKernelGGL((seg_labels_kernel<T, C>), dim3(tiles), dim3(kT), 0, st, m, g, probs, K, labels);
+            else
+                hipLaunchKernelGGL((seg_semantic_kernel<T, C>), dim3(tiles, (unsigned)ceil_div(K, 8 * C)), dim3(kT), 0, st, m, g, probs, K, out);
+        });
+    });
+}
+
+// seg_instance_kernel over T entries: the partial sums of their scores (masks_out NULL) or their 0/1 masks
+void launch_instance(const void* masks, int dtype, const SegGeom& g, const int64_t* sel_q, int T, float* masks_out, float2* partial,
+                     hipStream_t st)
+{
+    const dim3 grid((unsigned)ceil_div((int64_t)g.H * g.W, kInstPix), (unsigned)T);
+    with_mask_type(dtype, masks, [&](auto* m) {
+        hipLaunchKernelGGL(seg_instance_kernel<elem_t<decltype(m)>>, grid, dim3(kT), 0, st, m, g, sel_q, masks_out, partial);
+    });
+}
+
+// seg_rle_bits_kernel over T entries into bits [T, nwords]
+void launch_rle_bits(const void* masks, int dtype, const SegGeom& g, const int64_t* sel_q, int T, int64_t nwords, unsigned long long* bits,
+                     hipStream_t st)
+{
+    const dim3 grid((unsigned)ceil_div((int64_t)g.H * g.W, kInstPix), (unsigned)T);
+    with_mask_type(dtype, masks, [&](auto* m) {
+        hipLaunchKernelGGL(seg_rle_bits_kernel<elem_t<decltype(m)>>, grid, dim3(kT), 0, st, m, g, sel_q, nwords, bits);
+    });
 }
 
 }  // namespace
@@ -940,84 +1015,58 @@ extern "C" int mpf_seg_softmax(const float* cls, int Q, int K1, float object_mas
 extern "C" int mpf_seg_semantic(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
                                 int H, int W, const float* probs, int K, float* out, void* stream)
 {
-    if (int e = check_geom("seg_semantic", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_semantic", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!probs || !out) return mpf::fail(MPF_E_NULL, "seg_semantic: NULL buffer");
     if (K <= 0) return mpf::fail(MPF_E_SHAPE, "seg_semantic: K must be positive");
-    if ((int64_t)K * H * W >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "seg_semantic: output too large");
-    hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
-    const int cpt = K <= 32 ? 4 : K <= 64 ? 8 : K <= 96 ? 12 : 24;
-    const dim3 grid((unsigned)((HW + kSemPix - 1) / kSemPix), (unsigned)((K + 8 * cpt - 1) / (8 * cpt)));
+    if (K * HW >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "seg_semantic: output too large");
+    hipStream_t st = (hipStream_t)stream;
     mpf::prof_begin(st);
     mpf::set_kernel("seg_semantic_kernel");
-#define MPF_SEM(T, C)                                                                                                                \
-    hipLaunchKernelGGL((seg_semantic_kernel<T, C>), grid, dim3(kT), 0, st, (const T*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H, W, \
-                       probs, K, out)
-#define MPF_SEM_T(T)                   \
-    do {                               \
-        if (cpt == 4) MPF_SEM(T, 4);   \
-        else if (cpt == 8) MPF_SEM(T, 8);   \
-        else if (cpt == 12) MPF_SEM(T, 12); \
-        else MPF_SEM(T, 24);           \
-    } while (0)
-    if (dtype == MPF_F32) MPF_SEM_T(float);
-    else MPF_SEM_T(__hip_bfloat16);
-#undef MPF_SEM_T
-#undef MPF_SEM
-    mpf::prof_end("seg_semantic_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * K * HW, 2.0 * K * Q * (double)HW);
+    launch_product(masks, dtype, g, probs, K, out, nullptr, st);
+    mpf::prof_end("seg_semantic_kernel", st, logit_bytes(Q, g, dtype) + 4.0 * K * HW, 2.0 * K * Q * (double)HW);
     return mpf::check(hipGetLastError(), "mpf_seg_semantic");
 }
 
 extern "C" size_t mpf_seg_instance_workspace_bytes(int T, int H, int W)
 {
     if (T <= 0 || H <= 0 || W <= 0) return 0;
-    const int64_t tiles = ((int64_t)H * W + kInstPix - 1) / kInstPix;
-    return (size_t)(T * tiles) * sizeof(float2);
+    return (size_t)(T * ceil_div((int64_t)H * W, kInstPix)) * sizeof(float2);
 }
 
 extern "C" int mpf_seg_instance_scores(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi,
                                        int wi, int H, int W, const int64_t* sel_q, const float* cls_score, int T, float* scores,
                                        void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (int e = check_geom("seg_instance_scores", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_instance_scores", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!sel_q || !cls_score || !scores || !workspace) return mpf::fail(MPF_E_NULL, "seg_instance_scores: NULL buffer");
-    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_scores: need 1 <= T <= 65535 entries");
+    if (int e = check_entries("seg_instance_scores", T)) return e;
     if (workspace_bytes < mpf_seg_instance_workspace_bytes(T, H, W)) return mpf::fail(MPF_E_SHAPE, "seg_instance_scores: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W;
-    const int tiles = (int)((HW + kInstPix - 1) / kInstPix);
+    const int tiles = (int)ceil_div((int64_t)H * W, kInstPix);
     mpf::prof_begin(st);
     mpf::set_kernel("seg_instance_kernel+seg_instance_reduce_kernel");
-    if (dtype == MPF_F32)
-        hipLaunchKernelGGL(seg_instance_kernel<float>, dim3(tiles, T), dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi,
-                           H, W, sel_q, (float*)nullptr, (float2*)workspace);
-    else
-        hipLaunchKernelGGL(seg_instance_kernel<__hip_bfloat16>, dim3(tiles, T), dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h,
-                           w, Hp, Wp, hi, wi, H, W, sel_q, (float*)nullptr, (float2*)workspace);
-    hipLaunchKernelGGL(seg_instance_reduce_kernel, dim3((T + kT / 64 - 1) / (kT / 64)), dim3(kT), 0, st, (const float2*)workspace, tiles, T, cls_score,
-                       scores);
-    mpf::prof_end("seg_instance_scores", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + 8.0 * T * tiles);
+    launch_instance(masks, dtype, g, sel_q, T, nullptr, (float2*)workspace, st);
+    hipLaunchKernelGGL(seg_instance_reduce_kernel, dim3((unsigned)ceil_div(T, kT / 64)), dim3(kT), 0, st, (const float2*)workspace, tiles, T,
+                       cls_score, scores);
+    mpf::prof_end("seg_instance_scores", st, logit_bytes(T, g, dtype) + 8.0 * T * tiles);
     return mpf::check(hipGetLastError(), "mpf_seg_instance_scores");
 }
 
 extern "C" int mpf_seg_instance_masks(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi,
                                       int wi, int H, int W, const int64_t* sel_q, int T, float* masks_out, void* stream)
 {
-    if (int e = check_geom("seg_instance_masks", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_instance_masks", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!sel_q || !masks_out) return mpf::fail(MPF_E_NULL, "seg_instance_masks: NULL buffer");
-    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_masks: need 1 <= T <= 65535 entries");
+    if (int e = check_entries("seg_instance_masks", T)) return e;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W;
-    const int tiles = (int)((HW + kInstPix - 1) / kInstPix);
     mpf::prof_begin(st);
     mpf::set_kernel("seg_instance_kernel");
-    if (dtype == MPF_F32)
-        hipLaunchKernelGGL(seg_instance_kernel<float>, dim3(tiles, T), dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi,
-                           H, W, sel_q, masks_out, (float2*)nullptr);
-    else
-        hipLaunchKernelGGL(seg_instance_kernel<__hip_bfloat16>, dim3(tiles, T), dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h,
-                           w, Hp, Wp, hi, wi, H, W, sel_q, masks_out, (float2*)nullptr);
-    mpf::prof_end("seg_instance_kernel", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * T * HW);
+    launch_instance(masks, dtype, g, sel_q, T, masks_out, nullptr, st);
+    mpf::prof_end("seg_instance_kernel", st, logit_bytes(T, g, dtype) + 4.0 * T * H * W);
     return mpf::check(hipGetLastError(), "mpf_seg_instance_masks");
 }
 
@@ -1025,7 +1074,8 @@ extern "C" int mpf_seg_panoptic_areas(const void* masks, int64_t stride_q, int d
                                       int wi, int H, int W, const int* kept, const float* kept_score, int* code, int* areas,
                                       void* stream)
 {
-    if (int e = check_geom("seg_panoptic_areas", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_panoptic_areas", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!kept || !kept_score || !code || !areas) return mpf::fail(MPF_E_NULL, "seg_panoptic_areas: NULL buffer");
     if (Q > kMaxQ) return mpf::fail(MPF_E_SHAPE, "seg_panoptic_areas: at most 1024 queries");
     hipStream_t st = (hipStream_t)stream;
@@ -1033,14 +1083,11 @@ extern "C" int mpf_seg_panoptic_areas(const void* masks, int64_t stride_q, int d
     if (int e = mpf::check(hipMemsetAsync(areas, 0, 3 * (size_t)Q * sizeof(int), st), "seg_panoptic_areas: memset")) return e;
     mpf::prof_begin(st);
     mpf::set_kernel("seg_panoptic_kernel");
-    const unsigned grid = (unsigned)((HW + kT - 1) / kT);
-    if (dtype == MPF_F32)
-        hipLaunchKernelGGL(seg_panoptic_kernel<float>, dim3(grid), dim3(kT), 0, st, (const float*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H,
-                           W, kept, kept_score, code, areas);
-    else
-        hipLaunchKernelGGL(seg_panoptic_kernel<__hip_bfloat16>, dim3(grid), dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, Q, h, w,
-                           Hp, Wp, hi, wi, H, W, kept, kept_score, code, areas);
-    mpf::prof_end("seg_panoptic_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * HW);
+    with_mask_type(dtype, masks, [&](auto* m) {
+        hipLaunchKernelGGL(seg_panoptic_kernel<elem_t<decltype(m)>>, dim3((unsigned)ceil_div(HW, kT)), dim3(kT), 0, st, m, g, kept, kept_score,
+                           code, areas);
+    });
+    mpf::prof_end("seg_panoptic_kernel", st, logit_bytes(Q, g, dtype) + 4.0 * HW);
     return mpf::check(hipGetLastError(), "mpf_seg_panoptic_areas");
 }
 
@@ -1053,7 +1100,7 @@ extern "C" int mpf_seg_panoptic_paint(const int* code, int H, int W, const int* 
     const int64_t HW = (int64_t)H * W;
     mpf::prof_begin(st);
     mpf::set_kernel("seg_paint_kernel");
-    hipLaunchKernelGGL(seg_paint_kernel, dim3((unsigned)((HW + kT - 1) / kT)), dim3(kT), 0, st, code, HW, lut, out);
+    hipLaunchKernelGGL(seg_paint_kernel, dim3((unsigned)ceil_div(HW, kT)), dim3(kT), 0, st, code, HW, lut, out);
     mpf::prof_end("seg_paint_kernel", st, 8.0 * HW);
     return mpf::check(hipGetLastError(), "mpf_seg_panoptic_paint");
 }
@@ -1061,30 +1108,16 @@ extern "C" int mpf_seg_panoptic_paint(const int* code, int H, int W, const int* 
 extern "C" int mpf_seg_semantic_labels(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
                                        int H, int W, const float* probs, int K, int* labels, void* stream)
 {
-    if (int e = check_geom("seg_semantic_labels", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_semantic_labels", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!probs || !labels) return mpf::fail(MPF_E_NULL, "seg_semantic_labels: NULL buffer");
     if (K <= 0) return mpf::fail(MPF_E_SHAPE, "seg_semantic_labels: K must be positive");
     hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
-    const int cpt = K <= 32 ? 4 : K <= 64 ? 8 : K <= 96 ? 12 : 24;      // as mpf_seg_semantic; K > 192: chunks of 192 in a loop
-    const dim3 grid((unsigned)((HW + kSemPix - 1) / kSemPix));
     mpf::prof_begin(st);
     mpf::set_kernel("seg_labels_kernel");
-#define MPF_LAB(T, C)                                                                                                              \
-    hipLaunchKernelGGL((seg_labels_kernel<T, C>), grid, dim3(kT), 0, st, (const T*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H, W, \
-                       probs, K, labels)
-#define MPF_LAB_T(T)                   \
-    do {                               \
-        if (cpt == 4) MPF_LAB(T, 4);   \
-        else if (cpt == 8) MPF_LAB(T, 8);   \
-        else if (cpt == 12) MPF_LAB(T, 12); \
-        else MPF_LAB(T, 24);           \
-    } while (0)
-    if (dtype == MPF_F32) MPF_LAB_T(float);
-    else MPF_LAB_T(__hip_bfloat16);
-#undef MPF_LAB_T
-#undef MPF_LAB
-    mpf::prof_end("seg_labels_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + 4.0 * HW, 2.0 * K * Q * (double)HW);
+    launch_product(masks, dtype, g, probs, K, nullptr, labels, st);
+    mpf::prof_end("seg_labels_kernel", st, logit_bytes(Q, g, dtype) + 4.0 * HW, 2.0 * K * Q * (double)HW);
     return mpf::check(hipGetLastError(), "mpf_seg_semantic_labels");
 }
 
@@ -1102,25 +1135,11 @@ extern "C" int mpf_seg_labels_resize(const float* scores, int K, int hi, int wi,
     return mpf::check(hipGetLastError(), "mpf_seg_labels_resize");
 }
 
-namespace {
-int check_tta_mode(const char* who, int mode)
-{
-    static thread_local char msg[96];
-    if (mode & ~3) { snprintf(msg, sizeof msg, "%s: mode has bit 0 (add) and bit 1 (hflip) only, got %d", who, mode); return mpf::fail(MPF_E_SHAPE, msg); }
-    return 0;
-}
-// the float4 form of tta_put4: whole rows of four (mirrored: W itself) and 16-byte aligned planes
-int tta_vec(const float* acc, int H, int W, int mode)
-{
-    const int64_t HW = (int64_t)H * W;
-    return ((uintptr_t)acc & 15) == 0 && (HW & 3) == 0 && (!(mode & 2) || (W & 3) == 0);
-}
-}  // namespace
-
 extern "C" int mpf_seg_tta_accumulate(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
                                       int H, int W, const float* probs, int K, int mode, float* acc, void* stream)
 {
-    if (int e = check_geom("seg_tta_accumulate", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_tta_accumulate", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!probs || !acc) return mpf::fail(MPF_E_NULL, "seg_tta_accumulate: NULL buffer");
     if (K <= 0) return mpf::fail(MPF_E_SHAPE, "seg_tta_accumulate: K must be positive");
     if (int e = check_tta_mode("seg_tta_accumulate", mode)) return e;
@@ -1129,27 +1148,17 @@ extern "C" int mpf_seg_tta_accumulate(const void* masks, int64_t stride_q, int d
     const int64_t HW = (int64_t)H * W;
     // class tiles of 16 per workgroup: ADE20K's 150 classes take 10 (160), larger sets chunks of 12 (192) on blockIdx.y
     const int mt = K <= 32 ? 2 : K <= 64 ? 4 : K <= 128 ? 8 : K <= 160 ? 10 : 12;
-    const dim3 grid((unsigned)((HW + kSemPix - 1) / kSemPix), (unsigned)((K + 16 * mt - 1) / (16 * mt)));
+    const dim3 grid((unsigned)ceil_div(HW, kSemPix), (unsigned)ceil_div(K, 16 * mt));
     const int vec = tta_vec(acc, H, W, mode);
     mpf::prof_begin(st);
     mpf::set_kernel("seg_tta_accumulate_kernel");
-#define MPF_TTA(T, M)                                                                                                                      \
-    hipLaunchKernelGGL((seg_tta_accumulate_kernel<T, M>), grid, dim3(kT), 0, st, (const T*)masks, stride_q, Q, h, w, Hp, Wp, hi, wi, H, W, \
-                       probs, K, mode, vec, acc)
-#define MPF_TTA_T(T)                      \
-    do {                                  \
-        if (mt == 2) MPF_TTA(T, 2);       \
-        else if (mt == 4) MPF_TTA(T, 4);  \
-        else if (mt == 8) MPF_TTA(T, 8);  \
-        else if (mt == 10) MPF_TTA(T, 10); \
-        else MPF_TTA(T, 12);              \
-    } while (0)
-    if (dtype == MPF_F32) MPF_TTA_T(float);
-    else MPF_TTA_T(__hip_bfloat16);
-#undef MPF_TTA_T
-#undef MPF_TTA
-    mpf::prof_end("seg_tta_accumulate_kernel", st, (double)Q * h * w * (dtype == MPF_F32 ? 4 : 2) + ((mode & 1) ? 8.0 : 4.0) * K * HW,
-                  2.0 * K * Q * (double)HW);
+    with_mask_type(dtype, masks, [&](auto* m) {
+        with_int<2, 4, 8, 10, 12>(mt, [&](auto tiles) {
+            hipLaunchKernelGGL((seg_tta_accumulate_kernel<elem_t<decltype(m)>, decltype(tiles)::value>), grid, dim3(kT), 0, st, m, g, probs, K,
+                               mode, vec, acc);
+        });
+    });
+    mpf::prof_end("seg_tta_accumulate_kernel", st, logit_bytes(Q, g, dtype) + ((mode & 1) ? 8.0 : 4.0) * K * HW, 2.0 * K * Q * (double)HW);
     return mpf::check(hipGetLastError(), "mpf_seg_tta_accumulate");
 }
 
@@ -1243,9 +1252,10 @@ extern "C" int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, i
                                           int wi, int H, int W, const int64_t* sel_q, int T, int64_t* offsets, void* workspace,
                                           size_t workspace_bytes, void* stream)
 {
-    if (int e = check_geom("seg_instance_rle_count", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_instance_rle_count", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!sel_q || !offsets || !workspace) return mpf::fail(MPF_E_NULL, "seg_instance_rle_count: NULL buffer");
-    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_count: need 1 <= T <= 65535 entries");
+    if (int e = check_entries("seg_instance_rle_count", T)) return e;
     const RleLayout l = rle_layout(T, H, W);
     if (workspace_bytes < l.total) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_count: workspace too small");
     if (((uintptr_t)workspace & 7) != 0) return mpf::fail(MPF_E_SHAPE, "seg_instance_rle_count: workspace must be 8-byte aligned");
@@ -1255,19 +1265,13 @@ extern "C" int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, i
     unsigned long long* bits = (unsigned long long*)(ws + l.bits);
     int64_t* tile_off = (int64_t*)(ws + l.tile_off);
     int* tile_cnt = (int*)(ws + l.tile_cnt);
-    const dim3 gbits((unsigned)((HW + kInstPix - 1) / kInstPix), (unsigned)T);
     mpf::prof_begin(st);
     mpf::set_kernel("seg_rle_bits_kernel+seg_rle_count_kernel+seg_rle_scan_kernel");
-    if (dtype == MPF_F32)
-        hipLaunchKernelGGL(seg_rle_bits_kernel<float>, gbits, dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi, H, W, sel_q,
-                           l.nwords, bits);
-    else
-        hipLaunchKernelGGL(seg_rle_bits_kernel<__hip_bfloat16>, gbits, dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h, w, Hp, Wp,
-                           hi, wi, H, W, sel_q, l.nwords, bits);
+    launch_rle_bits(masks, dtype, g, sel_q, T, l.nwords, bits, st);
     hipLaunchKernelGGL(seg_rle_count_kernel, dim3((unsigned)l.tiles, (unsigned)T), dim3(kT), 0, st, (const unsigned long long*)bits, l.nwords,
                        HW, tile_cnt);
     hipLaunchKernelGGL(seg_rle_scan_kernel, dim3(1), dim3(kT), 0, st, (const int*)tile_cnt, (int)l.tiles, T, tile_off, offsets);
-    mpf::prof_end("seg_rle_bits_kernel", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + (double)T * HW / 8);
+    mpf::prof_end("seg_rle_bits_kernel", st, logit_bytes(T, g, dtype) + (double)T * HW / 8);
     return mpf::check(hipGetLastError(), "mpf_seg_instance_rle_count");
 }
 
@@ -1275,22 +1279,17 @@ extern "C" int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, i
 extern "C" int mpf_seg_instance_bits(const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
                                      int H, int W, const int64_t* sel_q, int T, uint64_t* bits, void* stream)
 {
-    if (int e = check_geom("seg_instance_bits", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W)) return e;
+    SegGeom g;
+    if (int e = check_geom("seg_instance_bits", masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W, g)) return e;
     if (!sel_q || !bits) return mpf::fail(MPF_E_NULL, "seg_instance_bits: NULL buffer");
-    if (T <= 0 || T > 65535) return mpf::fail(MPF_E_SHAPE, "seg_instance_bits: need 1 <= T <= 65535 entries");
+    if (int e = check_entries("seg_instance_bits", T)) return e;
     if (((uintptr_t)bits & 7) != 0) return mpf::fail(MPF_E_SHAPE, "seg_instance_bits: bits must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W, nwords = (HW + 63) / 64;
-    const dim3 gbits((unsigned)((HW + kInstPix - 1) / kInstPix), (unsigned)T);
+    const int64_t HW = (int64_t)H * W;
     mpf::prof_begin(st);
     mpf::set_kernel("seg_rle_bits_kernel");
-    if (dtype == MPF_F32)
-        hipLaunchKernelGGL(seg_rle_bits_kernel<float>, gbits, dim3(kT), 0, st, (const float*)masks, stride_q, h, w, Hp, Wp, hi, wi, H, W, sel_q,
-                           nwords, (unsigned long long*)bits);
-    else
-        hipLaunchKernelGGL(seg_rle_bits_kernel<__hip_bfloat16>, gbits, dim3(kT), 0, st, (const __hip_bfloat16*)masks, stride_q, h, w, Hp, Wp,
-                           hi, wi, H, W, sel_q, nwords, (unsigned long long*)bits);
-    mpf::prof_end("seg_rle_bits_kernel", st, (double)T * h * w * (dtype == MPF_F32 ? 4 : 2) + (double)T * HW / 8);
+    launch_rle_bits(masks, dtype, g, sel_q, T, ceil_div(HW, 64), (unsigned long long*)bits, st);
+    mpf::prof_end("seg_rle_bits_kernel", st, logit_bytes(T, g, dtype) + (double)T * HW / 8);
     return mpf::check(hipGetLastError(), "mpf_seg_instance_bits");
 }
 

@@ -156,69 +156,81 @@ def segment_table(labels, mask_area, original_area, intersection, thing_ids, ove
 
 
 # ---- native calls -----------------------------------------------------------------------------------------------------------
-def _geom(masks_n, image_size, padded_hw, out_hw):
-    Q, h, w = masks_n.shape
-    return [Q, h, w, int(padded_hw[0]), int(padded_hw[1]), int(image_size[0]), int(image_size[1]), int(out_hw[0]), int(out_hw[1])]
-
-
-def _masks_arg(pm):
-    """(pointer of image 0, stride_q, dtype code) of [N, Q, h, w] logits whose [h, w] planes are contiguous."""
+def _planes(pm):
+    """[N, Q, h, w] mask logits as the kernels read them: fp32 / bf16 with contiguous [h, w] planes (copied only if they are not)."""
     if pm.dtype not in _MASK_DTYPES:
         raise TypeError(f"pred_masks must be float32 or bfloat16, got {pm.dtype}")
     if not (pm.stride(-1) == 1 and pm.stride(-2) == pm.shape[-1]):
         pm = pm.contiguous()
-    return pm, pm.stride(0), pm.stride(1), _lib.DTYPE[pm.dtype]
+    return pm
+
+
+class _View:
+    """One image's mask logits and sizes, as the per-pixel entry points take them: image ``n`` of ``pm`` ([N, Q, h, w] from
+    ``_planes``), its image size (hi, wi) on the padded grid and its output size (H, W).  Carries the device and stream of its
+    launches."""
+
+    def __init__(self, pm, n, image_size, padded_hw, out_hw, stream):
+        self.dev, self.stream = pm.device, stream
+        self.ptr = pm.data_ptr() + n * pm.stride(0) * pm.element_size()
+        self.stride_q, self.dtype = pm.stride(1), _lib.DTYPE[pm.dtype]
+        self.low = tuple(pm.shape[1:])                                       # Q, h, w
+        self.padded = (int(padded_hw[0]), int(padded_hw[1]))
+        self.image = (int(image_size[0]), int(image_size[1]))
+        self.out = (int(out_hw[0]), int(out_hw[1]))
+
+    def args(self, out_hw=None):
+        """The twelve leading arguments (masks, stride_q, dtype, Q, h, w, Hp, Wp, hi, wi, H, W) for the view's output size, or for
+        ``out_hw``: the "after" mode computes on the cropped padded grid, (hi, wi)."""
+        return (self.ptr, self.stride_q, self.dtype, *self.low, *self.padded, *self.image, *(out_hw or self.out))
 
 
 class _Image:
-    """Per-image launch state: the softmax prologue's outputs in one scratch buffer."""
+    """Per-image launch state: the softmax prologue's outputs in one scratch buffer.  Its layout: a float part {probs [Q, K],
+    max_score [Q], max_label [Q] (int32 bits), kept_score [Q]}, then an int part {count, kept query [Q], kept label [Q],
+    areas [3][Q]}, which is what panoptic inference copies to the host, in one piece."""
 
     def __init__(self, cls, K, thr, dev, stream, slot):
         Q = cls.shape[0]
         self.Q, self.K = Q, K
-        nbytes = 4 * (Q * K + 2 * Q + Q) + 4 * (1 + 2 * Q + 3 * Q)
-        ws = _lib.scratch(("seg_infer.softmax", slot), dev, stream, nbytes)
-        f = ws[:4 * (Q * K + 3 * Q)].view(torch.float32)
-        self.probs = f[:Q * K].view(Q, K)
-        self.max_score, self.max_label, self.kept_score = f[Q * K:Q * K + Q], f[Q * K + Q:Q * K + 2 * Q].view(torch.int32), f[Q * K + 2 * Q:]
-        # {count, kept query [Q], kept label [Q], areas [3][Q]}: one device-to-host copy for the panoptic table
-        self.ints = ws[4 * (Q * K + 3 * Q):4 * (Q * K + 3 * Q) + 4 * (1 + 5 * Q)].view(torch.int32)
-        self.kept, self.areas = self.ints[:1 + 2 * Q], self.ints[1 + 2 * Q:]
+        nf, ni = Q * K + 3 * Q, 1 + 5 * Q
+        ws = _lib.scratch(("seg_infer.softmax", slot), dev, stream, 4 * (nf + ni))
+        f, self.ints = ws[:4 * nf].view(torch.float32), ws[4 * nf:4 * (nf + ni)].view(torch.int32)
+        probs, self.max_score, max_label, self.kept_score = f.split([Q * K, Q, Q, Q])
+        self.probs, self.max_label = probs.view(Q, K), max_label.view(torch.int32)
+        self.kept, self.areas = self.ints.split([1 + 2 * Q, 3 * Q])
         _lib.call("mpf_seg_softmax", dev, cls.data_ptr(), Q, K + 1, float(thr), self.probs.data_ptr(), self.max_score.data_ptr(),
                   self.max_label.data_ptr(), self.kept.data_ptr(), self.kept_score.data_ptr(), stream)
 
 
-def _semantic(mptr, sq, dt, geom, probs, K, dev, stream):
-    H, W = geom[-2:]
-    out = torch.empty((K, H, W), dtype=torch.float32, device=dev)
-    _lib.call("mpf_seg_semantic", dev, mptr, sq, dt, *geom, probs.data_ptr(), K, out.data_ptr(), stream)
+def _semantic(view, img, out_hw=None):
+    """The scores [K, H, W] at the view's output size, or at ``out_hw``."""
+    out = torch.empty((img.K, *(out_hw or view.out)), dtype=torch.float32, device=view.dev)
+    _lib.call("mpf_seg_semantic", view.dev, *view.args(out_hw), img.probs.data_ptr(), img.K, out.data_ptr(), view.stream)
     return out
 
 
-def _semantic_labels(mptr, sq, dt, geom, probs, K, dev, stream):
+def _semantic_labels(view, img):
     """"before" mode: the label map straight from the logits, in one launch."""
-    H, W = geom[-2:]
-    out = torch.empty((H, W), dtype=torch.int32, device=dev)
-    _lib.call("mpf_seg_semantic_labels", dev, mptr, sq, dt, *geom, probs.data_ptr(), K, out.data_ptr(), stream)
+    out = torch.empty(view.out, dtype=torch.int32, device=view.dev)
+    _lib.call("mpf_seg_semantic_labels", view.dev, *view.args(), img.probs.data_ptr(), img.K, out.data_ptr(), view.stream)
     return out
 
 
-def _labels_resize(scores, out_hw, dev, stream):
+def _labels_resize(view, scores):
     """"after" mode: scores [K, hi, wi] on the cropped grid -> labels [H, W] of their bilinear resize."""
-    K, hi, wi = scores.shape
-    out = torch.empty(out_hw, dtype=torch.int32, device=dev)
-    _lib.call("mpf_seg_labels_resize", dev, scores.data_ptr(), K, hi, wi, int(out_hw[0]), int(out_hw[1]), out.data_ptr(), stream)
+    out = torch.empty(view.out, dtype=torch.int32, device=view.dev)
+    _lib.call("mpf_seg_labels_resize", view.dev, scores.data_ptr(), *scores.shape, *view.out, out.data_ptr(), view.stream)
     return out
 
 
-def _instance_rle(mptr, sq, dt, geom, query, T, dev, stream):
+def _instance_rle(view, query, T):
     """The masks of the sorted entries as uncompressed COCO RLE dicts; two device-to-host copies: offsets, then counts."""
-    H, W = geom[-2:]
+    (H, W), dev, stream = view.out, view.dev, view.stream
     nws = _lib.lib().mpf_seg_instance_rle_workspace_bytes(T, H, W)
     ws = _lib.scratch("seg_infer.rle", dev, stream, nws)
     offsets = torch.empty(T + 1, dtype=torch.int64, device=dev)
-    _lib.call("mpf_seg_instance_rle_count", dev, mptr, sq, dt, *geom, query.data_ptr(), T, offsets.data_ptr(), ws.data_ptr(), ws.numel(),
-              stream)
+    _lib.call("mpf_seg_instance_rle_count", dev, *view.args(), query.data_ptr(), T, offsets.data_ptr(), ws.data_ptr(), ws.numel(), stream)
     off = offsets.cpu().numpy()                          # copy 1: where every entry's counts lie
     total = int(off[T])
     pos = _lib.scratch("seg_infer.rle_pos", dev, stream, 4 * total)
@@ -229,11 +241,11 @@ def _instance_rle(mptr, sq, dt, geom, query, T, dev, stream):
     return [{"size": [H, W], "counts": host[off[t]:off[t + 1]].tolist()} for t in range(T)]
 
 
-def _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream):
+def _instance_selection(view, img, cfg, thing_lut):
     """The entries of instance_inference (maskformer_model.py:362-401), sorted by their final score, descending and stable
     -> (scores fp32 [T], labels int64 [T], query int64 [T] contiguous).  Shared by ``postprocess`` and ``instance_bits``."""
     Q, K = img.Q, img.K
-    H, W = geom[-2:]
+    (H, W), dev, stream = view.out, view.dev, view.stream
     k = min(int(cfg.test_topk_per_image), Q * K)
     sc, idx = img.probs.reshape(-1).topk(k, sorted=True)
     labels = idx % K
@@ -248,45 +260,35 @@ def _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream):
     scores = torch.empty(T, dtype=torch.float32, device=dev)
     nws = _lib.lib().mpf_seg_instance_workspace_bytes(T, H, W)
     ws = _lib.scratch("seg_infer.instance", dev, stream, nws)
-    _lib.call("mpf_seg_instance_scores", dev, mptr, sq, dt, *geom, query.data_ptr(), sc.data_ptr(), T, scores.data_ptr(), ws.data_ptr(),
+    _lib.call("mpf_seg_instance_scores", dev, *view.args(), query.data_ptr(), sc.data_ptr(), T, scores.data_ptr(), ws.data_ptr(),
               ws.numel(), stream)
     scores, order = scores.sort(descending=True, stable=True)
     return scores, labels[order], query[order].contiguous()
 
 
-def _instances(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream, image_hw):
-    H, W = geom[-2:]
-    scores, labels, query = _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream)
+def _instances(view, img, cfg, thing_lut):
+    (H, W), dev = view.out, view.dev
+    scores, labels, query = _instance_selection(view, img, cfg, thing_lut)
     T = int(scores.shape[0])
     Boxes, Instances = _structures()
-    result = Instances(image_hw)
-    rle = cfg.instance_masks == "rle"
-    if T == 0:
-        if rle:
-            result.pred_masks_rle = []
-        else:
-            result.pred_masks = torch.zeros((0, H, W), dtype=torch.float32, device=dev)
-        result.pred_boxes = Boxes(torch.zeros(0, 4))
-        result.scores = scores
-        result.pred_classes = labels
-        return result
-    if rle:
-        result.pred_masks_rle = _instance_rle(mptr, sq, dt, geom, query, T, dev, stream)
+    result = Instances((H, W))
+    if cfg.instance_masks == "rle":
+        result.pred_masks_rle = _instance_rle(view, query, T) if T else []
     else:
-        masks = torch.empty((T, H, W), dtype=torch.float32, device=dev)
-        _lib.call("mpf_seg_instance_masks", dev, mptr, sq, dt, *geom, query.data_ptr(), T, masks.data_ptr(), stream)
-        result.pred_masks = masks
+        result.pred_masks = torch.empty((T, H, W), dtype=torch.float32, device=dev)
+        if T:
+            _lib.call("mpf_seg_instance_masks", dev, *view.args(), query.data_ptr(), T, result.pred_masks.data_ptr(), view.stream)
     result.pred_boxes = Boxes(torch.zeros(T, 4))
     result.scores = scores
     result.pred_classes = labels
     return result
 
 
-def _panoptic(mptr, sq, dt, geom, img, cfg, dev, stream):
+def _panoptic(view, img, cfg):
     Q = img.Q
-    H, W = geom[-2:]
+    (H, W), dev, stream = view.out, view.dev, view.stream
     code = torch.empty((H, W), dtype=torch.int32, device=dev)
-    _lib.call("mpf_seg_panoptic_areas", dev, mptr, sq, dt, *geom, img.kept.data_ptr(), img.kept_score.data_ptr(), code.data_ptr(),
+    _lib.call("mpf_seg_panoptic_areas", dev, *view.args(), img.kept.data_ptr(), img.kept_score.data_ptr(), code.data_ptr(),
               img.areas.data_ptr(), stream)
     host = img.ints.cpu()                                # the one device-to-host copy of panoptic inference
     n = int(host[0])
@@ -300,8 +302,10 @@ def _panoptic(mptr, sq, dt, geom, img, cfg, dev, stream):
     return ids, segments_info
 
 
-def _head_outputs(who, pred_logits, pred_masks, cfg):
-    """The checks and per-batch launch state that ``postprocess`` and ``instance_bits`` share."""
+def _images(who, pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
+    """The checks of ``postprocess`` and ``instance_bits`` on the head's outputs, then their iteration over the batch: yields
+    (view, img, thing_lut) per image: the softmax prologue of the image launched, and the per-batch table of the thing classes
+    (None unless instance and panoptic inference run together)."""
     if not (pred_masks.is_cuda and pred_logits.is_cuda):
         raise RuntimeError(f"{who}: Not implemented on the CPU (device tensors only)")
     N, Q, K1 = pred_logits.shape
@@ -310,7 +314,7 @@ def _head_outputs(who, pred_logits, pred_masks, cfg):
         raise ValueError(f"pred_logits has {K} classes + no-object, config {cfg.num_classes}")
     if pred_masks.dim() != 4 or pred_masks.shape[:2] != (N, Q):
         raise ValueError(f"pred_masks {tuple(pred_masks.shape)} does not match pred_logits {tuple(pred_logits.shape)}")
-    pm, sn, sq, dt = _masks_arg(pred_masks)
+    pm = _planes(pred_masks)
     dev = pm.device
     thing_lut = None
     if cfg.instance_on and cfg.panoptic_on:
@@ -319,7 +323,11 @@ def _head_outputs(who, pred_logits, pred_masks, cfg):
             if 0 <= i < K:
                 thing_lut[i] = True
         thing_lut = thing_lut.to(dev)
-    return N, K, pm, sn, sq, dt, dev, thing_lut, _lib.stream_ptr(dev), pred_logits.detach().float()
+    stream = _lib.stream_ptr(dev)
+    logits = pred_logits.detach().float()
+    for n in range(N):
+        view = _View(pm, n, image_sizes[n], padded_hw, output_sizes[n], stream)
+        yield view, _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n), thing_lut
 
 
 def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
@@ -332,32 +340,24 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
     "instances" (pred_masks [T, height, width] 0/1 fp32, pred_boxes zeros, scores, pred_classes), per the *_on flags.
     cfg.semantic_labels: "sem_seg_labels" int32 [height, width] in place of "sem_seg"; cfg.instance_masks == "rle":
     instances.pred_masks_rle (list of T {"size", "counts"} dicts) in place of pred_masks."""
-    N, K, pm, sn, sq, dt, dev, thing_lut, stream, logits = _head_outputs("postprocess", pred_logits, pred_masks, cfg)
     out = []
-    for n in range(N):
-        mptr = pm.data_ptr() + n * sn * pm.element_size()
-        hi, wi = int(image_sizes[n][0]), int(image_sizes[n][1])
-        H, W = int(output_sizes[n][0]), int(output_sizes[n][1])
-        img = _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n)
+    for view, img, thing_lut in _images("postprocess", pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
         res = {}
         if cfg.semantic_on and cfg.semantic_labels:
             if cfg.sem_seg_postprocess_before_inference:
-                res["sem_seg_labels"] = _semantic_labels(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img.probs, K, dev,
-                                                         stream)
+                res["sem_seg_labels"] = _semantic_labels(view, img)
             else:   # the scores on the cropped padded grid (network resolution), then resize + argmax in one pass
-                r = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (hi, wi)), img.probs, K, dev, stream)
-                res["sem_seg_labels"] = _labels_resize(r, (H, W), dev, stream)
+                res["sem_seg_labels"] = _labels_resize(view, _semantic(view, img, view.image))
         elif cfg.semantic_on:
             if cfg.sem_seg_postprocess_before_inference:
-                res["sem_seg"] = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img.probs, K, dev, stream)
+                res["sem_seg"] = _semantic(view, img)
             else:   # inference on the cropped padded grid, then the reference's own resize of the K planes (:264-265)
-                r = _semantic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (hi, wi)), img.probs, K, dev, stream)
-                res["sem_seg"] = F.interpolate(r[None], size=(H, W), mode="bilinear", align_corners=False)[0]
+                r = _semantic(view, img, view.image)
+                res["sem_seg"] = F.interpolate(r[None], size=view.out, mode="bilinear", align_corners=False)[0]
         if cfg.panoptic_on:
-            res["panoptic_seg"] = _panoptic(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, dev, stream)
+            res["panoptic_seg"] = _panoptic(view, img, cfg)
         if cfg.instance_on:
-            res["instances"] = _instances(mptr, sq, dt, _geom(pm[n], (hi, wi), padded_hw, (H, W)), img, cfg, thing_lut, dev, stream,
-                                          (H, W))
+            res["instances"] = _instances(view, img, cfg, thing_lut)
         out.append(res)
     return out
 
@@ -369,19 +369,14 @@ def instance_bits(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes,
     dense [T, H, W] masks are never written."""
     if not cfg.instance_on:
         raise ValueError("instance_bits needs instance_on")
-    N, K, pm, sn, sq, dt, dev, thing_lut, stream, logits = _head_outputs("instance_bits", pred_logits, pred_masks, cfg)
     out = []
-    for n in range(N):
-        mptr = pm.data_ptr() + n * sn * pm.element_size()
-        hi, wi = int(image_sizes[n][0]), int(image_sizes[n][1])
-        H, W = int(output_sizes[n][0]), int(output_sizes[n][1])
-        geom = _geom(pm[n], (hi, wi), padded_hw, (H, W))
-        img = _Image(logits[n].contiguous(), K, cfg.object_mask_threshold, dev, stream, n)
-        scores, labels, query = _instance_selection(mptr, sq, dt, geom, img, cfg, thing_lut, dev, stream)
+    for view, img, thing_lut in _images("instance_bits", pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
+        H, W = view.out
+        scores, labels, query = _instance_selection(view, img, cfg, thing_lut)
         T = int(scores.shape[0])
-        bits = torch.empty((T, (H * W + 63) // 64), dtype=torch.int64, device=dev)
+        bits = torch.empty((T, (H * W + 63) // 64), dtype=torch.int64, device=view.dev)
         if T:
-            _lib.call("mpf_seg_instance_bits", dev, mptr, sq, dt, *geom, query.data_ptr(), T, bits.data_ptr(), stream)
+            _lib.call("mpf_seg_instance_bits", view.dev, *view.args(), query.data_ptr(), T, bits.data_ptr(), view.stream)
         out.append({"bits": bits, "size": (H, W), "scores": scores, "pred_classes": labels})
     return out
 
@@ -427,7 +422,7 @@ class SemanticTTA:
             raise ValueError(f"every view of an image has the same classes and output size: got {(K, H, W)}, first view {self._shape}")
         if not (pred_masks.is_cuda and pred_logits.is_cuda):
             raise RuntimeError("SemanticTTA.add: Not implemented on the CPU (device tensors only)")
-        pm, _, sq, dt = _masks_arg(pred_masks[None])
+        pm = _planes(pred_masks[None])
         dev = pm.device
         stream = _lib.stream_ptr(dev)
         if not self._count:
@@ -438,16 +433,15 @@ class SemanticTTA:
                 self._acc = torch.empty((K, H, W), dtype=torch.float32, device=dev)
         elif dev != self._acc.device:
             raise RuntimeError(f"view on {dev}, the accumulator on {self._acc.device}")
+        view = _View(pm, 0, image_size, padded_hw, (H, W), stream)
         img = _Image(pred_logits.detach().float().contiguous(), K, cfg.object_mask_threshold, dev, stream, "tta")
         mode = (TTA_ADD if self._count else 0) | (TTA_HFLIP if hflip else 0)
-        hi, wi = int(image_size[0]), int(image_size[1])
         if cfg.sem_seg_postprocess_before_inference:
-            _lib.call("mpf_seg_tta_accumulate", dev, pm.data_ptr(), sq, dt, *_geom(pm[0], (hi, wi), padded_hw, (H, W)), img.probs.data_ptr(),
-                      K, mode, self._acc.data_ptr(), stream)
+            _lib.call("mpf_seg_tta_accumulate", dev, *view.args(), img.probs.data_ptr(), K, mode, self._acc.data_ptr(), stream)
         else:   # the scores on the cropped padded grid (store mode, never mirrored), then resize + flip + add in one pass
+            hi, wi = view.image
             r = _lib.scratch("seg_infer.tta_scores", dev, stream, 4 * K * hi * wi)
-            _lib.call("mpf_seg_tta_accumulate", dev, pm.data_ptr(), sq, dt, *_geom(pm[0], (hi, wi), padded_hw, (hi, wi)),
-                      img.probs.data_ptr(), K, 0, r.data_ptr(), stream)
+            _lib.call("mpf_seg_tta_accumulate", dev, *view.args(view.image), img.probs.data_ptr(), K, 0, r.data_ptr(), stream)
             _lib.call("mpf_seg_tta_resize_add", dev, r.data_ptr(), K, hi, wi, H, W, mode, self._acc.data_ptr(), stream)
         self._count += 1
 

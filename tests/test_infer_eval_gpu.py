@@ -4,7 +4,7 @@ confusion matrix against numpy's bincount, run-length masks against the dense "p
 
 Shapes: the _coco_inputs recipe of test_infer_gpu.py scaled down to low-res (50, 76), padded (200, 304), image (197, 301) and an
 odd output that is no multiple of any tile; Q = 100 and 37 (not a multiple of the 32-query staging round); K = 19, 150 and 200
-(a second 192-class chunk)."""
+(a second 192-class chunk), and for the "before" labels also 40 and 80 (the 64- and 96-class tiles)."""
 import dataclasses
 
 import numpy as np
@@ -62,7 +62,7 @@ def _assert_inside_the_band(labels, sem, tag):
 # ---- 1. labels, "before" mode ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("Q", [100, 37])
-@pytest.mark.parametrize("K", [19, 150, 200])
+@pytest.mark.parametrize("K", [19, 40, 80, 150, 200])
 def test_labels_before_mode_equal_the_argmax_of_the_scores(K, Q, dtype):
     lg, mk = _inputs(K, Q, dtype)
     sem, lab = _semantic_pair(lg, mk, IMAGE, PADDED, OUT)

@@ -11,7 +11,8 @@ Shapes: three view geometries (low-res, padded, image), each added plain and fli
 outputs (97, 131) (odd, H * W no multiple of 4: the per-pixel epilogue), (96, 132) (the float4 epilogue, also mirrored) and
 (96, 131) (float4 for the plain views, per pixel for the mirrored ones);
 (K, Q) = (19, 100), (150, 37) (Q no multiple of 4 or 32), (200, 100) (a second chunk of 192 classes), (5, 3) (Q below one MFMA k-step,
-K below one 16-row tile); fp32 and bf16 masks; both config modes.
+K below one 16-row tile), (40, 37) and (80, 37) (the 64- and 96-class tiles of the VALU kernels, 4 and 8 MFMA row tiles); fp32 and
+bf16 masks; both config modes.
 
 The bound rtol = atol = 1e-5 is the project's bound for "sem_seg" (tests/test_infer_gpu.py).  It follows from the formats too: an fp32
 dot product of Q non-negative terms is off by at most about Q * 2^-24 relative in any order (6e-6 at Q = 100), the sum over the views
@@ -35,7 +36,7 @@ GEOMS = {"A": ((50, 76), (200, 304), (197, 301)), "B": ((32, 48), (128, 192), (1
 VIEWS = [("A", False), ("A", True), ("B", False), ("B", True), ("C", False), ("C", True)]
 OUT_ODD, OUT_VEC = (97, 131), (96, 132)
 OUT_MIXED = (96, 131)         # H * W a multiple of 4, W not: plain views take the float4 epilogue, mirrored ones the per-pixel one
-KQ = [(19, 100), (150, 37), (200, 100), (5, 3)]
+KQ = [(19, 100), (150, 37), (200, 100), (5, 3), (40, 37), (80, 37)]
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
 MODES = {"before": True, "after": False}
 
