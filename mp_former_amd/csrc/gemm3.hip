@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <atomic>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "mpf_common.h"
 #include "amax.h"
@@ -402,7 +403,7 @@ __device__ __attribute__((aligned(16))) unsigned g3_const[12] = {0u, 0u, 0u, 0u,
 // cached per device ordinal (a process-wide cache would hand a second GPU a pointer into the first one's memory)
 int g3_consts(const float** out, const char* who)
 {
-    constexpr int kMaxDev = 64;
+    constexpr int kMaxDev = mpf::kMaxDevices;
     static std::atomic<const float*> cache[kMaxDev];
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return mpf::check(e, who);
@@ -415,11 +416,6 @@ int g3_consts(const float** out, const char* who)
     }
     *out = c;
     return 0;
-}
-
-inline void g3_no_bits(G3& p, const float* consts)
-{
-    p.gbits = reinterpret_cast<const unsigned char*>(consts + 8); p.ldgbits = 0; p.gbits_cm = 0; p.gbits_out = nullptr; p.ldgbits_out = 0;
 }
 
 // returns the largest |value| this thread stored (SCALED kernels; 0 otherwise)
@@ -1677,78 +1673,275 @@ extern "C" int mpf_gemm3_split_grouped(const MpfSplitItem* items_device, int n_i
     return mpf::check(hipGetLastError(), "mpf_gemm3_split_grouped");
 }
 
-// 128 x 256 / 96 x 256 tiles (gemm3_tn2_kernel: two 128-column passes over one A image per K step) for fp32 A without the
-// addend rows and N a multiple of 256; row blocks of 96 when they need fewer (rounds x rows) on the chip's workgroup slots
-// (M = 43 008, N = 256: 448 tiles instead of 336 for 512 slots).  Starts the launch-log record itself; false = not taken.
-static bool g3_launch_two_pass(G3& p, hipStream_t st)
-{
-    if (g_two_pass <= 0 || p.N % 256 != 0 || p.N < g_two_pass) return false;
-    static int slots2 = 0;
-    if (!slots2) {
-        int dev = 0, cus = 0;
-        slots2 = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) ? 2 * cus : 512;
-    }
-    p.tiles_n = p.N / 256;
-    const int t128 = ((p.M + 127) / 128) * p.tiles_n, t96 = ((p.M + 95) / 96) * p.tiles_n;
-    const double c128 = (double)((t128 + slots2 - 1) / slots2) * 128.0, c96 = (double)((t96 + slots2 - 1) / slots2) * 96.0;
-    const bool use96r = g_two_pass_rows == 96 || (g_two_pass_rows == 0 && c96 < c128);
-    p.ntiles = use96r ? t96 : t128;
-    p.tm0 = 0; p.ntiles2 = 0; p.tiles_n2 = 0;
-    mpf::prof_begin(st);
-    mpf::set_kernel(use96r ? "gemm3_tn_kernel<96x256>" : "gemm3_tn_kernel<128x256>");
-    if (p.a_amax) {
-        mpf::set_kernel(use96r ? "gemm3_tn_kernel<h2 96x256>" : "gemm3_tn_kernel<h2 128x256>");
-        if (use96r) hipLaunchKernelGGL((gemm3_tn2_kernel<96, false, true>), dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL((gemm3_tn2_kernel<128, false, true>), dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-        return true;
-    }
-    if (use96r) hipLaunchKernelGGL(gemm3_tn2_kernel<96>, dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    else hipLaunchKernelGGL(gemm3_tn2_kernel<128>, dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    return true;
-}
+// ------------------------------------------------------------------------------------------------
+// Host layer of the products: every entry point validates its arguments, FILLS the parameter struct (g3_fill / g3n_fill: one
+// place that knows every field), CHOOSES a route (g3_tn_route, g3_conv_route, g3n_*_route: the kernel, its launch shape and the
+// tile fields of the struct, nothing launched) and LAUNCHES it (g3_launch: the only hipLaunchKernel of the products).
+// DESIGN.md section 4 has the routes as one table.
+// ------------------------------------------------------------------------------------------------
+namespace {
 
-static int g3_tn_impl(const float* a, int64_t lda, const float* a2, int a2_rows, const void* b_planes,
-                      const float* bias, const float* c_in, int64_t ldcin, const float* c_in2, int64_t ldcin2,
-                      const float* gate, int64_t ldgate, float* c, int64_t ldc, int M, int N, int K,
-                      int relu, void* stream, const float* a_amax, const float* b_amax, float* out_amax,
-                      const unsigned char* gbits = nullptr, int64_t ldgbits = 0, unsigned char* gbits_out = nullptr,
-                      int64_t ldgbits_out = 0);
-
-// weight-stationary kernel (gemm3_ws.h): one persistent workgroup per CU; the N / 256 column groups of a row range on one XCD
-static int g3_launch_ws(G3& p, hipStream_t st)
-{
-    const int ncg = p.N / 256;
-    const int cus = mpf::cu_count();
-    int per_xcd = cus / 8 / ncg * ncg;                 // workgroups per XCD: a multiple of the column groups
-    if (per_xcd < ncg) per_xcd = ncg;
-    int workers = per_xcd / ncg * 8;                   // row workers
-    const int tiles16 = (p.M + 15) / 16;
-    if (workers > tiles16) workers = ((tiles16 + 7) / 8) * 8;
-    const int rpw = ((p.M + workers - 1) / workers + 15) / 16 * 16;
-    const int grid = workers * ncg;                    // block b: xcd = b & 7, slot = b >> 3: column group slot % ncg, row worker (slot / ncg) * 8 + xcd
-    // instantiated epilogues (cin, gate bits, relu, bits out): plain | + addend | ReLU | ReLU + addend | ReLU + mask out | bit-mask gate (+ addend)
-    const int key = (p.cin_cm ? 8 : 0) | (p.gbits_cm ? 4 : 0) | (p.relu ? 2 : 0) | (p.gbits_out ? 1 : 0);
+// what g3_launch needs to know about a route; fn == nullptr: the route does not apply
+struct Route {
     const void* fn = nullptr;
-    int slot = 0;
-#define WS_CASE(K_, I_, E_, G_, R_, B_) case K_: fn = (const void*)gemm3_ws_kernel<E_, G_, R_, B_>; slot = I_; break;
-    switch (key) {
-        WS_CASE(0, 0, 0, false, false, false) WS_CASE(8, 1, 1, false, false, false) WS_CASE(2, 2, 0, false, true, false)
-        WS_CASE(10, 3, 1, false, true, false) WS_CASE(3, 4, 0, false, true, true) WS_CASE(4, 5, 0, true, false, false)
-        WS_CASE(12, 6, 1, true, false, false)
-        default: return -1000;          // not instantiated: the tiled kernel
-    }
-#undef WS_CASE
-    static mpf::LdsAttr attr[7];
-    if (int e = mpf::ensure_dynamic_lds(fn, kWsLds, attr[slot])) return e;
+    const char* name = nullptr;        // as logged (mpf_last_kernel, the launch log): tests and tools match on it
+    const char* what = nullptr;        // the label of a HIP error
+    int threads = kThreads;
+    int blocks = 0;                    // workgroups: the tiles, rounded up to the 8 XCDs
+    size_t lds = 0;                    // dynamic LDS bytes, with the (kernel, device) record of the attribute call
+    mpf::LdsAttr* attr = nullptr;
+    double w_el = 6.0;                 // TN: bytes read per weight element (three bf16 planes: 6, two fp16 planes: 4)
+    int arg[2] = {0, 0};               // the ws kernel's two arguments after the struct (rows per worker, column groups)
+};
+
+struct Work { double bytes, flops; };      // algorithmic traffic and flops of a launch, for the launch log
+
+// the profiler record opens and closes here
+template <typename P>
+int g3_launch(const Route& r, const P& p, hipStream_t st, const Work w)
+{
+    if (r.lds)
+        if (int e = mpf::ensure_dynamic_lds(r.fn, r.lds, *r.attr)) return e;
     mpf::prof_begin(st);
-    mpf::set_kernel("gemm3_tn_kernel<h2 ws>");
-    {
-        void* args[] = {(void*)&p, (void*)&rpw, (void*)&ncg};
-        if (hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(kWsThreads), args, kWsLds, st); e != hipSuccess) return mpf::check(e, "gemm3_ws_kernel");
-    }
-    mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)p.M * p.K + (double)p.M * p.N) + 4.0 * (double)p.N * p.K, 2.0 * p.M * (double)p.N * p.K);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_tn_h2(ws)");
+    mpf::set_kernel(r.name);
+    void* args[] = {(void*)&p, (void*)&r.arg[0], (void*)&r.arg[1]};       // (a kernel takes as many as it declares)
+    if (hipError_t e = hipLaunchKernel(r.fn, dim3(r.blocks), dim3(r.threads), args, r.lds, st); e != hipSuccess) return mpf::check(e, r.what);
+    mpf::prof_end(r.name, st, w.bytes, w.flops);
+    return mpf::check(hipGetLastError(), r.what);
 }
+
+// grids are whole multiples of the 8 XCDs (workgroups past the last tile return at once)
+constexpr int round8(int tiles) { return (tiles + 7) / 8 * 8; }
+constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+// the chip's workgroup slots for the 256-thread kernels: two per CU
+inline int g3_slots() { return 2 * mpf::cu_count(); }
+
+// 96-wide column tiles when they waste fewer columns than 128-wide ones (N = 288 = 3 x 96)
+struct ColTile { int bn, tiles_n; };
+inline ColTile g3_col_tile(int N)
+{
+    const int t128 = cdiv(N, 128), t96 = cdiv(N, 96);
+    return t96 * 96 < t128 * 128 ? ColTile{96, t96} : ColTile{128, t128};
+}
+
+// ---- TN products and the 3x3 convolution (G3) ----
+
+// A TN problem with every optional operand ABSENT: bias / addends / gate / bit mask point at g3_const with leading dimension and
+// column multiplier 0, no addend rows, no convolution, no mixed tail, 192-row tn3 tiles.  The caller sets c or c16 and what it has.
+int g3_fill(G3& p, const char* who, const void* a, int64_t lda, const void* planes, const float* bias, int64_t ldc, int M, int N, int K)
+{
+    const float* consts = nullptr;
+    if (int rc = g3_consts(&consts, who)) return rc;
+    p = G3{};
+    p.a = (const float*)a; p.lda = lda; p.bp = (const unsigned short*)planes; p.plane = (int64_t)N * K; p.ldc = ldc;
+    p.M = M; p.N = N; p.K = K;
+    p.bias = bias ? bias : consts; p.bias_cm = bias ? 1 : 0;
+    p.cin = p.cin2 = consts; p.gate = consts + 4;
+    p.gbits = reinterpret_cast<const unsigned char*>(consts + 8);
+    p.cv_sign = 1;
+    p.t3_bm = kT3BM;
+    return 0;
+}
+
+// an optional fp32 epilogue operand that is present
+inline void g3_operand(const float*& slot, int64_t& ld, int& cm, const float* v, int64_t ldv)
+{
+    if (v) { slot = v; ld = ldv; cm = 1; }
+}
+
+// A (K columns, or the cv_cin channels of the image in convolution mode) and C once, the weight planes once
+inline Work g3_tn_work(const G3& p, const Route& r, double a_el = 4.0)
+{
+    const double M = p.M, N = p.N, K = p.K;
+    return {a_el * M * (p.cv_cin ? p.cv_cin : p.K) + (p.c16 ? 2.0 : 4.0) * M * N + r.w_el * N * K, 2.0 * M * N * K};
+}
+
+// weight-stationary kernel (gemm3_ws.h): one persistent workgroup per CU; the N / 256 column groups of a row range on one XCD.
+// Only some epilogues are instantiated: the others take the next route.
+Route g3_ws_route(const G3& p)
+{
+    // key = addend 8 | bit-mask gate 4 | ReLU 2 | mask out 1
+    static const struct { int key; const void* fn; } kEpilogues[] = {
+        {0, (const void*)gemm3_ws_kernel<0, false, false, false>},  {8, (const void*)gemm3_ws_kernel<1, false, false, false>},
+        {2, (const void*)gemm3_ws_kernel<0, false, true, false>},   {10, (const void*)gemm3_ws_kernel<1, false, true, false>},
+        {3, (const void*)gemm3_ws_kernel<0, false, true, true>},    {4, (const void*)gemm3_ws_kernel<0, true, false, false>},
+        {12, (const void*)gemm3_ws_kernel<1, true, false, false>}};
+    static mpf::LdsAttr attr[sizeof(kEpilogues) / sizeof(kEpilogues[0])];
+    const int key = (p.cin_cm ? 8 : 0) | (p.gbits_cm ? 4 : 0) | (p.relu ? 2 : 0) | (p.gbits_out ? 1 : 0);
+    Route r;
+    for (size_t i = 0; i < sizeof(kEpilogues) / sizeof(kEpilogues[0]); ++i) {
+        if (kEpilogues[i].key != key) continue;
+        const int ncg = p.N / 256;
+        int per_xcd = mpf::cu_count() / 8 / ncg * ncg;     // workgroups per XCD: a multiple of the column groups
+        if (per_xcd < ncg) per_xcd = ncg;
+        int workers = per_xcd / ncg * 8;                   // row workers
+        const int tiles16 = cdiv(p.M, 16);
+        if (workers > tiles16) workers = round8(tiles16);
+        r.fn = kEpilogues[i].fn; r.name = "gemm3_tn_kernel<h2 ws>"; r.what = "mpf_gemm3_tn_h2(ws)";
+        r.threads = kWsThreads; r.lds = kWsLds; r.attr = &attr[i]; r.w_el = 4.0;
+        r.blocks = workers * ncg;              // block b: xcd = b & 7, slot = b >> 3: column group slot % ncg, row worker (slot / ncg) * 8 + xcd
+        r.arg[0] = cdiv(cdiv(p.M, workers), 16) * 16;      // rows per worker
+        r.arg[1] = ncg;
+    }
+    return r;
+}
+
+// The route of a TN product, in the order tried (a_bf16: A is a bf16 matrix, mpf_gemm3_tn_ex).  Writes the tile fields of p.
+Route g3_tn_route(G3& p, bool a_bf16, const char* what)
+{
+    const bool h2 = p.a_amax != nullptr, a2 = p.a2 != nullptr, a_al16 = ((uintptr_t)p.a & 15) == 0;
+    const int M = p.M, N = p.N;
+    const ColTile ct = g3_col_tile(N);
+    const int tiles_m = cdiv(M, kBM);
+    p.tiles_n = ct.tiles_n;
+    p.ntiles = tiles_m * ct.tiles_n;
+    Route r;
+    r.what = what;
+    r.w_el = h2 ? 4.0 : 6.0;
+    // 1. weight-stationary (N >= g_ws: at N = 256 the 64 MB of weight fragments the workgroups fetch once per launch cost what the
+    //    tiled kernel's re-reads do)
+    if (h2 && !a2 && !p.gate_cm && !p.cin2_cm && g_ws > 0 && N >= g_ws && p.K == kWsK && N % 256 == 0 && a_al16) {
+        const Route ws = g3_ws_route(p);
+        if (ws.fn) return ws;
+    }
+    // 2. 192 x 256 tiles, ONE workgroup per CU: only where they fill the chip — the last (or only) round of tiles must cover at least
+    //    3/4 of the CUs (43 008 rows: 224 tiles on 256 CUs; 16 800 rows would be 88 tiles against 175 half-size tiles of the
+    //    two-pass kernel on two workgroup slots per CU: config D's head measured 11.62 -> 11.79 ms per step with them)
+    if (h2 && !a2 && g_tn3 && N % 256 == 0 && M >= 2048 && a_al16 && p.lda % 4 == 0) {
+        const int cus = mpf::cu_count(), nt3 = cdiv(M, kT3BM) * (N / 256), rem = nt3 % cus;
+        if (g_tn3 == 2 || (nt3 >= cus * 3 / 4 && (rem == 0 || 4 * rem >= 3 * cus || nt3 >= 4 * cus))) {
+            // 176-row tiles (96 + 80: the second row half one MFMA row tile shorter) when they need no more rounds of the chip than
+            // 192-row tiles do: a workgroup's time goes with its rows, and 43 008 rows are 245 tiles of 176 on 256 CUs (224 of 192)
+            const int nt176 = cdiv(M, 176) * (N / 256);
+            static mpf::LdsAttr attr;
+            if (g_tn3_176 && cdiv(nt176, cus) <= cdiv(nt3, cus)) p.t3_bm = 176;
+            p.tiles_n = N / 256;
+            p.ntiles = cdiv(M, p.t3_bm) * p.tiles_n;
+            r.fn = (const void*)gemm3_tn3_kernel;
+            r.name = p.t3_bm == kT3BM ? "gemm3_tn_kernel<h2 192x256>" : "gemm3_tn_kernel<h2 192x256:176>";
+            r.what = "mpf_gemm3_tn_h2(192x256)";
+            r.threads = kT3T; r.lds = kT3Lds; r.attr = &attr;
+            r.blocks = round8(p.ntiles);
+            return r;
+        }
+    }
+    // 3. 128 x 256 / 96 x 256 tiles (gemm3_tn2_kernel: two 128-column passes over one A image per K step) for fp32 A without the
+    //    addend rows and N a multiple of 256; row blocks of 96 when they need fewer (rounds x rows) on the chip's workgroup slots
+    //    (M = 43 008, N = 256: 448 tiles instead of 336 for 512 slots)
+    if (!a2 && !a_bf16 && g_two_pass > 0 && N % 256 == 0 && N >= g_two_pass) {
+        const int slots = g3_slots();
+        p.tiles_n = N / 256;
+        const int t128 = cdiv(M, 128) * p.tiles_n, t96 = cdiv(M, 96) * p.tiles_n;
+        const bool rows96 = g_two_pass_rows == 96 || (g_two_pass_rows == 0 && cdiv(t96, slots) * 96 < cdiv(t128, slots) * 128);
+        p.ntiles = rows96 ? t96 : t128;
+        if (h2) {
+            r.fn = rows96 ? (const void*)gemm3_tn2_kernel<96, false, true> : (const void*)gemm3_tn2_kernel<128, false, true>;
+            r.name = rows96 ? "gemm3_tn_kernel<h2 96x256>" : "gemm3_tn_kernel<h2 128x256>";
+        } else {
+            r.fn = rows96 ? (const void*)gemm3_tn2_kernel<96> : (const void*)gemm3_tn2_kernel<128>;
+            r.name = rows96 ? "gemm3_tn_kernel<96x256>" : "gemm3_tn_kernel<128x256>";
+        }
+        r.blocks = round8(p.ntiles);
+        return r;
+    }
+    const bool w96 = ct.bn == 96;
+    r.blocks = round8(p.ntiles);
+    // 4. fp16 x 2, N % 256 != 0: the one-pass 128- / 96-column tiles
+    if (h2) {
+        r.fn = w96 ? (const void*)gemm3_tn_kernel<96, false, true> : (const void*)gemm3_tn_kernel<128, false, true>;
+        r.name = w96 ? "gemm3_tn_kernel<h2 96>" : "gemm3_tn_kernel<h2 128>";
+        r.what = "mpf_gemm3_tn_h2";
+        return r;
+    }
+    // 5. tail effect: when the last round of 128 x 128 tiles would fill at most half of the chip's workgroup slots, its row
+    //    blocks are cut into 128 x 64 tiles instead (gemm3_tn_mixed_kernel)
+    if (!w96 && N % 64 == 0 && g_mixed && !a_bf16 && !p.c16) {
+        const int slots = g3_slots(), rounds = p.ntiles / slots, rem = p.ntiles - rounds * slots;
+        if (rounds >= 1 && rem > 0 && 2 * rem <= slots && slots % p.tiles_n == 0) {
+            p.tm0 = rounds * (slots / p.tiles_n);
+            p.tiles_n2 = N / 64;
+            p.ntiles2 = (tiles_m - p.tm0) * p.tiles_n2;
+            p.ntiles = p.tm0 * p.tiles_n;
+            r.fn = a2 ? (const void*)gemm3_tn_mixed_kernel<true> : (const void*)gemm3_tn_mixed_kernel<false>;
+            r.name = "gemm3_tn_kernel<128+64>";
+            r.blocks = round8(p.ntiles) + round8(p.ntiles2);
+            return r;
+        }
+    }
+    // 6. one pass over 128 x 128 / 128 x 96 tiles
+    if (a_bf16) {
+        r.fn = w96 ? (const void*)gemm3_tn_abf_kernel<96> : (const void*)gemm3_tn_abf_kernel<128>;
+        r.name = "gemm3_tn_kernel<a16>";
+    } else if (a2) {
+        r.fn = w96 ? (const void*)gemm3_tn_kernel<96, true> : (const void*)gemm3_tn_kernel<128, true>;
+        r.name = w96 ? "gemm3_tn_kernel<96>" : "gemm3_tn_kernel<128>";
+    } else {
+        r.fn = w96 ? (const void*)gemm3_tn_kernel<96, false> : (const void*)gemm3_tn_kernel<128, false>;
+        r.name = p.c16 ? "gemm3_tn_kernel<c16>" : w96 ? "gemm3_tn_kernel<96>" : "gemm3_tn_kernel<128>";
+    }
+    return r;
+}
+
+// 3x3 convolution (p.cv_*): 128 x 256 two-pass tiles where Cout allows (always in the fp16 x 2 form, whose entry point requires
+// Cout % 256 == 0), else 128 x 128
+Route g3_conv_route(G3& p)
+{
+    const bool h2 = p.a_amax != nullptr, two_pass = h2 || (g_two_pass > 0 && p.N % 256 == 0);
+    Route r;
+    r.what = "mpf_gemm3_conv3x3";
+    r.w_el = h2 ? 4.0 : 6.0;
+    r.name = h2 ? "gemm3_conv_kernel<h2>" : "gemm3_conv_kernel";
+    r.fn = h2 ? (const void*)gemm3_tn2_kernel<128, true, true> : two_pass ? (const void*)gemm3_tn2_kernel<128, true> : (const void*)gemm3_conv_kernel;
+    p.tiles_n = two_pass ? p.N / 256 : cdiv(p.N, 128);
+    p.ntiles = cdiv(p.M, kBM) * p.tiles_n;
+    r.blocks = round8(p.ntiles);
+    return r;
+}
+
+int g3_tn_impl(const float* a, int64_t lda, const float* a2, int a2_rows, const void* b_planes,
+               const float* bias, const float* c_in, int64_t ldcin, const float* c_in2, int64_t ldcin2,
+               const float* gate, int64_t ldgate, float* c, int64_t ldc, int M, int N, int K,
+               int relu, void* stream, const float* a_amax, const float* b_amax, float* out_amax,
+               const unsigned char* gbits = nullptr, int64_t ldgbits = 0, unsigned char* gbits_out = nullptr,
+               int64_t ldgbits_out = 0)
+{
+    if (!a || !b_planes || !c) return mpf::fail(MPF_E_NULL, "gemm3_tn: NULL buffer");
+    if (M <= 0 || N <= 0 || K <= 0) return mpf::fail(MPF_E_SHAPE, "gemm3_tn: bad sizes");
+    if (K % kBK != 0 || N % 4 != 0 || lda % 4 != 0 || ldc % 4 != 0 || (c_in && ldcin % 4 != 0) || (c_in2 && ldcin2 % 4 != 0) ||
+        (gate && ldgate % 4 != 0))
+        return mpf::fail(MPF_E_SHAPE, "gemm3_tn: K must be a multiple of 32; N, lda, ldc multiples of 4");
+    if (a2 && a2_rows <= 0) return mpf::fail(MPF_E_SHAPE, "gemm3_tn: a2_rows must be positive");
+    G3 p;
+    if (int rc = g3_fill(p, "gemm3_tn: constants", a, lda, b_planes, bias, ldc, M, N, K)) return rc;
+    p.c = c; p.a2 = a2; p.a2_rows = a2_rows; p.relu = relu;
+    g3_operand(p.cin, p.ldcin, p.cin_cm, c_in, ldcin);
+    g3_operand(p.cin2, p.ldcin2, p.cin2_cm, c_in2, ldcin2);
+    g3_operand(p.gate, p.ldgate, p.gate_cm, gate, ldgate);
+    if (gbits) { p.gbits = gbits; p.ldgbits = ldgbits; p.gbits_cm = 1; }
+    p.gbits_out = gbits_out; p.ldgbits_out = ldgbits_out;
+    p.a_amax = a_amax; p.b_amax = b_amax; p.out_amax = out_amax;
+    const Route r = g3_tn_route(p, false, "mpf_gemm3_tn");
+    return g3_launch(r, p, (hipStream_t)stream, g3_tn_work(p, r));
+}
+
+int g3_conv_impl(const float* x, const void* w_planes, const float* bias, float* y, int n_img, int H, int W, int Cin,
+                 int Cout, int transposed, void* stream, const float* x_amax, const float* w_amax, float* out_amax)
+{
+    if (!x || !w_planes || !y) return mpf::fail(MPF_E_NULL, "gemm3_conv3x3: NULL buffer");
+    if (n_img <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 != 0 || Cout % 4 != 0)
+        return mpf::fail(MPF_E_SHAPE, "gemm3_conv3x3: Cin must be a multiple of 32, Cout of 4");
+    const int64_t M64 = (int64_t)n_img * H * W;
+    if (M64 >= (1ll << 31) / 4 || M64 * Cin >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_conv3x3: image too large");
+    G3 p;
+    if (int rc = g3_fill(p, "gemm3_conv3x3: constants", x, Cin, w_planes, bias, Cout, (int)M64, Cout, 9 * Cin)) return rc;
+    p.c = y;
+    p.cv_H = H; p.cv_W = W; p.cv_cin = Cin; p.cv_sign = transposed ? -1 : 1;
+    p.a_amax = x_amax; p.b_amax = w_amax; p.out_amax = out_amax;
+    const Route r = g3_conv_route(p);
+    return g3_launch(r, p, (hipStream_t)stream, g3_tn_work(p, r));
+}
+
+}  // namespace
 
 extern "C" int mpf_gemm3_tn(const float* a, int64_t lda, const float* a2, int a2_rows, const void* b_planes,
                             const float* bias, const float* c_in, int64_t ldcin, const float* c_in2, int64_t ldcin2,
@@ -1782,193 +1975,28 @@ extern "C" int mpf_gemm3_tn_h2_bits(const float* a, int64_t lda, const float* a_
                       a_amax, b_amax, out_amax, gate_bits, ldgbits, gate_bits_out, ldgbits_out);
 }
 
-static int g3_tn_impl(const float* a, int64_t lda, const float* a2, int a2_rows, const void* b_planes,
-                      const float* bias, const float* c_in, int64_t ldcin, const float* c_in2, int64_t ldcin2,
-                      const float* gate, int64_t ldgate, float* c, int64_t ldc, int M, int N, int K,
-                      int relu, void* stream, const float* a_amax, const float* b_amax, float* out_amax,
-                      const unsigned char* gbits, int64_t ldgbits, unsigned char* gbits_out, int64_t ldgbits_out)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (!a || !b_planes || !c) return mpf::fail(MPF_E_NULL, "gemm3_tn: NULL buffer");
-    if (M <= 0 || N <= 0 || K <= 0) return mpf::fail(MPF_E_SHAPE, "gemm3_tn: bad sizes");
-    if (K % kBK != 0 || N % 4 != 0 || lda % 4 != 0 || ldc % 4 != 0 || (c_in && ldcin % 4 != 0) || (c_in2 && ldcin2 % 4 != 0) ||
-        (gate && ldgate % 4 != 0))
-        return mpf::fail(MPF_E_SHAPE, "gemm3_tn: K must be a multiple of 32; N, lda, ldc multiples of 4");
-    if (a2 && a2_rows <= 0) return mpf::fail(MPF_E_SHAPE, "gemm3_tn: a2_rows must be positive");
-    G3 p;
-    p.a_amax = nullptr; p.b_amax = nullptr; p.out_amax = nullptr;
-    p.a = a; p.a2 = a2; p.bp = (const unsigned short*)b_planes; p.bias = bias; p.cin = c_in; p.c = c;
-    p.cin2 = c_in2; p.gate = gate; p.ldcin2 = ldcin2; p.ldgate = ldgate;
-    p.lda = lda; p.ldc = ldc; p.ldcin = ldcin; p.plane = (int64_t)N * K;
-    p.M = M; p.N = N; p.K = K; p.a2_rows = a2_rows; p.relu = relu; p.c16 = nullptr;
-    p.a_amax = a_amax; p.b_amax = b_amax; p.out_amax = out_amax;
-    {
-        const float* consts = nullptr;
-        if (int rc = g3_consts(&consts, "gemm3_tn: constants")) return rc;
-        p.bias_cm = bias ? 1 : 0; p.cin_cm = c_in ? 1 : 0; p.cin2_cm = c_in2 ? 1 : 0; p.gate_cm = gate ? 1 : 0;
-        if (!bias) p.bias = consts;
-        if (!c_in) { p.cin = consts; p.ldcin = 0; }
-        if (!c_in2) { p.cin2 = consts; p.ldcin2 = 0; }
-        if (!gate) { p.gate = consts + 4; p.ldgate = 0; }
-        g3_no_bits(p, consts);
-        if (gbits) { p.gbits = gbits; p.ldgbits = ldgbits; p.gbits_cm = 1; }
-        p.gbits_out = gbits_out; p.ldgbits_out = ldgbits_out;
-    }
-    const int tiles_m = (M + kBM - 1) / kBM;
-    // 96-wide column tiles when they waste fewer columns (e.g. N = 288 = 3 x 96)
-    const int waste128 = ((N + 127) / 128) * 128 - N, waste96 = ((N + 95) / 96) * 96 - N;
-    const bool use96 = waste96 < waste128;
-    p.tiles_n = use96 ? (N + 95) / 96 : (N + 127) / 128;
-    p.ntiles = tiles_m * p.tiles_n;
-    p.tm0 = 0; p.ntiles2 = 0; p.tiles_n2 = 0;
-    // (N >= g_ws: at N = 256 the 64 MB of weight fragments the workgroups fetch once per launch cost what the tiled kernel's re-reads do)
-    if (a_amax && !a2 && !gate && !c_in2 && g_ws > 0 && N >= g_ws && K == kWsK && N % 256 == 0 && ((uintptr_t)a & 15) == 0) {
-        const int r = g3_launch_ws(p, st);
-        if (r != -1000) return r;
-    }
-    // 192 x 256 tiles, ONE workgroup per CU: only where they fill the chip — the last (or only) round of tiles must cover at least
-    // 3/4 of the CUs (43 008 rows: 224 tiles on 256 CUs; 16 800 rows would be 88 tiles against 175 half-size tiles of the
-    // two-pass kernel on two workgroup slots per CU: config D's head measured 11.62 -> 11.79 ms per step with them)
-    bool tn3 = a_amax && !a2 && g_tn3 && N % 256 == 0 && M >= 2048 && ((uintptr_t)a & 15) == 0 && lda % 4 == 0;
-    int t3_bm = kT3BM;
-    if (tn3) {
-        const int cus = mpf::cu_count(), nt3 = ((M + kT3BM - 1) / kT3BM) * (N / 256), rem = nt3 % cus;
-        tn3 = g_tn3 == 2 || (nt3 >= cus * 3 / 4 && (rem == 0 || 4 * rem >= 3 * cus || nt3 >= 4 * cus));
-        // 176-row tiles (96 + 80: the second row half one MFMA row tile shorter) when they need no more rounds of the chip than
-        // 192-row tiles do: a workgroup's time goes with its rows, and 43 008 rows are 245 tiles of 176 on 256 CUs (224 of 192)
-        const int nt176 = ((M + 175) / 176) * (N / 256);
-        if (g_tn3_176 && (nt176 + cus - 1) / cus <= (nt3 + cus - 1) / cus) t3_bm = 176;
-    }
-    if (tn3) {
-        static mpf::LdsAttr attr;
-        if (int e = mpf::ensure_dynamic_lds((const void*)gemm3_tn3_kernel, kT3Lds, attr)) return e;
-        p.tiles_n = N / 256;
-        p.t3_bm = t3_bm;
-        p.ntiles = ((M + t3_bm - 1) / t3_bm) * p.tiles_n;
-        mpf::prof_begin(st);
-        mpf::set_kernel(t3_bm == kT3BM ? "gemm3_tn_kernel<h2 192x256>" : "gemm3_tn_kernel<h2 192x256:176>");
-        {
-            void* args[] = {(void*)&p};
-            if (hipError_t e = hipLaunchKernel((const void*)gemm3_tn3_kernel, dim3(((p.ntiles + 7) / 8) * 8), dim3(kT3T), args, kT3Lds, st); e != hipSuccess)
-                return mpf::check(e, "gemm3_tn3_kernel");
-        }
-        mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)M * K + (double)M * N) + 4.0 * (double)N * K, 2.0 * M * (double)N * K);
-        return mpf::check(hipGetLastError(), "mpf_gemm3_tn_h2(192x256)");
-    }
-    if (!a2 && g3_launch_two_pass(p, st)) {
-        mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)M * K + (double)M * N) + (a_amax ? 4.0 : 6.0) * (double)N * K, 2.0 * M * (double)N * K);
-        return mpf::check(hipGetLastError(), "mpf_gemm3_tn");
-    }
-    if (a_amax) {       // N % 256 != 0: the one-pass 128- / 96-column tiles
-        const int grid_h = ((p.ntiles + 7) / 8) * 8;
-        mpf::prof_begin(st);
-        if (use96) {
-            mpf::set_kernel("gemm3_tn_kernel<h2 96>");
-            hipLaunchKernelGGL((gemm3_tn_kernel<96, false, true>), dim3(grid_h), dim3(kThreads), 0, st, p);
-        } else {
-            mpf::set_kernel("gemm3_tn_kernel<h2 128>");
-            hipLaunchKernelGGL((gemm3_tn_kernel<128, false, true>), dim3(grid_h), dim3(kThreads), 0, st, p);
-        }
-        mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)M * K + (double)M * N) + 4.0 * (double)N * K, 2.0 * M * (double)N * K);
-        return mpf::check(hipGetLastError(), "mpf_gemm3_tn_h2");
-    }
-    // tail effect: when the last round of 128 x 128 tiles would fill at most half of the chip's workgroup slots, its row
-    // blocks are cut into 128 x 64 tiles instead (gemm3_tn_mixed_kernel)
-    if (!use96 && N % 64 == 0 && g_mixed) {
-        static int slots = 0;
-        if (!slots) {
-            int dev = 0, cus = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-                slots = 2 * cus;
-            else
-                slots = 512;
-        }
-        const int rounds = p.ntiles / slots, rem = p.ntiles - rounds * slots;
-        if (rounds >= 1 && rem > 0 && 2 * rem <= slots && slots % p.tiles_n == 0) {
-            const int main_blocks = rounds * (slots / p.tiles_n);
-            p.tm0 = main_blocks;
-            p.tiles_n2 = N / 64;
-            p.ntiles2 = (tiles_m - main_blocks) * p.tiles_n2;
-            p.ntiles = main_blocks * p.tiles_n;
-            const int grid_mixed = ((p.ntiles + 7) / 8) * 8 + ((p.ntiles2 + 7) / 8) * 8;
-            mpf::prof_begin(st);
-            mpf::set_kernel("gemm3_tn_kernel<128+64>");
-            if (a2) hipLaunchKernelGGL(gemm3_tn_mixed_kernel<true>, dim3(grid_mixed), dim3(kThreads), 0, st, p);
-            else hipLaunchKernelGGL(gemm3_tn_mixed_kernel<false>, dim3(grid_mixed), dim3(kThreads), 0, st, p);
-            mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)M * K + (double)M * N) + 6.0 * (double)N * K, 2.0 * M * (double)N * K);
-            return mpf::check(hipGetLastError(), "mpf_gemm3_tn");
-        }
-    }
-    const int grid = ((p.ntiles + 7) / 8) * 8;
-    mpf::prof_begin(st);
-    if (use96) {
-        mpf::set_kernel("gemm3_tn_kernel<96>");
-        if (a2) hipLaunchKernelGGL((gemm3_tn_kernel<96, true>), dim3(grid), dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL((gemm3_tn_kernel<96, false>), dim3(grid), dim3(kThreads), 0, st, p);
-    } else {
-        mpf::set_kernel("gemm3_tn_kernel<128>");
-        if (a2) hipLaunchKernelGGL((gemm3_tn_kernel<128, true>), dim3(grid), dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL((gemm3_tn_kernel<128, false>), dim3(grid), dim3(kThreads), 0, st, p);
-    }
-    mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)M * K + (double)M * N) + 6.0 * (double)N * K, 2.0 * M * (double)N * K);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_tn");
-}
-
 extern "C" int mpf_gemm3_tn_ex(const void* a, int a_dtype, int64_t lda, const void* b_planes, const float* bias, const float* c_in,
                                int64_t ldcin, void* c, int c_dtype, int64_t ldc, int M, int N, int K, int relu, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (!a || !b_planes || !c) return mpf::fail(MPF_E_NULL, "gemm3_tn_ex: NULL buffer");
     if ((a_dtype != MPF_F32 && a_dtype != MPF_BF16) || (c_dtype != MPF_F32 && c_dtype != MPF_BF16))
         return mpf::fail(MPF_E_DTYPE, "gemm3_tn_ex: a / c must be MPF_F32 or MPF_BF16");
-    const int aal = a_dtype == MPF_BF16 ? 8 : 4;
-    if (M <= 0 || N <= 0 || K <= 0 || K % kBK != 0 || N % 4 != 0 || lda % aal != 0 || ldc % 4 != 0 || (c_in && ldcin % 4 != 0) ||
+    const bool a16 = a_dtype == MPF_BF16;
+    if (M <= 0 || N <= 0 || K <= 0 || K % kBK != 0 || N % 4 != 0 || lda % (a16 ? 8 : 4) != 0 || ldc % 4 != 0 || (c_in && ldcin % 4 != 0) ||
         ((uintptr_t)a & 15))
         return mpf::fail(MPF_E_SHAPE, "gemm3_tn_ex: K must be a multiple of 32, N / ldc of 4, 16-byte aligned A rows");
-    if (a_dtype == MPF_F32 && c_dtype == MPF_F32)
+    if (!a16 && c_dtype == MPF_F32)
         return mpf_gemm3_tn((const float*)a, lda, nullptr, 0, b_planes, bias, c_in, ldcin, nullptr, 0, nullptr, 0, (float*)c, ldc, M, N, K, relu, stream);
-    const float* consts = nullptr;
-    if (int rc = g3_consts(&consts, "gemm3_tn_ex: constants")) return rc;
     G3 p;
-    p.a_amax = nullptr; p.b_amax = nullptr; p.out_amax = nullptr;
-    p.a = (const float*)a; p.a2 = nullptr; p.bp = (const unsigned short*)b_planes;
-    p.bias = bias ? bias : consts; p.bias_cm = bias ? 1 : 0;
-    p.cin = c_in ? c_in : consts; p.ldcin = c_in ? ldcin : 0; p.cin_cm = c_in ? 1 : 0;
-    p.cin2 = consts; p.ldcin2 = 0; p.cin2_cm = 0; p.gate = consts + 4; p.ldgate = 0; p.gate_cm = 0;
-    g3_no_bits(p, consts);
-    p.c = c_dtype == MPF_F32 ? (float*)c : nullptr; p.c16 = c_dtype == MPF_BF16 ? (unsigned short*)c : nullptr;
-    p.lda = lda; p.ldc = ldc; p.plane = (int64_t)N * K;
-    p.M = M; p.N = N; p.K = K; p.a2_rows = 0; p.relu = relu;
-    p.cv_H = p.cv_W = p.cv_cin = 0; p.cv_sign = 1;
-    p.tm0 = 0; p.ntiles2 = 0; p.tiles_n2 = 0;
-    const int tiles_m = (M + kBM - 1) / kBM;
-    const int waste128 = ((N + 127) / 128) * 128 - N, waste96 = ((N + 95) / 96) * 96 - N;
-    const bool use96 = waste96 < waste128;
-    p.tiles_n = use96 ? (N + 95) / 96 : (N + 127) / 128;
-    p.ntiles = tiles_m * p.tiles_n;
-    if (a_dtype == MPF_F32 && g3_launch_two_pass(p, st)) {
-        mpf::prof_end(mpf_last_kernel(), st, 4.0 * (double)M * K + 2.0 * (double)M * N + 6.0 * (double)N * K, 2.0 * M * (double)N * K);
-        return mpf::check(hipGetLastError(), "mpf_gemm3_tn_ex");
-    }
-    const dim3 grid(((p.ntiles + 7) / 8) * 8);
-    mpf::prof_begin(st);
-    if (a_dtype == MPF_BF16) {
-        mpf::set_kernel("gemm3_tn_kernel<a16>");
-        if (use96) hipLaunchKernelGGL(gemm3_tn_abf_kernel<96>, grid, dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL(gemm3_tn_abf_kernel<128>, grid, dim3(kThreads), 0, st, p);
-    } else {
-        mpf::set_kernel("gemm3_tn_kernel<c16>");
-        if (use96) hipLaunchKernelGGL((gemm3_tn_kernel<96, false>), grid, dim3(kThreads), 0, st, p);
-        else hipLaunchKernelGGL((gemm3_tn_kernel<128, false>), grid, dim3(kThreads), 0, st, p);
-    }
+    if (int rc = g3_fill(p, "gemm3_tn_ex: constants", a, lda, b_planes, bias, ldc, M, N, K)) return rc;
+    if (c_dtype == MPF_BF16) p.c16 = (unsigned short*)c;
+    else p.c = (float*)c;
+    p.relu = relu;
+    g3_operand(p.cin, p.ldcin, p.cin_cm, c_in, ldcin);
+    const Route r = g3_tn_route(p, a16, "mpf_gemm3_tn_ex");
     // flops: the fp32 GEMM it stands for (a bf16 A needs 3 of the 6 products)
-    mpf::prof_end(mpf_last_kernel(), st, (a_dtype == MPF_BF16 ? 2.0 : 4.0) * (double)M * K + (c_dtype == MPF_BF16 ? 2.0 : 4.0) * (double)M * N + 6.0 * (double)N * K,
-                  2.0 * M * (double)N * K);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_tn_ex");
+    return g3_launch(r, p, (hipStream_t)stream, g3_tn_work(p, r, a16 ? 2.0 : 4.0));
 }
-
-static int g3_conv_impl(const float* x, const void* w_planes, const float* bias, float* y, int n_img, int H, int W, int Cin,
-                        int Cout, int transposed, void* stream, const float* x_amax, const float* w_amax, float* out_amax);
 
 extern "C" int mpf_gemm3_conv3x3(const float* x, const void* w_planes, const float* bias, float* y, int n_img, int H, int W, int Cin,
                                  int Cout, int transposed, void* stream)
@@ -1984,149 +2012,92 @@ extern "C" int mpf_gemm3_conv3x3_h2(const float* x, const float* x_amax, const v
     return g3_conv_impl(x, w_planes_h2, bias, y, n_img, H, W, Cin, Cout, transposed, stream, x_amax, w_amax, out_amax);
 }
 
-static int g3_conv_impl(const float* x, const void* w_planes, const float* bias, float* y, int n_img, int H, int W, int Cin,
-                        int Cout, int transposed, void* stream, const float* x_amax, const float* w_amax, float* out_amax)
+// ---- NT products (weight gradients; G3N) ----
+namespace {
+
+// A weight-gradient problem over R rows with nothing optional: no b2, no column sums of B, no transposed output, no convolution,
+// fp32 form; dense partial results per split.  el_a / el_b: bytes per element of the operands (4, or 2 for a bf16 matrix).  The
+// operands' spans feed the buffer descriptors and must stay below 4 GiB (a row pitch below 2 GiB).
+int g3n_fill(G3N& p, const char* who, const void* a, int64_t lda, int el_a, const void* b, int64_t ldb, int el_b, float* c_part,
+             float* csum_a, int R, int Mdim, int Ndim, int rows_per_split)
 {
-    hipStream_t st = (hipStream_t)stream;
-    if (!x || !w_planes || !y) return mpf::fail(MPF_E_NULL, "gemm3_conv3x3: NULL buffer");
-    if (n_img <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 != 0 || Cout % 4 != 0)
-        return mpf::fail(MPF_E_SHAPE, "gemm3_conv3x3: Cin must be a multiple of 32, Cout of 4");
-    const int64_t M64 = (int64_t)n_img * H * W;
-    if (M64 >= (1ll << 31) / 4 || M64 * Cin >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_conv3x3: image too large");
-    G3 p;
-    p.a_amax = nullptr; p.b_amax = nullptr; p.out_amax = nullptr;
-    const float* consts = nullptr;
-    if (int rc = g3_consts(&consts, "gemm3_conv3x3: constants")) return rc;
-    p.a = x; p.a2 = nullptr; p.bp = (const unsigned short*)w_planes; p.c = y;
-    p.bias = bias ? bias : consts; p.bias_cm = bias ? 1 : 0;
-    p.cin = consts; p.ldcin = 0; p.cin_cm = 0; p.cin2 = consts; p.ldcin2 = 0; p.cin2_cm = 0; p.gate = consts + 4; p.ldgate = 0; p.gate_cm = 0;
-    g3_no_bits(p, consts);
-    p.M = (int)M64; p.N = Cout; p.K = 9 * Cin; p.lda = Cin; p.ldc = Cout; p.plane = (int64_t)Cout * p.K;
-    p.a2_rows = 0; p.relu = 0; p.c16 = nullptr;
-    p.cv_H = H; p.cv_W = W; p.cv_cin = Cin; p.cv_sign = transposed ? -1 : 1;
-    p.tiles_n = (Cout + 127) / 128;
-    p.ntiles = ((p.M + kBM - 1) / kBM) * p.tiles_n;
-    p.tm0 = 0; p.ntiles2 = 0; p.tiles_n2 = 0;
-    mpf::prof_begin(st);
-    mpf::set_kernel("gemm3_conv_kernel");
-    p.a_amax = x_amax; p.b_amax = w_amax; p.out_amax = out_amax;
-    if (x_amax) mpf::set_kernel("gemm3_conv_kernel<h2>");
-    if (x_amax) {
-        p.tiles_n = Cout / 256;
-        p.ntiles = ((p.M + kBM - 1) / kBM) * p.tiles_n;
-        hipLaunchKernelGGL((gemm3_tn2_kernel<128, true, true>), dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    } else if (g_two_pass > 0 && Cout % 256 == 0) {       // 128 x 256 tiles, two passes over one A image per K step
-        p.tiles_n = Cout / 256;
-        p.ntiles = ((p.M + kBM - 1) / kBM) * p.tiles_n;
-        hipLaunchKernelGGL((gemm3_tn2_kernel<128, true>), dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    } else
-    hipLaunchKernelGGL(gemm3_conv_kernel, dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)p.M * Cin + (double)p.M * Cout) + (x_amax ? 4.0 : 6.0) * (double)Cout * p.K,
-                  2.0 * p.M * (double)Cout * p.K);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_conv3x3");
+    const uint64_t ab = ((uint64_t)(R - 1) * lda + Mdim) * el_a, bb = ((uint64_t)(R - 1) * ldb + Ndim) * el_b;
+    if (ab >= (1ull << 32) || bb >= (1ull << 32) || lda * el_a >= (1ll << 31) || ldb * el_b >= (1ll << 31)) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "%s: an operand spans 4 GiB or more", who);
+        return mpf::fail(MPF_E_TOO_LARGE, msg);
+    }
+    p = G3N{};
+    p.a = (const float*)a; p.b = (const float*)b; p.c = c_part; p.csum_a = csum_a;
+    p.lda = lda; p.ldb = ldb;
+    p.R = R; p.Mdim = Mdim; p.Ndim = Ndim; p.rows_per_split = rows_per_split;
+    p.nsplit = cdiv(R, rows_per_split);
+    p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
+    p.c_ss = (int64_t)Mdim * Ndim; p.csa_ss = Mdim; p.csb_ss = Ndim;
+    return 0;
 }
 
-static int g3_nt_impl(const float* a, int64_t lda, const float* b, int64_t ldb, const float* b2, int64_t ldb2, int b2_rows,
-                      float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
-                      int transpose_out, void* stream, const float* a_amax, const float* b_amax);
-
-extern "C" int mpf_gemm3_nt(const float* a, int64_t lda, const float* b, int64_t ldb, const float* b2, int64_t ldb2, int b2_rows,
-                            float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
-                            int transpose_out, void* stream)
+// bm x bn output tiles, each over every split
+inline void g3n_tiles(G3N& p, int bm, int bn)
 {
-    return g3_nt_impl(a, lda, b, ldb, b2, ldb2, b2_rows, c_part, csum_a, csum_b, R, Mdim, Ndim, rows_per_split, transpose_out, stream,
-                      nullptr, nullptr);
+    p.tiles_m = cdiv(p.Mdim, bm);
+    p.tiles_n = cdiv(p.Ndim, bn);
+    p.ntiles = p.tiles_m * p.tiles_n * p.nsplit;
 }
 
-extern "C" int mpf_gemm3_nt_h2(const float* a, int64_t lda, const float* a_amax, const float* b, int64_t ldb, const float* b_amax,
-                               float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
-                               int transpose_out, void* stream)
+inline Route g3n_route(const void* fn, const char* name, const char* what, int tiles)
 {
-    if (!a_amax || !b_amax) return mpf::fail(MPF_E_NULL, "gemm3_nt_h2: NULL amax");
-    return g3_nt_impl(a, lda, b, ldb, nullptr, 0, 0, c_part, csum_a, csum_b, R, Mdim, Ndim, rows_per_split, transpose_out, stream,
-                      a_amax, b_amax);
+    Route r;
+    r.fn = fn; r.name = name; r.what = what; r.blocks = round8(tiles);
+    return r;
 }
 
-static int g3_nt_impl(const float* a, int64_t lda, const float* b, int64_t ldb, const float* b2, int64_t ldb2, int b2_rows,
-                      float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
-                      int transpose_out, void* stream, const float* a_amax, const float* b_amax)
+// the 256 x 256 tiles of gemm3_nt2.h: 8 waves, one workgroup per CU
+inline Route g3n_route_256(const void* fn, mpf::LdsAttr& attr, const char* name, const char* what, int tiles)
 {
-    hipStream_t st = (hipStream_t)stream;
+    Route r = g3n_route(fn, name, what, tiles);
+    r.threads = kN2T; r.lds = kN2Lds; r.attr = &attr;
+    return r;
+}
+
+// both operands and every split's partial result once (B: Ndim columns, or the cv_cin channels of the image in convolution mode)
+inline Work g3n_work(const G3N& p, double a_el = 4.0, double b_el = 4.0)
+{
+    const double R = p.R, M = p.Mdim, N = p.Ndim;
+    return {a_el * R * M + b_el * R * (p.cv_cin ? p.cv_cin : p.Ndim) + 4.0 * p.nsplit * M * N, 2.0 * R * M * N};
+}
+
+int g3_nt_impl(const float* a, int64_t lda, const float* b, int64_t ldb, const float* b2, int64_t ldb2, int b2_rows,
+               float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
+               int transpose_out, void* stream, const float* a_amax, const float* b_amax)
+{
     if (!a || !b || !c_part) return mpf::fail(MPF_E_NULL, "gemm3_nt: NULL buffer");
     if (R <= 0 || Mdim <= 0 || Ndim <= 0 || rows_per_split <= 0 || rows_per_split % kBK != 0)
         return mpf::fail(MPF_E_SHAPE, "gemm3_nt: bad sizes (rows_per_split must be a positive multiple of 32)");
     if (b2 && b2_rows <= 0) return mpf::fail(MPF_E_SHAPE, "gemm3_nt: b2_rows must be positive");
     if (!transpose_out && Ndim % 4 != 0) return mpf::fail(MPF_E_SHAPE, "gemm3_nt: Ndim must be a multiple of 4 unless transpose_out");
     G3N p;
-    p.a_amax = nullptr; p.b_amax = nullptr;
-    p.a = a; p.b = b; p.b2 = b2; p.c = c_part; p.csum_a = csum_a; p.csum_b = csum_b;
-    p.lda = lda; p.ldb = ldb; p.ldb2 = ldb2;
-    p.R = R; p.Mdim = Mdim; p.Ndim = Ndim; p.b2_rows = b2_rows; p.rows_per_split = rows_per_split;
-    p.nsplit = (R + rows_per_split - 1) / rows_per_split;
-    p.transpose_out = transpose_out;
-    {
-        const uint64_t ab = ((uint64_t)(R - 1) * lda + Mdim) * 4, bb = ((uint64_t)(R - 1) * ldb + Ndim) * 4;
-        if (ab >= (1ull << 32) || bb >= (1ull << 32) || lda * 4 >= (1ll << 31) || ldb * 4 >= (1ll << 31))
-            return mpf::fail(MPF_E_TOO_LARGE, "gemm3_nt: an operand spans 4 GiB or more");
-        p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-    }
-    p.tiles_m = (Mdim + kBM - 1) / kBM;
-    const int waste128 = ((Ndim + 127) / 128) * 128 - Ndim, waste96 = ((Ndim + 95) / 96) * 96 - Ndim;
-    const bool use96 = waste96 < waste128;
-    p.tiles_n = use96 ? (Ndim + 95) / 96 : (Ndim + 127) / 128;
-    p.ntiles = p.tiles_m * p.tiles_n * p.nsplit;
-    p.c_ss = (int64_t)p.Mdim * p.Ndim; p.csa_ss = p.Mdim; p.csb_ss = p.Ndim;
-    const int grid = ((p.ntiles + 7) / 8) * 8;
+    if (int rc = g3n_fill(p, "gemm3_nt", a, lda, 4, b, ldb, 4, c_part, csum_a, R, Mdim, Ndim, rows_per_split)) return rc;
+    p.b2 = b2; p.ldb2 = ldb2; p.b2_rows = b2_rows; p.csum_b = csum_b; p.transpose_out = transpose_out;
     p.a_amax = a_amax; p.b_amax = b_amax;
-    mpf::prof_begin(st);
-    if (a_amax) {
-        if (use96) {
-            mpf::set_kernel("gemm3_nt_kernel<96>h2");
-            hipLaunchKernelGGL((gemm3_nt_kernel<96, false, false, false, false, true>), dim3(grid), dim3(kThreads), 0, st, p);
-        } else {
-            mpf::set_kernel("gemm3_nt_kernel<128>h2");
-            hipLaunchKernelGGL((gemm3_nt_kernel<128, false, false, false, false, true>), dim3(grid), dim3(kThreads), 0, st, p);
-        }
-    } else if (use96) {
-        mpf::set_kernel("gemm3_nt_kernel<96>");
-        hipLaunchKernelGGL(gemm3_nt_kernel<96>, dim3(grid), dim3(kThreads), 0, st, p);
-    } else {
-        mpf::set_kernel("gemm3_nt_kernel<128>");
-        hipLaunchKernelGGL(gemm3_nt_kernel<128>, dim3(grid), dim3(kThreads), 0, st, p);
-    }
-    mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)R * Mdim + (double)R * Ndim + (double)p.nsplit * Mdim * Ndim),
-                  2.0 * R * (double)Mdim * Ndim);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_nt");
+    const bool w96 = g3_col_tile(Ndim).bn == 96;
+    g3n_tiles(p, kBM, w96 ? 96 : 128);
+    const void* fn = a_amax ? (w96 ? (const void*)gemm3_nt_kernel<96, false, false, false, false, true>
+                                   : (const void*)gemm3_nt_kernel<128, false, false, false, false, true>)
+                            : (w96 ? (const void*)gemm3_nt_kernel<96> : (const void*)gemm3_nt_kernel<128>);
+    const char* name = a_amax ? (w96 ? "gemm3_nt_kernel<96>h2" : "gemm3_nt_kernel<128>h2") : (w96 ? "gemm3_nt_kernel<96>" : "gemm3_nt_kernel<128>");
+    return g3_launch(g3n_route(fn, name, "mpf_gemm3_nt", p.ntiles), p, (hipStream_t)stream, g3n_work(p));
 }
 
 template <typename Item, bool H2>
-static int g3_nt_grouped_impl(const Item* items, int n_items, int R, int rows_per_split, int64_t split_stride, void* stream);
-
-extern "C" int mpf_gemm3_nt_grouped(const MpfNtItem* items, int n_items, int R, int rows_per_split, int64_t split_stride,
-                                    void* stream)
+int g3_nt_grouped_impl(const Item* items, int n_items, int R, int rows_per_split, int64_t split_stride, void* stream)
 {
-    return g3_nt_grouped_impl<MpfNtItem, false>(items, n_items, R, rows_per_split, split_stride, stream);
-}
-
-extern "C" int mpf_gemm3_nt_grouped_h2(const MpfNtItemH2* items, int n_items, int R, int rows_per_split, int64_t split_stride,
-                                       void* stream)
-{
-    return g3_nt_grouped_impl<MpfNtItemH2, true>(items, n_items, R, rows_per_split, split_stride, stream);
-}
-
-template <typename Item, bool H2>
-static int g3_nt_grouped_impl(const Item* items, int n_items, int R, int rows_per_split, int64_t split_stride, void* stream)
-{
-    hipStream_t st = (hipStream_t)stream;
     if (!items) return mpf::fail(MPF_E_NULL, "gemm3_nt_grouped: NULL items");
     if (n_items <= 0 || n_items > kNtGroupMax) return mpf::fail(MPF_E_SHAPE, "gemm3_nt_grouped: 1..8 items");
     if (R <= 0 || rows_per_split <= 0 || rows_per_split % kBK != 0 || split_stride <= 0)
         return mpf::fail(MPF_E_SHAPE, "gemm3_nt_grouped: bad sizes (rows_per_split must be a positive multiple of 32)");
-    G3NG g;
-    memset(&g, 0, sizeof(g));
-    const int nsplit = (R + rows_per_split - 1) / rows_per_split;
-    int tiles = 0;
-    double bytes = 0.0, flops = 0.0;
+    G3NG g{};
+    Work w{0.0, 0.0};
     bool big = H2 && g_nt2;                          // 256 x 256 tiles (gemm3_nt2.h): every dimension a multiple of 256
     for (int i = 0; i < n_items && big; ++i) big = items[i].Mdim % 256 == 0 && items[i].Ndim % 256 == 0 && items[i].Mdim > 0 && items[i].Ndim > 0;
     for (int i = 0; i < n_items; ++i) {
@@ -2135,45 +2106,59 @@ static int g3_nt_grouped_impl(const Item* items, int n_items, int R, int rows_pe
         if (it.Mdim <= 0 || it.Ndim <= 0 || it.Ndim % 4 != 0 || it.Mdim > (1 << 20) || it.Ndim > (1 << 20))
             return mpf::fail(MPF_E_SHAPE, "gemm3_nt_grouped: Ndim must be a positive multiple of 4");
         G3N& p = g.it[i];
-        p.a = it.a; p.b = it.b; p.b2 = nullptr; p.c = it.c_part; p.csum_a = it.csum_a; p.csum_b = nullptr;
-        p.lda = it.lda; p.ldb = it.ldb; p.ldb2 = 0;
-        p.R = R; p.Mdim = (int)it.Mdim; p.Ndim = (int)it.Ndim; p.b2_rows = 0; p.rows_per_split = rows_per_split;
-        p.nsplit = nsplit;
-        p.transpose_out = 0;
-        const uint64_t ab = ((uint64_t)(R - 1) * it.lda + it.Mdim) * 4, bb = ((uint64_t)(R - 1) * it.ldb + it.Ndim) * 4;
-        if (ab >= (1ull << 32) || bb >= (1ull << 32) || it.lda * 4 >= (1ll << 31) || it.ldb * 4 >= (1ll << 31))
-            return mpf::fail(MPF_E_TOO_LARGE, "gemm3_nt_grouped: an operand spans 4 GiB or more");
-        p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-        p.tiles_m = big ? p.Mdim / 256 : (p.Mdim + kBM - 1) / kBM;
-        p.tiles_n = big ? p.Ndim / 256 : (p.Ndim + 127) / 128;
-        p.ntiles = p.tiles_m * p.tiles_n * nsplit;
+        if (int rc = g3n_fill(p, "gemm3_nt_grouped", it.a, it.lda, 4, it.b, it.ldb, 4, it.c_part, it.csum_a, R, (int)it.Mdim, (int)it.Ndim,
+                              rows_per_split))
+            return rc;
         p.c_ss = p.csa_ss = split_stride; p.csb_ss = 0;
-        p.a_amax = nullptr; p.b_amax = nullptr;
+        g3n_tiles(p, big ? 256 : kBM, big ? 256 : 128);
         if constexpr (H2) {
             if (!it.a_amax || !it.b_amax) return mpf::fail(MPF_E_NULL, "gemm3_nt_grouped_h2: NULL amax");
             p.a_amax = it.a_amax; p.b_amax = it.b_amax;
         }
-        tiles += p.ntiles;
-        g.tile_end[i] = tiles;
-        bytes += 4.0 * ((double)R * p.Mdim + (double)R * p.Ndim + (double)nsplit * p.Mdim * p.Ndim);
-        flops += 2.0 * R * (double)p.Mdim * p.Ndim;
+        g.ntiles += p.ntiles;
+        g.tile_end[i] = g.ntiles;
+        const Work wi = g3n_work(p);
+        w.bytes += wi.bytes; w.flops += wi.flops;
     }
-    g.n_items = n_items; g.ntiles = tiles;
-    if (big) {
-        static mpf::LdsAttr attr;
-        if (int e = mpf::ensure_dynamic_lds((const void*)gemm3_nt2_group_kernel, kN2Lds, attr)) return e;
-        mpf::prof_begin(st);
-        mpf::set_kernel("gemm3_nt_group_kernel<h2 256x256>");
-        hipLaunchKernelGGL(gemm3_nt2_group_kernel, dim3(((tiles + 7) / 8) * 8), dim3(kN2T), kN2Lds, st, g);
-        mpf::prof_end(mpf_last_kernel(), st, bytes, flops);
-        return mpf::check(hipGetLastError(), "mpf_gemm3_nt_grouped(256x256)");
-    }
-    mpf::prof_begin(st);
-    mpf::set_kernel(H2 ? "gemm3_nt_group_kernel<h2>" : "gemm3_nt_group_kernel");
-    hipLaunchKernelGGL(gemm3_nt_group_kernel<H2>, dim3(((tiles + 7) / 8) * 8), dim3(kThreads), 0, st, g);
-    mpf::prof_end(mpf_last_kernel(), st, bytes, flops);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_nt_grouped");
+    g.n_items = n_items;
+    static mpf::LdsAttr attr;
+    const Route r = big ? g3n_route_256((const void*)gemm3_nt2_group_kernel, attr, "gemm3_nt_group_kernel<h2 256x256>",
+                                        "mpf_gemm3_nt_grouped(256x256)", g.ntiles)
+                        : g3n_route((const void*)gemm3_nt_group_kernel<H2>, H2 ? "gemm3_nt_group_kernel<h2>" : "gemm3_nt_group_kernel",
+                                    "mpf_gemm3_nt_grouped", g.ntiles);
+    return g3_launch(r, g, (hipStream_t)stream, w);
 }
+
+int g3_conv_wgrad_impl(const float* dy, const float* x, float* c_part, float* csum_dy, int n_img, int H, int W, int Cin,
+                       int Cout, int rows_per_split, void* stream, const float* dy_amax, const float* x_amax)
+{
+    if (!dy || !x || !c_part) return mpf::fail(MPF_E_NULL, "gemm3_conv3x3_wgrad: NULL buffer");
+    if (n_img <= 0 || H <= 0 || W <= 0 || W % 8 != 0 || Cin <= 0 || Cin % 128 != 0 || Cout <= 0 || rows_per_split <= 0 ||
+        rows_per_split % kBK != 0)
+        return mpf::fail(MPF_E_SHAPE, "gemm3_conv3x3_wgrad: needs W % 8 == 0, Cin % 128 == 0, rows_per_split % 32 == 0");
+    const int64_t R64 = (int64_t)n_img * H * W;
+    if (R64 * (Cin > Cout ? Cin : Cout) * 4 >= (1ll << 32)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_conv3x3_wgrad: an operand spans 4 GiB or more");
+    G3N p;
+    // B in memory is the image [R, Cin]; the product's columns are (tap, channel)
+    if (int rc = g3n_fill(p, "gemm3_conv3x3_wgrad", dy, Cout, 4, x, Cin, 4, c_part, csum_dy, (int)R64, Cout, Cin, rows_per_split)) return rc;
+    p.Ndim = 9 * Cin; p.c_ss = (int64_t)p.Mdim * p.Ndim; p.csb_ss = p.Ndim;
+    p.cv_H = H; p.cv_W = W; p.cv_cin = Cin;
+    p.a_amax = dy_amax; p.b_amax = x_amax;
+    Route r;
+    if (dy_amax && g_nt2 && Cout % 256 == 0 && Cin % 256 == 0) {       // 256 x 256 tiles (gemm3_nt2.h): half the operand traffic
+        static mpf::LdsAttr attr;
+        g3n_tiles(p, 256, 256);
+        r = g3n_route_256((const void*)gemm3_nt2_conv_kernel, attr, "gemm3_nt_kernel<conv3x3 h2 256x256>", "mpf_gemm3_conv3x3_wgrad(256x256)",
+                          p.ntiles);
+    } else {
+        g3n_tiles(p, kBM, 128);
+        r = dy_amax ? g3n_route((const void*)gemm3_nt_kernel<128, false, true, false, false, true>, "gemm3_nt_kernel<conv3x3 h2>",
+                                "mpf_gemm3_conv3x3_wgrad", p.ntiles)
+                    : g3n_route((const void*)gemm3_nt_kernel<128, false, true>, "gemm3_nt_kernel<conv3x3>", "mpf_gemm3_conv3x3_wgrad", p.ntiles);
+    }
+    return g3_launch(r, p, (hipStream_t)stream, g3n_work(p));
+}
+}  // namespace
 
 namespace {
 
@@ -2220,10 +2205,38 @@ __global__ __launch_bounds__(256) void nt_reduce_kernel(const float* __restrict_
 
 }  // namespace
 
+extern "C" int mpf_gemm3_nt(const float* a, int64_t lda, const float* b, int64_t ldb, const float* b2, int64_t ldb2, int b2_rows,
+                            float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
+                            int transpose_out, void* stream)
+{
+    return g3_nt_impl(a, lda, b, ldb, b2, ldb2, b2_rows, c_part, csum_a, csum_b, R, Mdim, Ndim, rows_per_split, transpose_out, stream,
+                      nullptr, nullptr);
+}
+
+extern "C" int mpf_gemm3_nt_h2(const float* a, int64_t lda, const float* a_amax, const float* b, int64_t ldb, const float* b_amax,
+                               float* c_part, float* csum_a, float* csum_b, int R, int Mdim, int Ndim, int rows_per_split,
+                               int transpose_out, void* stream)
+{
+    if (!a_amax || !b_amax) return mpf::fail(MPF_E_NULL, "gemm3_nt_h2: NULL amax");
+    return g3_nt_impl(a, lda, b, ldb, nullptr, 0, 0, c_part, csum_a, csum_b, R, Mdim, Ndim, rows_per_split, transpose_out, stream,
+                      a_amax, b_amax);
+}
+
+extern "C" int mpf_gemm3_nt_grouped(const MpfNtItem* items, int n_items, int R, int rows_per_split, int64_t split_stride,
+                                    void* stream)
+{
+    return g3_nt_grouped_impl<MpfNtItem, false>(items, n_items, R, rows_per_split, split_stride, stream);
+}
+
+extern "C" int mpf_gemm3_nt_grouped_h2(const MpfNtItemH2* items, int n_items, int R, int rows_per_split, int64_t split_stride,
+                                       void* stream)
+{
+    return g3_nt_grouped_impl<MpfNtItemH2, true>(items, n_items, R, rows_per_split, split_stride, stream);
+}
+
 extern "C" int mpf_gemm3_nt_ex(const void* a, int a_dtype, int64_t lda, const void* b, int b_dtype, int64_t ldb, float* c_part,
                                float* csum_a, int R, int Mdim, int Ndim, int rows_per_split, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (!a || !b || !c_part) return mpf::fail(MPF_E_NULL, "gemm3_nt_ex: NULL buffer");
     const bool a16 = a_dtype == MPF_BF16, b16 = b_dtype == MPF_BF16;
     if ((!a16 && a_dtype != MPF_F32) || (!b16 && b_dtype != MPF_F32) || (a16 && b16))
@@ -2233,34 +2246,12 @@ extern "C" int mpf_gemm3_nt_ex(const void* a, int a_dtype, int64_t lda, const vo
     if (R <= 0 || Mdim <= 0 || Ndim <= 0 || Ndim % 128 != 0 || rows_per_split <= 0 || rows_per_split % kBK != 0)
         return mpf::fail(MPF_E_SHAPE, "gemm3_nt_ex: Ndim must be a multiple of 128, rows_per_split a positive multiple of 32");
     G3N p;
-    p.a_amax = nullptr; p.b_amax = nullptr;
-    p.a = (const float*)a; p.b = (const float*)b; p.b2 = nullptr; p.c = c_part; p.csum_a = csum_a; p.csum_b = nullptr;
-    p.lda = lda; p.ldb = ldb; p.ldb2 = 0;
-    p.R = R; p.Mdim = Mdim; p.Ndim = Ndim; p.b2_rows = 0; p.rows_per_split = rows_per_split;
-    p.nsplit = (R + rows_per_split - 1) / rows_per_split;
-    p.transpose_out = 0;
-    p.cv_H = p.cv_W = p.cv_cin = 0;
-    {
-        const uint64_t ab = ((uint64_t)(R - 1) * lda + Mdim) * (a16 ? 2 : 4), bb = ((uint64_t)(R - 1) * ldb + Ndim) * (b16 ? 2 : 4);
-        if (ab >= (1ull << 32) || bb >= (1ull << 32)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_nt_ex: an operand spans 4 GiB or more");
-        p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-    }
-    p.tiles_m = (Mdim + kBM - 1) / kBM;
-    p.tiles_n = Ndim / 128;
-    p.ntiles = p.tiles_m * p.tiles_n * p.nsplit;
-    p.c_ss = (int64_t)p.Mdim * p.Ndim; p.csa_ss = p.Mdim; p.csb_ss = p.Ndim;
-    const dim3 grid(((p.ntiles + 7) / 8) * 8);
-    mpf::prof_begin(st);
-    mpf::set_kernel(a16 ? "gemm3_nt_kernel<a16>" : "gemm3_nt_kernel<b16>");
-    if (a16) hipLaunchKernelGGL((gemm3_nt_kernel<128, false, false, true, false>), grid, dim3(kThreads), 0, st, p);
-    else hipLaunchKernelGGL((gemm3_nt_kernel<128, false, false, false, true>), grid, dim3(kThreads), 0, st, p);
-    mpf::prof_end(mpf_last_kernel(), st, (a16 ? 2.0 : 4.0) * (double)R * Mdim + (b16 ? 2.0 : 4.0) * (double)R * Ndim + 4.0 * (double)p.nsplit * Mdim * Ndim,
-                  2.0 * R * (double)Mdim * Ndim);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_nt_ex");
+    if (int rc = g3n_fill(p, "gemm3_nt_ex", a, lda, a16 ? 2 : 4, b, ldb, b16 ? 2 : 4, c_part, csum_a, R, Mdim, Ndim, rows_per_split)) return rc;
+    g3n_tiles(p, kBM, 128);
+    const Route r = a16 ? g3n_route((const void*)gemm3_nt_kernel<128, false, false, true, false>, "gemm3_nt_kernel<a16>", "mpf_gemm3_nt_ex", p.ntiles)
+                        : g3n_route((const void*)gemm3_nt_kernel<128, false, false, false, true>, "gemm3_nt_kernel<b16>", "mpf_gemm3_nt_ex", p.ntiles);
+    return g3_launch(r, p, (hipStream_t)stream, g3n_work(p, a16 ? 2.0 : 4.0, b16 ? 2.0 : 4.0));
 }
-
-static int g3_conv_wgrad_impl(const float* dy, const float* x, float* c_part, float* csum_dy, int n_img, int H, int W, int Cin,
-                              int Cout, int rows_per_split, void* stream, const float* dy_amax, const float* x_amax);
 
 extern "C" int mpf_gemm3_conv3x3_wgrad(const float* dy, const float* x, float* c_part, float* csum_dy, int n_img, int H, int W, int Cin,
                                        int Cout, int rows_per_split, void* stream)
@@ -2273,51 +2264,6 @@ extern "C" int mpf_gemm3_conv3x3_wgrad_h2(const float* dy, const float* dy_amax,
 {
     if (!dy_amax || !x_amax) return mpf::fail(MPF_E_NULL, "gemm3_conv3x3_wgrad_h2: NULL amax");
     return g3_conv_wgrad_impl(dy, x, c_part, csum_dy, n_img, H, W, Cin, Cout, rows_per_split, stream, dy_amax, x_amax);
-}
-
-static int g3_conv_wgrad_impl(const float* dy, const float* x, float* c_part, float* csum_dy, int n_img, int H, int W, int Cin,
-                              int Cout, int rows_per_split, void* stream, const float* dy_amax, const float* x_amax)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (!dy || !x || !c_part) return mpf::fail(MPF_E_NULL, "gemm3_conv3x3_wgrad: NULL buffer");
-    if (n_img <= 0 || H <= 0 || W <= 0 || W % 8 != 0 || Cin <= 0 || Cin % 128 != 0 || Cout <= 0 || rows_per_split <= 0 ||
-        rows_per_split % kBK != 0)
-        return mpf::fail(MPF_E_SHAPE, "gemm3_conv3x3_wgrad: needs W % 8 == 0, Cin % 128 == 0, rows_per_split % 32 == 0");
-    const int64_t R64 = (int64_t)n_img * H * W;
-    if (R64 * (Cin > Cout ? Cin : Cout) * 4 >= (1ll << 32)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_conv3x3_wgrad: an operand spans 4 GiB or more");
-    G3N p;
-    p.a_amax = nullptr; p.b_amax = nullptr;
-    p.a = dy; p.b = x; p.b2 = nullptr; p.c = c_part; p.csum_a = csum_dy; p.csum_b = nullptr;
-    p.lda = Cout; p.ldb = Cin; p.ldb2 = 0;
-    p.R = (int)R64; p.Mdim = Cout; p.Ndim = 9 * Cin; p.b2_rows = 0; p.rows_per_split = rows_per_split;
-    p.nsplit = (p.R + rows_per_split - 1) / rows_per_split;
-    p.transpose_out = 0;
-    p.a_bytes = (unsigned)(R64 * Cout * 4); p.b_bytes = (unsigned)(R64 * Cin * 4);
-    p.cv_H = H; p.cv_W = W; p.cv_cin = Cin;
-    p.tiles_m = (Cout + kBM - 1) / kBM;
-    p.tiles_n = 9 * Cin / 128;
-    p.ntiles = p.tiles_m * p.tiles_n * p.nsplit;
-    p.c_ss = (int64_t)p.Mdim * p.Ndim; p.csa_ss = p.Mdim; p.csb_ss = p.Ndim;
-    p.a_amax = dy_amax; p.b_amax = x_amax;
-    if (dy_amax && g_nt2 && Cout % 256 == 0 && Cin % 256 == 0) {       // 256 x 256 tiles (gemm3_nt2.h): half the operand traffic
-        p.tiles_m = Cout / 256; p.tiles_n = 9 * Cin / 256;
-        p.ntiles = p.tiles_m * p.tiles_n * p.nsplit;
-        static mpf::LdsAttr attr;
-        if (int e = mpf::ensure_dynamic_lds((const void*)gemm3_nt2_conv_kernel, kN2Lds, attr)) return e;
-        mpf::prof_begin(st);
-        mpf::set_kernel("gemm3_nt_kernel<conv3x3 h2 256x256>");
-        hipLaunchKernelGGL(gemm3_nt2_conv_kernel, dim3(((p.ntiles + 7) / 8) * 8), dim3(kN2T), kN2Lds, st, p);
-        mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)p.R * Cout + (double)p.R * Cin + (double)p.nsplit * Cout * 9 * Cin),
-                      2.0 * p.R * (double)Cout * 9 * Cin);
-        return mpf::check(hipGetLastError(), "mpf_gemm3_conv3x3_wgrad(256x256)");
-    }
-    mpf::prof_begin(st);
-    mpf::set_kernel(dy_amax ? "gemm3_nt_kernel<conv3x3 h2>" : "gemm3_nt_kernel<conv3x3>");
-    if (dy_amax) hipLaunchKernelGGL((gemm3_nt_kernel<128, false, true, false, false, true>), dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    else hipLaunchKernelGGL((gemm3_nt_kernel<128, false, true>), dim3(((p.ntiles + 7) / 8) * 8), dim3(kThreads), 0, st, p);
-    mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)p.R * Cout + (double)p.R * Cin + (double)p.nsplit * Cout * 9 * Cin),
-                  2.0 * p.R * (double)Cout * 9 * Cin);
-    return mpf::check(hipGetLastError(), "mpf_gemm3_conv3x3_wgrad");
 }
 
 extern "C" size_t mpf_gemm_nt_bf16_workspace_bytes(int R, int Mdim, int Ndim, int rows_per_split)
@@ -2336,31 +2282,14 @@ extern "C" int mpf_gemm_nt_bf16(const void* a, int64_t lda, const void* b, int64
         return mpf::fail(MPF_E_SHAPE, "gemm_nt_bf16: bad sizes (rows_per_split % 32, Mdim % 4, Ndim % 4 must be 0)");
     if (workspace_bytes < mpf_gemm_nt_bf16_workspace_bytes(R, Mdim, Ndim, rows_per_split))
         return mpf::fail(MPF_E_SHAPE, "gemm_nt_bf16: workspace too small");
-    G3N p;
-    p.a_amax = nullptr; p.b_amax = nullptr;
-    p.a = static_cast<const float*>(a); p.b = static_cast<const float*>(b); p.b2 = nullptr;
-    p.nsplit = (R + rows_per_split - 1) / rows_per_split;
-    p.c = static_cast<float*>(workspace);
+    G3N p;      // the workspace holds the split partials, then their column sums
+    if (int rc = g3n_fill(p, "gemm_nt_bf16", a, lda, 2, b, ldb, 2, static_cast<float*>(workspace), nullptr, R, Mdim, Ndim, rows_per_split)) return rc;
     p.csum_a = p.c + (size_t)p.nsplit * Mdim * Ndim;
-    p.csum_b = nullptr;
-    p.lda = lda; p.ldb = ldb; p.ldb2 = 0;
-    p.R = R; p.Mdim = Mdim; p.Ndim = Ndim; p.b2_rows = 0; p.rows_per_split = rows_per_split;
-    p.transpose_out = 0;
-    {
-        const uint64_t ab = ((uint64_t)(R - 1) * lda + Mdim) * 2, bb = ((uint64_t)(R - 1) * ldb + Ndim) * 2;
-        if (ab >= (1ull << 32) || bb >= (1ull << 32)) return mpf::fail(MPF_E_TOO_LARGE, "gemm_nt_bf16: an operand spans 4 GiB or more");
-        p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
-    }
-    p.tiles_m = (Mdim + kBM - 1) / kBM;
-    p.tiles_n = (Ndim + 127) / 128;
-    p.ntiles = p.tiles_m * p.tiles_n * p.nsplit;
-    p.c_ss = (int64_t)p.Mdim * p.Ndim; p.csa_ss = p.Mdim; p.csb_ss = p.Ndim;
-    const int grid = ((p.ntiles + 7) / 8) * 8;
-    mpf::prof_begin(st);
-    mpf::set_kernel("gemm3_nt_kernel<128, bf16>");
-    hipLaunchKernelGGL((gemm3_nt_kernel<128, true>), dim3(grid), dim3(kThreads), 0, st, p);
-    mpf::prof_end("gemm3_nt_kernel<128, bf16>", st, 2.0 * ((double)R * Mdim * p.tiles_n + (double)R * Ndim * p.tiles_m) +
-                                                       4.0 * (double)p.nsplit * Mdim * Ndim);
+    g3n_tiles(p, kBM, 128);
+    // (this entry's log counts the operand re-reads of every tile row / column, and no flops)
+    const Work w{2.0 * ((double)R * Mdim * p.tiles_n + (double)R * Ndim * p.tiles_m) + 4.0 * (double)p.nsplit * Mdim * Ndim, 0.0};
+    if (int rc = g3_launch(g3n_route((const void*)gemm3_nt_kernel<128, true>, "gemm3_nt_kernel<128, bf16>", "mpf_gemm_nt_bf16", p.ntiles), p, st, w))
+        return rc;
     const int64_t cn = (int64_t)Mdim * Ndim, sn = csum_out ? Mdim : 0;
     const int64_t quads = (cn + sn) / 2;
     hipLaunchKernelGGL(nt_reduce_kernel<false>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, p.c, cn, p.csum_a, sn,
