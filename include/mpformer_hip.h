@@ -1356,6 +1356,32 @@ int mpf_seg_ap_match(const int* inter, const int* area_d, const int* area_g, int
                      const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Boundary AP on the device (csrc/seg_boundary.hip, csrc/seg_ap.hip): the second instance score of the reference, which
+ * tools/evaluate_coco_boundary_ap.py computes with boundary-iou-api (boundary_iou.coco_instance_api, iouType="boundary",
+ * dilation_ratio 0.020).  That package's mask_to_boundary zero-pads the mask, erodes it d times with a 3 x 3 element and keeps
+ * mask - eroded; its COCOeval.computeBoundaryIoU takes min(mask IoU, boundary IoU) per pair and leaves the rest of the evaluation
+ * as it is.  d = max(1, round(dilation_ratio * sqrt(H^2 + W^2))) is the caller's arithmetic.
+ *   mpf_seg_mask_boundary:      bits, out uint64 [M, nwords] in the layout above (p = x * H + y).  out = bits & ~eroded, where a
+ *                               pixel is eroded iff the whole (2d+1) x (2d+1) square around it is set, pixels outside the image
+ *                               counting as unset (2d + 1 > min(H, W): out == bits).  Output bits at or past H * W are zero.
+ *                               out MUST NOT alias or overlap bits: workgroups read their neighbours' columns of bits while others
+ *                               write out.  d >= 1 (else MPF_E_SHAPE); H * W < 2^31 and M <= 65535 (else MPF_E_TOO_LARGE); M == 0
+ *                               launches nothing.  Integer only, one writer per word: bitwise reproducible.
+ *   mpf_seg_ap_match_boundary:  mpf_seg_ap_match with a second set of counts, inter_b int32 [D, G], area_db int32 [D], area_gb
+ *                               int32 [G]: mpf_seg_mask_pairs of the two sides' BOUNDARIES, rows in score order like inter.  A
+ *                               pair's IoU is min(IoU of the mask counts, IoU of the boundary counts), the crowd rule applied to
+ *                               each (under "coco" a crowd's boundary IoU is inter_b / area_db).  Area ranges and the ignore rule
+ *                               of unmatched detections keep using gt_area / area_d.  Everything else, the records included, as
+ *                               mpf_seg_ap_match; the three new pointers NULL with D, G > 0: MPF_E_NULL.
+ */
+int mpf_seg_mask_boundary(const uint64_t* bits, int M, int H, int W, int d, uint64_t* out, void* stream);
+int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, const int* area_g, const int* inter_b, const int* area_db,
+                              const int* area_gb, int D, int G, const float* dt_score, const int* dt_cat, const int* gt_cat,
+                              const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn, const double* area_rngs, int A,
+                              int K, int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,9 @@ SIGNATURES = {
     "mpf_seg_ap_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
     "mpf_seg_ap_match": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp] + [_c_int] * 5
                          + [_c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "mpf_seg_mask_boundary": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_ap_match_boundary": (_c_int, [_c_vp] * 6 + [_c_int, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp] + [_c_int] * 5
+                                  + [_c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
 }
 
 

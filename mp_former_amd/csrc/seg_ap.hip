@@ -13,7 +13,10 @@
 //                            words zero
 //   seg_ap_match_kernel      one thread per (category, area range, IoU threshold): the loop of evaluateVid over the category's first
 //                            maxDet detections and its ground truths, non-ignored first; sets the "matched" / "ignored" bit of its
-//                            setting in the detections' records and adds the non-ignored ground truths to npig[k][a]
+//                            setting in the detections' records and adds the non-ignored ground truths to npig[k][a].
+//                            <true> (mpf_seg_ap_match_boundary): a second set of counts, those of the masks' boundaries
+//                            (seg_boundary.hip), and a pair's IoU is the smaller of the two (boundary-iou-api's computeBoundaryIoU,
+//                            which the reference's tools/evaluate_coco_boundary_ap.py runs); <false> reads the mask counts alone
 //
 // Exactness: counts are integers; iou = (double)inter / (double)union is the correctly rounded quotient of two integers below 2^53, as
 // python's float / float of the same integers is; the thresholds are the float64 values the host computed (np.linspace), uploaded as
@@ -113,8 +116,12 @@ __device__ __forceinline__ double ap_iou(int inter, int area_d, int area_g, bool
     return (double)inter / (double)uni;
 }
 
+// kBoundary: a second set of counts (the masks' boundaries, csrc/seg_boundary.hip) and the pair's IoU is the smaller of the two
+// (boundary-iou-api, COCOeval.computeBoundaryIoU); areas and ranges stay the masks'
+template <bool kBoundary>
 __global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restrict__ inter, const int* __restrict__ area_d,
-                                                            const int* __restrict__ area_g, int D, int G,
+                                                            const int* __restrict__ area_g, const int* __restrict__ inter_b,
+                                                            const int* __restrict__ area_db, const int* __restrict__ area_gb, int D, int G,
                                                             const int* __restrict__ dt_cat, const int* __restrict__ gt_cat,
                                                             const int* __restrict__ gt_crowd, const double* __restrict__ gt_area,
                                                             const double* __restrict__ thrs, int Tn, const double* __restrict__ rngs,
@@ -153,7 +160,8 @@ __global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restric
                 if (ig != pass) continue;
                 if (gtm[g] && !crowd) continue;                         // :312
                 if (m > -1 && m_ig == 0 && ig == 1) { stop = true; break; }     // :315
-                const double v = ap_iou(inter[(int64_t)d * G + g], area_d[d], area_g[g], crowd, crowd_rule);
+                double v = ap_iou(inter[(int64_t)d * G + g], area_d[d], area_g[g], crowd, crowd_rule);
+                if constexpr (kBoundary) v = fmin(v, ap_iou(inter_b[(int64_t)d * G + g], area_db[d], area_gb[g], crowd, crowd_rule));
                 if (v < best) continue;                                 // :318: equality takes the later ground truth
                 best = v;
                 m = g;
@@ -227,10 +235,12 @@ extern "C" size_t mpf_seg_ap_workspace_bytes(int G, int A, int Tn)
     return (size_t)A * Tn * G;
 }
 
-extern "C" int mpf_seg_ap_match(const int* inter, const int* area_d, const int* area_g, int D, int G, const float* dt_score,
-                                const int* dt_cat, const int* gt_cat, const int* gt_crowd, const double* gt_area, const double* iou_thrs,
-                                int Tn, const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
-                                int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
+// the body of both entries; boundary: the three boundary counts are checked and seg_ap_match_kernel<true> runs
+static int ap_match(const char* where, bool boundary, const int* inter, const int* area_d, const int* area_g, const int* inter_b,
+                    const int* area_db, const int* area_gb, int D, int G, const float* dt_score, const int* dt_cat, const int* gt_cat,
+                    const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn, const double* area_rngs, int A, int K,
+                    int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig, void* workspace, size_t workspace_bytes,
+                    void* stream)
 {
     if (D < 0 || G < 0 || K <= 0 || A <= 0 || Tn <= 0 || max_det <= 0 || image < 0)
         return mpf::fail(MPF_E_SHAPE, "seg_ap_match: need D, G >= 0, K, A, Tn, max_det > 0 and image >= 0");
@@ -241,18 +251,45 @@ extern "C" int mpf_seg_ap_match(const int* inter, const int* area_d, const int* 
     if (D && (!area_d || !dt_score || !dt_cat || !records)) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL detection buffer");
     if (G && (!area_g || !gt_cat || !gt_crowd || !gt_area || !workspace)) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL ground-truth buffer");
     if (D && G && !inter) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL pair counts");
+    if (boundary && D && G && (!inter_b || !area_db || !area_gb)) return mpf::fail(MPF_E_NULL, "seg_ap_match_boundary: NULL boundary counts");
     if (workspace_bytes < (size_t)A * Tn * G) return mpf::fail(MPF_E_SHAPE, "seg_ap_match: workspace smaller than mpf_seg_ap_workspace_bytes");
     if (D == 0 && G == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     mpf::prof_begin(st);
-    mpf::set_kernel("seg_ap_records_kernel+seg_ap_match_kernel");
+    mpf::set_kernel(boundary ? "seg_ap_records_kernel+seg_ap_match_kernel<boundary>" : "seg_ap_records_kernel+seg_ap_match_kernel");
     if (D)
         hipLaunchKernelGGL(seg_ap_records_kernel, dim3((unsigned)((D + kApT - 1) / kApT)), dim3(kApT), 0, st, dt_score, dt_cat, D, image,
                            (unsigned long long*)records);
     const int n = K * A * Tn;
-    hipLaunchKernelGGL(seg_ap_match_kernel, dim3((unsigned)((n + kApT - 1) / kApT)), dim3(kApT), 0, st, inter, area_d, area_g, D, G, dt_cat,
-                       gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
-                       (long long*)npig, (unsigned char*)workspace);
-    mpf::prof_end("seg_ap_match_kernel", st, 4.0 * D * G + 32.0 * D);
-    return mpf::check(hipGetLastError(), "mpf_seg_ap_match");
+    const dim3 grid((unsigned)((n + kApT - 1) / kApT));
+    if (boundary)
+        hipLaunchKernelGGL(seg_ap_match_kernel<true>, grid, dim3(kApT), 0, st, inter, area_d, area_g, inter_b, area_db, area_gb, D, G, dt_cat,
+                           gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
+                           (long long*)npig, (unsigned char*)workspace);
+    else
+        hipLaunchKernelGGL(seg_ap_match_kernel<false>, grid, dim3(kApT), 0, st, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_cat,
+                           gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
+                           (long long*)npig, (unsigned char*)workspace);
+    mpf::prof_end(boundary ? "seg_ap_match_kernel<boundary>" : "seg_ap_match_kernel", st, (boundary ? 8.0 : 4.0) * D * G + 32.0 * D);
+    return mpf::check(hipGetLastError(), where);
+}
+
+extern "C" int mpf_seg_ap_match(const int* inter, const int* area_d, const int* area_g, int D, int G, const float* dt_score,
+                                const int* dt_cat, const int* gt_cat, const int* gt_crowd, const double* gt_area, const double* iou_thrs,
+                                int Tn, const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
+                                int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return ap_match("mpf_seg_ap_match", false, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_score, dt_cat, gt_cat, gt_crowd,
+                    gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, const int* area_g, const int* inter_b, const int* area_db,
+                                         const int* area_gb, int D, int G, const float* dt_score, const int* dt_cat, const int* gt_cat,
+                                         const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn,
+                                         const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
+                                         int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return ap_match("mpf_seg_ap_match_boundary", true, inter, area_d, area_g, inter_b, area_db, area_gb, D, G, dt_score, dt_cat, gt_cat,
+                    gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace,
+                    workspace_bytes, stream);
 }

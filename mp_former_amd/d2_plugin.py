@@ -270,23 +270,32 @@ class PanopticQualityEvaluator:
 
 class InstanceAPEvaluator:
     """detectron2's evaluator protocol (``reset`` / ``process(inputs, outputs)`` / ``evaluate``) on inference.InstanceAP, in place
-    of ``COCOEvaluator`` for "segm": masks are packed and matched on the device, one record per detection crosses to the host at
-    ``evaluate``.  Writes no file and needs neither detectron2 nor pycocotools.
+    of ``COCOEvaluator`` for "segm" and of the reference's tools/evaluate_coco_boundary_ap.py (boundary-iou-api) for "boundary":
+    masks are packed and matched on the device, one record per detection and score crosses to the host at ``evaluate``.  Writes no
+    file and needs neither detectron2, pycocotools nor boundary_iou.
+
+    iou_types: any of "segm", "boundary"; one ``InstanceAP`` per type (``self.aps``), the masks of an image packed once and their
+    pair intersections counted once for all of them.  ``evaluate`` returns one key per type.
 
     Predictions: ``outputs[i]["instances"]`` with dense ``pred_masks`` [T, H, W], ``scores`` and ``pred_classes`` (packed here), or
     the dict of inference.instance_bits where the model was installed with ``install_native_inference(..., instance_bits=True)``.
     Ground truth: ``inputs[i]["instances"]`` with ``gt_masks`` (a [G, H, W] tensor or an object with ``.tensor``) and ``gt_classes``
     at the prediction's size; optional ``gt_iscrowd`` and ``gt_areas`` (missing: no crowd, the pixel counts)."""
 
-    def __init__(self, num_classes, class_names=None, device="cuda:0", **ap_options):
+    def __init__(self, num_classes, class_names=None, device="cuda:0", iou_types=("segm",), dilation_ratio=0.02, **ap_options):
         from .inference import InstanceAP
-        self.ap = InstanceAP(num_classes, device=device, **ap_options)
+        iou_types = tuple(iou_types)
+        if not iou_types or len(set(iou_types)) != len(iou_types):
+            raise ValueError(f"iou_types must list each wanted type once, got {iou_types!r}")
+        self.aps = {t: InstanceAP(num_classes, device=device, iou_type=t, dilation_ratio=dilation_ratio, **ap_options) for t in iou_types}
+        self.ap = self.aps[iou_types[0]]
         if class_names is not None and len(class_names) != self.ap.num_classes:
             raise ValueError(f"{len(class_names)} class names for {self.ap.num_classes} classes")
         self.class_names = class_names
 
     def reset(self):
-        self.ap.reset()
+        for ap in self.aps.values():
+            ap.reset()
 
     @staticmethod
     def _field(inst, name, default=None):
@@ -298,7 +307,7 @@ class InstanceAPEvaluator:
 
     def process(self, inputs, outputs):
         import torch
-        from .inference import pack_masks
+        from .inference import mask_pair_counts, pack_masks
         dev = self.ap.device
         for inp, out in zip(inputs, outputs):
             pred, gt = out["instances"], inp["instances"]
@@ -315,9 +324,12 @@ class InstanceAPEvaluator:
                 raise ValueError(f"gt_masks {tuple(gm.shape)} do not have the prediction's size {size}")
             G = gm.shape[0]
             crowd = self._field(gt, "gt_iscrowd")
-            self.ap.update(dt_bits, self._field(pred, "scores"), self._field(pred, "pred_classes"), pack_masks(gm.to(dev)),
-                           self._field(gt, "gt_classes"), torch.zeros(G, dtype=torch.int32) if crowd is None else crowd,
-                           self._field(gt, "gt_areas"))
+            args = (dt_bits, self._field(pred, "scores"), self._field(pred, "pred_classes"), pack_masks(gm.to(dev)),
+                    self._field(gt, "gt_classes"), torch.zeros(G, dtype=torch.int32) if crowd is None else crowd,
+                    self._field(gt, "gt_areas"))
+            counts = mask_pair_counts(args[0], args[3])      # once for every type
+            for ap in self.aps.values():
+                ap.update(*args, size=size, pair_counts=counts)
 
     def evaluate(self):
-        return {"segm": self.ap.results(self.class_names)}
+        return {t: ap.results(self.class_names) for t, ap in self.aps.items()}

@@ -801,6 +801,44 @@ def mask_pair_counts(a_bits, b_bits):
     return inter, area_a, area_b
 
 
+AP_IOU_TYPES = ("segm", "boundary")
+
+
+def boundary_dilation(H, W, dilation_ratio=0.02):
+    """boundary-iou-api's dilation distance for an H x W image: ``int(round(dilation_ratio * sqrt(H^2 + W^2)))`` with python's
+    round (halves to even), at least 1."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"need H, W > 0, got {H} x {W}")
+    return max(1, int(round(float(dilation_ratio) * np.sqrt(H ** 2 + W ** 2))))
+
+
+def _bits_size(bits, size, what):
+    """(H, W) of packed masks, checked against their words"""
+    if size is None or len(size) != 2:
+        raise ValueError(f"{what}: size must be (H, W), got {size!r}")
+    H, W = int(size[0]), int(size[1])
+    if H <= 0 or W <= 0 or bits.shape[1] != (H * W + 63) // 64:
+        raise ValueError(f"{what}: size {H} x {W} does not fit nwords = {bits.shape[1]} ({(H * W + 63) // 64} expected)")
+    return H, W
+
+
+def mask_boundaries(bits, size, dilation_ratio=0.02, d=None):
+    """Packed masks int64 [M, nwords] of an image of ``size`` (H, W) -> their boundaries in the same layout: ``mask & ~eroded``, the
+    erosion by ``d`` pixels (3 x 3 element, d iterations, outside the image unset) of boundary-iou-api's ``mask_to_boundary``.
+    ``d`` defaults to ``boundary_dilation(H, W, dilation_ratio)``."""
+    bits = _bits_arg(bits, "bits")
+    H, W = _bits_size(bits, size, "mask_boundaries")
+    d = boundary_dilation(H, W, dilation_ratio) if d is None else int(d)
+    if d < 1:
+        raise ValueError(f"d must be at least 1, got {d}")
+    dev = bits.device
+    out = torch.empty_like(bits)
+    if bits.shape[0]:
+        _lib.call("mpf_seg_mask_boundary", dev, bits.data_ptr(), bits.shape[0], H, W, d, out.data_ptr(), _lib.stream_ptr(dev))
+    return out
+
+
 class InstanceAP:
     """The per-image part of the COCO mask evaluation (``COCOeval.evaluateImg``; the reference carries the same body as
     ``evaluateVid`` in mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py:267-345) on the device, and its ``accumulate`` /
@@ -813,9 +851,18 @@ class InstanceAP:
     crowd_rule: "coco" = pycocotools' rleIou (a crowd ground truth's IoU is inter / detection area); "union" = the reference file's
     own computeIoU (the plain union for every pair).
 
+    iou_type: "segm" = mask AP; "boundary" = Boundary AP as tools/evaluate_coco_boundary_ap.py computes it with boundary-iou-api: a
+    pair's IoU is min(mask IoU, IoU of the two masks' boundaries), the boundaries ``mask_boundaries`` with ``dilation_ratio``;
+    area ranges, matching, accumulate and summarize are the same.
+
     Deviation: with ``gt_areas=None`` a ground truth's area is its pixel count (COCO reads the annotation's "area")."""
 
-    def __init__(self, num_classes, iou_thrs=None, area_rngs=None, max_dets=(1, 10, 100), crowd_rule="coco", device="cuda:0"):
+    def __init__(self, num_classes, iou_thrs=None, area_rngs=None, max_dets=(1, 10, 100), crowd_rule="coco", device="cuda:0",
+                 iou_type="segm", dilation_ratio=0.02):
+        if iou_type not in AP_IOU_TYPES:
+            raise ValueError(f"iou_type must be 'segm' or 'boundary', got {iou_type!r}")
+        self.iou_type = iou_type
+        self.dilation_ratio = float(dilation_ratio)
         self.num_classes = int(num_classes)
         if self.num_classes <= 0:
             raise ValueError("num_classes must be positive")
@@ -866,10 +913,12 @@ class InstanceAP:
             raise ValueError(f"{what} has {t.numel()} entries for {n} masks")
         return t
 
-    def update(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas=None):
+    def update(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas=None, size=None, pair_counts=None):
         """One image.  dt_bits int64 [D, nwords] and gt_bits int64 [G, nwords] packed masks on the device (``instance_bits`` /
         ``pack_masks``), scores [D], classes [D], gt_classes [G], gt_crowd [G] (0 / 1), gt_areas [G] or None (= the pixel counts).
         The detections may come in any order: they are sorted by score, descending and stable (the reference's mergesort of -score).
+        size: (H, W) of the image, required with iou_type="boundary" (the words alone do not tell H from W).
+        pair_counts: what ``mask_pair_counts(dt_bits, gt_bits)`` returned for these masks, where the caller has it already.
         No device-to-host copy."""
         if self.device.type != "cuda":
             raise RuntimeError("InstanceAP: Not implemented on the CPU (device tensors only)")
@@ -879,6 +928,15 @@ class InstanceAP:
         D, G = dt_bits.shape[0], gt_bits.shape[0]
         if D and G and dt_bits.shape[1] != gt_bits.shape[1]:
             raise ValueError(f"detections have {dt_bits.shape[1]} words per mask, ground truths {gt_bits.shape[1]}: not one image")
+        boundary = self.iou_type == "boundary"
+        if boundary:
+            if size is None:
+                raise ValueError("InstanceAP.update: iou_type='boundary' needs size=(H, W)")
+            H, W = _bits_size(dt_bits if D else gt_bits, size, "InstanceAP.update")
+        if pair_counts is not None:
+            inter, area_d, area_g = pair_counts
+            if tuple(inter.shape) != (D, G) or area_d.numel() != D or area_g.numel() != G or inter.dtype != torch.int32:
+                raise ValueError(f"pair_counts are not the int32 counts of {D} x {G} masks")
         self._buffers()
         dev = self.device
         scores = self._small(scores, D, torch.float32, "scores")
@@ -890,10 +948,17 @@ class InstanceAP:
         if D == 0 and G == 0:
             return
         nwords = dt_bits.shape[1] if D else gt_bits.shape[1]
-        inter, area_d, area_g = mask_pair_counts(dt_bits if D else dt_bits.new_empty((0, nwords)),
-                                                 gt_bits if G else gt_bits.new_empty((0, nwords)))
+        if not D:
+            dt_bits = dt_bits.new_empty((0, nwords))
+        if not G:
+            gt_bits = gt_bits.new_empty((0, nwords))
+        inter, area_d, area_g = mask_pair_counts(dt_bits, gt_bits) if pair_counts is None else pair_counts
         scores, order = scores.sort(descending=True, stable=True)
         classes, area_d, inter = classes[order].contiguous(), area_d[order].contiguous(), inter[order].contiguous()
+        if boundary:
+            d = boundary_dilation(H, W, self.dilation_ratio)
+            inter_b, area_db, area_gb = mask_pair_counts(mask_boundaries(dt_bits, (H, W), d=d), mask_boundaries(gt_bits, (H, W), d=d))
+            area_db, inter_b = area_db[order].contiguous(), inter_b[order].contiguous()
         gt_area = area_g.double() if gt_areas is None else self._small(gt_areas, G, torch.float64, "gt_areas")
         if self._n + D > self._rec.shape[0]:                # grow by doubling; the old buffer stays valid for the queued launches
             grown = torch.empty((max(2 * self._rec.shape[0], self._n + D), _AP_REC), dtype=torch.int64, device=dev)
@@ -903,8 +968,11 @@ class InstanceAP:
         Tn, A = self.iou_thrs.size, self.area_rngs.shape[0]
         ws = _lib.scratch("seg_ap.gt_marks", dev, stream, max(1, _lib.lib().mpf_seg_ap_workspace_bytes(G, A, Tn)))
         sp = self._settings.data_ptr()
-        _lib.call("mpf_seg_ap_match", dev, _lib.ptr(inter) if D and G else None, area_d.data_ptr() if D else None,
-                  area_g.data_ptr() if G else None, D, G, scores.data_ptr() if D else None, classes.data_ptr() if D else None,
+        counts = (_lib.ptr(inter) if D and G else None, area_d.data_ptr() if D else None, area_g.data_ptr() if G else None)
+        if boundary:
+            counts += (_lib.ptr(inter_b) if D and G else None, area_db.data_ptr() if D else None, area_gb.data_ptr() if G else None)
+        _lib.call("mpf_seg_ap_match_boundary" if boundary else "mpf_seg_ap_match", dev, *counts,
+                  D, G, scores.data_ptr() if D else None, classes.data_ptr() if D else None,
                   gt_cat.data_ptr() if G else None, crowd.data_ptr() if G else None, gt_area.data_ptr() if G else None, sp, Tn, sp + 8 * Tn,
                   A, self.num_classes, self.max_dets[-1], AP_CROWD_RULES[self.crowd_rule], image,
                   self._rec.data_ptr() + 8 * _AP_REC * self._n, self._npig.data_ptr(), ws.data_ptr(), ws.numel(), stream)

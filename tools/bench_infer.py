@@ -3,7 +3,7 @@ eval branch (tests/_infer_restate.py), per image on one GPU.  Prints one line pe
 inputs, the algorithmic bytes / FLOP of the native route and the fraction of the measured 6.3 TB/s copy rate or of the
 157 TF fp32 peak it reaches (whichever bound applies).
 
-    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta,pq,ap]
+    python tools/bench_infer.py [--iters 20] [--rows base,eval,tta,pq,ap,boundary]
 
 The ``eval`` rows measure the evaluation-form results (``semantic_labels``, ``SemSegConfusion``, ``instance_masks="rle"``) against
 the default route brought to the same end product: ``sem_seg`` + ``torch.argmax`` (+ ``.cpu()`` of the label map where the metric
@@ -26,6 +26,13 @@ The ``ap`` row (not in the default set; COCO instance case only) measures the pe
 + ``pack_masks`` of the ground truth + ``InstanceAP.update`` against ``postprocess`` with dense masks, ``pred_masks.cpu()`` and the
 numpy restatement of the COCO IoU and matching (tests/_ap_restate.py).  The ground truth (about 20 dense masks) is in place on
 both sides before the clock starts.  Wall-clock medians as above; the 4 T H W bytes of the masks cross on the parent side only.
+
+The ``boundary`` row (not in the default set; COCO instance case only; prints the ``ap`` row first, in the same run) measures
+Boundary AP on the ``ap`` row's scene (d = 17 at 480 x 719): ``instance_bits`` + ``pack_masks`` + ``InstanceAP(iou_type="boundary")
+.update`` against the only route there was before it: the dense masks to the host, ``scipy.ndimage.binary_erosion`` of every mask
+and the numpy restatement (tests/_boundary_restate.py's min of the two IoUs in tests/_ap_restate.py).  Same protocol as ``ap``:
+median of --iters, the host route's of --iters / 4, ground truth in place first.  ``added_over_ap_us`` is what the two boundary
+launches and the second pair count cost on top of mask AP.
 """
 import argparse
 import json
@@ -41,7 +48,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from _infer_restate import restate  # noqa: E402
 from mp_former_amd import _lib  # noqa: E402
 from mp_former_amd.inference import (InferenceConfig, InstanceAP, PanopticQuality, SemanticTTA, SemSegConfusion,  # noqa: E402
-                                     instance_bits, pack_masks, postprocess)
+                                     boundary_dilation, instance_bits, mask_boundaries, mask_pair_counts, pack_masks, postprocess)
 
 CASES = {
     # name: (K, low-res hw, padded, image, output, config)
@@ -290,8 +297,9 @@ def pq_rows(name, K, hw, padded, image, out, iters, dev):
                       "tp_fp_fn": [int(want[k].sum()) for k in ("tp", "fp", "fn")]}), flush=True)
 
 
-def ap_rows(name, K, hw, padded, image, out, iters, dev, n_gt=20):
-    """Instance mask AP of one image: the device route against the dense masks' copy to the host + the numpy restatement."""
+def ap_rows(name, K, hw, padded, image, out, iters, dev, n_gt=20, boundary=False):
+    """Instance mask AP of one image: the device route against the dense masks' copy to the host + the numpy restatement.
+    boundary: the Boundary AP row after it, on the same scene."""
     import numpy as np
     import _ap_restate as R
     cfg = InferenceConfig(num_classes=K, num_queries=100)
@@ -346,6 +354,57 @@ def ap_rows(name, K, hw, padded, image, out, iters, dev, n_gt=20):
                       "native_peak_MB": round(m_nat, 1), "parent_peak_MB": round(m_par, 1), "native_host_bytes": 0,
                       "parent_host_bytes": 4 * T * H * W, "records_equal_to_restatement": bool(same),
                       "matched_at_0.5": int(want["matched"][:, 0, 0].sum())}), flush=True)
+    if not boundary:
+        return
+    import _boundary_restate as B
+    from scipy import ndimage
+    d = boundary_dilation(H, W)
+    bap = InstanceAP(K, device=dev, iou_type="boundary")
+
+    def native_b():
+        b = instance_bits(lg, mk, [image], padded, [out], cfg)[0]
+        bap.update(b["bits"], b["scores"], b["pred_classes"], pack_masks(gt_dev), gt_cls, crowd, size=(H, W))
+
+    def to_boundaries(items):
+        box = np.ones((3, 3), dtype=bool)
+        return [{**o, "mask": o["mask"] & ~ndimage.binary_erosion(o["mask"], box, iterations=d, border_value=0)} for o in items]
+
+    def iou_min(dt, gt, max_det, crowd_rule):           # boundaries made once per image, outside: see parent_b
+        return np.minimum(B._MASK_IOU(dt, gt, max_det, crowd_rule),
+                          B._MASK_IOU([x["b"] for x in dt], [x["b"] for x in gt], max_det, crowd_rule)) if len(dt) or len(gt) else []
+
+    gts_b = [{**g, "b": b} for g, b in zip(gts, to_boundaries(gts))]      # the ground truth's boundaries are in place too
+
+    def parent_b():
+        i = postprocess(lg, mk, [image], padded, [out], cfg)[0]["instances"]
+        dts_h = host_dets(i)
+        dts_b = [{**x, "b": b} for x, b in zip(dts_h, to_boundaries(dts_h))]
+        R.compute_iou = iou_min
+        try:
+            return R.evaluate([(dts_b, gts_b)], K, R.COCO_AREA_RNGS, (1, 10, 100))
+        finally:
+            R.compute_iou = B._MASK_IOU
+
+    t_natb, m_natb = timed_wall(native_b, iters)
+    t_parb, m_parb = timed_wall(parent_b, max(3, iters // 4))
+    t_bnd, _ = timed_wall(lambda: (mask_boundaries(b0["bits"], (H, W), d=d), mask_boundaries(g0, (H, W), d=d)), iters)
+    bd, bg = mask_boundaries(b0["bits"], (H, W), d=d), mask_boundaries(g0, (H, W), d=d)
+    t_cnt, _ = timed_wall(lambda: mask_pair_counts(bd, bg), iters)
+    t_updb, _ = timed_wall(lambda: bap.update(b0["bits"], b0["scores"], b0["pred_classes"], g0, gt_cls, crowd, size=(H, W)), iters)
+    bap.reset()
+    native_b()
+    got = bap.stats()
+    want = R.expected_stats([(dts, gts)], K, R.COCO_AREA_RNGS, (1, 10, 100), eval_imgs=parent_b())
+    same = got["scores"].tobytes() == want["scores"].tobytes() and all(np.array_equal(got[k], want[k])
+                                                                        for k in ("category", "rank", "matched", "ignored", "npig"))
+    print(json.dumps({"case": name, "row": "boundary", "detections": T, "ground_truths": n_gt, "d": d, "native_us": round(t_natb, 1),
+                      "parent_us": round(t_parb, 1), "speedup": round(t_parb / t_natb, 2), "native_slower": bool(t_natb > t_parb),
+                      "ap_row_native_us": round(t_nat, 1), "added_over_ap_us": round(t_natb - t_nat, 1),
+                      "mask_boundaries_us": round(t_bnd, 1), "boundary_pair_counts_us": round(t_cnt, 1),
+                      "boundary_update_us": round(t_updb, 1), "mask_update_us": round(t_upd, 1),
+                      "native_peak_MB": round(m_natb, 1), "parent_peak_MB": round(m_parb, 1), "native_host_bytes": 0,
+                      "parent_host_bytes": 4 * T * H * W, "records_equal_to_restatement": bool(same),
+                      "matched_at_0.5": int(want["matched"][:, 0, 0].sum())}), flush=True)
 
 
 def work(K, cfg, hw, out, Q=100, T=100):
@@ -377,8 +436,8 @@ def main():
             tta_rows(name, args.iters, dev)
         if "pq" in kinds and name == "coco_panoptic_k133":
             pq_rows(name, K, hw, padded, image, out, args.iters, dev)
-        if "ap" in kinds and name == "coco_instance_k80":
-            ap_rows(name, K, hw, padded, image, out, args.iters, dev)
+        if ("ap" in kinds or "boundary" in kinds) and name == "coco_instance_k80":
+            ap_rows(name, K, hw, padded, image, out, args.iters, dev, boundary="boundary" in kinds)
         if "eval" in kinds:
             eval_rows(name, K, hw, padded, image, out, args.iters, dev)
         if "base" not in kinds:
