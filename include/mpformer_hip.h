@@ -1382,6 +1382,48 @@ int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, const int* ar
                               int K, int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/*
+ * Video instance segmentation (csrc/seg_video.hip, csrc/seg_ap.hip): the eval branch of the reference's VideoMaskFormer
+ * (mask2former_video/video_maskformer_model.py:204-287: forward's else branch and inference_video) and its YouTube-VIS score
+ * (mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py).  At test time a whole video is one clip: masks [Q, F, h, w], fp32
+ * or bf16, contiguous [h, w] planes, stride_q / stride_f elements between queries / frames (a slice of a larger decoder output is
+ * read in place).  The reference upsamples all Q x F planes to (Hp, Wp), then selects, crops, resizes and thresholds (:210-215,
+ * :263-270); here the selected entries sel_q int64 [T] are resampled alone, with the arithmetic of mpf_seg_instance_bits (F == 1
+ * gives its words bit for bit).
+ *   mpf_seg_video_bits:      bits uint64 [T, F, nwords] in the packed layout above (p = x * H + y, zero at and past H * W) =
+ *                            (resample(m_{sel_q[t], f}) > 0) (:270), and frame_area int32 [T, F] = the popcount of what was written
+ *                            (zeroed by the call, integer atomics: bitwise reproducible).  dense != NULL: also uint8 [T, F, H, W]
+ *                            row-major 0 / 1, the same decision.  One launch per clip.  F * H * W < 2^31 (a tube's pair counts are
+ *                            int32) and T, F <= 65535, else MPF_E_TOO_LARGE; T == 0 or F == 0 launches nothing.
+ *   mpf_seg_tube_areas:      avg_area float64 [M] from frame_area int32 [M, F]: (double)sum / (double)count over the frames with a
+ *                            non-zero area, 0.0 without one (:100-104; exact for sums below 2^53).  The per-frame areas of
+ *                            ground-truth tubes given as bits [G, F, nwords] come from mpf_seg_mask_pairs on the rows [G * F, nwords]
+ *                            with the other side empty (G == 0 there): one launch, where a popcount entry of its own would be one too.
+ *   mpf_seg_ap_match_tube:   mpf_seg_ap_match for ONE video.  inter / area_d / area_g are mpf_seg_mask_pairs over the tubes' rows
+ *                            [*, F * nwords] (a frame without annotation is all-zero words: iou_seq's union, :203-217, counts the
+ *                            other side's area there); gt_area and the new dt_area float64 [D] (score order) are the avg_area of
+ *                            both sides: the ranges test them (:283, :330) while the IoU keeps the integer counts.
+ *                            dt_area NULL with D > 0: MPF_E_NULL.
+ *   mpf_seg_bits_rle_*:      the count / write passes of mpf_seg_instance_rle_* on bits uint64 [M, nwords] the caller holds already
+ *                            (M = T * F for a clip, 1 <= M <= 65535): workspace of mpf_seg_bits_rle_workspace_bytes(M, H, W) bytes,
+ *                            8-byte aligned, offsets int64 [M + 1]; _write takes the same bits and workspace, total = offsets[M] read
+ *                            by the host, and gives counts uint32 [total] (pos uint32 [total] is scratch).  A twin of
+ *                            mpf_seg_instance_rle_write, whose workspace starts with bits of its own.
+ */
+int mpf_seg_video_bits(const void* masks, int64_t stride_q, int64_t stride_f, int dtype, int Q, int F, int h, int w, int Hp, int Wp,
+                       int hi, int wi, int H, int W, const int64_t* sel_q, int T, uint64_t* bits, int* frame_area,
+                       uint8_t* dense /* NULL: bits only */, void* stream);
+int mpf_seg_tube_areas(const int* frame_area, int M, int F, double* avg_area, void* stream);
+int mpf_seg_ap_match_tube(const int* inter, const int* area_d, const int* area_g, int D, int G, const float* dt_score, const int* dt_cat,
+                          const int* gt_cat, const int* gt_crowd, const double* gt_area, const double* dt_area, const double* iou_thrs,
+                          int Tn, const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
+                          int64_t* npig, void* workspace, size_t workspace_bytes, void* stream);
+size_t mpf_seg_bits_rle_workspace_bytes(int M, int H, int W);
+int mpf_seg_bits_rle_count(const uint64_t* bits, int M, int H, int W, int64_t* offsets, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int mpf_seg_bits_rle_write(const uint64_t* bits, const void* workspace, size_t workspace_bytes, int M, int H, int W,
+                           const int64_t* offsets, int64_t total, uint32_t* pos, uint32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

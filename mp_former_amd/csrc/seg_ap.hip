@@ -16,7 +16,10 @@
 //                            setting in the detections' records and adds the non-ignored ground truths to npig[k][a].
 //                            <true> (mpf_seg_ap_match_boundary): a second set of counts, those of the masks' boundaries
 //                            (seg_boundary.hip), and a pair's IoU is the smaller of the two (boundary-iou-api's computeBoundaryIoU,
-//                            which the reference's tools/evaluate_coco_boundary_ap.py runs); <false> reads the mask counts alone
+//                            which the reference's tools/evaluate_coco_boundary_ap.py runs); <false> reads the mask counts alone.
+//                            dt_area != NULL (mpf_seg_ap_match_tube): a video.  The counts are those of tubes (the frames' packed words
+//                            concatenated: popcount(a & b) is the tube intersection, area_a + area_b - inter iou_seq's union, :203-217)
+//                            and the ranges test avg_area on both sides (:283, :330); the same <false> instance otherwise
 //
 // Exactness: counts are integers; iou = (double)inter / (double)union is the correctly rounded quotient of two integers below 2^53, as
 // python's float / float of the same integers is; the thresholds are the float64 values the host computed (np.linspace), uploaded as
@@ -124,8 +127,8 @@ __global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restric
                                                             const int* __restrict__ area_db, const int* __restrict__ area_gb, int D, int G,
                                                             const int* __restrict__ dt_cat, const int* __restrict__ gt_cat,
                                                             const int* __restrict__ gt_crowd, const double* __restrict__ gt_area,
-                                                            const double* __restrict__ thrs, int Tn, const double* __restrict__ rngs,
-                                                            int A, int K, int max_det, int crowd_rule,
+                                                            const double* __restrict__ dt_area, const double* __restrict__ thrs, int Tn,
+                                                            const double* __restrict__ rngs, int A, int K, int max_det, int crowd_rule,
                                                             unsigned long long* __restrict__ rec, long long* __restrict__ npig,
                                                             unsigned char* __restrict__ gtm_all)
 {
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restric
             ignored = m_ig != 0;
             atomicOr(&rec[(int64_t)kApRec * d + 2], bit);
         } else {
-            const double da = (double)area_d[d];
+            const double da = dt_area ? dt_area[d] : (double)area_d[d];     // tubes: avg_area, not the IoU's pixel count
             ignored = da < lo || da > hi;                               // :330-331
         }
         if (ignored) atomicOr(&rec[(int64_t)kApRec * d + 3], bit);
@@ -235,12 +238,13 @@ extern "C" size_t mpf_seg_ap_workspace_bytes(int G, int A, int Tn)
     return (size_t)A * Tn * G;
 }
 
-// the body of both entries; boundary: the three boundary counts are checked and seg_ap_match_kernel<true> runs
+// the body of the three entries; boundary: the three boundary counts are checked and seg_ap_match_kernel<true> runs; dt_area (tubes,
+// else NULL): the area the ranges test for an unmatched detection, where the images' entries take the pixel count area_d
 static int ap_match(const char* where, bool boundary, const int* inter, const int* area_d, const int* area_g, const int* inter_b,
                     const int* area_db, const int* area_gb, int D, int G, const float* dt_score, const int* dt_cat, const int* gt_cat,
-                    const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn, const double* area_rngs, int A, int K,
-                    int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig, void* workspace, size_t workspace_bytes,
-                    void* stream)
+                    const int* gt_crowd, const double* gt_area, const double* dt_area, const double* iou_thrs, int Tn,
+                    const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig,
+                    void* workspace, size_t workspace_bytes, void* stream)
 {
     if (D < 0 || G < 0 || K <= 0 || A <= 0 || Tn <= 0 || max_det <= 0 || image < 0)
         return mpf::fail(MPF_E_SHAPE, "seg_ap_match: need D, G >= 0, K, A, Tn, max_det > 0 and image >= 0");
@@ -264,11 +268,11 @@ static int ap_match(const char* where, bool boundary, const int* inter, const in
     const dim3 grid((unsigned)((n + kApT - 1) / kApT));
     if (boundary)
         hipLaunchKernelGGL(seg_ap_match_kernel<true>, grid, dim3(kApT), 0, st, inter, area_d, area_g, inter_b, area_db, area_gb, D, G, dt_cat,
-                           gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
+                           gt_cat, gt_crowd, gt_area, dt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
                            (long long*)npig, (unsigned char*)workspace);
     else
         hipLaunchKernelGGL(seg_ap_match_kernel<false>, grid, dim3(kApT), 0, st, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_cat,
-                           gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
+                           gt_cat, gt_crowd, gt_area, dt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
                            (long long*)npig, (unsigned char*)workspace);
     mpf::prof_end(boundary ? "seg_ap_match_kernel<boundary>" : "seg_ap_match_kernel", st, (boundary ? 8.0 : 4.0) * D * G + 32.0 * D);
     return mpf::check(hipGetLastError(), where);
@@ -280,7 +284,21 @@ extern "C" int mpf_seg_ap_match(const int* inter, const int* area_d, const int* 
                                 int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
 {
     return ap_match("mpf_seg_ap_match", false, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_score, dt_cat, gt_cat, gt_crowd,
-                    gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace, workspace_bytes, stream);
+                    gt_area, nullptr, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace, workspace_bytes,
+                    stream);
+}
+
+// one video: the counts are those of the tubes (the frames' words concatenated), gt_area / dt_area their avg_area (mpf_seg_tube_areas)
+extern "C" int mpf_seg_ap_match_tube(const int* inter, const int* area_d, const int* area_g, int D, int G, const float* dt_score,
+                                     const int* dt_cat, const int* gt_cat, const int* gt_crowd, const double* gt_area,
+                                     const double* dt_area, const double* iou_thrs, int Tn, const double* area_rngs, int A, int K,
+                                     int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig, void* workspace,
+                                     size_t workspace_bytes, void* stream)
+{
+    if (D > 0 && !dt_area) return mpf::fail(MPF_E_NULL, "seg_ap_match_tube: NULL dt_area");
+    return ap_match("mpf_seg_ap_match_tube", false, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_score, dt_cat, gt_cat, gt_crowd,
+                    gt_area, dt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace, workspace_bytes,
+                    stream);
 }
 
 extern "C" int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, const int* area_g, const int* inter_b, const int* area_db,
@@ -290,6 +308,6 @@ extern "C" int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, co
                                          int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
 {
     return ap_match("mpf_seg_ap_match_boundary", true, inter, area_d, area_g, inter_b, area_db, area_gb, D, G, dt_score, dt_cat, gt_cat,
-                    gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace,
+                    gt_crowd, gt_area, nullptr, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace,
                     workspace_bytes, stream);
 }

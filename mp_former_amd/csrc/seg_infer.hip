@@ -42,95 +42,13 @@
 #include <type_traits>
 
 #include "mpf_common.h"
+#include "seg_shared.h"     // the composed resampling (SegGeom, pix_geom, resample) and the run-length passes, shared with seg_video.hip
 
 namespace {
 
-constexpr int kT = 256;            // threads per workgroup, every kernel
 constexpr int kSemPix = 128;       // semantic: output pixels per workgroup
 constexpr int kSemQ = 32;          // semantic: queries staged per LDS round
-constexpr int kInstPix = 1024;     // instance: output pixels per workgroup
 constexpr int kMaxQ = 1024;        // panoptic LDS histogram bound
-
-__device__ __forceinline__ float ldm(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float ldm(const __hip_bfloat16* p, int64_t i) { return __bfloat162float(p[i]); }
-
-// torch upsample_bilinear2d, align_corners=False, no explicit scale: scale = in / out in fp32,
-// src = max(scale * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1.
-// (__fmul_rn / __fadd_rn: no contraction into an FMA, the same roundings as the reference's separate operations)
-struct Tap {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ Tap tap(int dst, int in, int out)
-{
-    const float scale = (float)in / (float)out;
-    float src = __fsub_rn(__fmul_rn(scale, __fadd_rn((float)dst, 0.5f)), 0.5f);
-    src = src < 0.f ? 0.f : src;
-    Tap t;
-    t.i0 = (int)src;
-    t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
-    t.l1 = __fsub_rn(src, (float)t.i0);
-    t.l0 = __fsub_rn(1.f, t.l1);
-    return t;
-}
-
-// The composed geometry of one output pixel: stage 2 (crop [hi, wi] of the padded grid -> [H, W]) picks 2 x 2 intermediate
-// pixels, stage 1 ([h, w] -> [Hp, Wp]) resamples each of them from a 2 x 2 low-resolution neighbourhood.
-struct PixGeom {
-    int64_t off[2][2][4];          // [intermediate row a][intermediate col b][low-res tap r*2+c]
-    float w1[2][2][4];
-    float w2y[2], w2x[2];
-};
-// One view: Q logit planes [h, w] (stride_q elements apart) of a padded [Hp, Wp] grid whose [hi, wi] crop is the image, resized to
-// the [H, W] output.  check_geom fills it; every per-pixel kernel takes it by value.
-struct SegGeom {
-    int64_t stride_q;
-    int Q, h, w, Hp, Wp, hi, wi, H, W;
-};
-__device__ __forceinline__ void pix_geom(PixGeom& g, int y, int x, const SegGeom& s)
-{
-    const int h = s.h, w = s.w, Hp = s.Hp, Wp = s.Wp;
-    const Tap ty = tap(y, s.hi, s.H), tx = tap(x, s.wi, s.W);
-    g.w2y[0] = ty.l0; g.w2y[1] = ty.l1;
-    g.w2x[0] = tx.l0; g.w2x[1] = tx.l1;
-    const int ya[2] = {ty.i0, ty.i1}, xa[2] = {tx.i0, tx.i1};
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const Tap sy = tap(ya[a], h, Hp);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const Tap sx = tap(xa[b], w, Wp);
-            g.off[a][b][0] = (int64_t)sy.i0 * w + sx.i0;
-            g.off[a][b][1] = (int64_t)sy.i0 * w + sx.i1;
-            g.off[a][b][2] = (int64_t)sy.i1 * w + sx.i0;
-            g.off[a][b][3] = (int64_t)sy.i1 * w + sx.i1;
-            g.w1[a][b][0] = sy.l0; g.w1[a][b][1] = sy.l1;    // row weights (h0lambda, h1lambda)
-            g.w1[a][b][2] = sx.l0; g.w1[a][b][3] = sx.l1;    // column weights (w0lambda, w1lambda)
-        }
-    }
-}
-
-// torch's weight order at each stage: h0l * (w0l * x00 + w1l * x01) + h1l * (w0l * x10 + w1l * x11)
-__device__ __forceinline__ float lerp2(float h0, float h1, float w0, float w1, float x00, float x01, float x10, float x11)
-{
-    return __fadd_rn(__fmul_rn(h0, __fadd_rn(__fmul_rn(w0, x00), __fmul_rn(w1, x01))),
-                     __fmul_rn(h1, __fadd_rn(__fmul_rn(w0, x10), __fmul_rn(w1, x11))));
-}
-
-template <typename T>
-__device__ __forceinline__ float resample(const T* m, const PixGeom& g)
-{
-    float v[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const float* wt = g.w1[a][b];
-            v[a][b] = lerp2(wt[0], wt[1], wt[2], wt[3], ldm(m, g.off[a][b][0]), ldm(m, g.off[a][b][1]), ldm(m, g.off[a][b][2]),
-                            ldm(m, g.off[a][b][3]));
-        }
-    return lerp2(g.w2y[0], g.w2y[1], g.w2x[0], g.w2x[1], v[0][0], v[0][1], v[1][0], v[1][1]);
-}
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -560,15 +478,8 @@ __global__ __launch_bounds__(kConfT) void seg_confusion_kernel(const int* __rest
 // exactly as seg_instance_kernel decides it.  A boundary is a position whose bit differs from its predecessor's, with bit[-1] = 0:
 // the counts of an instance are the differences of {0, boundaries ..., H * W}, so they start with a (possibly empty) run of zeros.
 //   seg_rle_bits_kernel     64 positions per wave ballot -> one packed word; entry t = blockIdx.y
-//   seg_rle_count_kernel    boundaries per tile of kRleWords words (one word per thread), from the packed bits
-//   seg_rle_scan_kernel     ONE workgroup: exclusive scan of the tile counts in (entry, tile) order, + 1 end mark per entry
-//                           -> first packed slot of every tile (int64) and the per-entry offsets [T + 1]
-//   seg_rle_scatter_kernel  the boundary positions (and H * W as the end mark) to their slots: rank = tile start + a fixed-order
-//                           scan inside the workgroup, no atomics
-//   seg_rle_diff_kernel     counts[i] = pos[i] - pos[i - 1] (0 before the first slot of an entry: the slot after an end mark)
+//   seg_rle_count / _scan / _scatter / _diff_kernel   the passes from the packed bits to the counts: seg_shared.h
 // ----------------------------------------------------------------------------------------------------------------
-constexpr int kRleWords = kT;      // words (64 positions each) per tile of the count / scatter kernels
-
 template <typename T>
 __global__ __launch_bounds__(kT) void seg_rle_bits_kernel(const T* __restrict__ masks, const SegGeom s, const int64_t* __restrict__ sel_q,
                                                           int64_t nwords, unsigned long long* __restrict__ bits)
@@ -588,112 +499,6 @@ __global__ __launch_bounds__(kT) void seg_rle_bits_kernel(const T* __restrict__ 
         }
         const unsigned long long b = __ballot(on);
         if ((threadIdx.x & 63) == 0 && (p >> 6) < nwords) bits[t * nwords + (p >> 6)] = b;
-    }
-}
-
-// the boundary mask of word j of one entry (bits beyond H * W are 0 in the packed words and are masked out here)
-__device__ __forceinline__ unsigned long long rle_boundaries(const unsigned long long* __restrict__ row, int64_t j, int64_t HW)
-{
-    const unsigned long long wd = row[j];
-    const unsigned long long prev = j > 0 ? row[j - 1] >> 63 : 0ull;
-    unsigned long long s = wd ^ ((wd << 1) | prev);
-    const int64_t left = HW - j * 64;
-    if (left < 64) s &= (1ull << left) - 1ull;
-    return s;
-}
-
-// inclusive scan of one int per thread over the workgroup, in thread order -> (exclusive prefix of this thread, workgroup total)
-__device__ __forceinline__ int block_excl_scan(int v, int& total)
-{
-    __shared__ int wsum[kT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();                                         // (wsum may still be read from an earlier call)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kT / 64; ++i) {
-        if (i < wave) base += wsum[i];
-        total += wsum[i];
-    }
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(kT) void seg_rle_count_kernel(const unsigned long long* __restrict__ bits, int64_t nwords, int64_t HW,
-                                                           int* __restrict__ tile_cnt)
-{
-    const int t = blockIdx.y;
-    const int64_t j = (int64_t)blockIdx.x * kRleWords + threadIdx.x;
-    int c = 0;
-    if (j < nwords) c = __popcll(rle_boundaries(bits + t * nwords, j, HW));
-    int total;
-    block_excl_scan(c, total);
-    if (threadIdx.x == 0) tile_cnt[(int64_t)t * gridDim.x + blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kT) void seg_rle_scan_kernel(const int* __restrict__ tile_cnt, int tiles, int T, int64_t* __restrict__ tile_off,
-                                                          int64_t* __restrict__ offsets)
-{
-    __shared__ int64_t part[kT];
-    const int64_t n = (int64_t)T * tiles;
-    const int64_t per = (n + kT - 1) / kT;
-    const int64_t lo = min(n, per * threadIdx.x), hi = min(n, lo + per);
-    int64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += tile_cnt[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {                                   // 256 partial sums: serial, fixed order
-        int64_t run = 0;
-        for (int i = 0; i < kT; ++i) {
-            const int64_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        offsets[T] = run + T;
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t i = lo; i < hi; ++i) {
-        const int64_t t = i / tiles;
-        const int64_t off = run + t;                          // + one end mark for every earlier entry
-        tile_off[i] = off;
-        if (i % tiles == 0) offsets[t] = off;
-        run += tile_cnt[i];
-    }
-}
-
-__global__ __launch_bounds__(kT) void seg_rle_scatter_kernel(const unsigned long long* __restrict__ bits, int64_t nwords, int64_t HW,
-                                                             const int64_t* __restrict__ tile_off, const int64_t* __restrict__ offsets,
-                                                             int64_t cap, unsigned* __restrict__ pos)
-{
-    const int t = blockIdx.y;
-    const int64_t j = (int64_t)blockIdx.x * kRleWords + threadIdx.x;
-    unsigned long long s = 0ull;
-    if (j < nwords) s = rle_boundaries(bits + t * nwords, j, HW);
-    int total;
-    int64_t slot = tile_off[(int64_t)t * gridDim.x + blockIdx.x] + block_excl_scan(__popcll(s), total);
-    while (s) {
-        const int k = __ffsll((long long)s) - 1;
-        if (slot < cap) pos[slot] = (unsigned)(j * 64 + k);      // (cap: the caller's total; never short when it read offsets[T])
-        ++slot;
-        s &= s - 1ull;
-    }
-    if (j == nwords - 1 && offsets[t + 1] <= cap) pos[offsets[t + 1] - 1] = (unsigned)HW;
-}
-
-__global__ __launch_bounds__(kT) void seg_rle_diff_kernel(const unsigned* __restrict__ pos, const int64_t* __restrict__ total_p, int64_t cap,
-                                                          unsigned HW, unsigned* __restrict__ counts)
-{
-    const int64_t total = min(*total_p, cap);
-    for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
-        const unsigned before = i > 0 ? pos[i - 1] : HW;
-        counts[i] = pos[i] - (before == HW ? 0u : before);
     }
 }
 
@@ -890,32 +695,6 @@ __global__ __launch_bounds__(kT) void seg_tta_finish_kernel(float* __restrict__ 
 }
 
 // ---- host side: argument checks and launches that several entry points share -------------------------------------------------------
-// records "<who>: <what>" as the error (who = the entry point without its mpf_ prefix, as in every message of this file)
-int fail_who(int code, const char* who, const char* what)
-{
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return mpf::fail(code, msg);
-}
-
-// the twelve leading arguments of the per-pixel entry points, checked and gathered into g
-int check_geom(const char* who, const void* masks, int64_t stride_q, int dtype, int Q, int h, int w, int Hp, int Wp, int hi, int wi,
-               int H, int W, SegGeom& g)
-{
-    if (!masks) return fail_who(MPF_E_NULL, who, "NULL mask logits");
-    if (dtype != MPF_F32 && dtype != MPF_BF16) return fail_who(MPF_E_DTYPE, who, "mask logits must be f32 or bf16 (dtype)");
-    if (Q <= 0 || h <= 0 || w <= 0 || Hp <= 0 || Wp <= 0 || hi <= 0 || wi <= 0 || H <= 0 || W <= 0 || hi > Hp || wi > Wp ||
-        stride_q < (int64_t)h * w) {
-        char what[160];
-        snprintf(what, sizeof what, "bad sizes (Q %d, low-res %dx%d, padded %dx%d, image %dx%d, output %dx%d, stride_q %lld)", Q, h, w, Hp,
-                 Wp, hi, wi, H, W, (long long)stride_q);
-        return fail_who(MPF_E_SHAPE, who, what);
-    }
-    if ((int64_t)H * W >= (1ll << 31) || (int64_t)Q * stride_q >= (1ll << 40)) return fail_who(MPF_E_TOO_LARGE, who, "output too large");
-    g = SegGeom{stride_q, Q, h, w, Hp, Wp, hi, wi, H, W};
-    return 0;
-}
-
 // the entries of an instance route are blockIdx.y of its kernels
 int check_entries(const char* who, int T)
 {
@@ -936,21 +715,6 @@ int tta_vec(const float* acc, int H, int W, int mode)
     const int64_t HW = (int64_t)H * W;
     return ((uintptr_t)acc & 15) == 0 && (HW & 3) == 0 && (!(mode & 2) || (W & 3) == 0);
 }
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// bytes of n [h, w] planes of mask logits: what a per-pixel kernel reads
-double logit_bytes(double n, const SegGeom& g, int dtype) { return n * g.h * g.w * (dtype == MPF_F32 ? 4 : 2); }
-
-// f(masks as const T*) with T = the type of the mask logits; elem_t<decltype(pointer)> names T inside f
-template <typename F>
-void with_mask_type(int dtype, const void* masks, F&& f)
-{
-    if (dtype == MPF_F32) f((const float*)masks);
-    else f((const __hip_bfloat16*)masks);
-}
-template <typename P>
-using elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
 
 // f(std::integral_constant<int, V>) for the V among Vs that equals v: a run-time tile count to a template argument
 template <int... Vs, typename F>
@@ -1268,9 +1032,7 @@ extern "C" int mpf_seg_instance_rle_count(const void* masks, int64_t stride_q, i
     mpf::prof_begin(st);
     mpf::set_kernel("seg_rle_bits_kernel+seg_rle_count_kernel+seg_rle_scan_kernel");
     launch_rle_bits(masks, dtype, g, sel_q, T, l.nwords, bits, st);
-    hipLaunchKernelGGL(seg_rle_count_kernel, dim3((unsigned)l.tiles, (unsigned)T), dim3(kT), 0, st, (const unsigned long long*)bits, l.nwords,
-                       HW, tile_cnt);
-    hipLaunchKernelGGL(seg_rle_scan_kernel, dim3(1), dim3(kT), 0, st, (const int*)tile_cnt, (int)l.tiles, T, tile_off, offsets);
+    launch_rle_count_scan(bits, T, l.nwords, l.tiles, HW, tile_cnt, tile_off, offsets, st);
     mpf::prof_end("seg_rle_bits_kernel", st, logit_bytes(T, g, dtype) + (double)T * HW / 8);
     return mpf::check(hipGetLastError(), "mpf_seg_instance_rle_count");
 }
@@ -1308,10 +1070,8 @@ extern "C" int mpf_seg_instance_rle_write(const void* workspace, size_t workspac
     const char* ws = (const char*)workspace;
     mpf::prof_begin(st);
     mpf::set_kernel("seg_rle_scatter_kernel+seg_rle_diff_kernel");
-    hipLaunchKernelGGL(seg_rle_scatter_kernel, dim3((unsigned)l.tiles, (unsigned)T), dim3(kT), 0, st, (const unsigned long long*)(ws + l.bits),
-                       l.nwords, HW, (const int64_t*)(ws + l.tile_off), offsets, total, pos);
-    const unsigned gdiff = (unsigned)std::min<int64_t>((total + kT - 1) / kT, 8 * mpf::cu_count());
-    hipLaunchKernelGGL(seg_rle_diff_kernel, dim3(gdiff), dim3(kT), 0, st, (const unsigned*)pos, offsets + T, total, (unsigned)HW, counts);
+    launch_rle_write((const unsigned long long*)(ws + l.bits), T, l.nwords, l.tiles, HW, (const int64_t*)(ws + l.tile_off), offsets, total, pos,
+                     counts, st);
     mpf::prof_end("seg_rle_scatter_kernel", st, (double)T * HW / 8 + 12.0 * total);
     return mpf::check(hipGetLastError(), "mpf_seg_instance_rle_write");
 }

@@ -144,6 +144,106 @@ def install_native_inference(model, image_list_cls=None, semantic_labels=False, 
     return cfg
 
 
+def native_video_eval_forward(model, batched_inputs, cfg, image_list_cls=None):
+    """The eval branch of a reference ``VideoMaskFormer`` (mask2former_video/video_maskformer_model.py:180-188 + 204-225) with
+    inference.postprocess_video in place of its F.interpolate of all queries and ``inference_video``: the frames of the one video
+    normalised and padded together, ``backbone`` and ``sem_seg_head`` as they are, then the clip ``pred_logits[0]`` /
+    ``pred_masks[0]``.  ``cfg``: an inference.VideoInferenceConfig.  Returns the ``video_output`` dict in the form ``cfg.masks``."""
+    from .inference import postprocess_video
+    if image_list_cls is None:
+        from detectron2.structures import ImageList as image_list_cls
+    if len(batched_inputs) != 1:
+        raise ValueError(f"the video eval branch takes one video at a time (:208, :219), got {len(batched_inputs)}")
+    images = [frame.to(model.device) for video in batched_inputs for frame in video["image"]]
+    images = [(x - model.pixel_mean) / model.pixel_std for x in images]
+    images = image_list_cls.from_tensors(images, model.size_divisibility)
+    outputs = model.sem_seg_head(model.backbone(images.tensor))
+    image_size = images.image_sizes[0]
+    inp = batched_inputs[0]
+    out_size = (inp.get("height", image_size[0]), inp.get("width", image_size[1]))
+    return postprocess_video(outputs["pred_logits"][0], outputs["pred_masks"][0], image_size, tuple(images.tensor.shape[-2:]), out_size, cfg)
+
+
+def install_native_video_inference(model, masks="dense", image_list_cls=None):
+    """Route the eval branch of a reference ``VideoMaskFormer`` instance through ``native_video_eval_forward``; training is
+    unchanged.  ``masks``: "dense" (the reference's result, the masks one bool tensor on the device), "bits" (packed, for
+    ``YTVISEvaluatorHIP.process``) or "rle" (for ``YTVISEvaluatorHIP.results_json``).  Returns the inference.VideoInferenceConfig in
+    use."""
+    from .inference import VideoInferenceConfig
+    cfg = VideoInferenceConfig.from_video_maskformer(model, masks=masks)
+    train_forward = model.forward
+
+    def forward(batched_inputs):
+        if model.training:
+            return train_forward(batched_inputs)
+        return native_video_eval_forward(model, batched_inputs, cfg, image_list_cls)
+
+    model.forward = forward
+    return cfg
+
+
+class YTVISEvaluatorHIP:
+    """The reference's ``YTVISEvaluator`` (mask2former_video/data_video/ytvis_eval.py) where the ground truth is at hand, on
+    inference.TubeAP: tubes are matched on the device, one record per detection crosses to the host at ``evaluate``.  Needs neither
+    detectron2 nor pycocotools.
+
+    ``process(inputs, outputs)``: ``outputs`` the "bits" form of inference.postprocess_video (one video), ``inputs[0]["instances"]``
+    the video's ground-truth tubes: ``gt_masks`` dense [G, F, H, W] (any of ``pack_masks``' dtypes; a frame without annotation all
+    zero) or packed int64 [G, F, nwords], ``gt_classes`` [G], optional ``gt_iscrowd`` [G].
+    ``evaluate()`` -> {"segm": {AP, AP50, AP75, APs, APm, APl, AR1, AR10, AP-{name}...}} (ytvis_eval.py:205).
+    ``results_json(video_id, output)``: the submission entries of ``instances_to_coco_json_video`` (:256-293) from the "rle" form.
+    Their "counts" are uncompressed run lengths (column-major, starting with the zeros); compressing them to the COCO string
+    (pycocotools' ``frPyObjects``) is the caller's, as with the image route's ``pred_masks_rle``."""
+
+    def __init__(self, num_classes, class_names=None, device="cuda:0", **ap_options):
+        from .inference import TubeAP
+        self.ap = TubeAP(num_classes, device=device, **ap_options)
+        if class_names is not None and len(class_names) != self.ap.num_classes:
+            raise ValueError(f"{len(class_names)} class names for {self.ap.num_classes} classes")
+        self.class_names = class_names
+
+    def reset(self):
+        self.ap.reset()
+
+    def process(self, inputs, outputs):
+        import torch
+        from .inference import pack_masks
+        if len(inputs) != 1:
+            raise ValueError("More than one inputs are loaded for inference!")      # ytvis_eval.py:267
+        if "bits" not in outputs:
+            raise ValueError("YTVISEvaluatorHIP.process takes the 'bits' form of postprocess_video (install_native_video_inference("
+                             "model, masks='bits'))")
+        dev = self.ap.device
+        dt_bits = outputs["bits"]
+        F, nwords = dt_bits.shape[1:]
+        H, W = outputs["size"]
+        gt = inputs[0]["instances"]
+        gm = gt["gt_masks"]
+        gm = getattr(gm, "tensor", gm).to(dev)
+        G = gm.shape[0]
+        if G == 0:
+            gt_bits = dt_bits.new_empty((0, F, nwords))
+        elif gm.dim() == 4:
+            if tuple(gm.shape[1:]) != (F, H, W):
+                raise ValueError(f"gt_masks {tuple(gm.shape)} are not [G, {F}, {H}, {W}], the prediction's frames and size")
+            gt_bits = pack_masks(gm.reshape(G * F, H, W)).view(G, F, nwords)
+        else:
+            gt_bits = gm
+        crowd = gt.get("gt_iscrowd")
+        self.ap.update(dt_bits, outputs["pred_scores"], outputs["pred_labels"], gt_bits, gt["gt_classes"],
+                       torch.zeros(G, dtype=torch.int32) if crowd is None else crowd, dt_frame_area=outputs["frame_area"])
+
+    def evaluate(self):
+        return {"segm": self.ap.results(self.class_names)}
+
+    @staticmethod
+    def results_json(video_id, output):
+        if "pred_masks_rle" not in output:
+            raise ValueError("YTVISEvaluatorHIP.results_json takes the 'rle' form of postprocess_video")
+        return [{"video_id": video_id, "score": s, "category_id": l, "segmentations": segms}
+                for s, l, segms in zip(output["pred_scores"], output["pred_labels"], output["pred_masks_rle"])]
+
+
 def is_hflip(tfm):
     """True when any transform of a ``TransformList`` (or a bare list of transforms) is an ``HFlipTransform``
     (test_time_augmentation.py:87): by ``isinstance`` where fvcore is importable, else by class name."""

@@ -18,6 +18,11 @@ For an evaluation loop the largest results can be had in the form their consumer
 ``SemanticTTA`` is the reference's semantic test-time augmentation (mask2former/test_time_augmentation.py): the mean of the
 views' "sem_seg", flipped views mirrored back, accumulated view by view in one [K, H, W] buffer on the device.
 
+``postprocess_video`` is the eval branch of the reference's ``VideoMaskFormer`` (mask2former_video/video_maskformer_model.py:
+204-287) for one clip, on csrc/seg_video.hip: the top entries are selected first and only their frames are resampled, as dense
+bool masks, packed bits or run lengths; ``InstanceAP(tubes=True)`` / ``TubeAP`` scores such tubes as the reference's
+YouTube-VIS evaluation does.
+
 Deviations from the reference, by design:
 * ``instances`` are sorted by score, descending (the reference's ``topk(sorted=False)`` order is unspecified);
 * all results are fp32 whatever the mask dtype (bf16 logits are widened on load; the reference would compute in bf16).
@@ -381,8 +386,118 @@ def instance_bits(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes,
     return out
 
 
+# ---- video instance segmentation ------------------------------------------------------------------------------------------------
+VIDEO_MASK_FORMS = ("dense", "bits", "rle")
+
+
+@dataclass
+class VideoInferenceConfig:
+    """The inference attributes of the reference's ``VideoMaskFormer`` (mask2former_video/video_maskformer_model.py:255-287)."""
+    num_classes: int
+    num_queries: int = 100
+    topk: int = 10                      # the reference hard-codes 10 (:260)
+    masks: str = "dense"                # "dense": bool [T, F, H, W]; "bits": packed words and frame areas; "rle": uncompressed COCO RLE
+
+    def __post_init__(self):
+        if self.masks not in VIDEO_MASK_FORMS:
+            raise ValueError(f"masks must be one of {VIDEO_MASK_FORMS}, got {self.masks!r}")
+        if int(self.topk) <= 0:
+            raise ValueError("topk must be positive")
+
+    @classmethod
+    def from_video_maskformer(cls, model, masks="dense"):
+        """Read the attributes of a reference ``VideoMaskFormer`` instance."""
+        return cls(num_classes=int(model.sem_seg_head.num_classes), num_queries=int(model.num_queries), masks=masks)
+
+
+def bits_rle(bits, size):
+    """Packed masks int64 [M, nwords] of ``size`` (H, W) on the device -> M uncompressed COCO RLE dicts {"size", "counts"}: the count /
+    scan / scatter / difference passes of the instance route on bits the caller holds already (``mpf_seg_bits_rle_count`` /
+    ``_write``).  Two device-to-host copies whatever M is: the offsets, then the counts."""
+    bits = _bits_arg(bits, "bits")
+    H, W = _bits_size(bits, size, "bits_rle")
+    M, dev = bits.shape[0], bits.device
+    if M == 0:
+        return []
+    stream = _lib.stream_ptr(dev)
+    ws = _lib.scratch("seg_video.rle", dev, stream, _lib.lib().mpf_seg_bits_rle_workspace_bytes(M, H, W))
+    offsets = torch.empty(M + 1, dtype=torch.int64, device=dev)
+    _lib.call("mpf_seg_bits_rle_count", dev, bits.data_ptr(), M, H, W, offsets.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    off = offsets.cpu().numpy()                          # copy 1: where every mask's counts lie
+    total = int(off[M])
+    pos = _lib.scratch("seg_video.rle_pos", dev, stream, 4 * total)
+    counts = torch.empty(total, dtype=torch.int32, device=dev)
+    _lib.call("mpf_seg_bits_rle_write", dev, bits.data_ptr(), ws.data_ptr(), ws.numel(), M, H, W, offsets.data_ptr(), total, pos.data_ptr(),
+              counts.data_ptr(), stream)
+    host = counts.cpu().numpy().view(np.uint32)          # copy 2: the packed counts
+    return [{"size": [H, W], "counts": host[off[m]:off[m + 1]].tolist()} for m in range(M)]
+
+
+def postprocess_video(pred_logits, pred_masks, image_size, padded_hw, output_size, cfg):
+    """The reference's video eval branch after the head (mask2former_video/video_maskformer_model.py:204-225 and inference_video,
+    :255-287) for ONE clip: pred_logits [Q, K+1] (any float dtype; widened to fp32), pred_masks [Q, F, h, w] fp32 / bf16 with
+    contiguous [h, w] planes (a slice of a larger decoder output is read in place), image_size (hi, wi) of the frames on the padded
+    grid, padded_hw = images.tensor.shape[-2:], output_size (height, width), cfg a ``VideoInferenceConfig``.
+
+    The top ``cfg.topk`` (query, class) entries are selected first and only their F planes are resampled
+    (``seg_video_bits_kernel``): the reference's [Q, F, Hp, Wp] upsampled tensor never exists.  There is no mask-score factor: the
+    video route has none.  -> the reference's ``video_output`` dict, "image_size" (height, width) and, by ``cfg.masks``:
+    * "dense": "pred_scores" / "pred_labels" python lists, "pred_masks" bool [T, F, height, width];
+    * "rle":   the same lists and "pred_masks_rle", T lists of F {"size", "counts"} dicts (uncompressed, column-major);
+    * "bits":  "bits" int64 [T, F, nwords] (``instance_bits``' layout per frame), "frame_area" int32 [T, F], "size", and
+      "pred_scores" / "pred_labels" as device tensors: no device-to-host copy at all (the form ``TubeAP.update`` takes).
+    Every form carries "pred_queries", the query of each entry.  An empty ``pred_logits`` gives the reference's empty result.
+
+    Deviations from the reference, by design:
+    * the entries are sorted by score, descending and stable (the reference's ``topk(sorted=False)`` order is unspecified);
+    * the dense masks stay on the device (the reference returns a list of CPU tensors);
+    * bf16 logits are widened on load and resampled in fp32."""
+    if not (pred_masks.is_cuda and pred_logits.is_cuda):
+        raise RuntimeError("postprocess_video: Not implemented on the CPU (device tensors only)")
+    if pred_logits.dim() != 2 or pred_masks.dim() != 4 or pred_masks.shape[0] != pred_logits.shape[0]:
+        raise ValueError(f"one clip: pred_logits [Q, K+1] and pred_masks [Q, F, h, w], got {tuple(pred_logits.shape)} and "
+                         f"{tuple(pred_masks.shape)}")
+    Q, K = pred_logits.shape[0], pred_logits.shape[1] - 1
+    if Q and K != cfg.num_classes:
+        raise ValueError(f"pred_logits has {K} classes + no-object, config {cfg.num_classes}")
+    H, W = int(output_size[0]), int(output_size[1])
+    F_ = pred_masks.shape[1]
+    pm = _planes(pred_masks)
+    dev = pm.device
+    stream = _lib.stream_ptr(dev)
+    nwords = (H * W + 63) // 64
+    if Q == 0 or F_ == 0:
+        sc = torch.empty(0, dtype=torch.float32, device=dev)
+        labels = query = torch.empty(0, dtype=torch.int64, device=dev)
+    else:
+        img = _Image(pred_logits.detach().float().contiguous(), K, 0.0, dev, stream, "video")
+        sc, idx = img.probs.reshape(-1).topk(min(int(cfg.topk), Q * K), sorted=True)
+        sc, order = sc.sort(descending=True, stable=True)
+        idx = idx[order]
+        labels, query = idx % K, (idx // K).contiguous()
+    T = int(sc.shape[0])
+    bits = torch.empty((T, F_, nwords), dtype=torch.int64, device=dev)
+    frame_area = torch.empty((T, F_), dtype=torch.int32, device=dev)
+    dense = torch.empty((T, F_, H, W), dtype=torch.bool, device=dev) if cfg.masks == "dense" else None
+    if T:
+        _lib.call("mpf_seg_video_bits", dev, pm.data_ptr(), pm.stride(0), pm.stride(1), _lib.DTYPE[pm.dtype], Q, F_, pm.shape[2], pm.shape[3],
+                  int(padded_hw[0]), int(padded_hw[1]), int(image_size[0]), int(image_size[1]), H, W, query.data_ptr(), T, bits.data_ptr(),
+                  frame_area.data_ptr(), _lib.ptr(dense), stream)
+    out = {"image_size": (H, W)}
+    if cfg.masks == "bits":
+        out.update(pred_scores=sc, pred_labels=labels, pred_queries=query, bits=bits, frame_area=frame_area, size=(H, W))
+        return out
+    out.update(pred_scores=sc.tolist(), pred_labels=labels.tolist(), pred_queries=query.tolist())
+    if cfg.masks == "dense":
+        out["pred_masks"] = dense
+    else:
+        rle = bits_rle(bits.view(T * F_, nwords), (H, W))
+        out["pred_masks_rle"] = [rle[t * F_:(t + 1) * F_] for t in range(T)]
+    return out
+
+
 # ---- semantic test-time augmentation --------------------------------------------------------------------------------------------
-TTA_ADD, TTA_HFLIP = 1, 2      # the mode bits of mpf_seg_tta_accumulate / mpf_seg_tta_resize_add
+TTA_ADD, TTA_HFLIP = 1, 2     # the mode bits of mpf_seg_tta_accumulate / mpf_seg_tta_resize_add
 
 
 class SemanticTTA:
@@ -752,6 +867,7 @@ def pq_results(stats, thing_ids):
 # ---- instance mask AP on the device ---------------------------------------------------------------------------------------------
 AP_CROWD_RULES = {"coco": 0, "union": 1}      # the crowd_rule argument of mpf_seg_ap_match
 COCO_AREA_RNGS = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))     # all, small, medium, large
+YTVIS_AREA_RNGS = ((0.0, 1e10), (0.0, 128.0 ** 2), (128.0 ** 2, 256.0 ** 2), (256.0 ** 2, 1e10))    # ytvoseval.py:543
 _AP_REC = 4                                   # int64 words of a detection's record
 
 
@@ -855,19 +971,32 @@ class InstanceAP:
     pair's IoU is min(mask IoU, IoU of the two masks' boundaries), the boundaries ``mask_boundaries`` with ``dilation_ratio``;
     area ranges, matching, accumulate and summarize are the same.
 
+    tubes: the YouTube-VIS form of the same file (``TubeAP``): a "mask" is a tube int64 [F, nwords], the packed words of its frames,
+    an image a video.  The IoU is ``iou_seq`` (:203-217): the frames' words concatenated, a frame without annotation all-zero words.
+    The area ranges test ``avg_area`` (:100-104, :283, :330), the mean of a tube's non-zero frame areas
+    (``mpf_seg_tube_areas``), on both sides, through ``mpf_seg_ap_match_tube``.  The defaults become crowd_rule "union" (what the
+    reference file computes) and ``YTVIS_AREA_RNGS``; ``results`` adds AR1 and AR10.  Boundary IoU has no tube form.
+
     Deviation: with ``gt_areas=None`` a ground truth's area is its pixel count (COCO reads the annotation's "area")."""
 
-    def __init__(self, num_classes, iou_thrs=None, area_rngs=None, max_dets=(1, 10, 100), crowd_rule="coco", device="cuda:0",
-                 iou_type="segm", dilation_ratio=0.02):
+    def __init__(self, num_classes, iou_thrs=None, area_rngs=None, max_dets=(1, 10, 100), crowd_rule=None, device="cuda:0",
+                 iou_type="segm", dilation_ratio=0.02, tubes=False):
         if iou_type not in AP_IOU_TYPES:
             raise ValueError(f"iou_type must be 'segm' or 'boundary', got {iou_type!r}")
+        self.tubes = bool(tubes)
+        if self.tubes and iou_type != "segm":
+            raise ValueError("tubes=True evaluates mask tubes: iou_type must be 'segm'")
+        if crowd_rule is None:
+            crowd_rule = "union" if self.tubes else "coco"
+        if area_rngs is None:
+            area_rngs = YTVIS_AREA_RNGS if self.tubes else COCO_AREA_RNGS
         self.iou_type = iou_type
         self.dilation_ratio = float(dilation_ratio)
         self.num_classes = int(num_classes)
         if self.num_classes <= 0:
             raise ValueError("num_classes must be positive")
         self.iou_thrs = np.linspace(.5, 0.95, 10) if iou_thrs is None else np.array(iou_thrs, dtype=np.float64)
-        self.area_rngs = np.array(COCO_AREA_RNGS if area_rngs is None else area_rngs, dtype=np.float64)
+        self.area_rngs = np.array(area_rngs, dtype=np.float64)
         self.rec_thrs = np.linspace(.0, 1.00, 101)
         if self.iou_thrs.ndim != 1 or self.iou_thrs.size == 0:
             raise ValueError("iou_thrs must be a non-empty list of thresholds")
@@ -913,15 +1042,28 @@ class InstanceAP:
             raise ValueError(f"{what} has {t.numel()} entries for {n} masks")
         return t
 
-    def update(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas=None, size=None, pair_counts=None):
+    def update(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas=None, size=None, pair_counts=None,
+               dt_frame_area=None, gt_frame_area=None):
         """One image.  dt_bits int64 [D, nwords] and gt_bits int64 [G, nwords] packed masks on the device (``instance_bits`` /
         ``pack_masks``), scores [D], classes [D], gt_classes [G], gt_crowd [G] (0 / 1), gt_areas [G] or None (= the pixel counts).
         The detections may come in any order: they are sorted by score, descending and stable (the reference's mergesort of -score).
         size: (H, W) of the image, required with iou_type="boundary" (the words alone do not tell H from W).
         pair_counts: what ``mask_pair_counts(dt_bits, gt_bits)`` returned for these masks, where the caller has it already.
+        tubes: one video.  dt_bits int64 [D, F, nwords] (``postprocess_video``, "bits" form) and gt_bits int64 [G, F, nwords]
+        (``pack_masks`` of the frames; a frame without annotation all zero); dt_frame_area int32 [D, F] / gt_frame_area int32 [G, F]
+        where the caller has them (``postprocess_video`` returns the detections'), else counted here; gt_areas [G] replaces the ground
+        truths' avg_area.
         No device-to-host copy."""
         if self.device.type != "cuda":
             raise RuntimeError("InstanceAP: Not implemented on the CPU (device tensors only)")
+        if self.tubes:
+            dt_tubes, gt_tubes = _tubes_arg(dt_bits, "dt_bits"), _tubes_arg(gt_bits, "gt_bits")
+            if dt_tubes.shape[0] and gt_tubes.shape[0] and dt_tubes.shape[1:] != gt_tubes.shape[1:]:
+                raise ValueError(f"detections are tubes of {tuple(dt_tubes.shape[1:])} (frames, words), ground truths of "
+                                 f"{tuple(gt_tubes.shape[1:])}: not one video")
+            dt_bits, gt_bits = dt_tubes.flatten(1), gt_tubes.flatten(1)
+        elif dt_frame_area is not None or gt_frame_area is not None:
+            raise ValueError("InstanceAP.update: frame areas belong to tubes=True")
         dt_bits, gt_bits = _bits_arg(dt_bits, "dt_bits"), _bits_arg(gt_bits, "gt_bits")
         if dt_bits.device != self.device or gt_bits.device != self.device:
             raise RuntimeError(f"masks on {dt_bits.device} / {gt_bits.device}, the records on {self.device}")
@@ -959,7 +1101,13 @@ class InstanceAP:
             d = boundary_dilation(H, W, self.dilation_ratio)
             inter_b, area_db, area_gb = mask_pair_counts(mask_boundaries(dt_bits, (H, W), d=d), mask_boundaries(gt_bits, (H, W), d=d))
             area_db, inter_b = area_db[order].contiguous(), inter_b[order].contiguous()
-        gt_area = area_g.double() if gt_areas is None else self._small(gt_areas, G, torch.float64, "gt_areas")
+        if self.tubes:
+            dt_area = tube_avg_areas(tube_frame_areas(dt_tubes) if dt_frame_area is None else dt_frame_area, D)[order].contiguous()
+            tube_gt_area = tube_avg_areas(tube_frame_areas(gt_tubes) if gt_frame_area is None else gt_frame_area, G)
+        else:
+            tube_gt_area = None
+        own_area = area_g.double() if tube_gt_area is None else tube_gt_area
+        gt_area = own_area if gt_areas is None else self._small(gt_areas, G, torch.float64, "gt_areas")
         if self._n + D > self._rec.shape[0]:                # grow by doubling; the old buffer stays valid for the queued launches
             grown = torch.empty((max(2 * self._rec.shape[0], self._n + D), _AP_REC), dtype=torch.int64, device=dev)
             grown[:self._n] = self._rec[:self._n]
@@ -971,9 +1119,11 @@ class InstanceAP:
         counts = (_lib.ptr(inter) if D and G else None, area_d.data_ptr() if D else None, area_g.data_ptr() if G else None)
         if boundary:
             counts += (_lib.ptr(inter_b) if D and G else None, area_db.data_ptr() if D else None, area_gb.data_ptr() if G else None)
-        _lib.call("mpf_seg_ap_match_boundary" if boundary else "mpf_seg_ap_match", dev, *counts,
+        entry = "mpf_seg_ap_match_tube" if self.tubes else "mpf_seg_ap_match_boundary" if boundary else "mpf_seg_ap_match"
+        areas = (gt_area.data_ptr() if G else None,) + ((dt_area.data_ptr() if D else None,) if self.tubes else ())
+        _lib.call(entry, dev, *counts,
                   D, G, scores.data_ptr() if D else None, classes.data_ptr() if D else None,
-                  gt_cat.data_ptr() if G else None, crowd.data_ptr() if G else None, gt_area.data_ptr() if G else None, sp, Tn, sp + 8 * Tn,
+                  gt_cat.data_ptr() if G else None, crowd.data_ptr() if G else None, *areas, sp, Tn, sp + 8 * Tn,
                   A, self.num_classes, self.max_dets[-1], AP_CROWD_RULES[self.crowd_rule], image,
                   self._rec.data_ptr() + 8 * _AP_REC * self._n, self._npig.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         self._n += D
@@ -1018,19 +1168,62 @@ class InstanceAP:
 
     def results(self, class_names=None, stats=None):
         """detectron2's ``COCOEvaluator`` keys for "segm": AP, AP50, AP75, APs, APm, APl (x 100, nan where the statistic is -1) and
-        one AP-{name} per category (names default to the class index)."""
+        one AP-{name} per category (names default to the class index).  tubes: AR1 and AR10 too, statistics 6 and 7
+        (``YTVISEvaluator._derive_coco_results``, mask2former_video/data_video/ytvis_eval.py:205)."""
         K = self.num_classes
         if class_names is not None and len(class_names) != K:
             raise ValueError(f"{len(class_names)} class names for {K} classes")
         acc = self.accumulate(stats)
         st = ap_summarize(acc, self.iou_thrs, self.max_dets)
-        out = {name: float(st[i] * 100 if st[i] >= 0 else "nan") for i, name in enumerate(("AP", "AP50", "AP75", "APs", "APm", "APl"))}
+        metrics = ("AP", "AP50", "AP75", "APs", "APm", "APl") + (("AR1", "AR10") if self.tubes else ())     # ytvis_eval.py:205
+        out = {name: float(st[i] * 100 if st[i] >= 0 else "nan") for i, name in enumerate(metrics)}
         names = [str(i) for i in range(K)] if class_names is None else list(class_names)
         for k, name in enumerate(names):
             p = acc["precision"][:, :, k, 0, -1]
             p = p[p > -1]
             out[f"AP-{name}"] = float(np.mean(p) * 100) if p.size else float("nan")
         return out
+
+
+class TubeAP(InstanceAP):
+    """``InstanceAP(..., tubes=True)``: the YouTube-VIS evaluation of the reference (``YTVOSeval``) on packed mask tubes."""
+
+    def __init__(self, num_classes, **options):
+        super().__init__(num_classes, tubes=True, **options)
+
+
+def _tubes_arg(bits, what):
+    if not bits.is_cuda:
+        raise RuntimeError(f"{what}: Not implemented on the CPU (device tensors only)")
+    if bits.dim() != 3 or bits.dtype != torch.int64:
+        raise ValueError(f"{what} must be packed tubes int64 [M, F, nwords], got {bits.dtype} {tuple(bits.shape)}")
+    return bits.contiguous()
+
+
+def tube_frame_areas(tubes):
+    """Packed tubes int64 [M, F, nwords] -> their per-frame areas int32 [M, F]: ``mask_pair_counts`` on the M * F frame rows with the
+    other side empty (one launch)."""
+    tubes = _tubes_arg(tubes, "tubes")
+    M, F, nwords = tubes.shape
+    if M * F == 0:
+        return torch.zeros((M, F), dtype=torch.int32, device=tubes.device)
+    return mask_pair_counts(tubes.view(M * F, nwords), tubes.new_empty((0, nwords)))[1].view(M, F)
+
+
+def tube_avg_areas(frame_area, M=None):
+    """``avg_area`` of the reference's ``_toMask`` (ytvoseval.py:100-104) from frame areas int32 [M, F] on the device: the float64
+    mean over the frames with a non-zero area, 0.0 without one."""
+    if not frame_area.is_cuda:
+        raise RuntimeError("tube_avg_areas: Not implemented on the CPU (device tensors only)")
+    if frame_area.dim() != 2 or frame_area.dtype != torch.int32 or (M is not None and frame_area.shape[0] != M):
+        raise ValueError(f"frame areas must be int32 [{'M' if M is None else M}, F], got {frame_area.dtype} {tuple(frame_area.shape)}")
+    frame_area = frame_area.contiguous()
+    dev = frame_area.device
+    out = torch.empty(frame_area.shape[0], dtype=torch.float64, device=dev)
+    if frame_area.shape[0]:
+        _lib.call("mpf_seg_tube_areas", dev, frame_area.data_ptr(), frame_area.shape[0], frame_area.shape[1], out.data_ptr(),
+                  _lib.stream_ptr(dev))
+    return out
 
 
 def ap_accumulate(stats, K, iou_thrs, rec_thrs, A, max_dets):
