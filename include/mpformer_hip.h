@@ -257,6 +257,31 @@ int mpf_match_cost(const void* pred, int pred_dtype, int h, int w, const int64_t
                    int n_rows, int Tmax, int P, float w_mask, float w_dice, int rows_per_group, void* stream);
 
 /*
+ * mpf_match_cost for clips (mask2former_video/modeling/matcher.py:113-148): a prediction row is a tube of F frames and the two
+ * sums run over the F * P samples of one point set that every frame shares,
+ *   cost[row, t] = w_mask*(sum softplus(x) - sum x*t)/(F*P) + w_dice*(1 - (2 sum s*t + 1)/(sum s + sum t + 1)).
+ * The contract is mpf_match_cost's, with:
+ *   F, stride_f   frame f of row r is the dense [h, w] plane at pred + pred_offs[r] + f * stride_f (elements; stride_f >= h * w
+ *                 when F > 1), so pred_masks [B, Q, F, h, w] may be a strided view along its first two dimensions;
+ *   tsamp         rows of F * P floats, frame-major: what mpf_point_sample writes for the G * F ground-truth planes of the
+ *                 tubes (plane g * F + f) with coord_rows = the clip's point set; t_first counts such rows;
+ *   coords        coords[coord_rows[row]] [P, 2] is used for every frame;
+ *   workspace     mpf_match_cost_clip_workspace_bytes(n_rows, F, Tmax) bytes (0 when a size is <= 0): the per-(row, frame) sums
+ *                 of a first launch, which a second launch adds in frame order.  No float atomics: the result is bit-identical
+ *                 from run to run.
+ * P <= 38400 per FRAME (F * P is not bounded), F <= 65535, else MPF_E_TOO_LARGE; dtypes MPF_F32 / MPF_BF16, else MPF_E_DTYPE;
+ * a workspace smaller than the query's answer is MPF_E_SHAPE, a NULL one MPF_E_NULL; all of it is checked before any launch.
+ * bf16 planes of at most 128 KiB (byte size a multiple of 16) with rows_per_group >= 2 dividing n_rows are staged in LDS, one
+ * frame at a time, and the target samples are streamed once per 2 rows; rows_per_group may be odd.
+ */
+size_t mpf_match_cost_clip_workspace_bytes(int n_rows, int F, int Tmax);
+int mpf_match_cost_clip(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs, int F, int64_t stride_f,
+                        const float* coords, const int32_t* coord_rows, const float* tsamp,
+                        const int32_t* t_first, const int32_t* t_count, float* cost,
+                        int n_rows, int Tmax, int P, float w_mask, float w_dice, int rows_per_group,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Attention mask of the next decoder layer, fused (mask2former_transformer_decoder.py:1869-1875 +
  * :1814-1816 + :1780): out[n, q, i] (bytes, 1 = do not attend) =
  *   q <  pad : mp_rows[n, q, i]                       (mask-piloted queries: ground-truth rows)

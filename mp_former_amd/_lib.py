@@ -63,6 +63,9 @@ SIGNATURES = {
     "mpf_sample_select_uncertain": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_match_cost": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                 _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_int, _c_vp]),
+    "mpf_match_cost_clip_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
+    "mpf_match_cost_clip": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_int, ctypes.c_int64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                     _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_int, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_attn_mask": (_c_int, [_c_vp, _c_int, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, _c_vp, _c_int, _c_vp,
                                _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_attn_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),

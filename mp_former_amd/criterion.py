@@ -122,6 +122,28 @@ class _MaskLossFinalizeFn(torch.autograd.Function):
         return d, None, None, None
 
 
+def group_mask_losses(sums, gid, gid_d, G, norm, P):
+    """(loss_mask [G], loss_dice [G]) from the point sums [n, 4] of the step's rows: group g = the rows with gid == g (host array;
+    ``gid_d`` its device copy, or None to upload it when needed), mean_p BCE and dice summed per group and divided by norm [G]
+    (criterion.py:21-65, :189-190).  One native launch when every group is one run of the row list, index_add otherwise."""
+    n = len(gid)
+    change = np.flatnonzero(np.diff(gid)) + 1
+    starts = np.concatenate([[0], change])
+    one_run_each = len(np.unique(gid[starts])) == len(starts)
+    if _native_tail() and one_run_each:
+        runs = np.zeros((G, 2), dtype=np.int64)
+        runs[gid[starts], 0] = starts
+        runs[gid[starts], 1] = np.diff(np.concatenate([starts, [n]]))
+        fin = _MaskLossFinalizeFn.apply(sums, upload(runs, sums.device), norm, P)
+        return fin[0], fin[1]
+    per_mask = sums[:, 0] / P                                                  # mean_p BCE (criterion.py:48-65)
+    per_dice = 1 - (2 * sums[:, 1] + 1) / (sums[:, 2] + sums[:, 3] + 1)        # criterion.py:21-40
+    z = torch.zeros(G, dtype=torch.float32, device=sums.device)
+    if gid_d is None:
+        gid_d = upload(gid, sums.device)
+    return z.index_add(0, gid_d, per_mask) / norm, z.index_add(0, gid_d, per_dice) / norm
+
+
 class LossDict(dict):
     """The 60-entry loss dict of the reference interface; the entries are views of a few per-output
     vectors, which ``SetCriterion.weighted_total`` weights directly."""
@@ -342,21 +364,7 @@ class SetCriterion(nn.Module):
                 else:
                     norm = upload([float(num_masks) * m for m in mult], dev, torch.float32)
                 # the pairs of a group are one run of the pair list (laid out above: per output, matched then MP pairs)
-                change = np.flatnonzero(np.diff(gid)) + 1
-                starts = np.concatenate([[0], change])
-                one_run_each = len(np.unique(gid[starts])) == len(starts)
-                if _native_tail() and one_run_each:
-                    runs = np.zeros((G, 2), dtype=np.int64)
-                    runs[gid[starts], 0] = starts
-                    runs[gid[starts], 1] = np.diff(np.concatenate([starts, [n_pairs]]))
-                    fin = _MaskLossFinalizeFn.apply(sums, upload(runs, dev), norm, P)
-                    g_mask, g_dice = fin[0], fin[1]
-                else:
-                    per_mask = sums[:, 0] / P                                                  # mean_p BCE (criterion.py:48-65)
-                    per_dice = 1 - (2 * sums[:, 1] + 1) / (sums[:, 2] + sums[:, 3] + 1)        # criterion.py:21-40
-                    z = torch.zeros(G, dtype=torch.float32, device=dev)
-                    g_mask = z.index_add(0, gid_d, per_mask) / norm
-                    g_dice = z.index_add(0, gid_d, per_dice) / norm
+                g_mask, g_dice = group_mask_losses(sums, gid, gid_d, G, norm, P)
             else:
                 # no ground truth anywhere: sums over empty sets (still consume the draws for RNG parity)
                 _rng.rand_cat(over_parts, dev)

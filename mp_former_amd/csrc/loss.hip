@@ -551,25 +551,36 @@ __global__ __launch_bounds__(kSelThreads) void select_uncertain_kernel(
 //                + w_dice * (1 - (2 sum_p s_p t_p + 1) / (sum_p s_p + sum_p t_p + 1))
 // x sampled on the fly from the prediction map, t from the pre-sampled [.., P] ground-truth points.
 // One workgroup per row; TT targets at a time in registers.
+//
+// CLIP (mpf_match_cost_clip, mask2former_video/modeling/matcher.py:113-141): a row is a tube of gridDim.y frames whose planes lie
+// stride_f elements apart and a target row holds gridDim.y * P samples, frame-major; the point set is the same in every frame.
+// All five sums are additive over the frames, so workgroup (row, f) does exactly the work of the image form on frame f and,
+// instead of the cost, leaves its sums in partial[row][f][2 + 3 Tmax] = {softplus, sigmoid, then (x t, s t, t) per target};
+// match_cost_clip_fold_kernel adds the frames in order and applies the two formulas.  No atomics: bit-identical run to run.
 // ================================================================================================
 constexpr int kTT = 8;
 
-template <typename T>
+__host__ __device__ __forceinline__ int clip_partial_floats(int Tmax) { return 2 + 3 * Tmax; }
+
+template <typename T, bool CLIP>
 __global__ __launch_bounds__(kThreads) void match_cost_kernel(
     const T* __restrict__ pred, int h, int w, const int64_t* __restrict__ pred_offs,
     const float* __restrict__ coords, const int32_t* __restrict__ coord_rows,
     const float* __restrict__ tsamp, const int32_t* __restrict__ t_first, const int32_t* __restrict__ t_count,
-    float* __restrict__ cost, int Tmax, int P, float w_mask, float w_dice)
+    float* __restrict__ cost, int Tmax, int P, float w_mask, float w_dice, int64_t stride_f, float* __restrict__ partial)
 {
-    extern __shared__ float xs[];                    // [P] sampled logits of this row (gathered ONCE)
+    extern __shared__ float xs[];                    // [P] sampled logits of this row's frame (gathered ONCE)
     __shared__ float red[kThreads / 64];
     const int row = blockIdx.x;
+    const int f = CLIP ? blockIdx.y : 0, F = CLIP ? gridDim.y : 1;
     const int Tn = t_count[row];
     if (Tn == 0) return;
-    const T* pm = pred + pred_offs[row];
+    const T* pm = pred + pred_offs[row] + f * stride_f;
     const float2* c = reinterpret_cast<const float2*>(coords) + (int64_t)coord_rows[row] * P;
     const int T0 = t_first[row];
-    float* out = cost + (int64_t)row * Tmax;
+    const int64_t t_len = (int64_t)F * P;              // floats per target row
+    const float* ts = tsamp + (int64_t)f * P;
+    float* out = CLIP ? partial + ((int64_t)row * F + f) * clip_partial_floats(Tmax) : cost + (int64_t)row * Tmax;
     float sp = 0.f, sg_sum = 0.f;
     for (int p = threadIdx.x; p < P; p += kThreads) {
         const float2 xy = c[p];
@@ -580,6 +591,7 @@ __global__ __launch_bounds__(kThreads) void match_cost_kernel(
     }
     sp = block_sum(sp, red);
     sg_sum = block_sum(sg_sum, red);                               // (block_sum's barriers publish xs)
+    if (CLIP && threadIdx.x == 0) { out[0] = sp; out[1] = sg_sum; }
     for (int tb = 0; tb < Tn; tb += kTT) {
         float ax[kTT], as[kTT], at[kTT];
 #pragma unroll
@@ -590,7 +602,7 @@ __global__ __launch_bounds__(kThreads) void match_cost_kernel(
 #pragma unroll
             for (int j = 0; j < kTT; ++j) {
                 if (tb + j < Tn) {
-                    const float tv = tsamp[(int64_t)(T0 + tb + j) * P + p];
+                    const float tv = ts[(int64_t)(T0 + tb + j) * t_len + p];
                     ax[j] += x * tv; as[j] += sg * tv; at[j] += tv;
                 }
             }
@@ -599,12 +611,39 @@ __global__ __launch_bounds__(kThreads) void match_cost_kernel(
         for (int j = 0; j < kTT; ++j) {
             const float sx = block_sum(ax[j], red), ss = block_sum(as[j], red), st = block_sum(at[j], red);
             if (threadIdx.x == 0 && tb + j < Tn) {
-                const float cm = (sp - sx) / (float)P;
-                const float cd = 1.f - (2.f * ss + 1.f) / (sg_sum + st + 1.f);
-                out[tb + j] = w_mask * cm + w_dice * cd;
+                if (CLIP) {
+                    float* o = out + 2 + 3 * (tb + j);
+                    o[0] = sx; o[1] = ss; o[2] = st;
+                } else {
+                    const float cm = (sp - sx) / (float)P;
+                    const float cd = 1.f - (2.f * ss + 1.f) / (sg_sum + st + 1.f);
+                    out[tb + j] = w_mask * cm + w_dice * cd;
+                }
             }
         }
     }
+}
+
+// cost[row, t] from the per-frame sums of the two CLIP kernels: frames added in index order, then the image form's formulas with
+// F * P points.  One thread per (row, t); t >= t_count[row] is left untouched.
+__global__ __launch_bounds__(kThreads) void match_cost_clip_fold_kernel(
+    const float* __restrict__ partial, const int32_t* __restrict__ t_count, float* __restrict__ cost,
+    int n_rows, int F, int Tmax, int P, float w_mask, float w_dice)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (int64_t)n_rows * Tmax) return;
+    const int row = (int)(i / Tmax), t = (int)(i - (int64_t)row * Tmax);
+    if (t >= t_count[row]) return;
+    const int W = clip_partial_floats(Tmax);
+    const float* p = partial + (int64_t)row * F * W;
+    float sp = 0.f, sg = 0.f, sx = 0.f, ss = 0.f, st = 0.f;
+    for (int f = 0; f < F; ++f, p += W) {
+        sp += p[0]; sg += p[1];
+        sx += p[2 + 3 * t]; ss += p[3 + 3 * t]; st += p[4 + 3 * t];
+    }
+    const float cm = (sp - sx) / ((float)F * (float)P);
+    const float cd = 1.f - (2.f * ss + 1.f) / (sg + st + 1.f);
+    cost[i] = w_mask * cm + w_dice * cd;
 }
 
 }  // namespace
@@ -688,25 +727,36 @@ __device__ __forceinline__ float wave_sum64(float v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-template <typename T, int G, int PT, int THREADS>
+// CLIP: workgroup (x, f) stages frame f of its rows and writes the per-frame sums (see match_cost_kernel); a run of `rpg` rows
+// that share their point set is cut into ceil(rpg / G) workgroups, the last one of a run taking the rows that are left.
+template <typename T, int G, int PT, int THREADS, bool CLIP>
 __global__ __launch_bounds__(THREADS) void match_cost_lds_kernel(
     const T* __restrict__ pred, int h, int w, const int64_t* __restrict__ pred_offs,
     const float* __restrict__ coords, const int32_t* __restrict__ coord_rows,
     const float* __restrict__ tsamp, const int32_t* __restrict__ t_first, const int32_t* __restrict__ t_count,
-    float* __restrict__ cost, int n_rows, int Tmax, int P, float w_mask, float w_dice, int plane_bytes)
+    float* __restrict__ cost, int n_rows, int Tmax, int P, float w_mask, float w_dice, int plane_bytes,
+    int64_t stride_f, float* __restrict__ partial, int rpg)
 {
     constexpr int TT = 4;                       // targets per pass
     constexpr int NV = 2 * G * TT + TT;         // values reduced per pass
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T* plane = reinterpret_cast<T*>(smem);
     float* red = reinterpret_cast<float*>(smem + plane_bytes);       // [16 waves][NV]
-    const int row0 = blockIdx.x * G;
+    int row0 = blockIdx.x * G, left = n_rows - row0;
+    if (CLIP) {
+        const int per = (rpg + G - 1) / G, run = blockIdx.x / per, sub = blockIdx.x - run * per;
+        row0 = run * rpg + sub * G;
+        left = rpg - sub * G;
+    }
+    const int f = CLIP ? blockIdx.y : 0, F = CLIP ? gridDim.y : 1;
     const int Tn = t_count[row0];
     if (Tn == 0) return;
     const int T0 = t_first[row0];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float2* c = reinterpret_cast<const float2*>(coords) + (int64_t)coord_rows[row0] * P;
-    const int ng = min(G, n_rows - row0);
+    const int ng = min(G, left);
+    const int64_t t_len = (int64_t)F * P;              // floats per target row
+    const float* ts = tsamp + (int64_t)f * P;
 
     float2 xy[PT];
 #pragma unroll
@@ -720,7 +770,7 @@ __global__ __launch_bounds__(THREADS) void match_cost_lds_kernel(
     for (int g = 0; g < G; ++g) {
         sp[g] = 0.f; sgs[g] = 0.f;
         __syncthreads();
-        if (g < ng) copy_plane_to_lds<THREADS>(plane, pred + pred_offs[row0 + g], plane_bytes, tid);
+        if (g < ng) copy_plane_to_lds<THREADS>(plane, pred + pred_offs[row0 + g] + f * stride_f, plane_bytes, tid);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < PT; ++j) {
@@ -768,7 +818,7 @@ __global__ __launch_bounds__(THREADS) void match_cost_lds_kernel(
                 // unconditional loads (indices clamped, values masked below): a load behind a run-time condition
                 // makes hipcc wait for each one separately — 100 dependent L2 round trips per pass
 #pragma unroll
-                for (int tt = 0; tt < TT; ++tt) tv[jj][tt] = tsamp[(int64_t)(T0 + min(tb + tt, Tn - 1)) * P + p];
+                for (int tt = 0; tt < TT; ++tt) tv[jj][tt] = ts[(int64_t)(T0 + min(tb + tt, Tn - 1)) * t_len + p];
             }
 #pragma unroll
             for (int jj = 0; jj < JC; ++jj) {
@@ -814,9 +864,16 @@ __global__ __launch_bounds__(THREADS) void match_cost_lds_kernel(
                     ss += red[k * NV + (g * TT + tt) * 2 + 1];
                     st += red[k * NV + 2 * G * TT + tt];
                 }
-                const float cm = (sp_tot - sx) / (float)P;
-                const float cd = 1.f - (2.f * ss + 1.f) / (sg_tot + st + 1.f);
-                cost[(int64_t)(row0 + g) * Tmax + tb + tt] = w_mask * cm + w_dice * cd;
+                if (CLIP) {
+                    float* o = partial + ((int64_t)(row0 + g) * F + f) * clip_partial_floats(Tmax);
+                    if (tb + tt == 0) { o[0] = sp_tot; o[1] = sg_tot; }
+                    o += 2 + 3 * (tb + tt);
+                    o[0] = sx; o[1] = ss; o[2] = st;
+                } else {
+                    const float cm = (sp_tot - sx) / (float)P;
+                    const float cd = 1.f - (2.f * ss + 1.f) / (sg_tot + st + 1.f);
+                    cost[(int64_t)(row0 + g) * Tmax + tb + tt] = w_mask * cm + w_dice * cd;
+                }
             }
         }
     }
@@ -1008,23 +1065,28 @@ static bool launch_mask_loss_fwd_lds(const void* pred, int pred_dtype, int h, in
 
 // 512 threads x 25 points: the samples of 4 rows stay in registers without spilling (1024 threads leave
 // 128 VGPRs per lane: 180 spilled registers and 2.6x the time)
+// F == 0: the image form.  F >= 1 (mpf_match_cost_clip): per-frame sums into `partial`, any G >= 2 (the workgroups of a run
+// handle its tail), planes of at most 128 KiB.
 template <typename T>
 static bool launch_match_cost_lds(const T* pred, int h, int w, const int64_t* pred_offs, const float* coords,
                                   const int32_t* coord_rows, const float* tsamp, const int32_t* t_first, const int32_t* t_count,
                                   float* cost, int n_rows, int Tmax, int P, float w_mask, float w_dice, int G, hipStream_t st,
-                                  int* err)
+                                  int* err, int F = 0, int64_t stride_f = 0, float* partial = nullptr)
 {
     constexpr int THREADS = 512, PT = 25;
     const int plane_bytes = h * w * (int)sizeof(T);
     constexpr int GQ = 2;                      // rows per workgroup (4 would need ~300 registers per lane)
-    if (G % GQ != 0 || plane_bytes % 16 != 0 || plane_bytes > 136 * 1024 || P > PT * THREADS || n_rows % GQ != 0) return false;
+    if (plane_bytes % 16 != 0 || P > PT * THREADS) return false;
+    if (F ? (G < 2 || n_rows % G != 0 || plane_bytes > 128 * 1024) : (G % GQ != 0 || plane_bytes > 136 * 1024 || n_rows % GQ != 0))
+        return false;
     constexpr int NV = 2 * GQ * 4 + 4;
     const size_t lds = (size_t)plane_bytes + (THREADS / 64) * NV * sizeof(float);
-    auto kfn = match_cost_lds_kernel<T, GQ, PT, THREADS>;
+    auto kfn = F ? match_cost_lds_kernel<T, GQ, PT, THREADS, true> : match_cost_lds_kernel<T, GQ, PT, THREADS, false>;
     *err = mpf::check(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute");
     if (*err) return true;
-    hipLaunchKernelGGL(kfn, dim3(n_rows / GQ), dim3(THREADS), lds, st, pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first,
-                       t_count, cost, n_rows, Tmax, P, w_mask, w_dice, plane_bytes);
+    const dim3 grid = F ? dim3((n_rows / G) * ((G + GQ - 1) / GQ), F) : dim3(n_rows / GQ);
+    hipLaunchKernelGGL(kfn, grid, dim3(THREADS), lds, st, pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first,
+                       t_count, cost, n_rows, Tmax, P, w_mask, w_dice, plane_bytes, stride_f, partial, G);
     return true;
 }
 
@@ -1052,18 +1114,80 @@ extern "C" int mpf_match_cost(const void* pred, int pred_dtype, int h, int w, co
     }
     if (pred_dtype == MPF_F32) {
         mpf::set_kernel("match_cost_kernel<float>");
-        hipLaunchKernelGGL(match_cost_kernel<float>, dim3(n_rows), dim3(kThreads), (size_t)P * 4, st, (const float*)pred, h, w,
-                           pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice);
+        hipLaunchKernelGGL((match_cost_kernel<float, false>), dim3(n_rows), dim3(kThreads), (size_t)P * 4, st, (const float*)pred, h, w,
+                           pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, (int64_t)0,
+                           (float*)nullptr);
     } else if (pred_dtype == MPF_BF16) {
         mpf::set_kernel("match_cost_kernel<bf16>");
-        hipLaunchKernelGGL(match_cost_kernel<__hip_bfloat16>, dim3(n_rows), dim3(kThreads), (size_t)P * 4, st,
+        hipLaunchKernelGGL((match_cost_kernel<__hip_bfloat16, false>), dim3(n_rows), dim3(kThreads), (size_t)P * 4, st,
                            (const __hip_bfloat16*)pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first, t_count,
-                           cost, Tmax, P, w_mask, w_dice);
+                           cost, Tmax, P, w_mask, w_dice, (int64_t)0, (float*)nullptr);
     } else {
         return mpf::fail(MPF_E_DTYPE, "mpf_match_cost: pred dtype must be MPF_F32 or MPF_BF16");
     }
     mpf::prof_end(mpf_last_kernel(), st, (double)n_rows * P * (8.0 + 16.0 + 4.0 * Tmax));
     return mpf::check(hipGetLastError(), "mpf_match_cost");
+}
+
+extern "C" size_t mpf_match_cost_clip_workspace_bytes(int n_rows, int F, int Tmax)
+{
+    if (n_rows <= 0 || F <= 0 || Tmax <= 0) return 0;
+    return (size_t)n_rows * F * clip_partial_floats(Tmax) * sizeof(float);
+}
+
+extern "C" int mpf_match_cost_clip(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs, int F, int64_t stride_f,
+                                   const float* coords, const int32_t* coord_rows, const float* tsamp,
+                                   const int32_t* t_first, const int32_t* t_count, float* cost,
+                                   int n_rows, int Tmax, int P, float w_mask, float w_dice, int rows_per_group,
+                                   void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!pred || !pred_offs || !coords || !coord_rows || !tsamp || !t_first || !t_count || !cost)
+        return mpf::fail(MPF_E_NULL, "match_cost_clip: NULL buffer");
+    if (n_rows < 0 || Tmax <= 0 || P <= 0 || h <= 0 || w <= 0 || F <= 0 || rows_per_group <= 0)
+        return mpf::fail(MPF_E_SHAPE, "match_cost_clip: bad sizes");
+    if (stride_f < (int64_t)h * w && F > 1) return mpf::fail(MPF_E_SHAPE, "match_cost_clip: the frames of a row overlap (stride_f < h * w)");
+    if (pred_dtype != MPF_F32 && pred_dtype != MPF_BF16) return mpf::fail(MPF_E_DTYPE, "mpf_match_cost_clip: pred dtype must be MPF_F32 or MPF_BF16");
+    // per FRAME, as in mpf_match_cost: the generic kernel keeps one frame's logits in LDS, never the F * P of a tube
+    if ((size_t)P * 4 > 150 * 1024) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_clip: more than 38400 points per frame");
+    if (F > 65535) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_clip: more than 65535 frames (grid.y)");
+    if ((int64_t)n_rows * Tmax > (int64_t)kThreads * 0x7fffffff) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_clip: cost matrix too large");
+    if (n_rows == 0) return 0;
+    if (!workspace) return mpf::fail(MPF_E_NULL, "match_cost_clip: NULL workspace");
+    if (workspace_bytes < mpf_match_cost_clip_workspace_bytes(n_rows, F, Tmax))
+        return mpf::fail(MPF_E_SHAPE, "match_cost_clip: workspace too small (mpf_match_cost_clip_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    float* partial = (float*)workspace;
+    const size_t xs_bytes = (size_t)P * 4;
+    mpf::prof_begin(st);
+    bool done = false;
+    if (pred_dtype == MPF_BF16 && rows_per_group >= 2) {
+        int err = 0;
+        mpf::set_kernel("match_cost_clip_lds_kernel<bf16>");
+        done = launch_match_cost_lds((const __hip_bfloat16*)pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost,
+                                     n_rows, Tmax, P, w_mask, w_dice, rows_per_group, st, &err, F, stride_f, partial);
+        if (err) return err;
+    }
+    if (!done && pred_dtype == MPF_F32) {
+        mpf::set_kernel("match_cost_clip_kernel<float>");
+        auto kfn = match_cost_kernel<float, true>;
+        if (xs_bytes > 32 * 1024)
+            if (int e = mpf::check(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs_bytes), "hipFuncSetAttribute")) return e;
+        hipLaunchKernelGGL(kfn, dim3(n_rows, F), dim3(kThreads), xs_bytes, st, (const float*)pred, h, w, pred_offs, coords, coord_rows,
+                           tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, stride_f, partial);
+    } else if (!done) {
+        mpf::set_kernel("match_cost_clip_kernel<bf16>");
+        auto kfn = match_cost_kernel<__hip_bfloat16, true>;
+        if (xs_bytes > 32 * 1024)
+            if (int e = mpf::check(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs_bytes), "hipFuncSetAttribute")) return e;
+        hipLaunchKernelGGL(kfn, dim3(n_rows, F), dim3(kThreads), xs_bytes, st, (const __hip_bfloat16*)pred, h, w, pred_offs, coords,
+                           coord_rows, tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, stride_f, partial);
+    }
+    if (int e = mpf::check(hipGetLastError(), "mpf_match_cost_clip")) return e;
+    const int64_t cells = (int64_t)n_rows * Tmax;
+    hipLaunchKernelGGL(match_cost_clip_fold_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, partial,
+                       t_count, cost, n_rows, F, Tmax, P, w_mask, w_dice);
+    mpf::prof_end(mpf_last_kernel(), st, (double)n_rows * F * ((double)h * w * 2.0 + P * 8.0 / 2 + P * 4.0 * Tmax / 2));
+    return mpf::check(hipGetLastError(), "mpf_match_cost_clip");
 }
 
 extern "C" int mpf_sample_select_uncertain(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs,

@@ -182,6 +182,36 @@ def install_native_video_inference(model, masks="dense", image_list_cls=None):
     return cfg
 
 
+def install_native_video_training(model):
+    """Give a reference ``VideoMaskFormer`` instance the native losses of a clip (video_losses.py): ``model.criterion`` becomes a
+    ``VideoSetCriterion`` built from the old one's fields (matcher weights and points, ``num_classes``, ``weight_dict``,
+    ``eos_coef``, ``losses`` and the three sampling parameters) and ``model.prepare_targets`` one that calls
+    ``prepare_video_targets`` (bool masks, no float copy).  The training branch of ``forward`` (:190-203) runs on as it is; the
+    eval branch and ``install_native_video_inference`` are not touched.  Returns the new criterion."""
+    from .video_losses import VideoHungarianMatcher, VideoSetCriterion, prepare_video_targets
+    old = model.criterion
+    matcher = VideoHungarianMatcher(cost_class=old.matcher.cost_class, cost_mask=old.matcher.cost_mask,
+                                    cost_dice=old.matcher.cost_dice, num_points=old.matcher.num_points)
+    criterion = VideoSetCriterion(old.num_classes, matcher=matcher, weight_dict=old.weight_dict, eos_coef=old.eos_coef,
+                                  losses=old.losses, num_points=old.num_points, oversample_ratio=old.oversample_ratio,
+                                  importance_sample_ratio=old.importance_sample_ratio)
+    criterion.to(old.empty_weight.device)
+    criterion.train(getattr(old, "training", True))
+
+    def prepare_targets(targets, images):
+        padded_hw = tuple(images.tensor.shape[-2:])
+        out = []
+        for video in targets:
+            frames = [fr.to(model.device) for fr in video["instances"]]
+            out.append(prepare_video_targets([fr.gt_masks.tensor for fr in frames], [fr.gt_ids for fr in frames],
+                                             frames[-1].gt_classes, padded_hw))
+        return out
+
+    model.criterion = criterion
+    model.prepare_targets = prepare_targets
+    return criterion
+
+
 class YTVISEvaluatorHIP:
     """The reference's ``YTVISEvaluator`` (mask2former_video/data_video/ytvis_eval.py) where the ground truth is at hand, on
     inference.TubeAP: tubes are matched on the device, one record per detection crosses to the host at ``evaluate``.  Needs neither

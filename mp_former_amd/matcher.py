@@ -82,7 +82,7 @@ class HungarianMatcher(nn.Module):
         has a target.  Draws the matcher's point sets either way (RNG parity)."""
         L = len(outs)
         N, Q = outs[0]["pred_logits"].shape[:2]
-        gt = gt or GTMasks(targets)
+        gt = gt or self._store(targets)
         dev = gt.device
         P = self.num_points
         tags = tags or ["match"] + [f"match_{i}" for i in range(L - 1)]
@@ -131,14 +131,23 @@ class HungarianMatcher(nn.Module):
             tsamp = self._gt_samples(gt, gt_offs_d, coords, gcrow_d, dev)
             C = match_cost(mapset, pred_offs_d, coords, crow_d, tsamp, tfirst_d, tcount_d, Tmax,
                            self.cost_mask, self.cost_dice, rows_per_group=Q).view(L, N, Q, Tmax)   # rows are (l, b, q), q fastest
-        # ---- class cost: -softmax(logits)[:, labels]  (matcher.py:105-111) ------------------------
+        return self._add_class_cost(C, outs, targets, gt)
+
+    def _add_class_cost(self, C, outs, targets, gt):
+        """C [L, N, Q, Tmax] (mask + dice part) + the class cost -softmax(logits)[:, labels]  (matcher.py:105-111)"""
+        L, N, Q, Tmax = C.shape
         logits = torch.stack([o["pred_logits"] for o in outs]).float()                  # [L,N,Q,K+1]
-        labels = torch.zeros((N, Tmax), dtype=torch.int64, device=dev)
+        labels = torch.zeros((N, Tmax), dtype=torch.int64, device=C.device)
         for b, t in enumerate(targets):
             if gt.counts[b]:
                 labels[b, :gt.counts[b]] = t["labels"]
         prob = logits.softmax(-1)
         return (C - self.cost_class * torch.gather(prob, 3, labels[None, :, None, :].expand(L, N, Q, Tmax))).contiguous()
+
+    @staticmethod
+    def _store(targets):
+        """the ground-truth store of a batch (the video matcher keeps tubes: video_losses.GTTubes)"""
+        return GTMasks(targets)
 
     @staticmethod
     def _gt_samples(gt, gt_offs_d, coords, gcrow_d, dev):
@@ -155,7 +164,7 @@ class HungarianMatcher(nn.Module):
         `mapset` / `map_index` optionally give a MapSet that already contains the mask tensors."""
         L = len(outs)
         N = outs[0]["pred_logits"].shape[0]
-        gt = gt or GTMasks(targets)
+        gt = gt or self._store(targets)
         empty = (torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int64))
         C = self.cost_matrices(outs, targets, gt=gt, tags=tags, mapset=mapset, map_index=map_index)
         if C is None:

@@ -156,6 +156,21 @@ def match_cost(ms, offs, coords, coord_rows, tsamp, t_first, t_count, Tmax, w_ma
     return cost
 
 
+def match_cost_clip(ms, offs, F, coords, coord_rows, tsamp, t_first, t_count, Tmax, w_mask, w_dice, rows_per_group=1):
+    """match_cost for tubes (mpf_match_cost_clip): ``ms`` holds [B, Q * F, h, w] maps, offs[i] = frame 0 of row i, its frames lie
+    h * w elements apart; tsamp rows are F * P floats, frame-major -> cost [n, Tmax] f32."""
+    n = offs.numel()
+    P = coords.shape[-2]
+    cost = torch.zeros((n, Tmax), dtype=torch.float32, device=ms.device)
+    if n:
+        st = _lib.stream_ptr(ms.device)
+        ws = _lib.scratch("match_cost_clip", ms.device, st, _lib.lib().mpf_match_cost_clip_workspace_bytes(n, F, Tmax))
+        _lib.call("mpf_match_cost_clip", ms.device, ms.base_ptr, _lib.DTYPE[ms.dtype], ms.h, ms.w, offs.data_ptr(), F, ms.h * ms.w,
+                  coords.data_ptr(), coord_rows.data_ptr(), tsamp.data_ptr(), t_first.data_ptr(), t_count.data_ptr(), cost.data_ptr(),
+                  n, Tmax, P, float(w_mask), float(w_dice), int(rows_per_group), ws.data_ptr(), ws.numel(), st)
+    return cost
+
+
 def _mask_loss_sums_forward(ctx, ms, pred_offs, gt, gt_rows, coords):
     """forward of MaskLossSums / MaskLossSumsCompact; leaves (gt_u8, gt_hw, gdt, ms) on ctx"""
     # gt: GTMasks (its bit-packed copy is used when present) or a [R, H, W] byte tensor
