@@ -719,17 +719,8 @@ int mpf_grouped_scale_cast(const MpfScaleCastItem* items_device, int n_items, in
  *   mpf_gemm3_tn_h2: mpf_gemm3_tn without the a2 rows; out_amax (may be NULL) receives max |C|.
  */
 #define MPF_AMAX_SLOT_FLOATS 512
-/* producers of amax slots outside the GEMMs (encoder LayerNorms, msdeformattn.py:123-131):
- *   mpf_res_ln256_forward_b: mpf_res_ln256_forward that also writes an UPPER BOUND of |y| into y_bound (16 max|gamma| +
- *     max|beta|: a normalised row of 256 values cannot exceed sqrt(255)) and of |y + padd| into yplus_bound (that + the value of
- *     the slot padd_amax) — no pass over the data; a bound a few binades above the true maximum costs the split nothing it needs;
- *   mpf_res_ln256_backward_ws_amax: mpf_res_ln256_backward_ws that records max |ds| in ds_amax (one atomic per workgroup). */
-int mpf_res_ln256_forward_b(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta, float* s_out, float* y32,
-                            void* y16, float* mean, float* rstd, int rows, float eps, const float* padd, int padd_rows, float* y_plus,
-                            float* y_bound, const float* padd_amax, float* yplus_bound, void* stream);
-int mpf_res_ln256_backward_ws_amax(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
-                                   const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta, int rows,
-                                   void* workspace, size_t workspace_bytes, float* ds_amax, void* stream);
+/* (producers of amax slots outside the GEMMs: the encoder LayerNorms, mpf_res_ln256_forward_b / _backward_ws_amax /
+ * _backward_partial_amax, declared with the mpf_res_ln256_* family below) */
 typedef struct MpfAmaxItem {
     const float* src;
     float* out;
@@ -1031,20 +1022,52 @@ int mpf_upload_small(const void* host_src, void* device_dst, int64_t nbytes, voi
  * y is written as fp32 (y32, the next residual) and/or bf16 (y16, the next GEMM operand); s_out
  * (optional), mean, rstd [rows] are what the backward needs.  y_plus (optional) = y + padd[row %
  * padd_rows]: the "src + pos" query input of the next encoder layer (msdeformattn.py:124).
- * Backward: g = gy32 + gy16 + gy_plus (any may be NULL) -> ds32 / ds16 (same values, fp32 / bf16;
- * either may be NULL) and dgamma / dbeta ACCUMULATED with float atomics (zero them before the first call).
+ * mpf_res_ln256_forward_b: the same, also writing an UPPER BOUND of |y| into the amax slot y_bound (16 max|gamma| + max|beta|:
+ * a normalised row of 256 values cannot exceed sqrt(255)) and, if yplus_bound is given, of |y + padd| into it (that + the
+ * value of the slot padd_amax) — no pass over the data; a bound a few binades above the true maximum costs the fp16 x 2
+ * split nothing it needs.
  */
 int mpf_res_ln256_forward(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
                           float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
                           const float* padd, int padd_rows, float* y_plus, void* stream);
+int mpf_res_ln256_forward_b(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta, float* s_out, float* y32,
+                            void* y16, float* mean, float* rstd, int rows, float eps, const float* padd, int padd_rows, float* y_plus,
+                            float* y_bound, const float* padd_amax, float* yplus_bound, void* stream);
+/*
+ * Backward, all entry points: g = gy32 + gy16 + gy_plus (any may be NULL, not all) -> ds32 / ds16 (same values, fp32 / bf16;
+ * either may be NULL, not both).  Every workgroup sums dgamma / dbeta over its rows (rows per workgroup = ceil(rows / 1024)
+ * rounded up to a multiple of 4); the entry points differ in how these per-workgroup sums become the parameter gradients:
+ *   mpf_res_ln256_backward               float atomics into dgamma / dbeta [256] each, which the caller ZEROES before the first
+ *                                        call (they accumulate); not bit-reproducible; no workspace.
+ *   mpf_res_ln256_backward_ws            partials [workgroup][2][256] into `workspace`, summed in a fixed order by a second
+ *                                        launch into dgamma / dbeta (fully written: no zeroing; deterministic).  workspace:
+ *                                        mpf_res_ln256_backward_workspace_bytes(rows) bytes, any contents.
+ *   mpf_res_ln256_backward_ws_amax       _ws that also records max |ds| in the amax slot ds_amax (zeroed by the caller; one
+ *                                        atomic max per workgroup; must not be NULL).
+ *   mpf_res_ln256_backward_partial       the first half of _ws alone, for callers that run SEVERAL LayerNorm backwards over the
+ *                                        same number of rows and reduce them with ONE launch: the partials into `partials`
+ *                                        (mpf_res_ln256_backward_workspace_bytes(rows) bytes); no dgamma / dbeta.
+ *   mpf_res_ln256_backward_partial_amax  _partial recording max |ds| in ds_amax — the only entry where ds_amax may be NULL
+ *                                        (then it is _partial).
+ *   mpf_ln_partial_reduce                the second half: out[z][2][256] = (dgamma, dbeta) of LayerNorm z < n_ln, the fixed-order
+ *                                        sums of the partials at partials + z * stride_bytes (a multiple of 4, at least the
+ *                                        size above); `rows` as in the calls that wrote them.
+ *   mpf_res_ln256_backward_det           one launch: the partials go to `workspace` and the workgroup that ARRIVES LAST sums
+ *                                        them in workgroup order into dgamma_dbeta [2][256] (fully written; deterministic; for a
+ *                                        few hundred rows).  workspace: mpf_res_ln256_backward_det_workspace_bytes(rows) bytes
+ *                                        = a ticket word at byte 0, the partials from byte 256.  The first 4 bytes must be ZERO
+ *                                        on entry and are zero again on exit, so one zero-initialised buffer serves every call.
+ */
 int mpf_res_ln256_backward(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
                            const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
                            int rows, void* stream);
-/* The same with dgamma / dbeta reduced through per-workgroup partials in a fixed order (no float atomics: deterministic, and
- * the two vectors need no zero-initialisation).  workspace: mpf_res_ln256_backward_workspace_bytes(rows) bytes. */
-/* The two halves of mpf_res_ln256_backward_ws as separate calls (several LayerNorm backwards, ONE reduce launch): `partials`
- * of LayerNorm z at partials_base + z * stride_bytes, each mpf_res_ln256_backward_workspace_bytes(rows) bytes; out[z][2][256] =
- * (dgamma, dbeta) of LayerNorm z, summed in a fixed order. */
+size_t mpf_res_ln256_backward_workspace_bytes(int rows);
+int mpf_res_ln256_backward_ws(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
+                              const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta, int rows,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mpf_res_ln256_backward_ws_amax(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
+                                   const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta, int rows,
+                                   void* workspace, size_t workspace_bytes, float* ds_amax, void* stream);
 int mpf_res_ln256_backward_partial(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
                                    const void* gy16, const float* gy_plus, float* ds32, void* ds16, int rows, void* partials,
                                    size_t partials_bytes, void* stream);

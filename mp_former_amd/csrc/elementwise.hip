@@ -246,8 +246,12 @@ extern "C" int mpf_bias_act(const void* x, const float* bias, const void* res, v
 // :165-169: tgt = LayerNorm(tgt + tgt2)), C = 256:  s = x + t (x fp32 residual stream, t bf16 or fp32
 // branch output, may be NULL), y = LN(s) * gamma + beta, written as fp32 (next residual) and/or bf16
 // (next GEMM operand) in ONE pass; mean / rstd saved for the backward.  One wave per row, 4 columns
-// per lane.  Backward: g = gy32 + gy16 -> ds (fp32 and/or bf16 copies) and per-block partial sums of
-// dgamma / dbeta accumulated with float atomics into zero-initialised vectors.
+// per lane.  Backward: g = gy32 + gy16 + gy_plus -> ds (fp32 and/or bf16 copies, optionally max |ds|
+// into an amax slot) and per-workgroup sums of dgamma / dbeta, which become the parameter gradients in
+// one of three ways (template parameter PART; include/mpformer_hip.h lists the entry points):
+// 0 float atomics into zero-initialised vectors; 1 partials [workgroup][2][256] summed in a fixed order
+// by ln_partial_reduce_kernel (_ws: right away; _partial: one reduce launch for several LayerNorms);
+// 2 the same partials summed by the workgroup that arrives last (_det: one launch, for few rows).
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -457,36 +461,14 @@ __global__ __launch_bounds__(1024) void ln_partial_reduce_kernel(const float* __
 
 }  // namespace
 
-static int res_ln256_forward_impl(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
-                                  float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
-                                  const float* padd, int padd_rows, float* y_plus, void* stream, float* y_bound,
-                                  const float* padd_amax, float* yplus_bound);
-
-extern "C" int mpf_res_ln256_forward(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
-                                     float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
-                                     const float* padd, int padd_rows, float* y_plus, void* stream)
-{
-    return res_ln256_forward_impl(x, t, t_dtype, gamma, beta, s_out, y32, y16, mean, rstd, rows, eps, padd, padd_rows, y_plus, stream,
-                                  nullptr, nullptr, nullptr);
-}
-
-extern "C" int mpf_res_ln256_forward_b(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
-                                       float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
-                                       const float* padd, int padd_rows, float* y_plus, float* y_bound, const float* padd_amax,
-                                       float* yplus_bound, void* stream)
-{
-    if (!y_bound || (yplus_bound && (!padd_amax || !y_plus))) return mpf::fail(MPF_E_NULL, "res_ln256_forward_b: NULL amax slot");
-    return res_ln256_forward_impl(x, t, t_dtype, gamma, beta, s_out, y32, y16, mean, rstd, rows, eps, padd, padd_rows, y_plus, stream,
-                                  y_bound, padd_amax, yplus_bound);
-}
-
+// ---- host layer of the family: every entry point is check, launch, status (rows == 0: nothing to do, no check) ----
+// forward, with or without the bound slots (all three NULL: mpf_res_ln256_forward)
 static int res_ln256_forward_impl(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
                                   float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
                                   const float* padd, int padd_rows, float* y_plus, void* stream, float* y_bound,
                                   const float* padd_amax, float* yplus_bound)
 {
     hipStream_t st = (hipStream_t)stream;
-    if (rows == 0) return 0;
     if (!x || !gamma || !beta || !mean || !rstd || (!y32 && !y16)) return mpf::fail(MPF_E_NULL, "res_ln256_forward: NULL buffer");
     if (rows < 0 || (y_plus && (!padd || padd_rows <= 0))) return mpf::fail(MPF_E_SHAPE, "res_ln256_forward: bad rows / missing addend");
     const dim3 grid((rows + 3) / 4);
@@ -504,24 +486,70 @@ static int res_ln256_forward_impl(const float* x, const void* t, int t_dtype, co
     return mpf::check(hipGetLastError(), "mpf_res_ln256_forward");
 }
 
-extern "C" int mpf_res_ln256_backward(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
-                                      const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
-                                      int rows, void* stream)
+extern "C" int mpf_res_ln256_forward(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
+                                     float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
+                                     const float* padd, int padd_rows, float* y_plus, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (rows == 0) return 0;
-    if (!s || !mean || !rstd || !gamma || (!gy32 && !gy16 && !gy_plus) || (!ds32 && !ds16) || !dgamma || !dbeta)
-        return mpf::fail(MPF_E_NULL, "res_ln256_backward: NULL buffer");
-    if (rows < 0) return mpf::fail(MPF_E_SHAPE, "res_ln256_backward: bad rows");
-    // ~1024 blocks at most; each block reduces its rows' dgamma / dbeta before the atomics
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    const dim3 grid((rows + rpb - 1) / rpb);
+    return res_ln256_forward_impl(x, t, t_dtype, gamma, beta, s_out, y32, y16, mean, rstd, rows, eps, padd, padd_rows, y_plus, stream,
+                                  nullptr, nullptr, nullptr);
+}
+
+extern "C" int mpf_res_ln256_forward_b(const float* x, const void* t, int t_dtype, const float* gamma, const float* beta,
+                                       float* s_out, float* y32, void* y16, float* mean, float* rstd, int rows, float eps,
+                                       const float* padd, int padd_rows, float* y_plus, float* y_bound, const float* padd_amax,
+                                       float* yplus_bound, void* stream)
+{
+    if (rows == 0) return 0;
+    if (!y_bound || (yplus_bound && (!padd_amax || !y_plus))) return mpf::fail(MPF_E_NULL, "res_ln256_forward_b: NULL amax slot");
+    return res_ln256_forward_impl(x, t, t_dtype, gamma, beta, s_out, y32, y16, mean, rstd, rows, eps, padd, padd_rows, y_plus, stream,
+                                  y_bound, padd_amax, yplus_bound);
+}
+
+namespace {
+
+// THE grid rule of the backward: ~1024 workgroups at most, each sums dgamma / dbeta over its `rpb` rows (a multiple of the 4
+// waves).  The size of a partial buffer, the partials the reduce kernel walks and the ticket count of the one-launch form
+// all follow from `blocks`; rows > 0.
+struct LnGrid { int rpb, blocks; };
+LnGrid ln_grid(int rows)
+{
+    const int rpb = ((rows + 1023) / 1024 + 3) / 4 * 4;
+    return {rpb, (rows + rpb - 1) / rpb};
+}
+
+// what every backward entry point reads and writes (its parameter-gradient outputs differ: ln_bwd_launch)
+struct LnBwdOps {
+    const float *s, *mean, *rstd, *gamma, *gy32;
+    const void* gy16;
+    const float* gy_plus;
+    float* ds32;
+    void* ds16;
+    int rows;
+};
+
+// the shared rejections, reported under the entry point's name.  own_ptrs: the entry's own buffers are all there; room: its
+// workspace holds the partials of `rows` rows (true where it has none); shape_msg: what it calls a failure of rows / room
+int ln_bwd_check(const char* entry, const LnBwdOps& o, bool own_ptrs, bool room, const char* shape_msg)
+{
+    const bool null = !o.s || !o.mean || !o.rstd || !o.gamma || (!o.gy32 && !o.gy16 && !o.gy_plus) || (!o.ds32 && !o.ds16) || !own_ptrs;
+    if (!null && o.rows >= 0 && room) return 0;
+    char msg[96];
+    snprintf(msg, sizeof(msg), "%s: %s", entry, null ? "NULL buffer" : shape_msg);
+    return mpf::fail(null ? MPF_E_NULL : MPF_E_SHAPE, msg);
+}
+
+// PART 0: p0 / p1 = dgamma / dbeta (float atomics);  1: p0 = the partial buffer (p1 unused);  2: p0 = the workspace (ticket word,
+// partials from byte 256), p1 = the output pair [2][256]
+template <int PART>
+void ln_bwd_launch(const LnBwdOps& o, float* p0, float* p1, float* ds_amax, hipStream_t st)
+{
+    const LnGrid g = ln_grid(o.rows);
     mpf::set_kernel("res_ln256_bwd_kernel");
 #define RLN_BWD(A, B, C)                                                                                                          \
-    hipLaunchKernelGGL((res_ln256_bwd_kernel<A, B, C>), grid, dim3(256), 0, st, s, mean, rstd, gamma, gy32, (const __bf16*)gy16, gy_plus, \
-                       ds32, (__bf16*)ds16, dgamma, dbeta, rows, rpb)
-    switch ((gy32 ? 4 : 0) | (gy16 ? 2 : 0) | (gy_plus ? 1 : 0)) {
+    hipLaunchKernelGGL((res_ln256_bwd_kernel<A, B, C, PART>), dim3(g.blocks), dim3(256), 0, st, o.s, o.mean, o.rstd, o.gamma, o.gy32, \
+                       (const __bf16*)o.gy16, o.gy_plus, o.ds32, (__bf16*)o.ds16, p0, p1, o.rows, g.rpb, ds_amax)
+    switch ((o.gy32 ? 4 : 0) | (o.gy16 ? 2 : 0) | (o.gy_plus ? 1 : 0)) {
         case 1: RLN_BWD(false, false, true); break;
         case 2: RLN_BWD(false, true, false); break;
         case 3: RLN_BWD(false, true, true); break;
@@ -531,28 +559,53 @@ extern "C" int mpf_res_ln256_backward(const float* s, const float* mean, const f
         default: RLN_BWD(true, true, true); break;
     }
 #undef RLN_BWD
-    return mpf::check(hipGetLastError(), "mpf_res_ln256_backward");
 }
+
+}  // namespace
 
 extern "C" size_t mpf_res_ln256_backward_workspace_bytes(int rows)
 {
-    if (rows <= 0) return 0;
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    return (size_t)((rows + rpb - 1) / rpb) * 512 * sizeof(float);
+    return rows <= 0 ? 0 : (size_t)ln_grid(rows).blocks * 512 * sizeof(float);
+}
+
+// the ticket word (its own 256 bytes), then the partials
+extern "C" size_t mpf_res_ln256_backward_det_workspace_bytes(int rows)
+{
+    return rows <= 0 ? 0 : 256 + mpf_res_ln256_backward_workspace_bytes(rows);
+}
+
+// float atomics into zero-initialised dgamma / dbeta
+extern "C" int mpf_res_ln256_backward(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
+                                      const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
+                                      int rows, void* stream)
+{
+    if (rows == 0) return 0;
+    const LnBwdOps o{s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, rows};
+    if (int e = ln_bwd_check("res_ln256_backward", o, dgamma && dbeta, true, "bad rows")) return e;
+    ln_bwd_launch<0>(o, dgamma, dbeta, nullptr, (hipStream_t)stream);
+    return mpf::check(hipGetLastError(), "mpf_res_ln256_backward");
 }
 
 // the same backward with the parameter gradients reduced WITHOUT atomics (deterministic; dgamma / dbeta need no zeroing)
-static int res_ln256_backward_ws_impl(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
-                                      const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
-                                      int rows, void* workspace, size_t workspace_bytes, void* stream, float* ds_amax);
+static int res_ln256_backward_ws_impl(const LnBwdOps& o, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                      float* ds_amax, hipStream_t st)
+{
+    if (int e = ln_bwd_check("res_ln256_backward_ws", o, dgamma && dbeta && workspace,
+                             workspace_bytes >= mpf_res_ln256_backward_workspace_bytes(o.rows), "bad rows / workspace too small"))
+        return e;
+    float* part = (float*)workspace;
+    ln_bwd_launch<1>(o, part, part, ds_amax, st);
+    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3(2, 8), dim3(1024), 0, st, (const float*)part, ln_grid(o.rows).blocks, dgamma, dbeta);
+    return mpf::check(hipGetLastError(), "mpf_res_ln256_backward_ws");
+}
 
 extern "C" int mpf_res_ln256_backward_ws(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
                                          const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
                                          int rows, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return res_ln256_backward_ws_impl(s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, dgamma, dbeta, rows, workspace, workspace_bytes,
-                                      stream, nullptr);
+    if (rows == 0) return 0;
+    return res_ln256_backward_ws_impl({s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, rows}, dgamma, dbeta, workspace,
+                                      workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
 // ... recording the largest |ds| in an amax slot (zeroed by the caller) for the fp16 x 2 GEMMs that consume ds
@@ -560,48 +613,29 @@ extern "C" int mpf_res_ln256_backward_ws_amax(const float* s, const float* mean,
                                               const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
                                               int rows, void* workspace, size_t workspace_bytes, float* ds_amax, void* stream)
 {
-    if (!ds_amax) return mpf::fail(MPF_E_NULL, "res_ln256_backward_ws_amax: NULL amax slot");
-    return res_ln256_backward_ws_impl(s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, dgamma, dbeta, rows, workspace, workspace_bytes,
-                                      stream, ds_amax);
-}
-
-static int res_ln256_backward_ws_impl(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
-                                      const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma, float* dbeta,
-                                      int rows, void* workspace, size_t workspace_bytes, void* stream, float* ds_amax)
-{
-    hipStream_t st = (hipStream_t)stream;
     if (rows == 0) return 0;
-    if (!s || !mean || !rstd || !gamma || (!gy32 && !gy16 && !gy_plus) || (!ds32 && !ds16) || !dgamma || !dbeta || !workspace)
-        return mpf::fail(MPF_E_NULL, "res_ln256_backward_ws: NULL buffer");
-    if (rows < 0 || workspace_bytes < mpf_res_ln256_backward_workspace_bytes(rows))
-        return mpf::fail(MPF_E_SHAPE, "res_ln256_backward_ws: bad rows / workspace too small");
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    const dim3 grid((rows + rpb - 1) / rpb);
-    float* part = (float*)workspace;
-    mpf::set_kernel("res_ln256_bwd_kernel");
-#define RLN_BWDP(A, B, C)                                                                                                         \
-    hipLaunchKernelGGL((res_ln256_bwd_kernel<A, B, C, 1>), grid, dim3(256), 0, st, s, mean, rstd, gamma, gy32, (const __bf16*)gy16,    \
-                       gy_plus, ds32, (__bf16*)ds16, part, part, rows, rpb, ds_amax)
-    switch ((gy32 ? 4 : 0) | (gy16 ? 2 : 0) | (gy_plus ? 1 : 0)) {
-        case 1: RLN_BWDP(false, false, true); break;
-        case 2: RLN_BWDP(false, true, false); break;
-        case 3: RLN_BWDP(false, true, true); break;
-        case 4: RLN_BWDP(true, false, false); break;
-        case 5: RLN_BWDP(true, false, true); break;
-        case 6: RLN_BWDP(true, true, false); break;
-        default: RLN_BWDP(true, true, true); break;
-    }
-#undef RLN_BWDP
-    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3(2, 8), dim3(1024), 0, st, (const float*)part, (int)grid.x, dgamma, dbeta);
-    return mpf::check(hipGetLastError(), "mpf_res_ln256_backward_ws");
+    if (!ds_amax) return mpf::fail(MPF_E_NULL, "res_ln256_backward_ws_amax: NULL amax slot");
+    return res_ln256_backward_ws_impl({s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, rows}, dgamma, dbeta, workspace,
+                                      workspace_bytes, ds_amax, (hipStream_t)stream);
 }
 
 // The two halves of mpf_res_ln256_backward_ws as separate calls, for callers that run SEVERAL LayerNorm backwards and reduce
-// their parameter gradients together (a decoder layer: three LayerNorms, one reduce launch at the end of the layer):
-//   mpf_res_ln256_backward_partial: ds + the per-workgroup partial sums into `partials`
-//                                   (mpf_res_ln256_backward_workspace_bytes(rows) bytes);
-//   mpf_ln_partial_reduce: out[z][2][256] = fixed-order sums of the partials of LayerNorm z (z < n_ln, `stride_bytes` apart).
+// their parameter gradients together (a decoder layer: three LayerNorms, one reduce launch at the end of the layer).
+// ds_amax: an amax slot for the largest |ds| (zeroed by the caller; may be NULL)
+extern "C" int mpf_res_ln256_backward_partial_amax(const float* s, const float* mean, const float* rstd, const float* gamma,
+                                                   const float* gy32, const void* gy16, const float* gy_plus, float* ds32, void* ds16,
+                                                   int rows, void* partials, size_t partials_bytes, float* ds_amax, void* stream)
+{
+    if (rows == 0) return 0;
+    const LnBwdOps o{s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, rows};
+    if (int e = ln_bwd_check("res_ln256_backward_partial", o, partials != nullptr,
+                             partials_bytes >= mpf_res_ln256_backward_workspace_bytes(rows), "bad rows / buffer too small"))
+        return e;
+    float* part = (float*)partials;
+    ln_bwd_launch<1>(o, part, part, ds_amax, (hipStream_t)stream);
+    return mpf::check(hipGetLastError(), "mpf_res_ln256_backward_partial");
+}
+
 extern "C" int mpf_res_ln256_backward_partial(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
                                               const void* gy16, const float* gy_plus, float* ds32, void* ds16, int rows, void* partials,
                                               size_t partials_bytes, void* stream)
@@ -610,84 +644,27 @@ extern "C" int mpf_res_ln256_backward_partial(const float* s, const float* mean,
                                                stream);
 }
 
-// ... recording the largest |ds| in an amax slot (zeroed by the caller; may be NULL)
-extern "C" int mpf_res_ln256_backward_partial_amax(const float* s, const float* mean, const float* rstd, const float* gamma,
-                                                   const float* gy32, const void* gy16, const float* gy_plus, float* ds32, void* ds16,
-                                                   int rows, void* partials, size_t partials_bytes, float* ds_amax, void* stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (rows == 0) return 0;
-    if (!s || !mean || !rstd || !gamma || (!gy32 && !gy16 && !gy_plus) || (!ds32 && !ds16) || !partials)
-        return mpf::fail(MPF_E_NULL, "res_ln256_backward_partial: NULL buffer");
-    if (rows < 0 || partials_bytes < mpf_res_ln256_backward_workspace_bytes(rows))
-        return mpf::fail(MPF_E_SHAPE, "res_ln256_backward_partial: bad rows / buffer too small");
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    const dim3 grid((rows + rpb - 1) / rpb);
-    float* part = (float*)partials;
-    mpf::set_kernel("res_ln256_bwd_kernel");
-#define RLN_BWDQ(A, B, C)                                                                                                         \
-    hipLaunchKernelGGL((res_ln256_bwd_kernel<A, B, C, 1>), grid, dim3(256), 0, st, s, mean, rstd, gamma, gy32, (const __bf16*)gy16,       \
-                       gy_plus, ds32, (__bf16*)ds16, part, part, rows, rpb, ds_amax)
-    switch ((gy32 ? 4 : 0) | (gy16 ? 2 : 0) | (gy_plus ? 1 : 0)) {
-        case 1: RLN_BWDQ(false, false, true); break;
-        case 2: RLN_BWDQ(false, true, false); break;
-        case 3: RLN_BWDQ(false, true, true); break;
-        case 4: RLN_BWDQ(true, false, false); break;
-        case 5: RLN_BWDQ(true, false, true); break;
-        case 6: RLN_BWDQ(true, true, false); break;
-        default: RLN_BWDQ(true, true, true); break;
-    }
-#undef RLN_BWDQ
-    return mpf::check(hipGetLastError(), "mpf_res_ln256_backward_partial");
-}
-
+// out[z][2][256] = fixed-order sums of the partials of LayerNorm z (z < n_ln, `stride_bytes` apart), `rows` as in the calls that wrote them
 extern "C" int mpf_ln_partial_reduce(const void* partials, size_t stride_bytes, int rows, int n_ln, float* out, void* stream)
 {
     if (!partials || !out) return mpf::fail(MPF_E_NULL, "ln_partial_reduce: NULL buffer");
     if (rows <= 0 || n_ln <= 0 || n_ln > 65535 || (stride_bytes & 3)) return mpf::fail(MPF_E_SHAPE, "ln_partial_reduce: bad sizes");
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    const int blocks = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3(2, 8, n_ln), dim3(1024), 0, (hipStream_t)stream, (const float*)partials, blocks, out,
-                       out + 256, (int64_t)(stride_bytes / 4));
+    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3(2, 8, n_ln), dim3(1024), 0, (hipStream_t)stream, (const float*)partials,
+                       ln_grid(rows).blocks, out, out + 256, (int64_t)(stride_bytes / 4));
     return mpf::check(hipGetLastError(), "mpf_ln_partial_reduce");
 }
 
 // few rows (the decoder's query side): ONE launch, the workgroup that arrives last sums the partials in block order
-extern "C" size_t mpf_res_ln256_backward_det_workspace_bytes(int rows)
-{
-    return rows <= 0 ? 0 : 256 + mpf_res_ln256_backward_workspace_bytes(rows);
-}
-
 extern "C" int mpf_res_ln256_backward_det(const float* s, const float* mean, const float* rstd, const float* gamma, const float* gy32,
                                           const void* gy16, const float* gy_plus, float* ds32, void* ds16, float* dgamma_dbeta, int rows,
                                           void* workspace, size_t workspace_bytes, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (rows == 0) return 0;
-    if (!s || !mean || !rstd || !gamma || (!gy32 && !gy16 && !gy_plus) || (!ds32 && !ds16) || !dgamma_dbeta || !workspace)
-        return mpf::fail(MPF_E_NULL, "res_ln256_backward_det: NULL buffer");
-    if (rows < 0 || workspace_bytes < mpf_res_ln256_backward_det_workspace_bytes(rows))
-        return mpf::fail(MPF_E_SHAPE, "res_ln256_backward_det: bad rows / workspace too small");
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    const dim3 grid((rows + rpb - 1) / rpb);
-    float* ws = (float*)workspace;
-    mpf::set_kernel("res_ln256_bwd_kernel");
-#define RLN_BWDD(A, B, C)                                                                                                         \
-    hipLaunchKernelGGL((res_ln256_bwd_kernel<A, B, C, 2>), grid, dim3(256), 0, st, s, mean, rstd, gamma, gy32, (const __bf16*)gy16,       \
-                       gy_plus, ds32, (__bf16*)ds16, ws, dgamma_dbeta, rows, rpb)
-    switch ((gy32 ? 4 : 0) | (gy16 ? 2 : 0) | (gy_plus ? 1 : 0)) {
-        case 1: RLN_BWDD(false, false, true); break;
-        case 2: RLN_BWDD(false, true, false); break;
-        case 3: RLN_BWDD(false, true, true); break;
-        case 4: RLN_BWDD(true, false, false); break;
-        case 5: RLN_BWDD(true, false, true); break;
-        case 6: RLN_BWDD(true, true, false); break;
-        default: RLN_BWDD(true, true, true); break;
-    }
-#undef RLN_BWDD
+    const LnBwdOps o{s, mean, rstd, gamma, gy32, gy16, gy_plus, ds32, ds16, rows};
+    if (int e = ln_bwd_check("res_ln256_backward_det", o, dgamma_dbeta && workspace,
+                             workspace_bytes >= mpf_res_ln256_backward_det_workspace_bytes(rows), "bad rows / workspace too small"))
+        return e;
+    ln_bwd_launch<2>(o, (float*)workspace, dgamma_dbeta, nullptr, (hipStream_t)stream);
     return mpf::check(hipGetLastError(), "mpf_res_ln256_backward_det");
 }
 

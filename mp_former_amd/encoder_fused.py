@@ -31,7 +31,7 @@ from . import _lib
 from .gemm3 import (amax, amax_slots, gemm3_h2, gemm3_h2_bits, gemm3_nt, gemm3_nt_grouped, nt_reduce_levels, split_weights_grouped_h2,
                     workgroup_slots)
 from .msda import ms_deform_attn_backward_raw, ms_deform_attn_forward_raw
-from .resln import LnGradGroup, ln256_forward
+from .resln import LnGradGroup, ln256_forward, ln_partial_stride
 
 _EPS = 1e-5
 
@@ -418,7 +418,7 @@ def _native_backward(gout, prm, saved, planes_t, meta, dims, rps, split_level):
     out = torch.empty((nl, sum(n for _, n in outs)), dtype=torch.float32, device=dev)
     tmp = torch.empty(sum(n for _, n in tmps), dtype=torch.float32, device=dev)
     t = {k: tmp.data_ptr() + 4 * o for k, o in ot.items()}
-    ln_stride = (int(lib.mpf_res_ln256_backward_workspace_bytes(R)) + 255) & ~255
+    ln_stride = ln_partial_stride(R)
     ln_parts = torch.empty(2 * nl * ln_stride, dtype=torch.uint8, device=dev)
     host_shapes = meta["shapes"]._mpf_host
     need = lib.mpf_msda_backward_workspace_bytes(N, M, L, S, P, host_shapes.data_ptr())
