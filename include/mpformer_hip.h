@@ -511,6 +511,23 @@ int mpf_decoder_inputs_backward(const void* g_src, const void* g_kin, int g_dtyp
                                 int N, int C, void* stream);
 
 /*
+ * Clip decoder inputs of one feature level, B clips x T frames (mask2former_video/modeling/transformer_decoder/
+ * video_mask2former_transformer_decoder.py:385-393: level_embed, flatten, NTxCxHW => (TxHW)xNxC; the key input of :105 adds
+ * PositionEmbeddingSine3D, position_encoding.py:29-57, whose value is cat(pos_y, pos_x) + pos_z, :56):
+ *   src[(t * S + s), b, c] = x(b * T + t, c, s) + level_embed[c]
+ *   kin[(t * S + s), b, c] = src[(t * S + s), b, c] + (pos_yx[s, c] + pos_z[t, c])
+ * fp32 arithmetic in the order written (the two tables are summed first, as :56 does).  x(n, c, s) = x[n * sx_n + s * sx_s + c]
+ * fp32 (unit channel stride; frame and pixel strides free, multiples of 4 elements, 16-byte aligned base), pos_yx [S, C] and
+ * pos_z [T, C] fp32; src / kin [(T * S), B, C] row-contiguous, out_dtype MPF_BF16 (autocast) or MPF_F32; C % 8 == 0.
+ * Backward: dx(b * T + t, c, s) = g_src[...] + g_kin[...] (either may be NULL), written with x's strides; memory between frames
+ * is not touched.
+ */
+int mpf_clip_inputs_forward(const float* x, int64_t sx_n, int64_t sx_s, const float* level_embed, const float* pos_yx,
+                            const float* pos_z, void* src, void* kin, int out_dtype, int S, int T, int B, int C, void* stream);
+int mpf_clip_inputs_backward(const void* g_src, const void* g_kin, int g_dtype, float* dx, int64_t sx_n, int64_t sx_s, int S, int T,
+                             int B, int C, void* stream);
+
+/*
  * Fused mask head -> next-layer attention mask (forward_prediction_heads, mask2former_transformer_decoder.py:1859-1877:
  * einsum("bqc,bchw->bqhw") + bilinear resize to the level grid + sigmoid < 0.5, detached), bf16.  The resize commutes
  * with the channel contraction, so the pixel-decoder features are resized once per step and level:

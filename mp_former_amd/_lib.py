@@ -135,6 +135,9 @@ SIGNATURES = {
     "mpf_decoder_inputs_forward": (_c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int,
                                             _c_vp]),
     "mpf_decoder_inputs_backward": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, _c_int, _c_vp]),
+    "mpf_clip_inputs_forward": (_c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int,
+                                         _c_int, _c_vp]),
+    "mpf_clip_inputs_backward": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_clip_adamw_step": (_c_int, [_c_vp, _c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                      _c_vp, _c_vp, _c_vp]),
     "mpf_transpose_f32": (_c_int, [_c_vp, ctypes.c_int64, _c_vp, ctypes.c_int64, _c_int, _c_int, _c_int, _c_vp]),

@@ -102,6 +102,67 @@ def registered():
 
 register()
 
+VIDEO_TRANSFORMER_DECODER_NAME = "VideoMultiScaleMaskedTransformerDecoder"
+
+
+def make_video_class(configurable=None):
+    """The registrable subclass of video_decoder.VideoMultiScaleMaskedTransformerDecoder, under the reference's own name."""
+    from . import video_decoder as _V
+    deco = configurable or _configurable
+
+    class VideoDecoderHIP(_V.VideoMultiScaleMaskedTransformerDecoder):
+        @deco
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+
+    VideoDecoderHIP.__name__ = VideoDecoderHIP.__qualname__ = VIDEO_TRANSFORMER_DECODER_NAME
+    return VideoDecoderHIP
+
+
+def register_video(transformer_decoder_registry=None, configurable=None):
+    """Register the native clip decoder under the reference's name ``VideoMultiScaleMaskedTransformerDecoder``
+    (video_mask2former_transformer_decoder.py:208), so that a video config selects it without an override.  Without a registry:
+    mask2former's ``TRANSFORMER_DECODER_REGISTRY`` (returns False, registering nothing, when detectron2 or mask2former is
+    missing); a registry that already holds the name — ``mask2former_video`` was imported first — refuses the second
+    registration as detectron2's ``Registry`` does, and ``install_native_video_decoder`` is then the way in.  With a registry: any
+    object with detectron2's ``Registry`` interface.  Returns the class (truthy) on success.  Independent of ``register()``; the
+    registered decoder composes with ``install_native_video_inference`` / ``install_native_video_training``, which replace other
+    parts of the model."""
+    if transformer_decoder_registry is None:
+        try:
+            from detectron2.config import configurable as d2_configurable
+            from mask2former.modeling.transformer_decoder.maskformer_transformer_decoder import TRANSFORMER_DECODER_REGISTRY
+        except ImportError:
+            return False
+        transformer_decoder_registry = TRANSFORMER_DECODER_REGISTRY
+        configurable = configurable or d2_configurable
+    cls = make_video_class(configurable)
+    transformer_decoder_registry.register(cls)
+    return cls
+
+
+def install_native_video_decoder(model):
+    """Replace ``model.sem_seg_head.predictor`` of a reference ``VideoMaskFormer`` — its torch
+    ``VideoMultiScaleMaskedTransformerDecoder`` — by the native module (video_decoder.py) built from the old one's fields, with
+    the old one's state dict loaded strictly, on its device and in its training mode.  Returns the new module.  Composes with
+    ``install_native_video_inference`` and ``install_native_video_training`` in any order: those replace the eval branch of
+    ``forward`` and the criterion, this the module between the pixel decoder and them."""
+    from .video_decoder import VideoMultiScaleMaskedTransformerDecoder
+    old = model.sem_seg_head.predictor
+    hidden = old.decoder_norm.normalized_shape[0]
+    proj = [m for m in old.input_proj if hasattr(m, "weight")]
+    new = VideoMultiScaleMaskedTransformerDecoder(
+        in_channels=proj[0].weight.shape[1] if proj else hidden, mask_classification=old.mask_classification,
+        num_classes=old.class_embed.out_features - 1, hidden_dim=hidden, num_queries=old.num_queries, nheads=old.num_heads,
+        dim_feedforward=old.transformer_ffn_layers[0].linear1.out_features, dec_layers=old.num_layers,
+        pre_norm=bool(old.transformer_ffn_layers[0].normalize_before), mask_dim=old.mask_embed.layers[-1].out_features,
+        enforce_input_project=bool(proj), num_frames=old.num_frames)
+    new.to(old.decoder_norm.weight.device)
+    new.load_state_dict(old.state_dict(), strict=True)
+    new.train(old.training)
+    model.sem_seg_head.predictor = new
+    return new
+
 
 def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None, instance_bits=False):
     """The eval branch of a reference ``MaskFormer`` (mask2former/maskformer_model.py:199-203 + 233-279) with the native

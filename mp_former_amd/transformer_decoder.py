@@ -669,7 +669,7 @@ class MultiScaleMaskedTransformerDecoderMaskDN(nn.Module):
                 for k in m._parameters:
                     n = (mname + "." if mname else "") + k
                     if m._parameters[k] is not None and not (".norm." in n or n.startswith("decoder_norm")
-                                                             or n.startswith(("query_feat", "level_embed", "label_enc"))):
+                                                             or n.startswith(("query_feat", "query_embed", "level_embed", "label_enc"))):
                         where.append((n, m, k))
             self.__dict__["_gemm_param_slots"] = (where, links, counts)
         named = [(n, m._parameters[k]) for n, m, k in where]
