@@ -1112,14 +1112,25 @@ extern "C" int mpf_match_cost(const void* pred, int pred_dtype, int h, int w, co
             return mpf::check(hipGetLastError(), "mpf_match_cost");
         }
     }
+    // the generic kernel keeps the row's P logits in dynamic LDS: above 32 KiB the limit is raised, as in mpf_match_cost_clip (once per
+    // device and size, not per launch: the matcher on materialised maps comes through here with 12544 points for every step)
+    const size_t xs_bytes = (size_t)P * 4;
     if (pred_dtype == MPF_F32) {
         mpf::set_kernel("match_cost_kernel<float>");
-        hipLaunchKernelGGL((match_cost_kernel<float, false>), dim3(n_rows), dim3(kThreads), (size_t)P * 4, st, (const float*)pred, h, w,
+        auto kfn = match_cost_kernel<float, false>;
+        static mpf::LdsAttr attr;
+        if (xs_bytes > 32 * 1024)
+            if (int e = mpf::ensure_dynamic_lds((const void*)kfn, xs_bytes, attr)) return e;
+        hipLaunchKernelGGL(kfn, dim3(n_rows), dim3(kThreads), xs_bytes, st, (const float*)pred, h, w,
                            pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, (int64_t)0,
                            (float*)nullptr);
     } else if (pred_dtype == MPF_BF16) {
         mpf::set_kernel("match_cost_kernel<bf16>");
-        hipLaunchKernelGGL((match_cost_kernel<__hip_bfloat16, false>), dim3(n_rows), dim3(kThreads), (size_t)P * 4, st,
+        auto kfn = match_cost_kernel<__hip_bfloat16, false>;
+        static mpf::LdsAttr attr;
+        if (xs_bytes > 32 * 1024)
+            if (int e = mpf::ensure_dynamic_lds((const void*)kfn, xs_bytes, attr)) return e;
+        hipLaunchKernelGGL(kfn, dim3(n_rows), dim3(kThreads), xs_bytes, st,
                            (const __hip_bfloat16*)pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first, t_count,
                            cost, Tmax, P, w_mask, w_dice, (int64_t)0, (float*)nullptr);
     } else {
