@@ -27,7 +27,9 @@ def _is_planes(x):
 
 
 def supported(me, mf):
-    """me [N, R, 256] bf16 with contiguous rows, mf [N, 256, H, W] bf16 channel-last planes, H * W a multiple of 128."""
+    """me [N, R, 256] bf16 with contiguous rows, mf [N, 256, H, W] bf16 channel-last planes, H * W a multiple of 128.
+    The forward alone takes any H * W % 4 == 0 (include/mpformer_hip.h); 128 is the backward's tile (d F works on 128-pixel
+    column tiles, d E on 64-pixel steps of 16-byte aligned gradient rows), and a product accepted here must be differentiable."""
     return (me.is_cuda and mf.is_cuda and me.dtype == torch.bfloat16 and mf.dtype == torch.bfloat16 and me.dim() == 3
             and mf.dim() == 4 and me.shape[2] == 256 and mf.shape[1] == 256 and me.shape[0] == mf.shape[0] and me.stride(2) == 1
             and me.stride(0) % 8 == 0 and me.stride(1) % 8 == 0 and me.data_ptr() % 16 == 0 and _is_planes(mf)

@@ -67,7 +67,12 @@ def mask_loss_grad(pred, gt, coords, g):
 def match_cost(masks, tgt, coords, w_mask, w_dice):
     """masks [Q, h, w] logits, tgt [T, H, W] 0/1, coords [1, P, 2] -> [Q, T] fp64: w_mask * (BCE of x against 1 where the target
     is set and against 0 where it is not, mean over the points) + w_dice * (1 - (2 s.t + 1) / (sum s + sum t + 1))"""
-    x, t = point_sample(masks, coords), point_sample(tgt, coords)
+    return match_cost_samples(point_sample(masks, coords), point_sample(tgt, coords), w_mask, w_dice)
+
+
+def match_cost_samples(x, t, w_mask, w_dice):
+    """the cost of ``match_cost`` from given samples: x [Q, P] logits, t [T, P] target samples (read as fp64) -> [Q, T] fp64"""
+    x, t = x.to(F64), t.to(F64)
     P = x.shape[1]
     softplus = lambda v: v.clamp(min=0) + torch.log1p(torch.exp(-v.abs()))
     cm = (softplus(-x) @ t.T + softplus(x) @ (1 - t).T) / P
