@@ -39,6 +39,29 @@ int mpf_abi_version(void);
 const char* mpf_last_error(void);
 
 /*
+ * ---- Multi-scale deformable attention (MSDA): the family --------------------------------------------------------------------
+ * Ten op entry points, two size queries and three diagnostics, all declared in this block.  The entries differ in what the
+ * caller has at hand; each picks its kernels from that ("MSDA host layer", has the full routing table):
+ *
+ *   entry                          the caller has                          kernels (fp32, 32 channels, 4 points, <= 4 levels | else)
+ *   mpf_msda_forward               device shapes only                      tiled <32,V> or generic<T> (option msda_fwd_variant)
+ *   mpf_msda_forward_hs            + shapes in host memory                 blocked                          | as mpf_msda_forward
+ *   mpf_msda_forward_raw           projection output + reference points    prep + tiled <32,1>
+ *   mpf_msda_forward_raw_hs        + shapes in host memory                 blocked<raw>, or prep + blocked  | as _forward_raw
+ *   mpf_msda_forward_dev           device shapes + a workspace             blocked<dev> (geometry on device) | as mpf_msda_forward
+ *   mpf_msda_backward              device shapes only                      tiled <32,V> or generic<T> (option msda_bwd_variant)
+ *   mpf_msda_backward_ws           host shapes + a workspace               bin + tile (+ spill)             | push + fill + pull
+ *   mpf_msda_backward_ws_raw       the same, grad_raw wanted               push + fill + pull
+ *   mpf_msda_backward_ws_raw_o     + the forward result, amax slots        bin + tile (+ spill)             | push + fill + pull, amax passes
+ *   mpf_msda_backward_dev          device shapes + a workspace             bin + tile <dev>                 | as mpf_msda_backward
+ *
+ * Argument faults are reported in one order: a NULL pointer (MPF_E_NULL), then the dtype (MPF_E_DTYPE), then the sizes
+ * (MPF_E_SHAPE); limits of one route (32-bit offsets: MPF_E_TOO_LARGE; workspace size and alignment: MPF_E_SHAPE) by that route.
+ * Size queries: mpf_msda_backward_workspace_bytes (_ws forms), mpf_msda_dev_workspace_bytes (_dev forms).
+ * Diagnostics: mpf_msda_dev_geometry, mpf_msda_stats, and mpf_last_kernel, which names the route a call took.
+ */
+
+/*
  * Multi-scale deformable attention, forward.
  * Replaces ms_deform_attn_forward (pybind: ops/src/vision.cpp:19; dispatcher
  * ops/src/ms_deform_attn.h:25-44; host ops/src/cuda/ms_deform_attn_cuda.cu:25-85; kernel
@@ -145,6 +168,44 @@ int mpf_msda_backward_ws(const void* value, const int64_t* host_spatial_shapes,
                          int batch, int spatial_size, int num_heads, int channels,
                          int num_levels, int num_query, int num_point, int dtype,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Module-level forms of the forward and the _ws backward (ops/modules/ms_deform_attn.py:103-117 folded in): the
+ * sampling locations and attention weights are derived inside the kernels from
+ *   raw[N*Lq, M*L*P*3]  = [sampling_offsets output (M,L,P,2) | attention_weights output (M,L*P)] of a row
+ *   ref_points[Lq, 2]    = the query's reference point, the same for every level (valid_ratios == 1)
+ *   attn = softmax over the L*P logits of (query, head);  loc = ref + offset / (W_l, H_l).
+ * Forward: loc_out / attn_out receive them (one preparation launch, then the gather kernel).  Backward (atomics-free
+ * formulation, as mpf_msda_backward_ws): grad_raw[N*Lq, M*L*P*3] replaces (grad_loc, grad_attn).
+ * fp32, 32 channels per head.
+ */
+int mpf_msda_forward_raw(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                         const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
+                         int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                         int num_point, int dtype, void* stream);
+int mpf_msda_forward_raw_hs(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                            const int64_t* host_spatial_shapes,
+                            const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
+                            int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                            int num_point, int dtype, void* stream);
+int mpf_msda_backward_ws_raw(const void* value, const int64_t* host_spatial_shapes,
+                             const void* sampling_loc, const void* attn_weight, const void* grad_output,
+                             void* grad_value, void* grad_raw,
+                             int batch, int spatial_size, int num_heads, int channels,
+                             int num_levels, int num_query, int num_point, int dtype,
+                             void* workspace, size_t workspace_bytes, void* stream);
+/* the same with `output` = the forward result [N, Lq, M*32] of these inputs (MSDeformAttn keeps it for output_proj's
+ * backward, ops/modules/ms_deform_attn.py:117-124): sum_j attn_j * d attn_j of a (query, head) equals
+ * <grad_output, output>, which lets every sample's gradient be formed where its value rows are (msda_block.hip, "bin + tile").
+ * grad_raw_amax / grad_value_amax (NULL or amax slots, MPF_AMAX_SLOT_FLOATS floats, zeroed by the caller): the largest
+ * magnitudes of the two results, recorded by the kernels that write them (one atomic max per workgroup) for the fp16 x 2 GEMMs
+ * that consume them — the separate amax passes over the two tensors are not needed */
+int mpf_msda_backward_ws_raw_o(const void* value, const int64_t* host_spatial_shapes,
+                               const void* sampling_loc, const void* attn_weight, const void* grad_output,
+                               const void* output, void* grad_value, void* grad_raw,
+                               int batch, int spatial_size, int num_heads, int channels,
+                               int num_levels, int num_query, int num_point, int dtype,
+                               void* workspace, size_t workspace_bytes, float* grad_raw_amax, float* grad_value_amax, void* stream);
 
 /*
  * Tuning / introspection knobs (process-wide; for benchmarks and tests).
@@ -367,44 +428,6 @@ int mpf_attn_delta(const void* dout, const void* out, float* delta, int Lq, int 
  * backward derives from the query side (nn.MultiheadAttention backward, mask2former_transformer_decoder.py:42-52, :100-112) */
 int mpf_attn_bwd_prep(const void* q, const void* dout, const void* out, void* qT, void* doT, float* delta, int Lq, int LqP, int N,
                       int H, void* stream);
-
-/*
- * Module-level forms of the two ops above (ops/modules/ms_deform_attn.py:103-117 folded in): the
- * sampling locations and attention weights are derived inside the kernels from
- *   raw[N*Lq, M*L*P*3]  = [sampling_offsets output (M,L,P,2) | attention_weights output (M,L*P)] of a row
- *   ref_points[Lq, 2]    = the query's reference point, the same for every level (valid_ratios == 1)
- *   attn = softmax over the L*P logits of (query, head);  loc = ref + offset / (W_l, H_l).
- * Forward: loc_out / attn_out receive them (one preparation launch, then the gather kernel).  Backward (atomics-free
- * formulation, as mpf_msda_backward_ws): grad_raw[N*Lq, M*L*P*3] replaces (grad_loc, grad_attn).
- * fp32, 32 channels per head.
- */
-int mpf_msda_forward_raw(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                         const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
-                         int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
-                         int num_point, int dtype, void* stream);
-int mpf_msda_forward_raw_hs(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                            const int64_t* host_spatial_shapes,
-                            const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
-                            int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
-                            int num_point, int dtype, void* stream);
-int mpf_msda_backward_ws_raw(const void* value, const int64_t* host_spatial_shapes,
-                             const void* sampling_loc, const void* attn_weight, const void* grad_output,
-                             void* grad_value, void* grad_raw,
-                             int batch, int spatial_size, int num_heads, int channels,
-                             int num_levels, int num_query, int num_point, int dtype,
-                             void* workspace, size_t workspace_bytes, void* stream);
-/* the same with `output` = the forward result [N, Lq, M*32] of these inputs (MSDeformAttn keeps it for output_proj's
- * backward, ops/modules/ms_deform_attn.py:117-124): sum_j attn_j * d attn_j of a (query, head) equals
- * <grad_output, output>, which lets every sample's gradient be formed where its value rows are (msda_block.hip, "bin + tile").
- * grad_raw_amax / grad_value_amax (NULL or amax slots, MPF_AMAX_SLOT_FLOATS floats, zeroed by the caller): the largest
- * magnitudes of the two results, recorded by the kernels that write them (one atomic max per workgroup) for the fp16 x 2 GEMMs
- * that consume them — the separate amax passes over the two tensors are not needed */
-int mpf_msda_backward_ws_raw_o(const void* value, const int64_t* host_spatial_shapes,
-                               const void* sampling_loc, const void* attn_weight, const void* grad_output,
-                               const void* output, void* grad_value, void* grad_raw,
-                               int batch, int spatial_size, int num_heads, int channels,
-                               int num_levels, int num_query, int num_point, int dtype,
-                               void* workspace, size_t workspace_bytes, float* grad_raw_amax, float* grad_value_amax, void* stream);
 
 /*
  * fp32 GEMM of the pixel-decoder encoder's Linear layers (reference: nn.Linear inside

@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mpf_common.h"
+#include "msda_host.h"
 
 namespace {
 
@@ -457,221 +457,17 @@ __global__ __launch_bounds__(kThreads) void msda_bwd_generic(
 int g_fwd_variant = 0;
 int g_bwd_variant = 0;
 
-template <int D, int V>
-hipError_t launch_fwd_tiled(const float* value, const int64_t* shapes, const int64_t* lsi,
-                            const float* loc, const float* attn, float* out,
-                            int N, int S, int M, int L, int Lq, int P, hipStream_t st)
+// launch size of a tiled kernel: kThreads / (32 / V) (query, head) pairs per workgroup, `per_point` LDS bytes per sample
+struct TiledSize { int total_qm, ntiles, grid; size_t lds; };
+template <int V>
+TiledSize tiled_size(const MsdaProblem& p, int per_point)
 {
-    constexpr int QMB = kThreads / (D / V);
-    const int total_qm = N * Lq * M;
-    const int ntiles = (total_qm + QMB - 1) / QMB;
-    const int grid = ((ntiles + 7) / 8) * 8;
-    const size_t lds = (size_t)QMB * L * P * 32;
-    hipLaunchKernelGGL((msda_fwd_tiled_f32<D, V>), dim3(grid), dim3(kThreads), lds, st,
-                       value, shapes, lsi, loc, attn, out, S, M, L, Lq, P, total_qm, ntiles,
-                       (unsigned)((size_t)N * S * M * D * 4));
-    return hipGetLastError();
-}
-
-template <int D, int V>
-hipError_t launch_bwd_tiled(const float* value, const int64_t* shapes, const int64_t* lsi,
-                            const float* loc, const float* attn, const float* go,
-                            float* gv, float* gl, float* ga,
-                            int N, int S, int M, int L, int Lq, int P, hipStream_t st)
-{
-    constexpr int QMB = kThreads / (D / V);
-    const int total_qm = N * Lq * M;
-    const int ntiles = (total_qm + QMB - 1) / QMB;
-    const int grid = ((ntiles + 7) / 8) * 8;
-    const size_t lds = (size_t)QMB * L * P * 52;
-    hipLaunchKernelGGL((msda_bwd_tiled_f32<D, V>), dim3(grid), dim3(kThreads), lds, st,
-                       value, shapes, lsi, loc, attn, go, gv, gl, ga, S, M, L, Lq, P, total_qm, ntiles);
-    return hipGetLastError();
-}
-
-int check_args(int batch, int S, int M, int D, int L, int Lq, int P, int dtype)
-{
-    if (dtype != MPF_F32 && dtype != MPF_F64) return mpf::fail(MPF_E_DTYPE, "msda: dtype must be MPF_F32 or MPF_F64");
-    if (batch <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0)
-        return mpf::fail(MPF_E_SHAPE, "msda: all sizes must be positive");
-    if (L > kMaxLevels) return mpf::fail(MPF_E_SHAPE, "msda: num_levels > 16 not supported");
-    return 0;
-}
-
-// the tiled kernels use 32-bit element offsets and need a 16-byte aligned row
-bool tiled_ok(int batch, int S, int M, int D, int L, int Lq, int P, int dtype, int V)
-{
-    if (dtype != MPF_F32 || D != 32) return false;
-    const int64_t nv = (int64_t)batch * S * M * D;
-    const int64_t nq = (int64_t)batch * Lq * M * L * P * 2;
-    if (nv * 4 >= (1ll << 31) || nq >= (1ll << 31)) return false;   // value bytes < 2 GiB: byte offsets in buffer loads
-    const size_t lds = (size_t)(kThreads / (D / V)) * L * P * 52;
-    return lds <= 64 * 1024;
+    constexpr int QMB = kThreads / (32 / V);
+    const int total_qm = p.N * p.Lq * p.M, ntiles = (total_qm + QMB - 1) / QMB;
+    return {total_qm, ntiles, ((ntiles + 7) / 8) * 8, (size_t)QMB * p.L * p.P * per_point};
 }
 
 }  // namespace
-
-static int forward_impl(const void* value, const int64_t* spatial_shapes,
-                        const int64_t* level_start_index, const int64_t* host_spatial_shapes, const void* sampling_loc,
-                        const void* attn_weight, void* output,
-                        int batch, int spatial_size, int num_heads, int channels,
-                        int num_levels, int num_query, int num_point,
-                        int dtype, void* stream)
-{
-    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels,
-              Lq = num_query, P = num_point;
-    if (int e = check_args(N, S, M, D, L, Lq, P, dtype)) return e;
-    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !output)
-        return mpf::fail(MPF_E_NULL, "msda_forward: NULL buffer");
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t err;
-    int variant = g_fwd_variant;
-    if (variant == 0 && host_spatial_shapes) {
-        // production path: spatially blocked kernel (msda_block.hip); -1000 = not its shapes
-        const int r = mpf::msda_block_forward(value, host_spatial_shapes, sampling_loc, attn_weight, output, N, S, M, D, L, Lq, P,
-                                              dtype, st);
-        if (r != -1000) return r;
-    }
-    if (variant == 0) variant = 3;  // measured: 32 lanes x 4 B beats 8 lanes x 16 B (profiles/)
-    if (variant == 2 && !tiled_ok(N, S, M, D, L, Lq, P, dtype, 4)) variant = 1;
-    if (variant == 3 && !tiled_ok(N, S, M, D, L, Lq, P, dtype, 1)) variant = 1;
-    if (variant == 4 && !tiled_ok(N, S, M, D, L, Lq, P, dtype, 2)) variant = 1;
-    const double esz_f = dtype == MPF_F32 ? 4.0 : 8.0;
-    // algorithmic bytes: value + loc + attn read once, out written once
-    const double alg_bytes = esz_f * ((double)N * S * M * D + (double)N * Lq * M * L * P * 3 + (double)N * Lq * M * D);
-    mpf::prof_begin(st);
-    if (variant == 4) {
-        mpf::set_kernel("msda_fwd_tiled_f32<32,2>");
-        err = launch_fwd_tiled<32, 2>((const float*)value, spatial_shapes, level_start_index,
-                                      (const float*)sampling_loc, (const float*)attn_weight,
-                                      (float*)output, N, S, M, L, Lq, P, st);
-    } else if (variant == 2) {
-        mpf::set_kernel("msda_fwd_tiled_f32<32,4>");
-        err = launch_fwd_tiled<32, 4>((const float*)value, spatial_shapes, level_start_index,
-                                      (const float*)sampling_loc, (const float*)attn_weight,
-                                      (float*)output, N, S, M, L, Lq, P, st);
-    } else if (variant == 3) {
-        mpf::set_kernel("msda_fwd_tiled_f32<32,1>");
-        err = launch_fwd_tiled<32, 1>((const float*)value, spatial_shapes, level_start_index,
-                                      (const float*)sampling_loc, (const float*)attn_weight,
-                                      (float*)output, N, S, M, L, Lq, P, st);
-    } else {
-        const int64_t total = (int64_t)N * Lq * M * D;
-        const int grid = (int)((total + kThreads - 1) / kThreads < 65536 * 8 ? (total + kThreads - 1) / kThreads : 65536 * 8);
-        if (dtype == MPF_F32) {
-            mpf::set_kernel("msda_fwd_generic<float>");
-            hipLaunchKernelGGL(msda_fwd_generic<float>, dim3(grid), dim3(kThreads), 0, st,
-                               (const float*)value, spatial_shapes, level_start_index,
-                               (const float*)sampling_loc, (const float*)attn_weight, (float*)output,
-                               S, M, D, L, Lq, P, total);
-        } else {
-            mpf::set_kernel("msda_fwd_generic<double>");
-            hipLaunchKernelGGL(msda_fwd_generic<double>, dim3(grid), dim3(kThreads), 0, st,
-                               (const double*)value, spatial_shapes, level_start_index,
-                               (const double*)sampling_loc, (const double*)attn_weight, (double*)output,
-                               S, M, D, L, Lq, P, total);
-        }
-        err = hipGetLastError();
-    }
-    mpf::prof_end(mpf_last_kernel(), st, alg_bytes);
-    return mpf::check(err, "mpf_msda_forward");
-}
-
-extern "C" int mpf_msda_forward(const void* value, const int64_t* spatial_shapes,
-                                const int64_t* level_start_index, const void* sampling_loc,
-                                const void* attn_weight, void* output,
-                                int batch, int spatial_size, int num_heads, int channels,
-                                int num_levels, int num_query, int num_point,
-                                int dtype, void* stream)
-{
-    return forward_impl(value, spatial_shapes, level_start_index, nullptr, sampling_loc, attn_weight, output, batch, spatial_size,
-                        num_heads, channels, num_levels, num_query, num_point, dtype, stream);
-}
-
-extern "C" int mpf_msda_forward_hs(const void* value, const int64_t* spatial_shapes,
-                                   const int64_t* level_start_index, const int64_t* host_spatial_shapes,
-                                   const void* sampling_loc, const void* attn_weight, void* output,
-                                   int batch, int spatial_size, int num_heads, int channels,
-                                   int num_levels, int num_query, int num_point,
-                                   int dtype, void* stream)
-{
-    return forward_impl(value, spatial_shapes, level_start_index, host_spatial_shapes, sampling_loc, attn_weight, output, batch,
-                        spatial_size, num_heads, channels, num_levels, num_query, num_point, dtype, stream);
-}
-
-extern "C" int mpf_msda_backward(const void* value, const int64_t* spatial_shapes,
-                                 const int64_t* level_start_index, const void* sampling_loc,
-                                 const void* attn_weight, const void* grad_output,
-                                 void* grad_value, void* grad_sampling_loc, void* grad_attn_weight,
-                                 int batch, int spatial_size, int num_heads, int channels,
-                                 int num_levels, int num_query, int num_point,
-                                 int dtype, void* stream)
-{
-    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels,
-              Lq = num_query, P = num_point;
-    if (int e = check_args(N, S, M, D, L, Lq, P, dtype)) return e;
-    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight ||
-        !grad_output || !grad_value || !grad_sampling_loc || !grad_attn_weight)
-        return mpf::fail(MPF_E_NULL, "msda_backward: NULL buffer");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t esz = dtype == MPF_F32 ? 4 : 8;
-    hipError_t err = hipMemsetAsync(grad_value, 0, (size_t)N * S * M * D * esz, st);
-    if (err != hipSuccess) return mpf::check(err, "mpf_msda_backward(memset)");
-    int variant = g_bwd_variant;
-    if (variant == 0) variant = 3;  // atomics cost per (instruction, 128-B row): keep rows whole
-    if (variant == 2 && !tiled_ok(N, S, M, D, L, Lq, P, dtype, 4)) variant = 1;
-    if (variant == 3 && !tiled_ok(N, S, M, D, L, Lq, P, dtype, 1)) variant = 1;
-    if (variant == 4 && !tiled_ok(N, S, M, D, L, Lq, P, dtype, 2)) variant = 1;
-    // algorithmic bytes: value, loc, attn, grad_out read once; the three gradients written once
-    const double alg_bytes = (double)esz * (2.0 * N * S * M * D + 2.0 * N * Lq * M * L * P * 3 + (double)N * Lq * M * D);
-    mpf::prof_begin(st);
-    if (variant == 4) {
-        mpf::set_kernel("msda_bwd_tiled_f32<32,2>");
-        err = launch_bwd_tiled<32, 2>((const float*)value, spatial_shapes, level_start_index,
-                                      (const float*)sampling_loc, (const float*)attn_weight,
-                                      (const float*)grad_output, (float*)grad_value,
-                                      (float*)grad_sampling_loc, (float*)grad_attn_weight,
-                                      N, S, M, L, Lq, P, st);
-    } else if (variant == 2) {
-        mpf::set_kernel("msda_bwd_tiled_f32<32,4>");
-        err = launch_bwd_tiled<32, 4>((const float*)value, spatial_shapes, level_start_index,
-                                      (const float*)sampling_loc, (const float*)attn_weight,
-                                      (const float*)grad_output, (float*)grad_value,
-                                      (float*)grad_sampling_loc, (float*)grad_attn_weight,
-                                      N, S, M, L, Lq, P, st);
-    } else if (variant == 3) {
-        mpf::set_kernel("msda_bwd_tiled_f32<32,1>");
-        err = launch_bwd_tiled<32, 1>((const float*)value, spatial_shapes, level_start_index,
-                                      (const float*)sampling_loc, (const float*)attn_weight,
-                                      (const float*)grad_output, (float*)grad_value,
-                                      (float*)grad_sampling_loc, (float*)grad_attn_weight,
-                                      N, S, M, L, Lq, P, st);
-    } else {
-        const int64_t total_qm = (int64_t)N * Lq * M;
-        const int64_t want = (total_qm + 3) / 4;
-        const int grid = (int)(want < 65536 * 8 ? want : 65536 * 8);
-        if (dtype == MPF_F32) {
-            mpf::set_kernel("msda_bwd_generic<float>");
-            hipLaunchKernelGGL(msda_bwd_generic<float>, dim3(grid), dim3(kThreads), 0, st,
-                               (const float*)value, spatial_shapes, level_start_index,
-                               (const float*)sampling_loc, (const float*)attn_weight,
-                               (const float*)grad_output, (float*)grad_value,
-                               (float*)grad_sampling_loc, (float*)grad_attn_weight,
-                               S, M, D, L, Lq, P, total_qm);
-        } else {
-            mpf::set_kernel("msda_bwd_generic<double>");
-            hipLaunchKernelGGL(msda_bwd_generic<double>, dim3(grid), dim3(kThreads), 0, st,
-                               (const double*)value, spatial_shapes, level_start_index,
-                               (const double*)sampling_loc, (const double*)attn_weight,
-                               (const double*)grad_output, (double*)grad_value,
-                               (double*)grad_sampling_loc, (double*)grad_attn_weight,
-                               S, M, D, L, Lq, P, total_qm);
-        }
-        err = hipGetLastError();
-    }
-    mpf::prof_end(mpf_last_kernel(), st, alg_bytes);
-    return mpf::check(err, "mpf_msda_backward");
-}
 
 namespace mpf {
 int set_msda_option(const char* key, int v)
@@ -720,58 +516,91 @@ __global__ __launch_bounds__(kThreads) void msda_prep_kernel(const float* __rest
     attn[gi] = expf(s_lg[threadIdx.x] - mx) / sum;
     reinterpret_cast<float2*>(loc)[gi] = make_float2(rp.x + o.x / W, rp.y + o.y / H);
 }
+
+template <typename T>
+hipError_t launch_fwd_generic(const MsdaProblem& p, const MsdaOperands& o)
+{
+    const int64_t total = p.n_rows(), want = (total + kThreads - 1) / kThreads;
+    const int grid = (int)(want < 65536 * 8 ? want : 65536 * 8);
+    hipLaunchKernelGGL(msda_fwd_generic<T>, dim3(grid), dim3(kThreads), 0, o.stream, (const T*)o.value, o.shapes, o.lsi, (const T*)o.loc,
+                       (const T*)o.attn, (T*)o.out, p.S, p.M, p.D, p.L, p.Lq, p.P, total);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_bwd_generic(const MsdaProblem& p, const MsdaOperands& o)
+{
+    const int64_t total_qm = (int64_t)p.N * p.Lq * p.M, want = (total_qm + 3) / 4;
+    const int grid = (int)(want < 65536 * 8 ? want : 65536 * 8);
+    hipLaunchKernelGGL(msda_bwd_generic<T>, dim3(grid), dim3(kThreads), 0, o.stream, (const T*)o.value, o.shapes, o.lsi, (const T*)o.loc,
+                       (const T*)o.attn, (const T*)o.grad_out, (T*)o.grad_value, (T*)o.grad_loc, (T*)o.grad_attn, p.S, p.M, p.D, p.L, p.Lq,
+                       p.P, total_qm);
+    return hipGetLastError();
+}
 }  // namespace
 
-static int forward_raw_impl(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                            const int64_t* host_spatial_shapes,
-                            const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
-                            int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
-                            int num_point, int dtype, void* stream)
+namespace mpf {
+int msda_fwd_variant() { return g_fwd_variant; }
+int msda_bwd_variant() { return g_bwd_variant; }
+
+// the tiled kernels use 32-bit element offsets and need a 16-byte aligned row
+bool msda_tiled_ok(const MsdaProblem& p, int V)
 {
-    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-    if (int e = check_args(N, S, M, D, L, Lq, P, dtype)) return e;
-    if (!value || !spatial_shapes || !level_start_index || !raw || !ref_points || !output || !loc_out || !attn_out)
-        return mpf::fail(MPF_E_NULL, "msda_forward_raw: NULL buffer");
-    if (!tiled_ok(N, S, M, D, L, Lq, P, dtype, 1) || L * P > 32)
-        return mpf::fail(MPF_E_DTYPE, "msda_forward_raw: fp32 with 32 channels per head and L*P <= 32 only");
-    hipStream_t st = (hipStream_t)stream;
-    if (g_fwd_variant == 0 && host_spatial_shapes) {
-        // softmax / location arithmetic inside the blocked forward kernel (loc_out / attn_out written by it)
-        const int r = mpf::msda_block_forward(value, host_spatial_shapes, loc_out, attn_out, output, N, S, M, D, L, Lq, P, dtype, st, raw,
-                                              ref_points);
-        if (r != -1000) return r;
-    }
-    const int groups = N * Lq * M, gpb = kThreads / (L * P);
-    mpf::set_kernel("msda_prep_kernel");
-    hipLaunchKernelGGL(msda_prep_kernel, dim3((groups + gpb - 1) / gpb), dim3(kThreads), 0, st, (const float*)raw,
-                       (const float*)ref_points, spatial_shapes, (float*)loc_out, (float*)attn_out, groups, M, L, Lq, P);
-    if (g_fwd_variant == 0 && host_spatial_shapes) {
-        const int r = mpf::msda_block_forward(value, host_spatial_shapes, loc_out, attn_out, output, N, S, M, D, L, Lq, P, dtype, st);
-        if (r != -1000) return r;
-    }
-    mpf::prof_begin(st);
-    mpf::set_kernel("msda_fwd_tiled_f32<32,1>");
-    hipError_t err = launch_fwd_tiled<32, 1>((const float*)value, spatial_shapes, level_start_index, (const float*)loc_out,
-                                             (const float*)attn_out, (float*)output, N, S, M, L, Lq, P, st);
-    mpf::prof_end(mpf_last_kernel(), st, 4.0 * ((double)N * S * M * D + (double)N * Lq * M * L * P * 3 + (double)N * Lq * M * D));
-    return mpf::check(err, "mpf_msda_forward_raw");
+    if (p.dtype != MPF_F32 || p.D != 32) return false;
+    if (p.n_value() * 4 >= (1ll << 31) || p.n_samples() * 2 >= (1ll << 31)) return false;   // value bytes < 2 GiB: byte offsets in buffer loads
+    const size_t lds = (size_t)(kThreads / (p.D / V)) * p.L * p.P * 52;
+    return lds <= 64 * 1024;
 }
 
-extern "C" int mpf_msda_forward_raw(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                                    const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
-                                    int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
-                                    int num_point, int dtype, void* stream)
+// loc / attn of the raw forward from the projection output and the reference points
+void msda_launch_prep(const MsdaProblem& p, const MsdaOperands& o)
 {
-    return forward_raw_impl(value, spatial_shapes, level_start_index, nullptr, raw, ref_points, loc_out, attn_out, output, batch,
-                            spatial_size, num_heads, channels, num_levels, num_query, num_point, dtype, stream);
+    const int groups = p.N * p.Lq * p.M, gpb = kThreads / (p.L * p.P);
+    set_kernel("msda_prep_kernel");
+    hipLaunchKernelGGL(msda_prep_kernel, dim3((groups + gpb - 1) / gpb), dim3(kThreads), 0, o.stream, (const float*)o.raw,
+                       (const float*)o.ref, o.shapes, (float*)const_cast<void*>(o.loc), (float*)const_cast<void*>(o.attn), groups, p.M, p.L,
+                       p.Lq, p.P);
 }
 
-extern "C" int mpf_msda_forward_raw_hs(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                                       const int64_t* host_spatial_shapes,
-                                       const void* raw, const void* ref_points, void* loc_out, void* attn_out, void* output,
-                                       int batch, int spatial_size, int num_heads, int channels, int num_levels, int num_query,
-                                       int num_point, int dtype, void* stream)
+int msda_launch_forward(const MsdaProblem& p, const MsdaOperands& o, int V, const char* who)
 {
-    return forward_raw_impl(value, spatial_shapes, level_start_index, host_spatial_shapes, raw, ref_points, loc_out, attn_out, output,
-                            batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, dtype, stream);
+    hipError_t err = hipSuccess;
+    prof_begin(o.stream);
+    static const char* const kTiled[5] = {nullptr, "msda_fwd_tiled_f32<32,1>", "msda_fwd_tiled_f32<32,2>", nullptr, "msda_fwd_tiled_f32<32,4>"};
+    set_kernel(V ? kTiled[V] : p.dtype == MPF_F32 ? "msda_fwd_generic<float>" : "msda_fwd_generic<double>");
+    if (V)
+        with_int_of<1, 2, 4>(V, [&](auto v) {
+            const TiledSize t = tiled_size<decltype(v)::value>(p, 32);
+            hipLaunchKernelGGL((msda_fwd_tiled_f32<32, decltype(v)::value>), dim3(t.grid), dim3(kThreads), t.lds, o.stream, (const float*)o.value,
+                               o.shapes, o.lsi, (const float*)o.loc, (const float*)o.attn, (float*)o.out, p.S, p.M, p.L, p.Lq, p.P, t.total_qm,
+                               t.ntiles, (unsigned)((size_t)p.n_value() * 4));
+            err = hipGetLastError();
+        });
+    else
+        err = p.dtype == MPF_F32 ? launch_fwd_generic<float>(p, o) : launch_fwd_generic<double>(p, o);
+    prof_end(mpf_last_kernel(), o.stream, p.forward_bytes());
+    return check(err, who);
 }
+
+int msda_launch_backward(const MsdaProblem& p, const MsdaOperands& o, int V)
+{
+    hipError_t err = hipMemsetAsync(o.grad_value, 0, (size_t)p.n_value() * p.esz(), o.stream);
+    if (err != hipSuccess) return check(err, "mpf_msda_backward(memset)");
+    prof_begin(o.stream);
+    static const char* const kTiled[5] = {nullptr, "msda_bwd_tiled_f32<32,1>", "msda_bwd_tiled_f32<32,2>", nullptr, "msda_bwd_tiled_f32<32,4>"};
+    set_kernel(V ? kTiled[V] : p.dtype == MPF_F32 ? "msda_bwd_generic<float>" : "msda_bwd_generic<double>");
+    if (V)
+        with_int_of<1, 2, 4>(V, [&](auto v) {
+            const TiledSize t = tiled_size<decltype(v)::value>(p, 52);
+            hipLaunchKernelGGL((msda_bwd_tiled_f32<32, decltype(v)::value>), dim3(t.grid), dim3(kThreads), t.lds, o.stream, (const float*)o.value,
+                               o.shapes, o.lsi, (const float*)o.loc, (const float*)o.attn, (const float*)o.grad_out, (float*)o.grad_value,
+                               (float*)o.grad_loc, (float*)o.grad_attn, p.S, p.M, p.L, p.Lq, p.P, t.total_qm, t.ntiles);
+            err = hipGetLastError();
+        });
+    else
+        err = p.dtype == MPF_F32 ? launch_bwd_generic<float>(p, o) : launch_bwd_generic<double>(p, o);
+    prof_end(mpf_last_kernel(), o.stream, p.backward_bytes());
+    return check(err, "mpf_msda_backward");
+}
+}  // namespace mpf
+

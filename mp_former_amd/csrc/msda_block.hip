@@ -34,10 +34,11 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <new>
 #include <stdint.h>
 
 #include "amax.h"
-#include "mpf_common.h"
+#include "msda_host.h"
 
 namespace {
 
@@ -1172,7 +1173,7 @@ int g_region_rows = 217;      // forward: usable rows of the staged box (the buf
 int g_block_disable = 0;
 int g_fuse_prep = 1;        // mpf_set_option("msda_fuse_prep"): softmax / location arithmetic inside the forward kernel
 unsigned long long* g_dbg = nullptr;   // benchmarking only: s_memtime phase stamps of the push kernel, [workgroup][16]
-int g_push_ablate = 0;       // benchmarking only: 1 = no tile entries, 2 = no reduction, 4 = no box staging
+int g_tile_ablate = 0;       // benchmarking only: 1 = no tile entries, 2 = no reduction, 4 = no box staging
 int g_bwd_sorted = 0;        // mpf_set_option("msda_bwd_sorted"): sort every tile run before the tile kernel (bit-reproducible grad_value)
 int g_bin_reverse = 0;       // tests: bin kernel walks the query blocks backwards (another arrival order)
 // tests only (mpf_set_option("msda_stats", 1) / mpf_msda_stats): which route every (workgroup, level) took.
@@ -1297,40 +1298,48 @@ __host__ __device__ inline bool build_geom(GeomB& g, const int64_t* hs, const in
     return true;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using mpf::align256;
+using mpf::with_bool;
 
-bool block_ok(int N, int S, int M, int D, int L, int Lq, int P, int dtype)
+bool block_ok(const MsdaProblem& p)
 {
     if (g_block_disable) return false;
-    if (dtype != MPF_F32 || D != kD || P != kP || L < 1 || L > kMaxL) return false;
-    if ((int64_t)N * S * M * D * 4 >= (1ll << 31) || (int64_t)N * Lq * M * L * P * 8 >= (1ll << 31) ||
-        (int64_t)N * Lq * M * D * 4 >= (1ll << 31))
-        return false;
-    if ((int64_t)Lq >= (1 << 29)) return false;
+    if (p.dtype != MPF_F32 || p.D != kD || p.P != kP || p.L < 1 || p.L > kMaxL) return false;
+    if (p.n_value() * 4 >= (1ll << 31) || p.n_samples() * 8 >= (1ll << 31) || p.n_rows() * 4 >= (1ll << 31)) return false;
+    if ((int64_t)p.Lq >= (1 << 29)) return false;
     return true;
 }
 
 int region_bytes() { return ((g_region_rows + 31) / 32) * 32 * 128; }     // whole stage passes of 32 rows
 
+// f(std::integral_constant<int, L>{}) for the templated level counts
+template <class F>
+void with_levels(int L, F&& f) { mpf::with_int_of<1, 2, 3, 4>(L, f); }
+
+// The instantiated forms of the blocked kernels: f(RAW, DBG, DG).  DG (geometry on the device) exists only with RAW = false,
+// DBG = false; kernels without a DBG parameter are asked with dbg = false.
+template <class F>
+void with_form(bool raw, bool dbg, bool dg, F&& f)
+{
+    if (dg)
+        f(std::false_type{}, std::false_type{}, std::true_type{});
+    else
+        with_bool(raw, [&](auto RAW) { with_bool(dbg, [&](auto DBG) { f(RAW, DBG, std::false_type{}); }); });
+}
+
+// forward.  gd != NULL: geometry on the device, g carries only N, S, M (host arguments) and dev_grid is the launch size
 template <int NL>
 hipError_t launch_fwd(const float* value, const float* loc, const float* attn, float* out, const GeomB& g, hipStream_t st,
                       const float* raw = nullptr, const float* ref = nullptr, const GeomB* gd = nullptr, int dev_grid = 0)
 {
     const int nblocks = g.N * g.M * g.blocks_per_b;
-    const int grid = ((nblocks + 7) / 8) * 8;
+    const int grid = gd ? dev_grid : ((nblocks + 7) / 8) * 8;
     const size_t lds = kOffReg + region_bytes();
     const unsigned vb = (unsigned)((size_t)g.N * g.S * g.M * kD * 4);
-    if (gd) {          // geometry on the device: g carries only N, S, M (host arguments)
-        hipLaunchKernelGGL((msda_fwd_block_kernel<NL, false, true>), dim3(dev_grid), dim3(kT), lds, st, value, loc, attn, out, g, 0,
-                           g_region_rows, vb, nullptr, nullptr, g_stats, gd);
-        return hipGetLastError();
-    }
-    if (raw)
-        hipLaunchKernelGGL((msda_fwd_block_kernel<NL, true>), dim3(grid), dim3(kT), lds, st, value, loc, attn, out, g, nblocks,
-                           g_region_rows, vb, raw, ref, g_stats);
-    else
-        hipLaunchKernelGGL((msda_fwd_block_kernel<NL, false>), dim3(grid), dim3(kT), lds, st, value, loc, attn, out, g, nblocks,
-                           g_region_rows, vb, raw, ref, g_stats);
+    with_form(raw != nullptr, false, gd != nullptr, [&](auto RAW, auto, auto DG) {
+        hipLaunchKernelGGL((msda_fwd_block_kernel<NL, decltype(RAW)::value, decltype(DG)::value>), dim3(grid), dim3(kT), lds, st, value, loc,
+                           attn, out, g, nblocks, g_region_rows, vb, raw, ref, g_stats, gd);
+    });
     return hipGetLastError();
 }
 
@@ -1403,36 +1412,50 @@ WsLayout ws_layout(const GeomB& g)
     return w;
 }
 
-// backward: zero counters -> bin -> tile -> spill3.  fwd_out (the forward result, [N, Lq, M * 32]) is needed by the raw form only.
-template <int NL>
-hipError_t launch_bwd3(const float* value, const float* loc, const float* attn, const float* go, const float* fwd_out, float* gv,
-                       float* gl, float* ga, float* graw, const GeomB& g, void* workspace, hipStream_t st, float* graw_amax,
-                       float* gv_amax)
+// the buffers of the backward, carved from a workspace: tile counters and the overflow counter (one zero-filled run of words),
+// entry runs, spill list, delta[q, m] of the raw form (offset 0: none)
+struct Bwd3Buffers {
+    int *tile_count, *ovf_count;
+    unsigned* entries;
+    uint2* ovf;
+    float* delta;
+};
+
+Bwd3Buffers carve(void* workspace, size_t count, size_t ovf_count, size_t entries, size_t ovf, size_t delta)
 {
-    const WsLayout w = ws_layout(g);
     char* ws = (char*)workspace;
-    int* tile_count = (int*)(ws + w.off_count);
-    int* ovf_count = (int*)(ws + w.off_ovf_count);
-    unsigned* entries = (unsigned*)(ws + w.off_entries);
-    uint2* ovf = (uint2*)(ws + w.off_ovf);
-    float* delta = (float*)(ws + w.off_delta);
-    hipError_t err = zero_counters(ws, w.off_ovf_count + 4, st);
+    return {(int*)(ws + count), (int*)(ws + ovf_count), (unsigned*)(ws + entries), (uint2*)(ws + ovf), delta ? (float*)(ws + delta) : nullptr};
+}
+Bwd3Buffers bwd3_buffers(void* ws, const WsLayout& w) { return carve(ws, w.off_count, w.off_ovf_count, w.off_entries, w.off_ovf, w.off_delta); }
+Bwd3Buffers bwd3_buffers(void* ws, const MsdaDevPlan& b) { return carve(ws, b.off_count, b.off_ovf_count, b.off_entries, b.off_ovf, 0); }
+
+// backward: zero counters -> bin (-> sort) -> tile -> spill3.  The raw form (o.grad_raw) needs the forward result o.fwd_out.
+// gd != NULL: geometry on the device — g carries only the host arguments, the grids come from the caller's budget, and the
+// plain form without sorting, ablation or amax slots is the only one.
+template <int NL>
+hipError_t launch_bwd3(const MsdaProblem& p, const MsdaOperands& o, const GeomB& g, const Bwd3Buffers& b, const GeomB* gd = nullptr,
+                       int dev_blk_grid = 0, int dev_tile_grid = 0)
+{
+    hipStream_t st = o.stream;
+    const float *value = (const float*)o.value, *loc = (const float*)o.loc, *attn = (const float*)o.attn, *go = (const float*)o.grad_out;
+    float *gv = (float*)o.grad_value, *gl = (float*)o.grad_loc, *ga = (float*)o.grad_attn, *graw = gd ? nullptr : (float*)o.grad_raw;
+    const float* fwd_out = graw ? (const float*)o.fwd_out : nullptr;
+    float *graw_amax = graw ? o.graw_amax : nullptr, *gv_amax = graw ? o.gv_amax : nullptr;      // recorded by the raw form only
+    const bool dg = gd != nullptr, raw = graw != nullptr;
+    hipError_t err = zero_counters(b.tile_count, (size_t)((char*)(b.ovf_count + 1) - (char*)b.tile_count), st);
     if (err != hipSuccess) return err;
     const int nblocks = g.N * g.M * g.blocks_per_b;
-    const int grid = ((nblocks + 7) / 8) * 8;
-    constexpr int LP = NL * kP;
-    const double esz = 4.0;
-    const double n_samp = (double)g.N * g.Lq * g.M * LP, n_row = (double)g.N * g.Lq * g.M * kD;
+    const int grid = dg ? dev_blk_grid : ((nblocks + 7) / 8) * 8;
     mpf::prof_begin(st);
-    if (graw)
-        hipLaunchKernelGGL((msda_bwd_bin_kernel<NL, true>), dim3(grid), dim3(kT), 0, st, loc, attn, go, fwd_out, gl, ga, graw, delta, tile_count,
-                           entries, ovf_count, ovf, g, nblocks, g_stats, graw_amax, g_bin_reverse);
-    else
-        hipLaunchKernelGGL((msda_bwd_bin_kernel<NL, false>), dim3(grid), dim3(kT), 0, st, loc, attn, go, fwd_out, gl, ga, graw, delta, tile_count,
-                           entries, ovf_count, ovf, g, nblocks, g_stats, graw_amax, g_bin_reverse);
-    // algorithmic bytes of the pair (1344 e S N) are split as: bin = loc in; tile = the rest
-    mpf::prof_end("msda_bwd_bin_kernel", st, esz * n_samp * 2);
-    if (g_bwd_sorted) {
+    with_form(raw, false, dg, [&](auto RAW, auto, auto DG) {
+        hipLaunchKernelGGL((msda_bwd_bin_kernel<NL, decltype(RAW)::value, decltype(DG)::value>), dim3(grid), dim3(kT), 0, st, loc, attn, go,
+                           fwd_out, gl, ga, graw, b.delta, b.tile_count, b.entries, b.ovf_count, b.ovf, g, nblocks, g_stats, graw_amax,
+                           dg ? 0 : g_bin_reverse, gd);
+    });
+    mpf::prof_end("msda_bwd_bin_kernel", st, p.bin_bytes());
+    int* const tile_count = b.tile_count;
+    unsigned* const entries = b.entries;
+    if (g_bwd_sorted && !dg) {
         int cap_max = 2;
         for (int l = 0; l < g.L; ++l) cap_max = std::max(cap_max, g.cap[l]);
         int n2 = 2;
@@ -1443,50 +1466,37 @@ hipError_t launch_bwd3(const float* value, const float* loc, const float* attn, 
         if (ea != hipSuccess) return ea;
         mpf::prof_begin(st);
         hipLaunchKernelGGL(msda_sort_runs_kernel, dim3(g.N * g.M * g.tiles_per_bm), dim3(256), sort_lds, st, tile_count, entries, g);
-        mpf::prof_end("msda_sort_runs_kernel", st, esz * n_samp * 1.5625 * 2);
+        mpf::prof_end("msda_sort_runs_kernel", st, 4.0 * p.n_samples() * 1.5625 * 2);
     }
     const int nwg = g.N * g.M * g.wg_per_bm;
     const size_t lds = (size_t)kWP * kTWave;
-    const unsigned loc_bytes = (unsigned)((size_t)g.N * g.Lq * g.M * LP * 8);
+    const unsigned loc_bytes = (unsigned)((size_t)p.n_samples() * 8);
+    const bool dbg = !dg && (g_tile_ablate || g_dbg);
     mpf::prof_begin(st);
-    const dim3 tgrid(((nwg + 7) / 8) * 8);
-    if (g_push_ablate || g_dbg) {
-        if (graw)
-            hipLaunchKernelGGL((msda_bwd_tile_kernel<NL, true, true>), tgrid, dim3(kTP), lds, st, value, loc, attn, go, delta, tile_count,
-                               entries, gv, gl, ga, graw, g, nwg, loc_bytes, g_stats, g_push_ablate, g_dbg, graw_amax, gv_amax);
-        else
-            hipLaunchKernelGGL((msda_bwd_tile_kernel<NL, false, true>), tgrid, dim3(kTP), lds, st, value, loc, attn, go, delta, tile_count,
-                               entries, gv, gl, ga, graw, g, nwg, loc_bytes, g_stats, g_push_ablate, g_dbg, graw_amax, gv_amax);
-    } else if (graw)
-        hipLaunchKernelGGL((msda_bwd_tile_kernel<NL, true, false>), tgrid, dim3(kTP), lds, st, value, loc, attn, go, delta, tile_count,
-                           entries, gv, gl, ga, graw, g, nwg, loc_bytes, g_stats, 0, nullptr, graw_amax, gv_amax);
-    else
-        hipLaunchKernelGGL((msda_bwd_tile_kernel<NL, false, false>), tgrid, dim3(kTP), lds, st, value, loc, attn, go, delta, tile_count,
-                           entries, gv, gl, ga, graw, g, nwg, loc_bytes, g_stats, 0, nullptr, graw_amax, gv_amax);
-    mpf::prof_end("msda_bwd_tile_kernel", st, esz * ((double)g.N * g.S * g.M * kD * 2 + n_row + n_samp * 4));
-    if (graw)
-        hipLaunchKernelGGL((msda_bwd_spill3_kernel<NL, true>), dim3(64), dim3(kT), 0, st, value, loc, attn, go, delta, ovf_count, ovf, gv, gl, ga, graw, g, g_stats, graw_amax, gv_amax);
-    else
-        hipLaunchKernelGGL((msda_bwd_spill3_kernel<NL, false>), dim3(64), dim3(kT), 0, st, value, loc, attn, go, delta, ovf_count, ovf, gv, gl, ga, graw, g, g_stats, graw_amax, gv_amax);
+    const dim3 tgrid(dg ? dev_tile_grid : ((nwg + 7) / 8) * 8);
+    with_form(raw, dbg, dg, [&](auto RAW, auto DBG, auto DG) {
+        hipLaunchKernelGGL((msda_bwd_tile_kernel<NL, decltype(RAW)::value, decltype(DBG)::value, decltype(DG)::value>), tgrid, dim3(kTP), lds, st,
+                           value, loc, attn, go, b.delta, tile_count, entries, gv, gl, ga, graw, g, nwg, loc_bytes, g_stats,
+                           dbg ? g_tile_ablate : 0, dbg ? g_dbg : nullptr, graw_amax, gv_amax, gd);
+    });
+    mpf::prof_end("msda_bwd_tile_kernel", st, p.tile_bytes());
+    with_form(raw, false, dg, [&](auto RAW, auto, auto DG) {
+        hipLaunchKernelGGL((msda_bwd_spill3_kernel<NL, decltype(RAW)::value, decltype(DG)::value>), dim3(64), dim3(kT), 0, st, value, loc, attn,
+                           go, b.delta, b.ovf_count, b.ovf, gv, gl, ga, graw, g, g_stats, graw_amax, gv_amax, gd);
+    });
     return hipGetLastError();
 }
 
 // ---- geometry on the device (the reference's all-device op signature: ms_deform_attn.h:25-66 hands over spatial_shapes and
 // level_start_index as device tensors; nothing here copies them to the host) ------------------------------------------------------
-struct DevBudget {
-    int64_t tiles_bm, ent_bm;          // capacity per (image, head) of the tile counters / entry runs
-    int blk_grid, tile_grid;           // launch sizes (multiples of 8) of the query-block kernels / the tile kernel
-    size_t off_geom, off_count, off_ovf_count, off_entries, off_ovf, total;
-};
-
 // Everything the host can size from (N, S, M, L, Lq) alone.  A level of H x W pixels has ceil(H/4) ceil(W/4) <= H W / 4 + 1
 // tiles (thin maps are the worst case), so S / 4 + L counters per (image, head) always suffice; run capacities are what
 // build_geom derives for maps with sides that are multiples of 4 (12.5 Lq + 67 H W / 16 entries per level) + 25 %, and the
 // device shrinks them when an odd pyramid needs more (the spill list covers every sample).  Launch sizes: the counts of a
 // pyramid with sides that are multiples of 8 + slack; the kernels stride when the real count is larger.
-DevBudget dev_budget(int N, int S, int M, int L, int Lq, bool backward)
+MsdaDevPlan dev_budget(int N, int S, int M, int L, int Lq, bool backward)
 {
-    DevBudget b;
+    MsdaDevPlan b;
     b.tiles_bm = (int64_t)S / 4 + L;
     b.ent_bm = (int64_t)(1.25 * (12.5 * (double)L * (double)Lq + 67.0 * ((double)S / 16.0 + 8.0 * L))) + 1024;
     if (b.ent_bm < 4 * b.tiles_bm) b.ent_bm = 4 * b.tiles_bm;
@@ -1497,12 +1507,12 @@ DevBudget dev_budget(int N, int S, int M, int L, int Lq, bool backward)
     const int64_t tw = bm * (((int64_t)S / 16 * 3 + 7) / 8 + 4 * L);
     b.blk_grid = (int)std::min<int64_t>(((blk + 7) / 8) * 8, 1 << 30);
     b.tile_grid = (int)std::min<int64_t>(((tw + 7) / 8) * 8, 1 << 30);
-    b.off_geom = 0;
-    b.off_count = 1024;
+    b.off_count = 1024;          // (after the geometry record)
     b.off_ovf_count = b.off_count + (size_t)(bm * b.tiles_bm) * 4;
     b.off_entries = align256(b.off_ovf_count + 4);
     b.off_ovf = align256(b.off_entries + (backward ? (size_t)(bm * b.ent_bm) * 4 : 0));
     b.total = b.off_ovf + (backward ? (size_t)N * Lq * M * L * kP * 4 * 8 : 0);
+    b.applies = bm * b.ent_bm < (1ll << 31) && bm * b.tiles_bm < (1ll << 31);          // 32-bit indexing of the runs and counters
     return b;
 }
 static_assert(sizeof(GeomB) <= 1024, "GeomB must fit the workspace header");
@@ -1567,33 +1577,6 @@ __global__ __launch_bounds__(256) void msda_geom_kernel(const int64_t* __restric
     }
 }
 
-template <int NL>
-hipError_t launch_bwd3_dev(const float* value, const float* loc, const float* attn, const float* go, float* gv, float* gl, float* ga,
-                           const GeomB& gh, const GeomB* gd, const DevBudget& b, char* ws, hipStream_t st)
-{
-    int* tile_count = (int*)(ws + b.off_count);
-    int* ovf_count = (int*)(ws + b.off_ovf_count);
-    unsigned* entries = (unsigned*)(ws + b.off_entries);
-    uint2* ovf = (uint2*)(ws + b.off_ovf);
-    hipError_t err = zero_counters(ws + b.off_count, b.off_ovf_count + 4 - b.off_count, st);
-    if (err != hipSuccess) return err;
-    constexpr int LP = NL * kP;
-    const double n_samp = (double)gh.N * gh.Lq * gh.M * LP, n_row = (double)gh.N * gh.Lq * gh.M * kD;
-    mpf::prof_begin(st);
-    hipLaunchKernelGGL((msda_bwd_bin_kernel<NL, false, true>), dim3(b.blk_grid), dim3(kT), 0, st, loc, attn, go, nullptr, gl, ga, nullptr, nullptr,
-                       tile_count, entries, ovf_count, ovf, gh, 0, g_stats, nullptr, 0, gd);
-    mpf::prof_end("msda_bwd_bin_kernel", st, 4.0 * n_samp * 2);
-    const size_t lds = (size_t)kWP * kTWave;
-    const unsigned loc_bytes = (unsigned)((size_t)gh.N * gh.Lq * gh.M * LP * 8);
-    mpf::prof_begin(st);
-    hipLaunchKernelGGL((msda_bwd_tile_kernel<NL, false, false, true>), dim3(b.tile_grid), dim3(kTP), lds, st, value, loc, attn, go, nullptr,
-                       tile_count, entries, gv, gl, ga, nullptr, gh, 0, loc_bytes, g_stats, 0, nullptr, nullptr, nullptr, gd);
-    mpf::prof_end("msda_bwd_tile_kernel", st, 4.0 * ((double)gh.N * gh.S * gh.M * kD * 2 + n_row + n_samp * 4));
-    hipLaunchKernelGGL((msda_bwd_spill3_kernel<NL, false, true>), dim3(64), dim3(kT), 0, st, value, loc, attn, go, nullptr, ovf_count, ovf, gv, gl,
-                       ga, nullptr, gh, g_stats, nullptr, nullptr, gd);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int mpf_debug_set_buffer(void* p)
@@ -1619,31 +1602,6 @@ extern "C" int mpf_msda_stats(unsigned long long* out, int n, int reset)
 
 namespace mpf {
 
-// forward through the blocked kernel; returns -1000 when the problem is outside its shapes (caller falls back)
-int msda_block_forward(const void* value, const int64_t* host_shapes, const void* loc, const void* attn, void* out, int N, int S, int M,
-                       int D, int L, int Lq, int P, int dtype, hipStream_t st, const void* raw, const void* ref)
-{
-    if (!host_shapes || !block_ok(N, S, M, D, L, Lq, P, dtype)) return -1000;
-    if (raw && (g_fuse_prep == 0 || (int64_t)N * Lq * M * L * P * 12 >= (1ll << 31))) return -1000;
-    GeomB g;
-    if (!build_geom(g, host_shapes, nullptr, N, S, M, L, Lq)) return -1000;
-    mpf::prof_begin(st);
-    mpf::set_kernel(raw ? "msda_fwd_block_kernel<raw>" : "msda_fwd_block_kernel");
-    hipError_t err;
-    const float *rw = (const float*)raw, *rf = (const float*)ref;
-    switch (L) {
-        case 1: err = launch_fwd<1>((const float*)value, (const float*)loc, (const float*)attn, (float*)out, g, st, rw, rf); break;
-        case 2: err = launch_fwd<2>((const float*)value, (const float*)loc, (const float*)attn, (float*)out, g, st, rw, rf); break;
-        case 3: err = launch_fwd<3>((const float*)value, (const float*)loc, (const float*)attn, (float*)out, g, st, rw, rf); break;
-        default: err = launch_fwd<4>((const float*)value, (const float*)loc, (const float*)attn, (float*)out, g, st, rw, rf); break;
-    }
-    // value + loc/attn (read) + out; the raw form also WRITES loc / attn for the backward (the traffic of
-    // the msda_prep launch it replaces)
-    mpf::prof_end("msda_fwd_block_kernel", st,
-                  4.0 * ((double)N * S * M * D + (double)N * Lq * M * L * P * 3 * (raw ? 2 : 1) + (double)N * Lq * M * D));
-    return mpf::check(err, "msda_fwd_block_kernel");
-}
-
 size_t msda_block_workspace_bytes(const int64_t* host_shapes, int N, int M, int L, int Lq, int P)
 {
     if (!host_shapes || P != kP || L < 1 || L > kMaxL) return 0;
@@ -1654,32 +1612,96 @@ size_t msda_block_workspace_bytes(const int64_t* host_shapes, int N, int M, int 
     return ws_layout(g).total;
 }
 
-int msda_block_backward(const void* value, const int64_t* host_shapes, const void* loc, const void* attn, const void* go, void* gv,
-                        void* gl, void* ga, void* graw, int N, int S, int M, int D, int L, int Lq, int P, int dtype, void* workspace,
-                        size_t workspace_bytes, hipStream_t st, const void* fwd_out, float* graw_amax, float* gv_amax,
-                        bool* amax_recorded)
+// "are these your shapes", and if so the geometry of the call and the size of the backward's workspace
+MsdaBlockPlan msda_block_plan(const MsdaProblem& p, const int64_t* host_shapes)
 {
-    if (amax_recorded) *amax_recorded = false;
-    if (!host_shapes || !block_ok(N, S, M, D, L, Lq, P, dtype)) return -1000;
-    GeomB g;
-    if (!build_geom(g, host_shapes, nullptr, N, S, M, L, Lq)) return -1000;
-    if (workspace_bytes < ws_layout(g).total) return mpf::fail(MPF_E_SHAPE, "msda_backward_ws: workspace too small");
-    // the amax slots are filled by the bin + tile (+ spill) kernels of the raw form; on every other route the caller runs
-    // the amax passes itself (a switch or a geometry outside these kernels must not make the training step fail)
-    // the raw form needs the forward result (delta = <grad_out, out>): without it the caller's round-1 kernels run
-    if (graw && !fwd_out) return -1000;
-    if (!graw) graw_amax = gv_amax = nullptr;
-    else if (amax_recorded) *amax_recorded = true;
-    mpf::set_kernel("msda_bwd_block(bin+tile)");
-    hipError_t e3;
-    const float *v_ = (const float*)value, *l_ = (const float*)loc, *a_ = (const float*)attn, *g_ = (const float*)go, *o_ = (const float*)fwd_out;
-    switch (L) {
-        case 1: e3 = launch_bwd3<1>(v_, l_, a_, g_, o_, (float*)gv, (float*)gl, (float*)ga, (float*)graw, g, workspace, st, graw_amax, gv_amax); break;
-        case 2: e3 = launch_bwd3<2>(v_, l_, a_, g_, o_, (float*)gv, (float*)gl, (float*)ga, (float*)graw, g, workspace, st, graw_amax, gv_amax); break;
-        case 3: e3 = launch_bwd3<3>(v_, l_, a_, g_, o_, (float*)gv, (float*)gl, (float*)ga, (float*)graw, g, workspace, st, graw_amax, gv_amax); break;
-        default: e3 = launch_bwd3<4>(v_, l_, a_, g_, o_, (float*)gv, (float*)gl, (float*)ga, (float*)graw, g, workspace, st, graw_amax, gv_amax); break;
-    }
-    return mpf::check(e3, "msda_bwd_block(bin+tile)");
+    static_assert(sizeof(GeomB) <= sizeof(MsdaBlockPlan::geom) && alignof(GeomB) <= 8, "MsdaBlockPlan::geom holds a GeomB");
+    MsdaBlockPlan plan;
+    if (!host_shapes || !block_ok(p)) return plan;
+    GeomB& g = *new (plan.geom) GeomB;
+    if (!build_geom(g, host_shapes, nullptr, p.N, p.S, p.M, p.L, p.Lq)) return plan;
+    plan.applies = true;
+    plan.fuse_prep = g_fuse_prep != 0 && p.n_samples() * 12 < (1ll << 31);
+    plan.workspace_bytes = ws_layout(g).total;
+    return plan;
+}
+
+// forward through the blocked kernel under the name `kernel`.  raw: loc / attn are OUTPUTS computed from o.raw + o.ref (msda_prep
+// fused in); gd: the geometry record on the device (then g carries only the host arguments)
+static int run_forward(const MsdaProblem& p, const MsdaOperands& o, const GeomB& g, const char* kernel, bool raw, const GeomB* gd = nullptr,
+                       int dev_grid = 0)
+{
+    prof_begin(o.stream);
+    set_kernel(kernel);
+    hipError_t err = hipSuccess;
+    with_levels(p.L, [&](auto nl) {
+        err = launch_fwd<decltype(nl)::value>((const float*)o.value, (const float*)o.loc, (const float*)o.attn, (float*)o.out, g, o.stream,
+                                              raw ? (const float*)o.raw : nullptr, raw ? (const float*)o.ref : nullptr, gd, dev_grid);
+    });
+    prof_end("msda_fwd_block_kernel", o.stream, p.forward_bytes(raw));
+    return check(err, kernel);
+}
+
+// backward through bin + tile (+ spill).  With o.grad_raw (the raw form, which needs o.fwd_out: delta = <grad_out, out>) the
+// kernels fill the amax slots themselves.
+static int run_backward(const MsdaProblem& p, const MsdaOperands& o, const GeomB& g, const Bwd3Buffers& b, const char* kernel,
+                        const GeomB* gd = nullptr, int dev_blk_grid = 0, int dev_tile_grid = 0)
+{
+    set_kernel(kernel);
+    hipError_t err = hipSuccess;
+    with_levels(p.L, [&](auto nl) { err = launch_bwd3<decltype(nl)::value>(p, o, g, b, gd, dev_blk_grid, dev_tile_grid); });
+    return check(err, kernel);
+}
+
+int msda_block_forward(const MsdaProblem& p, const MsdaOperands& o, const MsdaBlockPlan& plan, bool raw)
+{
+    return run_forward(p, o, *reinterpret_cast<const GeomB*>(plan.geom), raw ? "msda_fwd_block_kernel<raw>" : "msda_fwd_block_kernel", raw);
+}
+
+int msda_block_backward(const MsdaProblem& p, const MsdaOperands& o, const MsdaBlockPlan& plan)
+{
+    if (o.workspace_bytes < plan.workspace_bytes) return fail(MPF_E_SHAPE, "msda_backward_ws: workspace too small");
+    const GeomB& g = *reinterpret_cast<const GeomB*>(plan.geom);
+    return run_backward(p, o, g, bwd3_buffers(o.workspace, ws_layout(g)), "msda_bwd_block(bin+tile)");
+}
+
+// the *_dev forms apply to the blocked kernels' shapes when the buffers sized from (N, S, M, L, Lq) stay within 32-bit indexing
+MsdaDevPlan msda_block_dev_plan(const MsdaProblem& p, bool backward)
+{
+    return block_ok(p) ? dev_budget(p.N, p.S, p.M, p.L, p.Lq, backward) : MsdaDevPlan();
+}
+
+// workspace checks, then the prologue of a *_dev call (msda_geom_kernel); gh = the host arguments the kernels take by value
+static int dev_prologue(const MsdaProblem& p, const MsdaOperands& o, const MsdaDevPlan& b, GeomB& gh, const char* too_small, float* o0,
+                        int64_t n0, float* o1 = nullptr, int64_t n1 = 0, float* o2 = nullptr, int64_t n2 = 0, float* grad_value = nullptr,
+                        int64_t nv = 0)
+{
+    if (!o.workspace || o.workspace_bytes < b.total) return fail(MPF_E_SHAPE, too_small);
+    if ((uintptr_t)o.workspace & 255) return fail(MPF_E_SHAPE, "msda_*_dev: workspace must be 256-byte aligned");
+    memset(&gh, 0, sizeof(gh));
+    gh.N = p.N; gh.S = p.S; gh.M = p.M; gh.L = p.L; gh.Lq = p.Lq;
+    hipLaunchKernelGGL(msda_geom_kernel, dim3(1), dim3(256), 0, o.stream, o.shapes, o.lsi, (unsigned char*)o.workspace, p.N, p.S, p.M, p.L, p.Lq,
+                       (long long)b.ent_bm, (long long)b.tiles_bm, o0, n0, o1, n1, o2, n2, grad_value, nv);
+    return check(hipGetLastError(), "msda_geom_kernel");
+}
+
+int msda_block_forward_dev(const MsdaProblem& p, const MsdaOperands& o, const MsdaDevPlan& b)
+{
+    GeomB gh;
+    if (int r = dev_prologue(p, o, b, gh, "msda_forward_dev: workspace too small (mpf_msda_dev_workspace_bytes)", (float*)o.out, p.n_rows()))
+        return r;
+    return run_forward(p, o, gh, "msda_fwd_block_kernel<dev>", false, (const GeomB*)o.workspace, b.blk_grid);
+}
+
+int msda_block_backward_dev(const MsdaProblem& p, const MsdaOperands& o, const MsdaDevPlan& b)
+{
+    GeomB gh;
+    const int64_t n_s = p.n_samples(), n_v = p.n_value();
+    if (int r = dev_prologue(p, o, b, gh, "msda_backward_dev: workspace too small (mpf_msda_dev_workspace_bytes)", (float*)o.grad_value, n_v,
+                             (float*)o.grad_loc, n_s * 2, (float*)o.grad_attn, n_s, (float*)o.grad_value, n_v))
+        return r;
+    return run_backward(p, o, gh, bwd3_buffers(o.workspace, b), "msda_bwd_block(bin+tile)<dev>", (const GeomB*)o.workspace, b.blk_grid,
+                        b.tile_grid);
 }
 
 int set_block_option(const char* key, int v)
@@ -1691,7 +1713,7 @@ int set_block_option(const char* key, int v)
     }
     if (!strcmp(key, "msda_block_disable")) { g_block_disable = v; return 0; }
     if (!strcmp(key, "msda_fuse_prep")) { g_fuse_prep = v; return 0; }
-    if (!strcmp(key, "msda_push_ablate2")) { g_push_ablate = v; return 0; }
+    if (!strcmp(key, "msda_push_ablate2")) { g_tile_ablate = v; return 0; }
     if (!strcmp(key, "msda_bwd_sorted")) { g_bwd_sorted = v != 0; return 0; }
     if (!strcmp(key, "msda_bin_reverse")) { g_bin_reverse = v != 0; return 0; }
     if (!strcmp(key, "msda_stats")) {
@@ -1715,95 +1737,8 @@ extern "C" size_t mpf_msda_dev_workspace_bytes(int batch, int spatial_size, int 
                                                int backward)
 {
     if (batch <= 0 || spatial_size <= 0 || num_heads <= 0 || num_levels < 1 || num_levels > kMaxL || num_query <= 0 || num_point != kP) return 0;
-    const DevBudget b = dev_budget(batch, spatial_size, num_heads, num_levels, num_query, backward != 0);
-    if ((int64_t)batch * num_heads * b.ent_bm >= (1ll << 31) || (int64_t)batch * num_heads * b.tiles_bm >= (1ll << 31)) return 0;
-    return b.total;
-}
-
-namespace {
-int dev_prologue(const int64_t* shapes, const int64_t* lsi, int N, int S, int M, int L, int Lq, bool backward, void* workspace,
-                 size_t workspace_bytes, DevBudget& b, GeomB& gh, hipStream_t st, const char* who, float* o0, int64_t n0, float* o1 = nullptr,
-                 int64_t n1 = 0, float* o2 = nullptr, int64_t n2 = 0, float* grad_value = nullptr, int64_t nv = 0)
-{
-    b = dev_budget(N, S, M, L, Lq, backward);
-    if ((int64_t)N * M * b.ent_bm >= (1ll << 31) || (int64_t)N * M * b.tiles_bm >= (1ll << 31)) return -1000;
-    if (!workspace || workspace_bytes < b.total) return mpf::fail(MPF_E_SHAPE, who);
-    if ((uintptr_t)workspace & 255) return mpf::fail(MPF_E_SHAPE, "msda_*_dev: workspace must be 256-byte aligned");
-    memset(&gh, 0, sizeof(gh));
-    gh.N = N; gh.S = S; gh.M = M; gh.L = L; gh.Lq = Lq;
-    hipLaunchKernelGGL(msda_geom_kernel, dim3(1), dim3(256), 0, st, shapes, lsi, (unsigned char*)workspace, N, S, M, L, Lq, (long long)b.ent_bm,
-                       (long long)b.tiles_bm, o0, n0, o1, n1, o2, n2, grad_value, nv);
-    return mpf::check(hipGetLastError(), "msda_geom_kernel");
-}
-}  // namespace
-
-extern "C" int mpf_msda_forward_dev(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const void* sampling_loc,
-                                    const void* attn_weight, void* output, int batch, int spatial_size, int num_heads, int channels,
-                                    int num_levels, int num_query, int num_point, int dtype, void* workspace, size_t workspace_bytes,
-                                    void* stream)
-{
-    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-    hipStream_t st = (hipStream_t)stream;
-    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !output)
-        return mpf::fail(MPF_E_NULL, "msda_forward_dev: NULL buffer");
-    DevBudget b;
-    GeomB gh;
-    int r = block_ok(N, S, M, D, L, Lq, P, dtype) ? dev_prologue(spatial_shapes, level_start_index, N, S, M, L, Lq, false, workspace, workspace_bytes,
-                                                                 b, gh, st, "msda_forward_dev: workspace too small (mpf_msda_dev_workspace_bytes)",
-                                                                 (float*)output, (int64_t)N * Lq * M * D)
-                                                  : -1000;
-    if (r == -1000)          // other dtypes / head widths / point counts: the kernels that read the shapes themselves
-        return mpf_msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, output, N, S, M, D, L, Lq, P, dtype, stream);
-    if (r) return r;
-    const GeomB* gd = (const GeomB*)workspace;
-    mpf::prof_begin(st);
-    mpf::set_kernel("msda_fwd_block_kernel<dev>");
-    hipError_t err;
-    const float *v_ = (const float*)value, *l_ = (const float*)sampling_loc, *a_ = (const float*)attn_weight;
-    switch (L) {
-        case 1: err = launch_fwd<1>(v_, l_, a_, (float*)output, gh, st, nullptr, nullptr, gd, b.blk_grid); break;
-        case 2: err = launch_fwd<2>(v_, l_, a_, (float*)output, gh, st, nullptr, nullptr, gd, b.blk_grid); break;
-        case 3: err = launch_fwd<3>(v_, l_, a_, (float*)output, gh, st, nullptr, nullptr, gd, b.blk_grid); break;
-        default: err = launch_fwd<4>(v_, l_, a_, (float*)output, gh, st, nullptr, nullptr, gd, b.blk_grid); break;
-    }
-    mpf::prof_end("msda_fwd_block_kernel", st, 4.0 * ((double)N * S * M * D + (double)N * Lq * M * L * P * 3 + (double)N * Lq * M * D));
-    return mpf::check(err, "msda_fwd_block_kernel<dev>");
-}
-
-extern "C" int mpf_msda_backward_dev(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const void* sampling_loc,
-                                     const void* attn_weight, const void* grad_output, void* grad_value, void* grad_sampling_loc,
-                                     void* grad_attn_weight, int batch, int spatial_size, int num_heads, int channels, int num_levels,
-                                     int num_query, int num_point, int dtype, void* workspace, size_t workspace_bytes, void* stream)
-{
-    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-    hipStream_t st = (hipStream_t)stream;
-    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !grad_output || !grad_value || !grad_sampling_loc ||
-        !grad_attn_weight)
-        return mpf::fail(MPF_E_NULL, "msda_backward_dev: NULL buffer");
-    DevBudget b;
-    GeomB gh;
-    const int64_t n_s = (int64_t)N * Lq * M * L * P, n_v = (int64_t)N * S * M * D;
-    int r = block_ok(N, S, M, D, L, Lq, P, dtype) ? dev_prologue(spatial_shapes, level_start_index, N, S, M, L, Lq, true, workspace, workspace_bytes,
-                                                                 b, gh, st, "msda_backward_dev: workspace too small (mpf_msda_dev_workspace_bytes)",
-                                                                 (float*)grad_value, n_v, (float*)grad_sampling_loc, n_s * 2,
-                                                                 (float*)grad_attn_weight, n_s, (float*)grad_value, n_v)
-                                                  : -1000;
-    if (r == -1000)
-        return mpf_msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
-                                 grad_attn_weight, N, S, M, D, L, Lq, P, dtype, stream);
-    if (r) return r;
-    const GeomB* gd = (const GeomB*)workspace;
-    mpf::set_kernel("msda_bwd_block(bin+tile)<dev>");
-    hipError_t e3;
-    const float *v_ = (const float*)value, *l_ = (const float*)sampling_loc, *a_ = (const float*)attn_weight, *g_ = (const float*)grad_output;
-    float *gv = (float*)grad_value, *gl = (float*)grad_sampling_loc, *ga = (float*)grad_attn_weight;
-    switch (L) {
-        case 1: e3 = launch_bwd3_dev<1>(v_, l_, a_, g_, gv, gl, ga, gh, gd, b, (char*)workspace, st); break;
-        case 2: e3 = launch_bwd3_dev<2>(v_, l_, a_, g_, gv, gl, ga, gh, gd, b, (char*)workspace, st); break;
-        case 3: e3 = launch_bwd3_dev<3>(v_, l_, a_, g_, gv, gl, ga, gh, gd, b, (char*)workspace, st); break;
-        default: e3 = launch_bwd3_dev<4>(v_, l_, a_, g_, gv, gl, ga, gh, gd, b, (char*)workspace, st); break;
-    }
-    return mpf::check(e3, "msda_bwd_block(bin+tile)<dev>");
+    const MsdaDevPlan b = dev_budget(batch, spatial_size, num_heads, num_levels, num_query, backward != 0);
+    return b.applies ? b.total : 0;
 }
 
 // tests / diagnostics: the geometry record a *_dev call left in its workspace (synchronises): out[0] = ok, [1] = contiguous,

@@ -31,7 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mpf_common.h"
+#include "msda_host.h"
 
 namespace {
 
@@ -556,8 +556,6 @@ bool build_geom(Geom& g, const int64_t* hs, int N, int S, int M, int L, int Lq, 
     return true;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" size_t mpf_msda_backward_workspace_bytes(int batch, int num_heads, int num_levels, int num_query,
@@ -571,66 +569,31 @@ extern "C" size_t mpf_msda_backward_workspace_bytes(int batch, int num_heads, in
     if (!build_geom(g, host_spatial_shapes, batch, (int)S, num_heads, num_levels, num_query, num_point)) return 0;
     const size_t T = (size_t)batch * num_heads * g.tiles_per_bm * 4;   // bins: tile x (pixel row mod 4)
     const size_t max_entries = (size_t)batch * num_query * num_heads * num_levels * num_point * 4;
-    const size_t binned = align256((3 * T + 1) * sizeof(int)) + max_entries * sizeof(Entry);
+    const size_t binned = mpf::align256((3 * T + 1) * sizeof(int)) + max_entries * sizeof(Entry);
     const size_t blocked = mpf::msda_block_workspace_bytes(host_spatial_shapes, batch, num_heads, num_levels, num_query, num_point);
     return binned > blocked ? binned : blocked;
 }
 
-// the amax slots of grad_value / grad_raw by a pass over the data: every route whose kernels do not record them themselves
-static int amax_after(const void* grad_value, const void* grad_raw, int N, int S, int M, int D, int L, int Lq, int P, float* graw_amax,
-                      float* gv_amax, void* stream)
+// push + fill + pull.  o.grad_raw: the raw form (the softmax backward inside the push kernel), else grad_loc / grad_attn
+int mpf::msda_binned_backward(const MsdaProblem& p, const MsdaOperands& o)
 {
-    if (gv_amax)
-        if (int r = mpf_amax_f32((const float*)grad_value, (int64_t)N * S * M * D, gv_amax, stream)) return r;
-    if (graw_amax && grad_raw)
-        if (int r = mpf_amax_f32((const float*)grad_raw, (int64_t)N * Lq * M * L * P * 3, graw_amax, stream)) return r;
-    return 0;
-}
-
-static int backward_ws_impl(const void* value, const int64_t* host_spatial_shapes,
-                            const void* sampling_loc, const void* attn_weight, const void* grad_output,
-                            void* grad_value, void* grad_sampling_loc, void* grad_attn_weight, void* grad_raw,
-                            int batch, int spatial_size, int num_heads, int channels,
-                            int num_levels, int num_query, int num_point, int dtype,
-                            void* workspace, size_t workspace_bytes, void* stream, const void* fwd_out = nullptr,
-                            float* graw_amax = nullptr, float* gv_amax = nullptr, bool skip_block = false)
-{
-    const int N = batch, S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-    if (!value || !host_spatial_shapes || !sampling_loc || !attn_weight || !grad_output || !grad_value ||
-        (!grad_raw && (!grad_sampling_loc || !grad_attn_weight)) || !workspace)
-        return mpf::fail(MPF_E_NULL, "msda_backward_ws: NULL buffer");
-    if (dtype != MPF_F32 || D != kD) return mpf::fail(MPF_E_DTYPE, "msda_backward_ws: fp32 with 32 channels per head only");
-    if (N <= 0 || S <= 0 || M <= 0 || L <= 0 || Lq <= 0 || P <= 0) return mpf::fail(MPF_E_SHAPE, "msda_backward_ws: bad sizes");
-    if (!skip_block) {   // production path: destination-side bin + tile kernels (msda_block.hip); -1000 = not its shapes
-        bool recorded = false;
-        const int r = mpf::msda_block_backward(value, host_spatial_shapes, sampling_loc, attn_weight, grad_output, grad_value,
-                                               grad_sampling_loc, grad_attn_weight, grad_raw, N, S, M, D, L, Lq, P, dtype, workspace,
-                                               workspace_bytes, (hipStream_t)stream, fwd_out, graw_amax, gv_amax, &recorded);
-        if (r != -1000) return (r != 0 || recorded) ? r : amax_after(grad_value, grad_raw, N, S, M, D, L, Lq, P, graw_amax, gv_amax, stream);
-    }
-    if (graw_amax || gv_amax) {      // round-1 route: same results, then the two amax passes
-        const int r = backward_ws_impl(value, host_spatial_shapes, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
-                                       grad_attn_weight, grad_raw, batch, spatial_size, num_heads, channels, num_levels, num_query,
-                                       num_point, dtype, workspace, workspace_bytes, stream, fwd_out, nullptr, nullptr, true);
-        return r ? r : amax_after(grad_value, grad_raw, N, S, M, D, L, Lq, P, graw_amax, gv_amax, stream);
-    }
-    (void)skip_block;
+    const int N = p.N, S = p.S, M = p.M, D = p.D, L = p.L, Lq = p.Lq, P = p.P;
+    void* const workspace = o.workspace;
     Geom g;
-    if (!build_geom(g, host_spatial_shapes, N, S, M, L, Lq, P))
+    if (!build_geom(g, o.host_shapes, N, S, M, L, Lq, P))
         return mpf::fail(MPF_E_SHAPE, "msda_backward_ws: unsupported level geometry (L <= 8, L*P <= 32, sum HW == S)");
-    if ((int64_t)N * S * M * D * 4 >= (1ll << 31) || (int64_t)N * Lq * M * L * P * 4 >= (1ll << 31) ||
-        (int64_t)N * Lq * M * D * 4 >= (1ll << 32))
+    if (p.n_value() * 4 >= (1ll << 31) || p.n_samples() * 4 >= (1ll << 31) || p.n_rows() * 4 >= (1ll << 32))
         return mpf::fail(MPF_E_TOO_LARGE, "msda_backward_ws: tensor too large for 32-bit indexing");
-    const size_t need = mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, host_spatial_shapes);
-    if (workspace_bytes < need) return mpf::fail(MPF_E_SHAPE, "msda_backward_ws: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+    const size_t need = mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, o.host_shapes);
+    if (o.workspace_bytes < need) return mpf::fail(MPF_E_SHAPE, "msda_backward_ws: workspace too small");
+    hipStream_t st = o.stream;
     const int ntiles = N * M * g.tiles_per_bm;
     const int T = ntiles * 4;                                     // bins
     int* tile_count = (int*)workspace;
     int* tile_start = tile_count + T;
     int* tile_cursor = tile_start + T;
     int* total = tile_cursor + T;
-    Entry* entries = (Entry*)((char*)workspace + align256((3 * (size_t)T + 1) * sizeof(int)));
+    Entry* entries = (Entry*)((char*)workspace + mpf::align256((3 * (size_t)T + 1) * sizeof(int)));
     hipError_t err = hipMemsetAsync(workspace, 0, (3 * (size_t)T + 1) * sizeof(int), st);
     if (err != hipSuccess) return mpf::check(err, "mpf_msda_backward_ws(memset)");
 
@@ -643,14 +606,14 @@ static int backward_ws_impl(const void* value, const int64_t* host_spatial_shape
     mpf::prof_begin(st);
     mpf::set_kernel("msda_bwd_push_kernel");
     hipLaunchKernelGGL(msda_bwd_push_kernel, dim3(grid), dim3(kThreads), lds_push, st,
-                       (const float*)value, (const float*)sampling_loc, (const float*)attn_weight,
-                       (const float*)grad_output, (float*)grad_sampling_loc, (float*)grad_attn_weight,
-                       tile_count, g, nchunks, nblocks, g_push_ablate, (unsigned)((size_t)N * S * M * D * 4), (float*)grad_raw);
+                       (const float*)o.value, (const float*)o.loc, (const float*)o.attn,
+                       (const float*)o.grad_out, (float*)o.grad_loc, (float*)o.grad_attn,
+                       tile_count, g, nchunks, nblocks, g_push_ablate, (unsigned)((size_t)N * S * M * D * 4), (float*)o.grad_raw);
     mpf::prof_end("msda_bwd_push_kernel", st, bytes_push);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, tile_start, total, T);
     mpf::prof_begin(st);
     hipLaunchKernelGGL(msda_bwd_fill_kernel, dim3(grid), dim3(kThreads), 0, st,
-                       (const float*)sampling_loc, (const float*)attn_weight, tile_start, tile_cursor, entries,
+                       (const float*)o.loc, (const float*)o.attn, tile_start, tile_cursor, entries,
                        g, nchunks, nblocks);
     mpf::prof_end("msda_bwd_fill_kernel", st, esz * (double)N * Lq * M * L * P * 3);
     mpf::prof_begin(st);
@@ -658,52 +621,11 @@ static int backward_ws_impl(const void* value, const int64_t* host_spatial_shape
     int ts_max = 4;
     for (int l = 0; l < L; ++l) ts_max = g.ts[l] > ts_max ? g.ts[l] : ts_max;
     hipLaunchKernelGGL(msda_bwd_pull_kernel, dim3(T), dim3(64), (size_t)(ts_max / 4) * ts_max * kD * 4 + 256, st,
-                       (const float*)grad_output, tile_start, tile_count, entries, (float*)grad_value, g,
+                       (const float*)o.grad_out, tile_start, tile_count, entries, (float*)o.grad_value, g,
                        (unsigned)((size_t)N * Lq * M * D * 4));
     mpf::prof_end("msda_bwd_pull_kernel", st, esz * ((double)N * Lq * M * D + (double)N * S * M * D));
     mpf::set_kernel("msda_bwd_binned(push+fill+pull)");
     return mpf::check(hipGetLastError(), "mpf_msda_backward_ws");
-}
-
-extern "C" int mpf_msda_backward_ws(const void* value, const int64_t* host_spatial_shapes,
-                                    const void* sampling_loc, const void* attn_weight, const void* grad_output,
-                                    void* grad_value, void* grad_sampling_loc, void* grad_attn_weight,
-                                    int batch, int spatial_size, int num_heads, int channels,
-                                    int num_levels, int num_query, int num_point, int dtype,
-                                    void* workspace, size_t workspace_bytes, void* stream)
-{
-    return backward_ws_impl(value, host_spatial_shapes, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
-                            grad_attn_weight, nullptr, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point,
-                            dtype, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mpf_msda_backward_ws_raw(const void* value, const int64_t* host_spatial_shapes,
-                                        const void* sampling_loc, const void* attn_weight, const void* grad_output,
-                                        void* grad_value, void* grad_raw,
-                                        int batch, int spatial_size, int num_heads, int channels,
-                                        int num_levels, int num_query, int num_point, int dtype,
-                                        void* workspace, size_t workspace_bytes, void* stream)
-{
-    if (!grad_raw) return mpf::fail(MPF_E_NULL, "msda_backward_ws_raw: NULL grad_raw");
-    return backward_ws_impl(value, host_spatial_shapes, sampling_loc, attn_weight, grad_output, grad_value, nullptr, nullptr,
-                            grad_raw, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, dtype,
-                            workspace, workspace_bytes, stream);
-}
-
-// raw form with the forward result at hand (the module keeps it): the softmax-backward sum of a (query, head) is
-// <grad_output, output> of that (query, head), so the destination-side kernels (bin + tile, msda_block.hip) apply
-extern "C" int mpf_msda_backward_ws_raw_o(const void* value, const int64_t* host_spatial_shapes,
-                                          const void* sampling_loc, const void* attn_weight, const void* grad_output,
-                                          const void* output, void* grad_value, void* grad_raw,
-                                          int batch, int spatial_size, int num_heads, int channels,
-                                          int num_levels, int num_query, int num_point, int dtype,
-                                          void* workspace, size_t workspace_bytes, float* grad_raw_amax, float* grad_value_amax,
-                                          void* stream)
-{
-    if (!grad_raw || !output) return mpf::fail(MPF_E_NULL, "msda_backward_ws_raw_o: NULL grad_raw / output");
-    return backward_ws_impl(value, host_spatial_shapes, sampling_loc, attn_weight, grad_output, grad_value, nullptr, nullptr,
-                            grad_raw, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point, dtype,
-                            workspace, workspace_bytes, stream, output, grad_raw_amax, grad_value_amax);
 }
 
 namespace mpf {

@@ -30,7 +30,7 @@ from torch.autograd import Function
 from . import _lib
 from .gemm3 import (amax, amax_slots, gemm3_h2, gemm3_h2_bits, gemm3_nt, gemm3_nt_grouped, nt_reduce_levels, split_weights_grouped_h2,
                     workgroup_slots)
-from .msda import ms_deform_attn_backward_raw, ms_deform_attn_forward_raw
+from .msda import host_workspace, ms_deform_attn_backward_raw, ms_deform_attn_forward_raw
 from .resln import LnGradGroup, ln256_forward, ln_partial_stride
 
 _EPS = 1e-5
@@ -421,11 +421,8 @@ def _native_backward(gout, prm, saved, planes_t, meta, dims, rps, split_level):
     ln_stride = ln_partial_stride(R)
     ln_parts = torch.empty(2 * nl * ln_stride, dtype=torch.uint8, device=dev)
     host_shapes = meta["shapes"]._mpf_host
-    need = lib.mpf_msda_backward_workspace_bytes(N, M, L, S, P, host_shapes.data_ptr())
-    if need == 0:
-        raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
     stream = _lib.stream_ptr(dev)
-    ws = _lib.scratch("msda_host", dev, stream, need)
+    ws = host_workspace(dev, stream, N, M, L, S, P, host_shapes)
     dgb = torch.empty((2 * nl, 2, 256), dtype=torch.float32, device=dev)
     ams, _ = _records(BwdAmax, amax_slots(len(BwdAmax._fields) * nl, dev).unbind(0), nl)
     tab = np.zeros((nl, len(_ENCB_FIELDS)), dtype=np.uint64)

@@ -58,6 +58,26 @@ def _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, i
     return batch, spatial_size, num_heads, channels, num_levels, num_query, num_point
 
 
+def _sizes(dims, dtype):
+    """the size tail every op entry point takes: N, S, M, D, L, Lq, P, MPF_* dtype code"""
+    return (*dims, _lib.DTYPE[dtype])
+
+
+def host_workspace(device, stream, N, M, L, Lq, P, host_shapes):
+    """The "msda_host" buffer of ``stream``, sized by mpf_msda_backward_workspace_bytes for these sizes and host shapes: the
+    workspace of the *_ws backward forms."""
+    need = _lib.lib().mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, host_shapes.data_ptr())
+    if need == 0:
+        raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
+    return _lib.scratch("msda_host", device, stream, need)
+
+
+def _workspace(device, nbytes=0):
+    """The "msda_dev" buffer of the current stream, at least ``nbytes``: the workspace of the *_dev routes, whose first KB holds
+    the geometry record (tests read it back)."""
+    return _lib.scratch("msda_dev", device, _lib.stream_ptr(device), nbytes, zeroed=True)
+
+
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step,
                            host_shapes=None):
     """-> output [N, Lq, M*D]; freshly allocated, computed on the current stream.  The spatially blocked production kernel runs
@@ -67,23 +87,21 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight)])
-    N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
+    dims = N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     hs = host_shapes if host_shapes is not None else _attached_host_shapes(spatial_shapes, level_start_index)
     lib = _lib.lib()
     stream = _lib.stream_ptr(value.device)
     if hs is None and _dev_applicable(value, D, L, P):
         # the reference's call (func.py:36): device tensors only -> geometry derived on the device, same blocked kernel
-        ws = _lib.scratch("msda_dev", value.device, stream, lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 0), zeroed=True)
+        ws = _workspace(value.device, lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 0))
         _lib.call("mpf_msda_forward_dev", value.device,
                   value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                  attn_weight.data_ptr(), out.data_ptr(), N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(),
-                  stream)
+                  attn_weight.data_ptr(), out.data_ptr(), *_sizes(dims, value.dtype), ws.data_ptr(), ws.numel(), stream)
     else:
         _lib.call("mpf_msda_forward_hs", value.device,
                   value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), _lib.ptr(hs),
-                  sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(),
-                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], stream)
+                  sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(), *_sizes(dims, value.dtype), stream)
     return out
 
 
@@ -138,12 +156,6 @@ def _dev_applicable(value, D, L, P):
     return value.dtype == torch.float32 and D == 32 and P == 4 and 1 <= L <= 4
 
 
-def _workspace(device, nbytes=0):
-    """The "msda_dev" buffer of the current stream, at least ``nbytes``: the workspace of the *_dev routes, whose first KB holds
-    the geometry record (tests read it back)."""
-    return _lib.scratch("msda_dev", device, _lib.stream_ptr(device), nbytes, zeroed=True)
-
-
 def _binned_applicable(value, D, L, P):
     return value.dtype == torch.float32 and D == 32 and L <= 8 and L * P <= 32
 
@@ -154,7 +166,7 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
                    ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
                    ("attn_weight", attn_weight), ("grad_output", grad_output)])
-    N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
+    dims = N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
     if grad_output.dtype != value.dtype or grad_output.numel() != N * Lq * M * D:
         raise RuntimeError("grad_output must be [N, Lq, M*D] in the dtype of value")
     gv = torch.empty_like(value)           # fully written by the native call
@@ -165,35 +177,28 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         hs = host_shapes if host_shapes is not None else _host_shapes(spatial_shapes, level_start_index)
     if hs is None and BWD_MODE != "atomic" and _dev_applicable(value, D, L, P):
         # the reference's call (func.py:46): device tensors only -> bin + tile kernels on a geometry built on the device
-        lib = _lib.lib()
-        need = lib.mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 1)
+        need = _lib.lib().mpf_msda_dev_workspace_bytes(N, S, M, L, Lq, P, 1)
         if need:
-            stream = _lib.stream_ptr(value.device)
-            ws = _lib.scratch("msda_dev", value.device, stream, need, zeroed=True)
+            ws = _workspace(value.device, need)
             _lib.call("mpf_msda_backward_dev", value.device,
                       value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
                       attn_weight.data_ptr(), grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-                      N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(), stream)
+                      *_sizes(dims, value.dtype), ws.data_ptr(), ws.numel(), _lib.stream_ptr(value.device))
             return [gv, gl, ga]
     if BWD_MODE == "binned" and hs is None:
         raise RuntimeError("MSDA binned backward requested but not applicable (needs fp32, D=32, L<=8, L*P<=32, host shapes)")
     if hs is not None:
-        lib = _lib.lib()
-        need = lib.mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, hs.data_ptr())
-        if need == 0:
-            raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
         stream = _lib.stream_ptr(value.device)
-        ws = _lib.scratch("msda_host", value.device, stream, need)
+        ws = host_workspace(value.device, stream, N, M, L, Lq, P, hs)
         _lib.call("mpf_msda_backward_ws", value.device,
                   value.data_ptr(), hs.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
                   grad_output.data_ptr(), gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(), stream)
+                  *_sizes(dims, value.dtype), ws.data_ptr(), ws.numel(), stream)
         return [gv, gl, ga]
     _lib.call("mpf_msda_backward", value.device,
               value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
               sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-              gv.data_ptr(), gl.data_ptr(), ga.data_ptr(),
-              N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], _lib.stream_ptr(value.device))
+              gv.data_ptr(), gl.data_ptr(), ga.data_ptr(), *_sizes(dims, value.dtype), _lib.stream_ptr(value.device))
     return [gv, gl, ga]
 
 
@@ -213,7 +218,7 @@ def ms_deform_attn_forward_raw(value, spatial_shapes, level_start_index, raw, re
               value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
               _lib.ptr(host_shapes), raw.data_ptr(), ref_points.data_ptr(),
               loc.data_ptr(), attn.data_ptr(), out.data_ptr(),
-              N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], _lib.stream_ptr(value.device))
+              *_sizes((N, S, M, D, L, Lq, P), value.dtype), _lib.stream_ptr(value.device))
     return out, loc, attn
 
 
@@ -225,24 +230,19 @@ def ms_deform_attn_backward_raw(value, host_shapes, sampling_loc, attn_weight, g
     _, Lq, _, L, P, _ = sampling_loc.shape
     gv = torch.empty_like(value)
     graw = torch.empty((N * Lq, M * L * P * 3), dtype=value.dtype, device=value.device)
-    lib = _lib.lib()
-    need = lib.mpf_msda_backward_workspace_bytes(N, M, L, Lq, P, host_shapes.data_ptr())
-    if need == 0:
-        raise RuntimeError("mpf_msda_backward_workspace_bytes rejected the level geometry")
     stream = _lib.stream_ptr(value.device)
-    ws = _lib.scratch("msda_host", value.device, stream, need)
+    ws = host_workspace(value.device, stream, N, M, L, Lq, P, host_shapes)
+    sizes = _sizes((N, S, M, D, L, Lq, P), value.dtype)
     if output is not None:
         assert output.is_contiguous() and output.numel() == N * Lq * M * D and output.dtype == value.dtype
         _lib.call("mpf_msda_backward_ws_raw_o", value.device,
                   value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
                   grad_output.data_ptr(), output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
-                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(),
-                  _lib.ptr(graw_amax), _lib.ptr(gv_amax), stream)
+                  *sizes, ws.data_ptr(), ws.numel(), _lib.ptr(graw_amax), _lib.ptr(gv_amax), stream)
     else:
         _lib.call("mpf_msda_backward_ws_raw", value.device,
                   value.data_ptr(), host_shapes.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                  grad_output.data_ptr(), gv.data_ptr(), graw.data_ptr(),
-                  N, S, M, D, L, Lq, P, _lib.DTYPE[value.dtype], ws.data_ptr(), ws.numel(), stream)
+                  grad_output.data_ptr(), gv.data_ptr(), graw.data_ptr(), *sizes, ws.data_ptr(), ws.numel(), stream)
     return gv, graw
 
 
