@@ -364,7 +364,9 @@ int mpf_attn_mask(const void* masks, int dtype, int64_t stride_n, int64_t stride
  *   mask: bytes, 1 = masked (-inf): [N, Lq, Lk] if mask_per_image else [Lq, Lk]; NULL = no mask.
  *         One mask for all heads.  A fully masked row yields zeros (the decoder never produces one).
  *   out [Lq, N, H*32] bf16     lse [N, H, Lq] f32 (log-sum-exp of the scaled scores; may be NULL)
- *   workspace: >= mpf_attn_workspace_bytes(Lq, Lk, N, H) bytes of device memory
+ *   workspace: >= mpf_attn_workspace_bytes(Lq, Lk, N, H) bytes of device memory, 16-byte aligned for the backward.  Two parts:
+ *     [splits, N, H, Lq, 32] partial O (or dQ) and [splits, N, H, Lq, 2] (max, sum) of the workgroup-level key splits,
+ *     rounded up to 256 bytes | the aux operands (below) of a backward that is not handed any, sized for a mask per image.
  */
 size_t mpf_attn_workspace_bytes(int Lq, int Lk, int N, int H);
 int mpf_attn_forward(const void* q, const void* k, const void* vt, const uint8_t* mask, int mask_per_image,
@@ -407,12 +409,13 @@ int mpf_attn_backward_kv(const void* q, const void* k, const void* v, int64_t kv
                          int64_t dkv_img_stride, int Lq, int LqP, int Lk, int N, int H, int head_dim, float scale, void* workspace,
                          size_t workspace_bytes, void* stream);
 /*
- * The dK / dV kernel of the backward (keys on the lane axis) reads the mask TRANSPOSED ([N or 1, Lk, LqP] bytes) and
- * (lse, delta) as pairs padded to LqP — its "aux" operands, mpf_attn_bwd_aux_bytes(Lq, Lk, N, H, mask_images) bytes
- * (mask_images = N for a per-image mask, 1 for a shared one, 0 without mask).  mpf_attn_bwd_prep_aux makes them in
- * the launch that also makes qT / doT / delta (mpf_attn_bwd_prep below); mpf_attn_backward_kv_aux consumes them.  The
- * entry points without aux make them themselves (one more launch) in the workspace, which mpf_attn_workspace_bytes
- * sizes for that.
+ * The dK / dV kernel of the backward (keys on the lane axis) reads its "aux" operands, 16-byte aligned,
+ * mpf_attn_bwd_aux_bytes(Lq, Lk, N, H, mask_images) bytes (mask_images = N for a per-image mask, 1 for a shared one, 0
+ * without mask; LqP = Lq rounded up to a multiple of 32):
+ *   [N, H, LqP] (lse, delta) pairs, rounded up to 256 bytes | maskT: [mask_images, Lk, LqP] bytes, the mask transposed
+ * mpf_attn_bwd_prep_aux makes them in the launch that also makes qT / doT / delta (mpf_attn_bwd_prep below);
+ * mpf_attn_backward_kv_aux consumes them.  The entry points without aux (and _kv_aux with aux = NULL) make them
+ * themselves (one more launch) in the second part of the workspace.
  */
 size_t mpf_attn_bwd_aux_bytes(int Lq, int Lk, int N, int H, int mask_images);
 int mpf_attn_bwd_prep_aux(const void* q, const void* dout, const void* out, const float* lse, const uint8_t* mask, int mask_per_image,

@@ -7,10 +7,8 @@
 // 8 heads x 32 dims.  The work is bound by streaming K / V and the byte mask, not by MFMA, so the
 // design is flash-decoding-like:
 //   * one WAVE per (16*QS query rows, head, image, key split); keys are split across waves so that the
-//     chip is filled although there are only ~14 query tiles.  Up to 16 splits of a query tile are the
-//     waves of ONE workgroup and merge their partial (max, sum, O) through LDS — for key counts up to
-//     4 096 the kernel writes the final bf16 output itself; longer key axes add a second level of
-//     splits across workgroups, merged by a small combine kernel;
+//     chip is filled although there are only ~14 query tiles: up to 8 waves of ONE workgroup merge through
+//     LDS, longer key axes add splits across workgroups and a combine kernel (attn_split, attn_host.h);
 //   * S^T = K Q^T with v_mfma_f32_16x16x32_bf16: K = head dim = 32 in ONE instruction per 16 keys x 16
 //     queries.  Operands come straight from global memory in MFMA layout: a lane loads 16 contiguous
 //     bytes of a K row (A operand) / of a Q row (B operand) — no LDS staging, every K byte is read once
@@ -32,7 +30,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "mpf_common.h"
+#include "attn_host.h"
 
 namespace {
 
@@ -91,7 +89,7 @@ __device__ __forceinline__ uint2 ld_mask8(const uint8_t* mrow, int key0, int lim
 // bytes of a query row one 8-byte load (was two 8-byte + two 4-byte loads on 32-byte pieces of twice as many cache lines).
 __device__ __forceinline__ int key_of_row(int t, int i) { return ((i >> 2) << 3) + 4 * t + (i & 3); }
 
-constexpr int kHD = 32;          // head dim
+constexpr int kHD = kAttnHD;
 constexpr float kNegInf = -INFINITY;
 
 __device__ __forceinline__ float xmax(float v)
@@ -123,7 +121,7 @@ struct AttnParams {
     int64_t k_row, k_img;         // element strides of k between sequence positions / images (N*E, E when dense)
 };
 
-constexpr int kMaxNW = 8;         // waves per workgroup of the forward / dQ kernels
+constexpr int kMaxNW = kAttnMaxNW;
 constexpr int kMergePitch = 36;   // floats per query row of a wave's partial in LDS (32 + 4: 16-byte aligned, rows 4 banks apart)
 constexpr int kMergeWave = 32 * kMergePitch + 64;   // floats per wave: 32 rows of O (or dQ) + (max, sum) per row
 
@@ -621,7 +619,6 @@ __global__ __launch_bounds__(256) void attn_sum_splits_kernel(const float* __res
     out[((int64_t)q * N + n) * E + h * kHD + d] = __float2bfloat16(acc);
 }
 
-
 // ------------------------------------------------------------------------------------------------
 // Layout helpers (one launch each instead of a handful of permute / pad / reduce kernels):
 //   transpose2: [L, N, E] -> [N, E, LP] for two tensors at once (K and V in the forward; Q and dO in
@@ -815,226 +812,159 @@ __global__ __launch_bounds__(256) void attn_bwd_aux_kernel(const float* __restri
 
 }  // namespace
 
-// Key splits of the forward / dQ kernels: one WAVE per (32 queries, head, image, split) and each wave walks its keys in
-// 32-key steps of ~2 us, so short waves are what makes these kernels fast: 128 keys per wave (64 for key axes up to 256),
-// doubled while that would mean more than ~4 096 waves (measured at config B, Lq = 120: level 1 (Lk = 4 096) 16 + 8 us with
-// 128 keys per wave against 24 + 5 with 256, level 2 (Lk = 16 384) 58 + 8 against 49 + 5).  Up to kMaxNW = 8 waves form the
-// workgroup of a query tile and merge through LDS — key axes up to 1 024 need no second pass; beyond that the workgroups'
-// partials go through the workspace and the combine / sum kernels.
-struct AttnSplit { int keys_per_wave, nw, wg_splits; };
-static int g_attn_occ = 4;      // mpf_set_option attn_occ (2 | 4): forward, aligned forms
-static int g_attn_nw = kMaxNW, g_attn_kpw = 0;     // A/B switches (mpf_set_option attn_nw / attn_kpw; 0 = the policy above)
-static AttnSplit attn_split(int Lq, int Lk, int N, int H)
-{
-    AttnSplit a;
-    int kpw = g_attn_kpw;
-    if (!kpw) {
-        const int64_t tiles = (int64_t)((Lq + 31) / 32) * N * H;
-        kpw = Lk <= 256 ? 64 : 128;
-        while (kpw < 512 && tiles * ((Lk + kpw - 1) / kpw) > 4096) kpw *= 2;
-    }
-    const int waves = (Lk + kpw - 1) / kpw;
-    a.keys_per_wave = kpw;
-    a.nw = waves < g_attn_nw ? waves : g_attn_nw;
-    a.wg_splits = (waves + a.nw - 1) / a.nw;
-    return a;
-}
-namespace mpf {
-int set_attn_option(const char* key, int v)
+int mpf::set_attn_option(const char* key, int v)
 {
     if (!strcmp(key, "attn_occ")) { if (v != 2 && v != 4) return -1; g_attn_occ = v; return 0; }
     if (!strcmp(key, "attn_nw")) { if (v < 1 || v > kMaxNW) return -1; g_attn_nw = v; return 0; }
     if (!strcmp(key, "attn_kpw")) { if (v && (v < 64 || (v & 63))) return -1; g_attn_kpw = v; return 0; }
     return 1;
 }
-}  // namespace mpf
 
-static size_t attn_part_bytes(int Lq, int Lk, int N, int H)
+static const __hip_bfloat16* bf(const void* p) { return (const __hip_bfloat16*)p; }
+static __hip_bfloat16* bf(void* p) { return (__hip_bfloat16*)p; }
+
+// the AL forms: whole 8-key pieces, 16-byte loads of the transposed operand (V^T / K^T), 8-byte loads of the mask
+static bool attn_aligned(int Lk, const void* operandT, const uint8_t* mask)
+{ return (Lk & 7) == 0 && ((uintptr_t)operandT & 15) == 0 && (!mask || ((uintptr_t)mask & 7) == 0); }
+
+// The forward / dQ launch over p (split fields: AttnSplit::fill): one workgroup of p.nw waves per (query tile, workgroup split, head,
+// image) with `wave_floats` of merge buffer per wave.  forms(AL, MK, launch) hands `launch` the kernel of that form.
+template <class P, class Forms>
+static void launch_split(const char* name, const P& p, const AttnProblem& pr, int wave_floats, const void* operandT, double bytes,
+                         double flops, hipStream_t st, Forms&& forms)
 {
-    const int splits = attn_split(Lq, Lk, N, H).wg_splits;
-    return (((size_t)splits * N * H * Lq * (kHD + 2) * sizeof(float)) + 255) & ~(size_t)255;
+    static_assert(32 * kMergePitch <= kMergeWave && kMaxNW * kMergeWave * sizeof(float) <= 64 * 1024,
+                  "the merge buffers (forward: kMergeWave, dQ: 32 * kMergePitch floats per wave) fit the default dynamic-LDS limit");
+    const dim3 grid(pr.q_tiles() * p.splits, pr.H, pr.N), block(64 * p.nw);
+    const size_t lds = (size_t)p.nw * wave_floats * sizeof(float);
+    mpf::prof_begin(st);
+    mpf::set_kernel(name);
+    mpf::with_bool(attn_aligned(pr.Lk, operandT, p.mask), [&](auto AL) {
+        mpf::with_bool(p.mask != nullptr, [&](auto MK) { forms(AL, MK, [&](auto kfn) { hipLaunchKernelGGL(kfn, grid, block, lds, st, p); }); });
+    });
+    mpf::prof_end(name, st, bytes, flops);
 }
-static size_t attn_ld2_bytes(int LqP, int N, int H) { return (((size_t)N * H * LqP * sizeof(float2)) + 255) & ~(size_t)255; }
+
+// What the backward derives from the query side, in one launch: Q^T, dO^T, delta (qT != NULL) and / or aux (with qT == NULL from delta_in)
+static void launch_prep(const AttnProblem& pr, const void* q, const void* dout, const void* out, const float* lse, const float* delta_in,
+                        const uint8_t* mask, void* qT, void* doT, float* delta, void* aux, hipStream_t st)
+{
+    const dim3 grid((qT ? pr.transpose_tiles() + pr.delta_blocks() : pr.ld2_blocks()) + (aux ? pr.mask_blocks() : 0)), block(256);
+    mpf::set_kernel(!qT ? "attn_bwd_aux_kernel" : aux ? "attn_bwd_prep_aux_kernel" : "attn_bwd_prep_kernel");
+    if (!qT)
+        hipLaunchKernelGGL(attn_bwd_aux_kernel, grid, block, 0, st, lse, delta_in, mask, (float2*)aux, pr.maskT_at(aux), pr.Lq, pr.LqP, pr.Lk,
+                           pr.N * pr.H, pr.ld2_blocks(), pr.tiles_q(), pr.tiles_k());
+    else if (aux)
+        hipLaunchKernelGGL(attn_bwd_prep_aux_kernel, grid, block, 0, st, bf(q), bf(dout), bf(out), lse, mask, bf(qT), bf(doT), delta, (float2*)aux,
+                           pr.maskT_at(aux), pr.Lq, pr.LqP, pr.Lk, pr.N, pr.H, pr.tiles_q(), pr.transpose_tiles(), pr.delta_blocks(),
+                           pr.tiles_q(), pr.tiles_k());
+    else
+        hipLaunchKernelGGL(attn_bwd_prep_kernel, grid, block, 0, st, bf(q), bf(dout), bf(out), bf(qT), bf(doT), delta, pr.Lq, pr.LqP, pr.N, pr.H,
+                           pr.tiles_q(), pr.transpose_tiles());
+}
 
 extern "C" size_t mpf_attn_bwd_aux_bytes(int Lq, int Lk, int N, int H, int mask_images)
 {
-    if (Lq <= 0 || Lk <= 0 || N <= 0 || H <= 0 || mask_images < 0) return 0;
-    const int LqP = (Lq + 31) / 32 * 32;
-    return attn_ld2_bytes(LqP, N, H) + (size_t)mask_images * Lk * LqP;
+    const AttnProblem pr{Lq, AttnProblem::round32(Lq), Lk, N, H, mask_images};
+    return pr.sizes_ok() && mask_images >= 0 ? pr.aux_bytes() : 0;
 }
 
 // (covers the split partials AND the aux operands of a backward called without aux: mask per image assumed)
 extern "C" size_t mpf_attn_workspace_bytes(int Lq, int Lk, int N, int H)
 {
-    if (Lq <= 0 || Lk <= 0 || N <= 0 || H <= 0) return 0;
-    return attn_part_bytes(Lq, Lk, N, H) + mpf_attn_bwd_aux_bytes(Lq, Lk, N, H, N);
+    const AttnProblem pr{Lq, AttnProblem::round32(Lq), Lk, N, H, N};
+    return pr.sizes_ok() ? pr.part_bytes(mpf::attn_split(pr).wg_splits) + pr.aux_bytes() : 0;
 }
 
-extern "C" int mpf_attn_forward(const void* q, const void* k, const void* vt, const uint8_t* mask, int mask_per_image,
-                                void* out, float* lse, int Lq, int Lk, int N, int H, int head_dim, float scale,
-                                void* workspace, size_t workspace_bytes, void* stream)
+extern "C" int mpf_attn_forward(const void* q, const void* k, const void* vt, const uint8_t* mask, int mask_per_image, void* out, float* lse,
+                                int Lq, int Lk, int N, int H, int head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return mpf_attn_forward_kv(q, k, 0, 0, vt, mask, mask_per_image, out, lse, Lq, Lk, N, H, head_dim, scale, workspace,
-                               workspace_bytes, stream);
+    return mpf_attn_forward_kv(q, k, 0, 0, vt, mask, mask_per_image, out, lse, Lq, Lk, N, H, head_dim, scale, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mpf_attn_forward_kv(const void* q, const void* k, int64_t k_row_stride, int64_t k_img_stride, const void* vt,
                                    const uint8_t* mask, int mask_per_image, void* out, float* lse, int Lq, int Lk, int N, int H,
                                    int head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!q || !k || !vt || !out || !workspace) return mpf::fail(MPF_E_NULL, "attn_forward: NULL buffer");
-    if (k_row_stride < 0 || k_img_stride < 0 || (k_row_stride | k_img_stride) % 8 || ((uintptr_t)k & 15))
-        return mpf::fail(MPF_E_SHAPE, "attn_forward: K strides must be non-negative multiples of 8 elements, K 16-byte aligned");
-    if (head_dim != kHD) return mpf::fail(MPF_E_SHAPE, "attn_forward: head_dim must be 32");
-    if (Lq <= 0 || Lk <= 0 || N <= 0 || H <= 0) return mpf::fail(MPF_E_SHAPE, "attn_forward: bad sizes");
-    if (workspace_bytes < mpf_attn_workspace_bytes(Lq, Lk, N, H)) return mpf::fail(MPF_E_SHAPE, "attn_forward: workspace too small");
+    const AttnProblem pr{Lq, AttnProblem::round32(Lq), Lk, N, H, AttnProblem::images(mask, mask_per_image, N)};
+    if (int e = mpf::attn_check("attn_forward", pr, {q, k, vt, out, workspace}, {k_row_stride, k_img_stride}, {k},
+                                "K strides must be non-negative multiples of 8 elements, K 16-byte aligned", head_dim, workspace_bytes,
+                                AttnProblem{Lq, pr.LqP, Lk, N, H, N}.aux_bytes(), {}))
+        return e;
     hipStream_t st = (hipStream_t)stream;
+    const AttnKV kv(k_row_stride, k_img_stride, N, pr.E());
+    const AttnSplit sp = mpf::attn_split(pr);
     AttnParams p;
-    p.q = (const __hip_bfloat16*)q; p.k = (const __hip_bfloat16*)k; p.vt = (const __hip_bfloat16*)vt;
-    p.mask = mask; p.mask_stride_n = mask_per_image ? (int64_t)Lq * Lk : 0;
-    p.Lq = Lq; p.Lk = Lk; p.N = N; p.H = H; p.E = H * kHD; p.scale = scale;
-    p.k_row = k_row_stride ? k_row_stride : (int64_t)N * p.E;
-    p.k_img = k_row_stride ? k_img_stride : p.E;
-    const AttnSplit sp = attn_split(Lq, Lk, N, H);
-    p.splits = sp.wg_splits; p.nw = sp.nw; p.keys_per_split = sp.keys_per_wave;
-    p.out = (__hip_bfloat16*)out; p.lse = lse;
-    p.part_o = (float*)workspace;
-    p.part_ml = p.part_o + (size_t)p.splits * N * H * Lq * kHD;
-    constexpr int QS = 2;
-    const int qtiles = (Lq + 16 * QS - 1) / (16 * QS);
-    const size_t lds = (size_t)p.nw * kMergeWave * sizeof(float);
-    mpf::prof_begin(st);
-    mpf::set_kernel("attn_fwd_kernel<2>");
-    {
-        const dim3 grid(qtiles * p.splits, H, N), block(64 * p.nw);
-        const bool al = (Lk & 7) == 0 && ((uintptr_t)p.vt & 15) == 0 && (!mask || ((uintptr_t)mask & 7) == 0);
-        static_assert(kMaxNW * kMergeWave * sizeof(float) <= 64 * 1024, "the merge buffer fits the default dynamic-LDS limit");
-        auto launch = [&](auto kfn) -> int {
-            hipLaunchKernelGGL(kfn, grid, block, lds, st, p);
-            return 0;
-        };
-        int e;
-        if (al && mask && g_attn_occ == 4) e = launch(attn_fwd_kernel<QS, true, true, 4>);
-        else if (al && g_attn_occ == 4) e = launch(attn_fwd_kernel<QS, true, false, 4>);
-        else if (al && mask) e = launch(attn_fwd_kernel<QS, true, true>);
-        else if (al) e = launch(attn_fwd_kernel<QS, true, false>);
-        else if (mask) e = launch(attn_fwd_kernel<QS, false, true>);
-        else e = launch(attn_fwd_kernel<QS, false, false>);
-        if (e) return e;
-    }
-    mpf::prof_end("attn_fwd_kernel<2>", st, 2.0 * ((double)Lk * N * p.E * 2 + (double)Lq * N * p.E) + (mask ? (double)N * Lq * Lk : 0.0),
-                  4.0 * Lq * (double)Lk * p.E * N);      // QK^T + PV
-    if (p.splits > 1) {
-        const int total = N * H * Lq * kHD;
-        hipLaunchKernelGGL(attn_combine_kernel, dim3((total + 255) / 256), dim3(256), 0, st, p.part_o, p.part_ml,
-                           (__hip_bfloat16*)out, lse, Lq, N, H, p.E, p.splits);
-    }
+    p.q = bf(q); p.k = bf(k); p.vt = bf(vt); p.mask = mask; p.mask_stride_n = mask_per_image ? (int64_t)Lq * Lk : 0;
+    p.Lq = Lq; p.Lk = Lk; p.N = N; p.H = H; p.E = pr.E(); p.scale = scale; p.k_row = kv.row; p.k_img = kv.img;
+    sp.fill(p);
+    p.out = bf(out); p.lse = lse; p.part_o = (float*)workspace; p.part_ml = p.part_o + (size_t)sp.wg_splits * pr.rows() * kHD;
+    launch_split("attn_fwd_kernel<2>", p, pr, kMergeWave, vt, pr.forward_bytes(), pr.flops(2), st, [](auto AL, auto MK, auto&& launch) {
+        if constexpr (!decltype(AL)::value) launch(attn_fwd_kernel<2, false, decltype(MK)::value>);
+        else mpf::with_int_of<2, 4>(mpf::g_attn_occ, [&](auto OCC) { launch(attn_fwd_kernel<2, true, decltype(MK)::value, decltype(OCC)::value>); });
+    });     // (flops: QK^T + PV)
+    if (sp.wg_splits > 1)
+        hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((pr.rows() * kHD + 255) / 256)), dim3(256), 0, st, p.part_o, p.part_ml, bf(out),
+                           lse, Lq, N, H, p.E, sp.wg_splits);
     return mpf::check(hipGetLastError(), "mpf_attn_forward");
 }
 
-extern "C" int mpf_attn_backward(const void* q, const void* k, const void* v, const void* kT, const void* qT,
-                                 const void* dout, const void* doutT, const uint8_t* mask, int mask_per_image,
-                                 const float* lse, const float* delta, void* dq, void* dk, void* dv,
-                                 int Lq, int LqP, int Lk, int N, int H, int head_dim, float scale,
-                                 void* workspace, size_t workspace_bytes, void* stream)
+extern "C" int mpf_attn_backward(const void* q, const void* k, const void* v, const void* kT, const void* qT, const void* dout, const void* doutT,
+                                 const uint8_t* mask, int mask_per_image, const float* lse, const float* delta, void* dq, void* dk, void* dv,
+                                 int Lq, int LqP, int Lk, int N, int H, int head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream)
 {
     return mpf_attn_backward_kv(q, k, v, 0, 0, kT, qT, dout, doutT, mask, mask_per_image, lse, delta, dq, dk, dv, 0, 0, Lq, LqP, Lk, N, H,
                                 head_dim, scale, workspace, workspace_bytes, stream);
 }
 
-extern "C" int mpf_attn_backward_kv(const void* q, const void* k, const void* v, int64_t kv_row_stride, int64_t kv_img_stride,
-                                    const void* kT, const void* qT, const void* dout, const void* doutT, const uint8_t* mask,
-                                    int mask_per_image, const float* lse, const float* delta, void* dq, void* dk, void* dv,
-                                    int64_t dkv_row_stride, int64_t dkv_img_stride, int Lq, int LqP, int Lk, int N, int H,
-                                    int head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream)
+extern "C" int mpf_attn_backward_kv(const void* q, const void* k, const void* v, int64_t kv_row_stride, int64_t kv_img_stride, const void* kT,
+                                    const void* qT, const void* dout, const void* doutT, const uint8_t* mask, int mask_per_image,
+                                    const float* lse, const float* delta, void* dq, void* dk, void* dv, int64_t dkv_row_stride,
+                                    int64_t dkv_img_stride, int Lq, int LqP, int Lk, int N, int H, int head_dim, float scale, void* workspace,
+                                    size_t workspace_bytes, void* stream)
 {
-    return mpf_attn_backward_kv_aux(q, k, v, kv_row_stride, kv_img_stride, kT, qT, dout, doutT, mask, mask_per_image, lse, delta, dq, dk,
-                                    dv, dkv_row_stride, dkv_img_stride, Lq, LqP, Lk, N, H, head_dim, scale, workspace, workspace_bytes,
-                                    nullptr, stream);
+    return mpf_attn_backward_kv_aux(q, k, v, kv_row_stride, kv_img_stride, kT, qT, dout, doutT, mask, mask_per_image, lse, delta, dq, dk, dv,
+                                    dkv_row_stride, dkv_img_stride, Lq, LqP, Lk, N, H, head_dim, scale, workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int mpf_attn_backward_kv_aux(const void* q, const void* k, const void* v, int64_t kv_row_stride, int64_t kv_img_stride,
                                         const void* kT, const void* qT, const void* dout, const void* doutT, const uint8_t* mask,
                                         int mask_per_image, const float* lse, const float* delta, void* dq, void* dk, void* dv,
                                         int64_t dkv_row_stride, int64_t dkv_img_stride, int Lq, int LqP, int Lk, int N, int H,
-                                        int head_dim, float scale, void* workspace, size_t workspace_bytes, const void* aux,
-                                        void* stream)
+                                        int head_dim, float scale, void* workspace, size_t workspace_bytes, const void* aux, void* stream)
 {
-    if (!q || !k || !v || !kT || !qT || !dout || !doutT || !lse || !delta || !dq || !dk || !dv || !workspace)
-        return mpf::fail(MPF_E_NULL, "attn_backward: NULL buffer");
-    if (LqP != (Lq + 31) / 32 * 32) return mpf::fail(MPF_E_SHAPE, "attn_backward: LqP must be Lq rounded up to a multiple of 32");
-    if (kv_row_stride < 0 || kv_img_stride < 0 || dkv_row_stride < 0 || dkv_img_stride < 0 ||
-        (kv_row_stride | kv_img_stride | dkv_row_stride | dkv_img_stride) % 8 ||
-        (((uintptr_t)k | (uintptr_t)v | (uintptr_t)dk | (uintptr_t)dv) & 15))
-        return mpf::fail(MPF_E_SHAPE, "attn_backward: K / V strides must be non-negative multiples of 8 elements, buffers 16-byte aligned");
-    if (head_dim != kHD) return mpf::fail(MPF_E_SHAPE, "attn_backward: head_dim must be 32");
-    if (Lq <= 0 || Lk <= 0 || N <= 0 || H <= 0 || LqP < Lq || (LqP & 31)) return mpf::fail(MPF_E_SHAPE, "attn_backward: bad sizes");
-    const int mimgs = mask ? (mask_per_image ? N : 1) : 0;
-    if (workspace_bytes < attn_part_bytes(Lq, Lk, N, H) + (aux ? 0 : mpf_attn_bwd_aux_bytes(Lq, Lk, N, H, mimgs)))
-        return mpf::fail(MPF_E_SHAPE, "attn_backward: workspace too small");
-    if ((uintptr_t)workspace & 15 || (aux && ((uintptr_t)aux & 15))) return mpf::fail(MPF_E_SHAPE, "attn_backward: workspace / aux must be 16-byte aligned");
+    const AttnProblem pr{Lq, LqP, Lk, N, H, AttnProblem::images(mask, mask_per_image, N)};
+    if (int e = mpf::attn_check("attn_backward", pr, {q, k, v, kT, qT, dout, doutT, lse, delta, dq, dk, dv, workspace},
+                                {kv_row_stride, kv_img_stride, dkv_row_stride, dkv_img_stride}, {k, v, dk, dv},
+                                "K / V strides must be non-negative multiples of 8 elements, buffers 16-byte aligned", head_dim, workspace_bytes,
+                                aux ? 0 : pr.aux_bytes(), {workspace, aux}))
+        return e;
     hipStream_t st = (hipStream_t)stream;
-    // aux operands of the dK / dV kernel: (lse, delta) pairs padded to LqP | the mask transposed (mpf_attn_bwd_prep_aux makes
-    // them in the launch that also makes qT / doT / delta; without aux they are made here, in the workspace)
-    const char* auxp = (const char*)aux;
-    if (!aux) {
-        char* a = (char*)workspace + attn_part_bytes(Lq, Lk, N, H);
-        const int ld_blocks = (N * H * Lq + 255) / 256, mq = (LqP + 63) / 64, mk = (Lk + 63) / 64;
-        mpf::set_kernel("attn_bwd_aux_kernel");
-        hipLaunchKernelGGL(attn_bwd_aux_kernel, dim3(ld_blocks + mimgs * mq * mk), dim3(256), 0, st, lse, delta, mask, (float2*)a,
-                           (uint8_t*)(a + attn_ld2_bytes(LqP, N, H)), Lq, LqP, Lk, N * H, ld_blocks, mq, mk);
-        auxp = a;
-    }
+    const AttnKV kv(kv_row_stride, kv_img_stride, N, pr.E()), dkv(dkv_row_stride, dkv_img_stride, N, pr.E());
+    const AttnSplit sp = mpf::attn_split(pr);
+    // aux operands of the dK / dV kernel: from mpf_attn_bwd_prep_aux, or made here in the workspace behind the partials
+    void* made = aux ? nullptr : (char*)workspace + pr.part_bytes(sp.wg_splits);
+    if (made) { launch_prep(pr, nullptr, nullptr, nullptr, lse, delta, mask, nullptr, nullptr, nullptr, made, st); aux = made; }
     AttnBwdParams p;
-    p.ld2 = (const float2*)auxp;
-    p.maskT = mask ? (const uint8_t*)(auxp + attn_ld2_bytes(LqP, N, H)) : nullptr;
-    p.maskT_stride_n = mask_per_image ? (int64_t)Lk * LqP : 0;
-    p.q = (const __hip_bfloat16*)q; p.k = (const __hip_bfloat16*)k; p.v = (const __hip_bfloat16*)v;
-    p.kT = (const __hip_bfloat16*)kT; p.qT = (const __hip_bfloat16*)qT;
-    p.dout = (const __hip_bfloat16*)dout; p.doT = (const __hip_bfloat16*)doutT;
-    p.mask = mask; p.mask_stride_n = mask_per_image ? (int64_t)Lq * Lk : 0;
-    p.lse = lse; p.delta = delta;
-    p.dk = (__hip_bfloat16*)dk; p.dv = (__hip_bfloat16*)dv; p.part_dq = (float*)workspace;
-    p.Lq = Lq; p.LqP = LqP; p.Lk = Lk; p.N = N; p.H = H; p.E = H * kHD; p.scale = scale;
-    p.kv_row = kv_row_stride ? kv_row_stride : (int64_t)N * p.E;
-    p.kv_img = kv_row_stride ? kv_img_stride : p.E;
-    p.dkv_row = dkv_row_stride ? dkv_row_stride : (int64_t)N * p.E;
-    p.dkv_img = dkv_row_stride ? dkv_img_stride : p.E;
-    const AttnSplit sp = attn_split(Lq, Lk, N, H);
-    p.splits = sp.wg_splits; p.nw = sp.nw; p.keys_per_split = sp.keys_per_wave;
-    p.dq = (__hip_bfloat16*)dq;
-    const double bytes = 2.0 * (4.0 * Lk * N * p.E + 4.0 * Lq * N * p.E) + (mask ? 2.0 * N * Lq * Lk : 0.0);
+    p.ld2 = (const float2*)aux; p.maskT = mask ? pr.maskT_at(aux) : nullptr; p.maskT_stride_n = mask_per_image ? (int64_t)Lk * LqP : 0;
+    p.q = bf(q); p.k = bf(k); p.v = bf(v); p.kT = bf(kT); p.qT = bf(qT); p.dout = bf(dout); p.doT = bf(doutT);
+    p.mask = mask; p.mask_stride_n = mask_per_image ? (int64_t)Lq * Lk : 0; p.lse = lse; p.delta = delta;
+    p.dq = bf(dq); p.dk = bf(dk); p.dv = bf(dv); p.part_dq = (float*)workspace;
+    p.Lq = Lq; p.LqP = LqP; p.Lk = Lk; p.N = N; p.H = H; p.E = pr.E(); p.scale = scale;
+    p.kv_row = kv.row; p.kv_img = kv.img; p.dkv_row = dkv.row; p.dkv_img = dkv.img;
+    sp.fill(p);              // (before the dK / dV launch: both kernels take the whole record)
     mpf::prof_begin(st);
     mpf::set_kernel("attn_bwd_kv_kernel");
-    if (mask) hipLaunchKernelGGL(attn_bwd_kv_kernel<true>, dim3((Lk + 31) / 32, H, N), dim3(64), 0, st, p);
-    else hipLaunchKernelGGL(attn_bwd_kv_kernel<false>, dim3((Lk + 31) / 32, H, N), dim3(64), 0, st, p);
-    mpf::prof_end("attn_bwd_kv_kernel", st, bytes * 0.5, 8.0 * Lq * (double)Lk * p.E * N);   // S, dP, dV, dK
-    constexpr int QS = 2;
-    const int qtiles = (Lq + 16 * QS - 1) / (16 * QS);
-    mpf::prof_begin(st);
-    mpf::set_kernel("attn_bwd_q_kernel<2>");
-    {
-        const dim3 grid(qtiles * p.splits, H, N), block(64 * p.nw);
-        const size_t lds = (size_t)p.nw * 32 * kMergePitch * sizeof(float);
-        const bool al = (Lk & 7) == 0 && ((uintptr_t)p.kT & 15) == 0 && (!mask || ((uintptr_t)mask & 7) == 0);
-        static_assert(kMaxNW * kMergeWave * sizeof(float) <= 64 * 1024, "the merge buffer fits the default dynamic-LDS limit");
-        auto launch = [&](auto kfn) -> int {
-            hipLaunchKernelGGL(kfn, grid, block, lds, st, p);
-            return 0;
-        };
-        int e;
-        if (al && mask) e = launch(attn_bwd_q_kernel<QS, true, true>);
-        else if (al) e = launch(attn_bwd_q_kernel<QS, true, false>);
-        else if (mask) e = launch(attn_bwd_q_kernel<QS, false, true>);
-        else e = launch(attn_bwd_q_kernel<QS, false, false>);
-        if (e) return e;
-    }
-    mpf::prof_end("attn_bwd_q_kernel<2>", st, bytes * 0.5, 6.0 * Lq * (double)Lk * p.E * N);  // S, dP, dQ
-    if (p.splits > 1) {
-        const int total = N * H * Lq * kHD;
-        hipLaunchKernelGGL(attn_sum_splits_kernel, dim3((total + 255) / 256), dim3(256), 0, st, p.part_dq,
-                           (__hip_bfloat16*)dq, Lq, N, H, p.E, p.splits);
-    }
+    mpf::with_bool(mask != nullptr, [&](auto MK) {
+        hipLaunchKernelGGL(attn_bwd_kv_kernel<decltype(MK)::value>, dim3(AttnProblem::round32(Lk) / 32, H, N), dim3(64), 0, st, p);
+    });
+    mpf::prof_end("attn_bwd_kv_kernel", st, pr.backward_bytes(), pr.flops(4));   // S, dP, dV, dK
+    launch_split("attn_bwd_q_kernel<2>", p, pr, 32 * kMergePitch, kT, pr.backward_bytes(), pr.flops(3), st, [](auto AL, auto MK, auto&& launch) {
+        launch(attn_bwd_q_kernel<2, decltype(AL)::value, decltype(MK)::value>);
+    });     // (flops: S, dP, dQ)
+    if (sp.wg_splits > 1)
+        hipLaunchKernelGGL(attn_sum_splits_kernel, dim3((unsigned)((pr.rows() * kHD + 255) / 256)), dim3(256), 0, st, p.part_dq, bf(dq), Lq, N, H,
+                           p.E, sp.wg_splits);
     return mpf::check(hipGetLastError(), "mpf_attn_backward");
 }
 
@@ -1043,34 +973,23 @@ extern "C" int mpf_attn_transpose2(const void* a, const void* b, void* aT, void*
     return mpf_attn_transpose2_strided(a, b, 0, 0, aT, bT, L, LP, N, E, stream);
 }
 
-extern "C" int mpf_attn_transpose2_strided(const void* a, const void* b, int64_t in_row_stride, int64_t in_img_stride, void* aT,
-                                           void* bT, int L, int LP, int N, int E, void* stream)
+extern "C" int mpf_attn_transpose2_strided(const void* a, const void* b, int64_t in_row_stride, int64_t in_img_stride, void* aT, void* bT, int L,
+                                           int LP, int N, int E, void* stream)
 {
-    if (!a || !b || !aT || !bT) return mpf::fail(MPF_E_NULL, "attn_transpose2: NULL buffer");
-    if (L <= 0 || LP < L || N <= 0 || E <= 0 || in_row_stride < 0 || in_img_stride < 0)
-        return mpf::fail(MPF_E_SHAPE, "attn_transpose2: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    const int NE = N * E;
+    if (mpf::any_null({a, b, aT, bT})) return mpf::failf(MPF_E_NULL, "attn_transpose2", "NULL buffer");
+    if (L <= 0 || LP < L || N <= 0 || E <= 0 || (in_row_stride | in_img_stride) < 0) return mpf::failf(MPF_E_SHAPE, "attn_transpose2", "bad sizes");
     mpf::set_kernel("attn_transpose2_kernel");
-    hipLaunchKernelGGL(attn_transpose2_kernel, dim3((LP + 63) / 64, (NE + 63) / 64), dim3(256), 0, st,
-                       (const __hip_bfloat16*)a, (const __hip_bfloat16*)b, (__hip_bfloat16*)aT, (__hip_bfloat16*)bT, L, LP, NE,
-                       in_row_stride ? E : 0, in_row_stride, in_img_stride);
+    hipLaunchKernelGGL(attn_transpose2_kernel, dim3((LP + 63) / 64, (N * E + 63) / 64), dim3(256), 0, (hipStream_t)stream, bf(a), bf(b), bf(aT),
+                       bf(bT), L, LP, N * E, in_row_stride ? E : 0 /* 0: dense rows of N * E columns */, in_row_stride, in_img_stride);
     return mpf::check(hipGetLastError(), "mpf_attn_transpose2");
 }
 
-extern "C" int mpf_attn_bwd_prep(const void* q, const void* dout, const void* out, void* qT, void* doT, float* delta, int Lq, int LqP,
-                                 int N, int H, void* stream)
+extern "C" int mpf_attn_bwd_prep(const void* q, const void* dout, const void* out, void* qT, void* doT, float* delta, int Lq, int LqP, int N,
+                                 int H, void* stream)
 {
-    if (!q || !dout || !out || !qT || !doT || !delta) return mpf::fail(MPF_E_NULL, "attn_bwd_prep: NULL buffer");
-    if (Lq <= 0 || LqP < Lq || N <= 0 || H <= 0) return mpf::fail(MPF_E_SHAPE, "attn_bwd_prep: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    const int NE = N * H * kHD;
-    const int tiles_x = (LqP + 63) / 64, n_tiles = tiles_x * ((NE + 63) / 64);
-    const int delta_blocks = (Lq * N * H * kHD + 255) / 256;
-    mpf::set_kernel("attn_bwd_prep_kernel");
-    hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(n_tiles + delta_blocks), dim3(256), 0, st, (const __hip_bfloat16*)q,
-                       (const __hip_bfloat16*)dout, (const __hip_bfloat16*)out, (__hip_bfloat16*)qT, (__hip_bfloat16*)doT, delta, Lq,
-                       LqP, N, H, tiles_x, n_tiles);
+    if (mpf::any_null({q, dout, out, qT, doT, delta})) return mpf::failf(MPF_E_NULL, "attn_bwd_prep", "NULL buffer");
+    if (Lq <= 0 || LqP < Lq || N <= 0 || H <= 0) return mpf::failf(MPF_E_SHAPE, "attn_bwd_prep", "bad sizes");
+    launch_prep(AttnProblem{Lq, LqP, 0, N, H, 0}, q, dout, out, nullptr, nullptr, nullptr, qT, doT, delta, nullptr, (hipStream_t)stream);
     return mpf::check(hipGetLastError(), "mpf_attn_bwd_prep");
 }
 
@@ -1078,32 +997,20 @@ extern "C" int mpf_attn_bwd_prep_aux(const void* q, const void* dout, const void
                                      int mask_per_image, int Lk, void* qT, void* doT, float* delta, void* aux, size_t aux_bytes, int Lq,
                                      int LqP, int N, int H, void* stream)
 {
-    if (!q || !dout || !out || !lse || !qT || !doT || !delta || !aux) return mpf::fail(MPF_E_NULL, "attn_bwd_prep_aux: NULL buffer");
-    if (Lq <= 0 || Lk <= 0 || LqP != (Lq + 31) / 32 * 32 || N <= 0 || H <= 0) return mpf::fail(MPF_E_SHAPE, "attn_bwd_prep_aux: bad sizes");
-    const int mimgs = mask ? (mask_per_image ? N : 1) : 0;
-    if (aux_bytes < mpf_attn_bwd_aux_bytes(Lq, Lk, N, H, mimgs) || ((uintptr_t)aux & 15))
-        return mpf::fail(MPF_E_SHAPE, "attn_bwd_prep_aux: aux too small or not 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int NE = N * H * kHD;
-    const int tiles_x = (LqP + 63) / 64, n_tiles = tiles_x * ((NE + 63) / 64);
-    const int delta_blocks = (Lq * N * H * kHD + 255) / 256;
-    const int mq = (LqP + 63) / 64, mk = (Lk + 63) / 64;
-    mpf::set_kernel("attn_bwd_prep_aux_kernel");
-    hipLaunchKernelGGL(attn_bwd_prep_aux_kernel, dim3(n_tiles + delta_blocks + mimgs * mq * mk), dim3(256), 0, st,
-                       (const __hip_bfloat16*)q, (const __hip_bfloat16*)dout, (const __hip_bfloat16*)out, lse, mask, (__hip_bfloat16*)qT,
-                       (__hip_bfloat16*)doT, delta, (float2*)aux, (uint8_t*)aux + attn_ld2_bytes(LqP, N, H), Lq, LqP, Lk, N, H, tiles_x,
-                       n_tiles, delta_blocks, mq, mk);
+    const AttnProblem pr{Lq, LqP, Lk, N, H, AttnProblem::images(mask, mask_per_image, N)};
+    if (mpf::any_null({q, dout, out, lse, qT, doT, delta, aux})) return mpf::failf(MPF_E_NULL, "attn_bwd_prep_aux", "NULL buffer");
+    if (!pr.sizes_ok() || LqP != AttnProblem::round32(Lq)) return mpf::failf(MPF_E_SHAPE, "attn_bwd_prep_aux", "bad sizes");
+    if (aux_bytes < pr.aux_bytes() || (size_t)aux % 16) return mpf::failf(MPF_E_SHAPE, "attn_bwd_prep_aux", "aux too small or not 16-byte aligned");
+    launch_prep(pr, q, dout, out, lse, nullptr, mask, qT, doT, delta, aux, (hipStream_t)stream);
     return mpf::check(hipGetLastError(), "mpf_attn_bwd_prep_aux");
 }
 
 extern "C" int mpf_attn_delta(const void* dout, const void* out, float* delta, int Lq, int N, int H, void* stream)
 {
-    if (!dout || !out || !delta) return mpf::fail(MPF_E_NULL, "attn_delta: NULL buffer");
-    if (Lq <= 0 || N <= 0 || H <= 0) return mpf::fail(MPF_E_SHAPE, "attn_delta: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    const int total = Lq * N * H * kHD;
+    if (mpf::any_null({dout, out, delta})) return mpf::failf(MPF_E_NULL, "attn_delta", "NULL buffer");
+    if (Lq <= 0 || N <= 0 || H <= 0) return mpf::failf(MPF_E_SHAPE, "attn_delta", "bad sizes");
     mpf::set_kernel("attn_delta_kernel");
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (const __hip_bfloat16*)dout,
-                       (const __hip_bfloat16*)out, delta, Lq, N, H);
+    hipLaunchKernelGGL(attn_delta_kernel, dim3(AttnProblem{Lq, Lq, 0, N, H, 0}.delta_blocks()), dim3(256), 0, (hipStream_t)stream, bf(dout),
+                       bf(out), delta, Lq, N, H);
     return mpf::check(hipGetLastError(), "mpf_attn_delta");
 }

@@ -21,6 +21,12 @@ int fail(int code, const char* msg)
     return code;
 }
 
+int failf(int code, const char* who, const char* what)
+{
+    snprintf(t_err, sizeof(t_err), "%s: %s", who, what);
+    return code;
+}
+
 int check(hipError_t err, const char* where)
 {
     if (err == hipSuccess) return 0;

@@ -4,12 +4,24 @@
 #include <string.h>
 
 #include <atomic>
+#include <initializer_list>
+#include <type_traits>
 
 #include "../../include/mpformer_hip.h"
 
 namespace mpf {
-// record an argument error (negative code) and return it
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// f(std::integral_constant<int, v>{}) for the v of Vs... that equals `v` (as with_int of seg_infer.hip)
+template <int... Vs, class F>
+void with_int_of(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+template <class F>
+void with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// record an argument error (negative code) and return it; failf: with the text "<who>: <what>"
 int fail(int code, const char* msg);
+int failf(int code, const char* who, const char* what);
+inline bool any_null(std::initializer_list<const void*> ps) { bool null = false; for (const void* p : ps) null |= !p; return null; }
 // map a hipError_t to the ABI return value (0 on success), recording the message
 int check(hipError_t err, const char* where);
 void set_kernel(const char* name);

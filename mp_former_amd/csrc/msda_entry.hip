@@ -4,10 +4,6 @@
 //   route    msda_forward_route / msda_backward_route: pure functions of the problem, the variant option, the operands present, the plan
 //   launch   the launcher of the chosen family, in msda.hip (tiled, generic, prep), msda_block.hip (blocked) or msda_bwd_binned.hip
 // DESIGN.md ("MSDA host layer") has the table entry x condition -> kernel sequence.
-#include <stdio.h>
-
-#include <initializer_list>
-
 #include "msda_host.h"
 
 namespace {
@@ -16,10 +12,8 @@ namespace {
 // per head only and say so in the dtype slot; their size text is their own.
 int msda_check(const char* who, const MsdaProblem& p, bool ws, std::initializer_list<const void*> required)
 {
-    char text[96];
-    const auto failf = [&](int code, const char* what) { snprintf(text, sizeof(text), "%s: %s", who, what); return mpf::fail(code, text); };
-    for (const void* q : required)
-        if (!q) return failf(MPF_E_NULL, "NULL buffer");
+    const auto failf = [&](int code, const char* what) { return mpf::failf(code, who, what); };
+    if (mpf::any_null(required)) return failf(MPF_E_NULL, "NULL buffer");
     const bool sizes_ok = p.N > 0 && p.S > 0 && p.M > 0 && p.D > 0 && p.L > 0 && p.Lq > 0 && p.P > 0;
     if (ws) {
         if (p.dtype != MPF_F32 || p.D != 32) return failf(MPF_E_DTYPE, "fp32 with 32 channels per head only");

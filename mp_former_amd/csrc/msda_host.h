@@ -2,8 +2,6 @@
 // fills one MsdaProblem and one MsdaOperands, checks them (msda_check), asks for a route (msda_forward_route /
 // msda_backward_route) and calls the launcher of that route in msda.hip, msda_block.hip or msda_bwd_binned.hip.
 #pragma once
-#include <type_traits>
-
 #include "mpf_common.h"
 
 struct MsdaProblem {
@@ -66,14 +64,6 @@ struct MsdaDevPlan {
 };
 
 namespace mpf {
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// f(std::integral_constant<int, v>{}) for the v of Vs... that equals `v` (as with_int of seg_infer.hip)
-template <int... Vs, class F>
-void with_int_of(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
-template <class F>
-void with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
-
 // msda.hip: first-generation kernels.  V = 4, 2, 1: msda_*_tiled_f32<32, V>; V = 0: msda_*_generic<T>
 int msda_fwd_variant();
 int msda_bwd_variant();
