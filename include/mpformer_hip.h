@@ -1515,6 +1515,35 @@ int mpf_seg_bits_rle_count(const uint64_t* bits, int M, int H, int W, int64_t* o
 int mpf_seg_bits_rle_write(const uint64_t* bits, const void* workspace, size_t workspace_bytes, int M, int H, int W,
                            const int64_t* offsets, int64_t total, uint32_t* pos, uint32_t* counts, void* stream);
 
+/*
+ * Shifted-window attention core of the Swin backbone (bf16 MFMA tiles; head_dim 32): per (image, window, head)
+ *   out = softmax(scale * q k^T + table[index(i, j), head] + shift_mask(i, j)) v
+ * — WindowAttention.forward between its qkv and proj Linears (mask2former/modeling/backbone/swin.py:131-171) together with the
+ * roll, window_partition, window_reverse and roll back of SwinTransformerBlock.forward (:235-295) and the attention mask of
+ * BasicLayer.forward (:413-440), none of which is materialised.
+ *   qkv    [B, Hp, Wp, 3 * heads * 32] bf16, dense: the qkv Linear on the padded, UN-rolled map, channels as the reference's
+ *          reshape(B_, N, 3, heads, 32).  Padding is the caller's (a padded token carries the Linear's bias).
+ *   table  [(2 ws - 1)^2, heads] f32: relative_position_bias_table, read in place; the index (:111-120) is computed.
+ *   out    [B, Hp, Wp, heads * 32] bf16 in un-rolled coordinates.
+ *   shift  the token at rolled position (r, c) lives at ((r + shift) mod Hp, (c + shift) mod Wp); with shift > 0, -100.0 is added
+ *          where the rolled regions (3 * rh + rc; rh = 0 if r < Hp - ws, 1 if r < Hp - shift, else 2; rc likewise) of the two
+ *          tokens differ; shift == 0: no mask.
+ * scale is applied to the fp32 product; the softmax is fp32 over the whole row; P is rounded to bf16 once for P v.
+ * Backward: dqkv [B, Hp, Wp, 3 * heads * 32] bf16 (every element written once) and dtable [(2 ws - 1)^2, heads] f32 (overwritten)
+ * from qkv, table, the forward's out and dout [B, Hp, Wp, heads * 32] bf16; lse is recomputed.  No atomics: two runs give the same
+ * bits.  workspace: mpf_win_attn_workspace_bytes(B, Hp, Wp, heads, ws) bytes (0 for unsupported sizes): per-workgroup partials of
+ * the table gradient, added in a fixed order by a second launch of the same call.
+ * Checked before any HIP call, in this order: NULL buffer (MPF_E_NULL); ws outside 2 .. 12, head_dim != 32, shift outside
+ * 0 .. ws - 1, non-positive sizes, Hp or Wp not a multiple of ws (MPF_E_SHAPE); qkv of 2^31 elements or more (MPF_E_TOO_LARGE);
+ * a buffer not 16-byte aligned, a workspace too small (MPF_E_SHAPE).
+ */
+size_t mpf_win_attn_workspace_bytes(int B, int Hp, int Wp, int heads, int ws);
+int mpf_win_attn_forward(const void* qkv, const float* table, void* out, int B, int Hp, int Wp, int heads, int head_dim, int ws,
+                         int shift, float scale, void* stream);
+int mpf_win_attn_backward(const void* qkv, const float* table, const void* out, const void* dout, void* dqkv, float* dtable, int B,
+                          int Hp, int Wp, int heads, int head_dim, int ws, int shift, float scale, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,9 @@ SIGNATURES = {
     "mpf_attn_bwd_prep_aux": (_c_int, [_c_vp] * 5 + [_c_int] * 2 + [_c_vp] * 4 + [ctypes.c_size_t] + [_c_int] * 4 + [_c_vp]),
     "mpf_attn_delta": (_c_int, [_c_vp] * 3 + [_c_int] * 3 + [_c_vp]),
     "mpf_attn_bwd_prep": (_c_int, [_c_vp] * 6 + [_c_int] * 4 + [_c_vp]),
+    "mpf_win_attn_workspace_bytes": (ctypes.c_size_t, [_c_int] * 5),
+    "mpf_win_attn_forward": (_c_int, [_c_vp] * 3 + [_c_int] * 7 + [ctypes.c_float, _c_vp]),
+    "mpf_win_attn_backward": (_c_int, [_c_vp] * 6 + [_c_int] * 7 + [ctypes.c_float, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_gemm3_split": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "mpf_gemm3_tn": (_c_int, [_c_vp, ctypes.c_int64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_vp, ctypes.c_int64,
                            _c_vp, ctypes.c_int64, _c_vp, ctypes.c_int64, _c_int, _c_int, _c_int, _c_int, _c_vp]),

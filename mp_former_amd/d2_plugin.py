@@ -19,6 +19,10 @@ neither: ``registered()`` is then False and tests/test_host_logic_cpu.py drives 
 detectron2's ``Registry`` interface).  The construction convention of the registries — ``cls(cfg, ...)`` resolved through
 ``cls.from_config`` — is detectron2's ``@configurable``; where detectron2 is absent the same call convention is provided by
 ``_configurable`` below, so the registered classes behave identically in both worlds.
+
+The backbone is selected the same way from detectron2's ``BACKBONE_REGISTRY`` (``MODEL.BACKBONE.NAME``): ``register_backbone()``
+adds ``D2SwinTransformerHIP`` (swin.py, native shifted-window attention) there; the override is
+``MODEL.BACKBONE.NAME D2SwinTransformerHIP``.
 """
 import functools
 
@@ -139,6 +143,70 @@ def register_video(transformer_decoder_registry=None, configurable=None):
     cls = make_video_class(configurable)
     transformer_decoder_registry.register(cls)
     return cls
+
+
+SWIN_BACKBONE_NAME = "D2SwinTransformerHIP"
+
+
+class _ShapeSpec:
+    """channels and stride of an output map, where detectron2's ShapeSpec is not at hand"""
+
+    def __init__(self, channels=None, height=None, width=None, stride=None):
+        self.channels, self.height, self.width, self.stride = channels, height, width, stride
+
+
+def make_backbone_class(backbone_base=None, shape_spec=None):
+    """``D2SwinTransformerHIP``: swin.SwinTransformer built from ``cfg.MODEL.SWIN.*`` as the reference's D2SwinTransformer is
+    (mask2former/modeling/backbone/swin.py:688-741), with ``output_shape()`` and ``size_divisibility``.  backbone_base:
+    detectron2's ``Backbone`` (a second base class, so that detectron2 accepts the instance); shape_spec: its ``ShapeSpec``."""
+    from . import swin as _S
+    spec = shape_spec or _ShapeSpec
+    bases = (_S.SwinTransformer,) + ((backbone_base,) if backbone_base is not None else ())
+
+    class D2SwinTransformerHIP(*bases):
+        def __init__(self, cfg, input_shape=None):
+            c = cfg.MODEL.SWIN
+            super().__init__(c.PRETRAIN_IMG_SIZE, c.PATCH_SIZE, 3, c.EMBED_DIM, c.DEPTHS, c.NUM_HEADS, c.WINDOW_SIZE, c.MLP_RATIO,
+                             c.QKV_BIAS, c.QK_SCALE, c.DROP_RATE, c.ATTN_DROP_RATE, c.DROP_PATH_RATE, _S.nn.LayerNorm, c.APE,
+                             c.PATCH_NORM, use_checkpoint=c.USE_CHECKPOINT)
+            self._out_features = list(c.OUT_FEATURES)
+            self._out_feature_strides = {f"res{i + 2}": 4 * 2 ** i for i in range(4)}
+            self._out_feature_channels = {f"res{i + 2}": self.num_features[i] for i in range(4)}
+
+        def forward(self, x):
+            assert x.dim() == 4, f"SwinTransformer takes an input of shape (N, C, H, W). Got {x.shape} instead!"
+            y = super().forward(x)
+            return {k: v for k, v in y.items() if k in self._out_features}
+
+        def output_shape(self):
+            return {n: spec(channels=self._out_feature_channels[n], stride=self._out_feature_strides[n]) for n in self._out_features}
+
+        @property
+        def size_divisibility(self):
+            return 32
+
+    D2SwinTransformerHIP.__name__ = D2SwinTransformerHIP.__qualname__ = SWIN_BACKBONE_NAME
+    return D2SwinTransformerHIP
+
+
+def register_backbone(backbone_registry=None, backbone_base=None, shape_spec=None):
+    """Register ``D2SwinTransformerHIP`` — selected by ``MODEL.BACKBONE.NAME D2SwinTransformerHIP``.  Without a registry:
+    detectron2's ``BACKBONE_REGISTRY``, ``Backbone`` and ``ShapeSpec`` (returns False, registering nothing, when detectron2 is
+    missing).  With a registry: any object with detectron2's ``Registry`` interface.  Returns the class (truthy) on success.
+    Independent of ``register()`` and ``register_video()``."""
+    if backbone_registry is None:
+        try:
+            from detectron2.layers import ShapeSpec
+            from detectron2.modeling import BACKBONE_REGISTRY, Backbone
+        except ImportError:
+            return False
+        backbone_registry, backbone_base, shape_spec = BACKBONE_REGISTRY, backbone_base or Backbone, shape_spec or ShapeSpec
+    cls = make_backbone_class(backbone_base, shape_spec)
+    backbone_registry.register(cls)
+    return cls
+
+
+register_backbone()     # (as register(): at import, a no-op without detectron2)
 
 
 def install_native_video_decoder(model):
