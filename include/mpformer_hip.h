@@ -729,6 +729,38 @@ int mpf_next_attn_mask(const MpfNextMask* m, void* stream);
 int mpf_decoder_layer_backward(const MpfDecoderLayer* layer, const MpfDecoderLayerGrad* grad, void* stream);
 
 /*
+ * Learned query positions (the clip decoder: video_mask2former_transformer_decoder.py:45-47, :104-106, :396), csrc/query_pos.hip.
+ * Rows are sequence-first, r = q * N + n, 256 channels; every buffer 16-byte aligned.
+ *   mpf_qpos_operand_forward: out[r, c] = bf16(x[r, c] + qpos[r / N, c]) — x fp32 [Q, N, 256], qpos fp32 [Q, 256], out bf16
+ *     [Q, N, 256]; the add in fp32, ONE round-to-nearest-even: the operand (x + query_pos) has under autocast.
+ *   mpf_qpos_backward: d_x0[r, c] += float(dxq0[r, c]) (fp32 [Q, N, 256], in-out) and
+ *     d_qpos[q, c] = sum over n = 0 .. N - 1, in that order, of (float(dxq0[q N + n, c]) + float(dxq1[q N + n, c])) in fp32
+ *     (fp32 [Q, 256], fully written); dxq0 / dxq1 bf16 [Q, N, 256].  One writer per element, no atomics: the same bits every run.
+ *
+ * The decoder layer above WITH query positions, as the clip decoder's reference composes it: the cross-attention query is
+ * projected from x0 + qpos, the self-attention query and key from x1 + qpos, its value from x1 alone.  MpfDecoderLayer and
+ * MpfDecoderLayerGrad keep their meaning; their members xb0 / d_xb0 are not used (may be NULL).  MpfDecoderLayerPos adds the
+ * position operand, the two bf16 operands the backward reads again, and the position gradient.  In the backward the gradients
+ * of both operands re-enter the fp32 chain of the residual stream (dxq1 before the cross block's LayerNorm backward, dxq0 into
+ * d_x0), the weight gradients of ca_wq and sa_wq | sa_wk contract with xq0 / xq1, sa_wv with xb1.  One host sequence serves both
+ * forms: without the operand it is the launch sequence of the calls above.  The NULL / shape checks of both structs precede
+ * every HIP call.  Scratch: mpf_decoder_layer_pos_scratch_bytes (the backward holds the two operand gradients and one more
+ * transposed copy); attn_ws as above.
+ */
+typedef struct MpfDecoderLayerPos {
+    const float* qpos;      /* [Qt, E] fp32, the same for every image */
+    void *xq0, *xq1;        /* [R, E] bf16: bf16(x0 + qpos), bf16(x1 + qpos); written by forward, read by backward */
+    float* d_qpos;          /* [Qt, E] fp32, written by backward (NULL in a forward call) */
+} MpfDecoderLayerPos;
+int mpf_qpos_operand_forward(const float* x, const float* qpos, void* out, int Q, int N, void* stream);
+int mpf_qpos_backward(const void* dxq0, const void* dxq1, float* d_x0, float* d_qpos, int Q, int N, void* stream);
+uint64_t mpf_decoder_layer_pos_struct_bytes(void); /* sizeof(MpfDecoderLayerPos) */
+uint64_t mpf_decoder_layer_pos_scratch_bytes(int Qt, int N, int H, int S, int ffn_dim, int backward);
+int mpf_decoder_layer_pos_forward(const MpfDecoderLayer* layer, const MpfDecoderLayerPos* pos, void* stream);
+int mpf_decoder_layer_pos_backward(const MpfDecoderLayer* layer, const MpfDecoderLayerPos* pos, const MpfDecoderLayerGrad* grad,
+                                   void* stream);
+
+/*
  * dst_i[c, j] = cast(src_i[c, j] * scale_i[c]) for a list of tensors in ONE launch (the FrozenBatchNorm
  * scale folded into every convolution weight of the bench backbone — detectron2 FrozenBatchNorm2d under
  * configs/coco/instance-segmentation/Base-COCO-InstanceSegmentation.yaml:2-15 — and the matching

@@ -121,6 +121,12 @@ SIGNATURES = {
     "mpf_lin256_res_ln_forward": (_c_int, [_c_vp] * 11 + [_c_int, ctypes.c_float, _c_vp]),
     "mpf_ln256_mlp3_forward": (_c_int, [_c_vp] * 10 + [_c_int, ctypes.c_float, _c_vp]),
     "mpf_decoder_layer_backward": (_c_int, [_c_vp, _c_vp, _c_vp]),
+    "mpf_qpos_operand_forward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp]),
+    "mpf_qpos_backward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp]),
+    "mpf_decoder_layer_pos_struct_bytes": (ctypes.c_uint64, []),
+    "mpf_decoder_layer_pos_scratch_bytes": (ctypes.c_uint64, [_c_int] * 6),
+    "mpf_decoder_layer_pos_forward": (_c_int, [_c_vp, _c_vp, _c_vp]),
+    "mpf_decoder_layer_pos_backward": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp]),
     "mpf_pool_features": (_c_int, [_c_vp, _c_int, _c_vp] + [_c_int] * 6 + [_c_vp]),
     "mpf_pool_features_cl": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_mask_head_bits": (_c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp, _c_int, _c_vp, _c_vp] + [_c_int] * 3 + [_c_vp]),

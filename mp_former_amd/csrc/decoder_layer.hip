@@ -4,6 +4,10 @@
 // elementwise.hip); what this file removes is the per-kernel cost of a Python autograd node (~20 us of
 // host time against 3-6 us of GPU time per launch), which made the decoder launch-bound.
 // Reference: mask2former_transformer_decoder.py:1784-1800 (the layer loop), :42-52, :100-112, :165-169.
+// The same sequence serves the clip decoder's layer, which adds learned query positions to the query of the cross-attention
+// and to the query and key of the self-attention (video_mask2former_transformer_decoder.py:415, :421; MpfDecoderLayerPos, the
+// mpf_decoder_layer_pos_* entry points): layer_forward / layer_backward take the position record or nullptr, and without it
+// issue exactly the image layer's launches.  The two position kernels are in query_pos.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -12,7 +16,7 @@
 namespace {
 
 constexpr int kE = 256;
-constexpr int kMaxDw = 8;        // weight-gradient problems per layer (6 with packed in-projection gradients, 8 without)
+constexpr int kMaxDw = 8;        // weight-gradient problems per layer (6 with packed in-projection gradients — 7 with query positions — 8 without)
 
 struct Carve {
     char* p;
@@ -55,13 +59,14 @@ struct BwdScratch {
     float *ds_a, *ds_b, *delta;
     void* aux;                   // aux operands of the attention dK / dV kernel (mpf_attn_bwd_aux_bytes: the larger of the two attentions)
     size_t aux_bytes;
-    uint16_t* tbuf;              // transposed [C, Rp] copies of the weight-gradient operands (2 F + 13 * 256 columns)
+    uint16_t* tbuf;              // transposed [C, Rp] copies of the weight-gradient operands (2 F + 13 * 256 columns; 14 with positions)
     void* ln_ws;                 // per-workgroup partial sums of the three LayerNorms' parameter gradients, ln_ws_bytes each
     size_t ln_ws_bytes;
+    void *dxq0, *dxq1;           // with query positions: the gradients of the operands bf16(x0 + qpos), bf16(x1 + qpos)
     size_t bytes;
 };
 
-BwdScratch bwd_scratch(void* base, int Qt, int N, int H, int F, int S)
+BwdScratch bwd_scratch(void* base, int Qt, int N, int H, int F, int S, bool pos)
 {
     Carve c(base);
     BwdScratch b;
@@ -87,21 +92,26 @@ BwdScratch bwd_scratch(void* base, int Qt, int N, int H, int F, int S)
         b.aux_bytes = ca > sa ? ca : sa;
         b.aux = c.take<char>(b.aux_bytes);
     }
-    b.tbuf = c.take<uint16_t>((size_t)(2 * F + 13 * kE) * ((R + 31) / 32 * 32));
+    b.tbuf = c.take<uint16_t>((size_t)(2 * F + (pos ? 14 : 13) * kE) * ((R + 31) / 32 * 32));
     b.ln_ws_bytes = (mpf_res_ln256_backward_workspace_bytes((int)R) + 255) & ~size_t(255);
     b.ln_ws = c.take<char>(3 * b.ln_ws_bytes);
+    b.dxq0 = pos ? c.take<uint16_t>(R * kE) : nullptr;       // (behind everything else: the layout without positions is unchanged)
+    b.dxq1 = pos ? c.take<uint16_t>(R * kE) : nullptr;
     b.bytes = c.used;
     return b;
 }
 
-int check_layer(const MpfDecoderLayer* L, const char* who)
+// P != nullptr: the layer takes query positions (the record is checked here too); xb0 is then not read
+int check_layer(const MpfDecoderLayer* L, const char* who, const MpfDecoderLayerPos* P = nullptr, bool backward = false)
 {
     if (!L) return mpf::fail(MPF_E_NULL, who);
+    if (P && (!P->qpos || !P->xq0 || !P->xq1 || (backward && !P->d_qpos)))
+        return mpf::fail(MPF_E_NULL, "decoder_layer: NULL buffer in MpfDecoderLayerPos");
     if (L->Qt <= 0 || L->N <= 0 || L->S <= 0 || L->ffn_dim <= 0 || L->H * 32 != kE || L->ffn_dim % 32)
         return mpf::fail(MPF_E_SHAPE, "decoder_layer: needs H * 32 == 256 channels, positive sizes, ffn_dim % 32 == 0");
     const void* need[] = {L->ca_wq, L->ca_bq, L->ca_wo, L->ca_bo, L->ca_gamma, L->ca_beta, L->sa_wq, L->sa_bq, L->sa_wk, L->sa_bk,
                           L->sa_wv, L->sa_bv, L->sa_wo, L->sa_bo, L->sa_gamma, L->sa_beta, L->ff_w1, L->ff_b1, L->ff_w2, L->ff_b2,
-                          L->ff_gamma, L->ff_beta, L->x0, L->xb0, L->k_c, L->v_c, L->mask_c, L->q_c, L->kT_c, L->o_c, L->lse_c,
+                          L->ff_gamma, L->ff_beta, L->x0, P ? L->x0 : L->xb0, L->k_c, L->v_c, L->mask_c, L->q_c, L->kT_c, L->o_c, L->lse_c,
                           L->s1, L->mean1, L->rstd1, L->xb1, L->q_s, L->k_s, L->v_s, L->kT_s, L->o_s, L->lse_s, L->s2, L->mean2,
                           L->rstd2, L->xb2, L->h, L->s3, L->mean3, L->rstd3, L->scratch, L->attn_ws};
     for (const void* q : need)
@@ -182,12 +192,25 @@ extern "C" uint64_t mpf_decoder_layer_struct_bytes(int which)
 extern "C" uint64_t mpf_decoder_layer_scratch_bytes(int Qt, int N, int H, int S, int ffn_dim, int backward)
 {
     if (Qt <= 0 || N <= 0 || H <= 0 || S <= 0 || ffn_dim <= 0) return 0;
-    return backward ? bwd_scratch(nullptr, Qt, N, H, ffn_dim, S).bytes : fwd_scratch(nullptr, Qt, N, S).bytes;
+    return backward ? bwd_scratch(nullptr, Qt, N, H, ffn_dim, S, false).bytes : fwd_scratch(nullptr, Qt, N, S).bytes;
 }
 
-extern "C" int mpf_decoder_layer_forward(const MpfDecoderLayer* L, void* st)
+extern "C" uint64_t mpf_decoder_layer_pos_struct_bytes(void) { return sizeof(MpfDecoderLayerPos); }
+
+extern "C" uint64_t mpf_decoder_layer_pos_scratch_bytes(int Qt, int N, int H, int S, int ffn_dim, int backward)
 {
-    MPF_TRY(check_layer(L, "decoder_layer_forward: NULL layer"));
+    if (Qt <= 0 || N <= 0 || H <= 0 || S <= 0 || ffn_dim <= 0) return 0;
+    return backward ? bwd_scratch(nullptr, Qt, N, H, ffn_dim, S, true).bytes : fwd_scratch(nullptr, Qt, N, S).bytes;
+}
+
+namespace {
+
+// The forward of both forms.  P == nullptr: the image decoder's layer (query, key and value operands are the stream's bf16
+// copies xb0 / xb1); P != nullptr: query positions (video_mask2former_transformer_decoder.py:415, :421) — the cross-attention
+// query from xq0 = bf16(x0 + qpos), the self-attention query and key from xq1 = bf16(x1 + qpos), its value from xb1.
+int layer_forward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, void* st)
+{
+    MPF_TRY(check_layer(L, "decoder_layer_forward: NULL layer", P, false));
     if (!L->x3 && !L->xb3) return mpf::fail(MPF_E_NULL, "decoder_layer_forward: no output buffer");
     const int Qt = L->Qt, N = L->N, H = L->H, S = L->S, F = L->ffn_dim, R = Qt * N;
     if (L->scratch_bytes < fwd_scratch(nullptr, Qt, N, S).bytes)
@@ -195,7 +218,8 @@ extern "C" int mpf_decoder_layer_forward(const MpfDecoderLayer* L, void* st)
     const FwdScratch f = fwd_scratch(L->scratch, Qt, N, S);
     const float scale = 0.17677669529663687f;       // 1 / sqrt(32)
     // cross-attention (:1784-1789) + post-norm
-    MPF_TRY(lin_fwd(L->xb0, L->ca_wq, L->ca_bq, L->q_c, R, kE, kE, 0, st));
+    if (P) MPF_TRY(mpf_qpos_operand_forward(L->x0, P->qpos, P->xq0, Qt, N, st));
+    MPF_TRY(lin_fwd(P ? P->xq0 : L->xb0, L->ca_wq, L->ca_bq, L->q_c, R, kE, kE, 0, st));
     MPF_TRY(mpf_attn_transpose2_strided(L->k_c, L->v_c, L->kv_row_stride, L->kv_img_stride, L->kT_c, f.vT_c, S, S, N, kE, st));
     MPF_TRY(mpf_attn_forward_kv(L->q_c, L->k_c, L->kv_row_stride, L->kv_img_stride, f.vT_c, L->mask_c, 1, L->o_c, L->lse_c, Qt, S, N,
                                 H, 32, scale, L->attn_ws, L->attn_ws_bytes, st));
@@ -209,12 +233,23 @@ extern "C" int mpf_decoder_layer_forward(const MpfDecoderLayer* L, void* st)
     }
     // self-attention (:1791-1795) + post-norm
     const size_t act = (size_t)R * kE * 2;
-    if (packed_weights(L) && L->k_s == at(L->q_s, act) && L->v_s == at(L->q_s, 2 * act)) {
+    const bool packed = packed_weights(L) && L->k_s == at(L->q_s, act) && L->v_s == at(L->q_s, 2 * act);
+    const void* xqk = L->xb1;                         // operand of the query and key projections
+    if (P) {
+        MPF_TRY(mpf_qpos_operand_forward(f.x1, P->qpos, P->xq1, Qt, N, st));
+        xqk = P->xq1;
+    }
+    if (packed && !P) {
         MPF_TRY(mpf_small_gemm_bf16_blocked(L->xb1, kE, 1, 0, 0, nullptr, L->sa_wq, kE, 1, L->sa_bq, nullptr, 0, L->q_s, kE, kE,
                                             (int64_t)R * kE, nullptr, R, 3 * kE, kE, 0, st));
+    } else if (packed) {
+        // [q_s | k_s] = xq1 . [Wq | Wk]^T as one blocked GEMM, v_s = xb1 . Wv^T
+        MPF_TRY(mpf_small_gemm_bf16_blocked(xqk, kE, 1, 0, 0, nullptr, L->sa_wq, kE, 1, L->sa_bq, nullptr, 0, L->q_s, kE, kE,
+                                            (int64_t)R * kE, nullptr, R, 2 * kE, kE, 0, st));
+        MPF_TRY(lin_fwd(L->xb1, L->sa_wv, L->sa_bv, L->v_s, R, kE, kE, 0, st));
     } else {
-        MPF_TRY(lin_fwd(L->xb1, L->sa_wq, L->sa_bq, L->q_s, R, kE, kE, 0, st));
-        MPF_TRY(lin_fwd(L->xb1, L->sa_wk, L->sa_bk, L->k_s, R, kE, kE, 0, st));
+        MPF_TRY(lin_fwd(xqk, L->sa_wq, L->sa_bq, L->q_s, R, kE, kE, 0, st));
+        MPF_TRY(lin_fwd(xqk, L->sa_wk, L->sa_bk, L->k_s, R, kE, kE, 0, st));
         MPF_TRY(lin_fwd(L->xb1, L->sa_wv, L->sa_bv, L->v_s, R, kE, kE, 0, st));
     }
     MPF_TRY(mpf_attn_transpose2(L->k_s, L->v_s, L->kT_s, f.vT_s, Qt, Qt, N, kE, st));
@@ -236,21 +271,23 @@ extern "C" int mpf_decoder_layer_forward(const MpfDecoderLayer* L, void* st)
     return 0;
 }
 
-extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDecoderLayerGrad* G, void* st)
+// The backward of both forms (P as in layer_forward).
+int layer_backward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, const MpfDecoderLayerGrad* G, void* st)
 {
-    MPF_TRY(check_layer(L, "decoder_layer_backward: NULL layer"));
+    MPF_TRY(check_layer(L, "decoder_layer_backward: NULL layer", P, true));
     if (!G) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: NULL grad");
     if (!G->g_x3 && !G->g_xb3) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: no upstream gradient");
-    const void* need[] = {G->d_x0, G->d_xb0, G->d_k_c, G->d_v_c, G->d_ca_wq, G->d_ca_bq, G->d_ca_wo, G->d_ca_bo, G->d_sa_wq, G->d_sa_bq,
+    const void* need[] = {G->d_x0, P ? (const void*)G->d_x0 : G->d_xb0,         // (d_xb0: no reader, no gradient with positions)
+                          G->d_k_c, G->d_v_c, G->d_ca_wq, G->d_ca_bq, G->d_ca_wo, G->d_ca_bo, G->d_sa_wq, G->d_sa_bq,
                           G->d_sa_wk, G->d_sa_bk, G->d_sa_wv, G->d_sa_bv, G->d_sa_wo, G->d_sa_bo, G->d_ff_w1, G->d_ff_b1, G->d_ff_w2,
                           G->d_ff_b2, G->d_ln};
     for (const void* q : need)
         if (!q) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: NULL buffer in MpfDecoderLayerGrad");
     const int Qt = L->Qt, N = L->N, H = L->H, S = L->S, F = L->ffn_dim, R = Qt * N;
     const int LqP = (Qt + 31) / 32 * 32;
-    if (L->scratch_bytes < bwd_scratch(nullptr, Qt, N, H, F, S).bytes)
+    if (L->scratch_bytes < bwd_scratch(nullptr, Qt, N, H, F, S, P != nullptr).bytes)
         return mpf::fail(MPF_E_SHAPE, "decoder_layer_backward: scratch too small");
-    const BwdScratch b = bwd_scratch(L->scratch, Qt, N, H, F, S);
+    const BwdScratch b = bwd_scratch(L->scratch, Qt, N, H, F, S, P != nullptr);
     const float scale = 0.17677669529663687f;
     float* dln = G->d_ln;
     // LayerNorm parameter gradients: the three backward launches leave per-workgroup partial sums, ONE launch at the end of the
@@ -279,25 +316,42 @@ extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDec
                                      b.dk_s, b.dv_s, 0, 0, Qt, LqP, Qt, N, H, 32, scale, L->attn_ws, L->attn_ws_bytes, b.aux, st));
     const size_t act = (size_t)R * kE * 2, wsz = (size_t)kE * kE * 2, bsz = (size_t)kE * 2;
     const bool grads_packed = b.dk_s == at(b.dq, act) && b.dv_s == at(b.dq, 2 * act);
-    if (packed_weights(L) && grads_packed) {
+    const void* xqk = P ? P->xq1 : L->xb1;          // operand of the query and key projections
+    if (packed_weights(L) && grads_packed && !P) {
         // dxb = [dq | dk | dv] . W_in (contraction over the 768 packed outputs, blocked over the three buffers)
         MPF_TRY(mpf_small_gemm_bf16_blocked(b.dq, kE, 1, kE, (int64_t)R * kE, nullptr, L->sa_wq, 1, kE, nullptr, nullptr, 0, b.dxb, kE,
                                             0, 0, nullptr, R, kE, 3 * kE, 0, st));
+    } else if (packed_weights(L) && grads_packed) {
+        // dxq1 = [dq | dk] . [Wq | Wk] (contraction over 512), dxb = dv . Wv
+        MPF_TRY(mpf_small_gemm_bf16_blocked(b.dq, kE, 1, kE, (int64_t)R * kE, nullptr, L->sa_wq, 1, kE, nullptr, nullptr, 0, b.dxq1, kE,
+                                            0, 0, nullptr, R, kE, 2 * kE, 0, st));
+        MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, nullptr, b.dxb, R, kE, kE, st));
+    } else if (P) {
+        MPF_TRY(lin_dx(b.dq, nullptr, L->sa_wq, nullptr, b.dxq1, R, kE, kE, st));
+        MPF_TRY(lin_dx(b.dk_s, nullptr, L->sa_wk, b.dxq1, b.dxq1, R, kE, kE, st));
+        MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, nullptr, b.dxb, R, kE, kE, st));
     } else {
         MPF_TRY(lin_dx(b.dq, nullptr, L->sa_wq, nullptr, b.dxb, R, kE, kE, st));
         MPF_TRY(lin_dx(b.dk_s, nullptr, L->sa_wk, b.dxb, b.dxb, R, kE, kE, st));
         MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, b.dxb, b.dxb, R, kE, kE, st));
     }
-    if (grads_packed && G->d_sa_wk == at(G->d_sa_wq, wsz) && G->d_sa_wv == at(G->d_sa_wq, 2 * wsz) &&
-        G->d_sa_bk == at(G->d_sa_bq, bsz) && G->d_sa_bv == at(G->d_sa_bq, 2 * bsz)) {
+    const bool dw_packed = grads_packed && G->d_sa_wk == at(G->d_sa_wq, wsz) && G->d_sa_wv == at(G->d_sa_wq, 2 * wsz) &&
+                           G->d_sa_bk == at(G->d_sa_bq, bsz) && G->d_sa_bv == at(G->d_sa_bq, 2 * bsz);
+    if (dw_packed && !P) {
         // dW_in [768, 256] = [dq | dk | dv]^T . xb1 and its 768 bias gradients as one problem (rows of A blocked)
         dw[ndw++] = dw_item(b.dq, nullptr, L->xb1, G->d_sa_wq, G->d_sa_bq, R, 3 * kE, kE, kE, (int64_t)R * kE);
+    } else if (dw_packed) {
+        // [dWq | dWk] [512, 256] = [dq | dk]^T . xq1 as one problem, dWv = dv^T . xb1
+        dw[ndw++] = dw_item(b.dq, nullptr, xqk, G->d_sa_wq, G->d_sa_bq, R, 2 * kE, kE, kE, (int64_t)R * kE);
+        dw[ndw++] = dw_item(b.dv_s, nullptr, L->xb1, G->d_sa_wv, G->d_sa_bv, R, kE, kE);
     } else {
-        dw[ndw++] = dw_item(b.dq, nullptr, L->xb1, G->d_sa_wq, G->d_sa_bq, R, kE, kE);
-        dw[ndw++] = dw_item(b.dk_s, nullptr, L->xb1, G->d_sa_wk, G->d_sa_bk, R, kE, kE);
+        dw[ndw++] = dw_item(b.dq, nullptr, xqk, G->d_sa_wq, G->d_sa_bq, R, kE, kE);
+        dw[ndw++] = dw_item(b.dk_s, nullptr, xqk, G->d_sa_wk, G->d_sa_bk, R, kE, kE);
         dw[ndw++] = dw_item(b.dv_s, nullptr, L->xb1, G->d_sa_wv, G->d_sa_bv, R, kE, kE);
     }
-    // cross-attention block: x1 = LN(x0 + Wo attn(Wq xb0, k_c, v_c))
+    // cross-attention block: x1 = LN(x0 + Wo attn(Wq xb0, k_c, v_c)); with positions the gradient of bf16(x1 + qpos) joins the
+    // fp32 gradient of x1 first (the sum autograd forms for the stream's two consumers)
+    if (P) MPF_TRY(mpf::bf16_rows_add256(b.dxq1, b.ds_b, R, st));
     MPF_TRY(mpf_res_ln256_backward_partial(L->s1, L->mean1, L->rstd1, L->ca_gamma, b.ds_b, b.dxb, nullptr, G->d_x0, b.dt1, R, ln_part,
                                            b.ln_ws_bytes, st));
     MPF_TRY(mpf_ln_partial_reduce(ln_part, b.ln_ws_bytes, R, 3, dln, st));      // dln = [ca | sa | ff] x (dgamma, dbeta)
@@ -308,8 +362,11 @@ extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDec
     MPF_TRY(mpf_attn_backward_kv_aux(L->q_c, L->k_c, L->v_c, L->kv_row_stride, L->kv_img_stride, L->kT_c, b.qT, b.dout, b.doT, L->mask_c,
                                      1, L->lse_c, b.delta, b.dq_c, G->d_k_c, G->d_v_c, G->dkv_row_stride, G->dkv_img_stride, Qt, LqP, S,
                                      N, H, 32, scale, L->attn_ws, L->attn_ws_bytes, b.aux, st));
-    MPF_TRY(lin_dx(b.dq_c, nullptr, L->ca_wq, nullptr, G->d_xb0, R, kE, kE, st));
-    dw[ndw++] = dw_item(b.dq_c, nullptr, L->xb0, G->d_ca_wq, G->d_ca_bq, R, kE, kE);
+    const void* xq_c = P ? P->xq0 : L->xb0;         // operand of the cross-attention's query projection
+    MPF_TRY(lin_dx(b.dq_c, nullptr, L->ca_wq, nullptr, P ? b.dxq0 : G->d_xb0, R, kE, kE, st));
+    // the gradient of bf16(x0 + qpos) goes to the fp32 stream, and with that of bf16(x1 + qpos) to the positions
+    if (P) MPF_TRY(mpf_qpos_backward(b.dxq0, b.dxq1, G->d_x0, P->d_qpos, Qt, N, st));
+    dw[ndw++] = dw_item(b.dq_c, nullptr, xq_c, G->d_ca_wq, G->d_ca_bq, R, kE, kE);
     if (g_dw_group == 2) {
         // the weight gradients contract over the ROWS of dY and x: on transposed [C, Rp] copies (one grouped launch) both operands
         // are contraction-contiguous, i.e. 16-byte fragment loads instead of eight 2-byte ones per fragment; same 32-row
@@ -335,10 +392,11 @@ extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDec
         tcopy(b.dk_s, nullptr, kE);
         tcopy(b.dv_s, nullptr, kE);
         const uint16_t* xb1T = tcopy(L->xb1, nullptr, kE);
+        const uint16_t* xqkT = P ? tcopy(P->xq1, nullptr, kE) : xb1T;
         const uint16_t* dt1T = tcopy(b.dt1, nullptr, kE);
         const uint16_t* ocT = tcopy(L->o_c, nullptr, kE);
         const uint16_t* dqcT = tcopy(b.dq_c, nullptr, kE);
-        const uint16_t* xb0T = tcopy(L->xb0, nullptr, kE);
+        const uint16_t* xb0T = tcopy(xq_c, nullptr, kE);
         MPF_TRY(mpf_transpose_group_bf16(tr, ntr, Rp, st));
         auto titem = [&](const uint16_t* aT, const uint16_t* bT, void* dwp, void* dbp, int J, int Kin) {
             MpfSmallGemmItem m;
@@ -352,12 +410,16 @@ extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDec
         tw[nt++] = titem(dt3T, hT, G->d_ff_w2, G->d_ff_b2, kE, F);
         tw[nt++] = titem(dhT, xb2T, G->d_ff_w1, G->d_ff_b1, F, kE);
         tw[nt++] = titem(dt2T, osT, G->d_sa_wo, G->d_sa_bo, kE, kE);
-        if (G->d_sa_wk == at(G->d_sa_wq, wsz) && G->d_sa_wv == at(G->d_sa_wq, 2 * wsz) && G->d_sa_bk == at(G->d_sa_bq, bsz) &&
-            G->d_sa_bv == at(G->d_sa_bq, 2 * bsz)) {
+        const bool tw_packed = G->d_sa_wk == at(G->d_sa_wq, wsz) && G->d_sa_wv == at(G->d_sa_wq, 2 * wsz) &&
+                               G->d_sa_bk == at(G->d_sa_bq, bsz) && G->d_sa_bv == at(G->d_sa_bq, 2 * bsz);
+        if (tw_packed && !P) {
             tw[nt++] = titem(dqT, xb1T, G->d_sa_wq, G->d_sa_bq, 3 * kE, kE);
+        } else if (tw_packed) {
+            tw[nt++] = titem(dqT, xqkT, G->d_sa_wq, G->d_sa_bq, 2 * kE, kE);
+            tw[nt++] = titem(dqT + (size_t)2 * kE * Rp, xb1T, G->d_sa_wv, G->d_sa_bv, kE, kE);
         } else {
-            tw[nt++] = titem(dqT, xb1T, G->d_sa_wq, G->d_sa_bq, kE, kE);
-            tw[nt++] = titem(dqT + (size_t)kE * Rp, xb1T, G->d_sa_wk, G->d_sa_bk, kE, kE);
+            tw[nt++] = titem(dqT, xqkT, G->d_sa_wq, G->d_sa_bq, kE, kE);
+            tw[nt++] = titem(dqT + (size_t)kE * Rp, xqkT, G->d_sa_wk, G->d_sa_bk, kE, kE);
             tw[nt++] = titem(dqT + (size_t)2 * kE * Rp, xb1T, G->d_sa_wv, G->d_sa_bv, kE, kE);
         }
         tw[nt++] = titem(dt1T, ocT, G->d_ca_wo, G->d_ca_bo, kE, kE);
@@ -372,6 +434,27 @@ extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDec
                                                 dw[t].J, dw[t].Kc, 0, st));
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mpf_decoder_layer_forward(const MpfDecoderLayer* L, void* st) { return layer_forward(L, nullptr, st); }
+
+extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDecoderLayerGrad* G, void* st)
+{
+    return layer_backward(L, nullptr, G, st);
+}
+
+extern "C" int mpf_decoder_layer_pos_forward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, void* st)
+{
+    if (!P) return mpf::fail(MPF_E_NULL, "decoder_layer_pos_forward: NULL position record");
+    return layer_forward(L, P, st);
+}
+
+extern "C" int mpf_decoder_layer_pos_backward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, const MpfDecoderLayerGrad* G, void* st)
+{
+    if (!P) return mpf::fail(MPF_E_NULL, "decoder_layer_pos_backward: NULL position record");
+    return layer_backward(L, P, G, st);
 }
 
 // The attention mask of the NEXT layer from this layer's residual stream (mask2former_transformer_decoder.py:1869-1875 with the

@@ -54,6 +54,8 @@ inline int cu_count()
     cache[dev].store(cus, std::memory_order_relaxed);
     return cus;
 }
+// acc[rows, 256] fp32 += g[rows, 256] bf16 (query_pos.hip): a bf16 gradient joining the fp32 chain of the decoder's residual stream
+int bf16_rows_add256(const void* g, float* acc, int64_t rows, void* stream);
 // per-subsystem option hooks: return 0 if handled, 1 if the key is not theirs, <0 on bad value
 int set_msda_option(const char* key, int v);
 int set_binned_option(const char* key, int v);

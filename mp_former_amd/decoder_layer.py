@@ -6,6 +6,10 @@ Same kernels and rounding points as the op-by-op path of transformer_decoder.py 
 core, res_ln) — what changes is who issues them: ~20 / ~45 launches per layer from C++ instead of one
 Python autograd node per launch, which left the GPU idle for most of the decoder.  bf16 autocast, 256
 channels, 8 heads, GPU only; the caller projects the cross-attention keys / values (library GEMMs).
+
+``decoder_layer`` is the image decoder's layer (no query positions); ``decoder_layer_pos`` the clip decoder's, with the learned
+query positions as an operand (video_mask2former_transformer_decoder.py:415, :421; MpfDecoderLayerPos, csrc/query_pos.hip).
+Both nodes share one implementation here (_LayerNode) and one host sequence in csrc/decoder_layer.hip.
 """
 import ctypes
 
@@ -40,15 +44,29 @@ class MpfDecoderLayerGrad(ctypes.Structure):
                 + [("d_ln", _vp), ("dkv_row_stride", ctypes.c_int64), ("dkv_img_stride", ctypes.c_int64), ("g_x3_plus", _vp)])
 
 
+class MpfDecoderLayerPos(ctypes.Structure):
+    """the query-position operand of a layer (the clip decoder), its two saved bf16 operands and its gradient"""
+    _fields_ = [(n, _vp) for n in ("qpos", "xq0", "xq1", "d_qpos")]
+
+
+_SAVED_POS = ("xq0", "xq1")          # bf16(x0 + qpos), bf16(x1 + qpos): behind the tensors of _SAVED in a layer's arena
 _checked = False
 _PARAM_DTYPES = tuple(torch.float32 if n in _LN else torch.bfloat16 for n in PARAM_NAMES)
 _layouts = {}
 
 
-def _arena_layout(R, E, N, S, Qt, H, F_):
-    """byte offsets of the saved tensors (_SAVED order) inside a layer's arena, and its size"""
-    key = (R, E, N, S, Qt, H, F_)
+def _arena_layout(R, E, N, S, Qt, H, F_, pos=False):
+    """byte offsets of the saved tensors (_SAVED order; with query positions _SAVED + _SAVED_POS) inside a layer's arena,
+    and its size"""
+    key = (R, E, N, S, Qt, H, F_, pos)
     hit = _layouts.get(key)
+    if hit is None and pos:
+        offs, tot = _arena_layout(R, E, N, S, Qt, H, F_)
+        more = []
+        for _ in _SAVED_POS:
+            more.append(tot)
+            tot += _al(R * E * 2)
+        hit = _layouts[key] = (offs + tuple(more), tot)
     if hit is None:
         sizes = {"q_c": R * E * 2, "kT_c": N * E * S * 2, "o_c": R * E * 2, "lse_c": N * H * Qt * 4,
                  "s1": R * E * 4, "mean1": R * 4, "rstd1": R * 4, "xb1": R * E * 2,
@@ -66,16 +84,16 @@ def _arena_layout(R, E, N, S, Qt, H, F_):
 _scratch_sizes = {}
 
 
-def _scratch_bytes(lib, Qt, N, H, S, F_):
+def _scratch_bytes(lib, Qt, N, H, S, F_, pos=False):
     """(layer scratch, attention workspace) bytes of a shape.  The attention workspace depends on run-time options (the key
     split: attn_nw / attn_kpw), so the cache is keyed on the option generation `_lib.set_option` advances."""
-    key = (Qt, N, H, S, F_, _lib.option_generation())
+    key = (Qt, N, H, S, F_, pos, _lib.option_generation())
     hit = _scratch_sizes.get(key)
     if hit is None:
         if len(_scratch_sizes) > 256:
             _scratch_sizes.clear()
-        hit = _scratch_sizes[key] = (max(lib.mpf_decoder_layer_scratch_bytes(Qt, N, H, S, F_, 0),
-                                         lib.mpf_decoder_layer_scratch_bytes(Qt, N, H, S, F_, 1)),
+        size = lib.mpf_decoder_layer_pos_scratch_bytes if pos else lib.mpf_decoder_layer_scratch_bytes
+        hit = _scratch_sizes[key] = (max(size(Qt, N, H, S, F_, 0), size(Qt, N, H, S, F_, 1)),
                                      max(lib.mpf_attn_workspace_bytes(Qt, S, N, H), lib.mpf_attn_workspace_bytes(Qt, Qt, N, H)))
     return hit
 
@@ -85,7 +103,8 @@ def _lib_checked():
     lib = _lib.lib()
     if not _checked:
         if (lib.mpf_decoder_layer_struct_bytes(0) != ctypes.sizeof(MpfDecoderLayer)
-                or lib.mpf_decoder_layer_struct_bytes(1) != ctypes.sizeof(MpfDecoderLayerGrad)):
+                or lib.mpf_decoder_layer_struct_bytes(1) != ctypes.sizeof(MpfDecoderLayerGrad)
+                or lib.mpf_decoder_layer_pos_struct_bytes() != ctypes.sizeof(MpfDecoderLayerPos)):
             raise RuntimeError("MpfDecoderLayer layout differs between decoder_layer.py and libmpformer_hip.so")
         _checked = True
     return lib
@@ -169,9 +188,12 @@ def _contig_strides(shape):
     return tuple(reversed(st))
 
 
-class DecoderLayerFn(Function):
+class _LayerNode:
+    """forward / backward of the two autograd nodes below.  ``pos``: the layer takes query positions — its second input is then
+    qpos fp32 [Qt, 256] (and its second gradient d_qpos) where the image layer has xb0 bf16 [Qt, N, 256] (d_xb0)."""
+
     @staticmethod
-    def forward(ctx, x0, xb0, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, *params):
+    def forward(ctx, pos, x0, second, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, params):
         lib = _lib_checked()
         Qt, N, E = x0.shape
         S = k_c.shape[0]
@@ -179,7 +201,11 @@ class DecoderLayerFn(Function):
         R = Qt * N
         dev = x0.device
         assert E == 256 and nheads * 32 == E and len(params) == len(PARAM_NAMES)
-        assert x0.dtype == torch.float32 and x0.is_contiguous() and xb0.dtype == torch.bfloat16 and xb0.is_contiguous()
+        assert x0.dtype == torch.float32 and x0.is_contiguous() and second.is_contiguous() and second.device == dev
+        if pos:
+            assert second.dtype == torch.float32 and second.shape == (Qt, E) and second.data_ptr() % 16 == 0
+        else:
+            assert second.dtype == torch.bfloat16 and second.shape == x0.shape
         # k_c / v_c: dense [S, N, E] or column blocks of a wider projection (same strides for both, rows 16-byte aligned)
         assert k_c.dtype == v_c.dtype == torch.bfloat16 and k_c.shape == v_c.shape == (S, N, E) and k_c.stride() == v_c.stride()
         assert k_c.stride(2) == 1 and k_c.stride(0) % 8 == 0 and k_c.stride(1) % 8 == 0
@@ -202,31 +228,41 @@ class DecoderLayerFn(Function):
         if fixed is not None:
             params = tuple(fixed)
         # one arena for everything the backward reads (offsets per shape cached)
-        offs, total = _arena_layout(R, E, N, S, Qt, nheads, F_)
+        offs, total = _arena_layout(R, E, N, S, Qt, nheads, F_, pos)
         arena = torch.empty(total, dtype=torch.uint8, device=dev)
         x3 = torch.empty_like(x0)
-        xb3 = torch.empty_like(xb0)
+        xb3 = torch.empty_like(x0, dtype=torch.bfloat16)
         L = MpfDecoderLayer()
         base = arena.data_ptr()
         for n, o in zip(_SAVED, offs):
             setattr(L, n, base + o)
         for n, v in zip(PARAM_NAMES, ptrs):
             setattr(L, n, v)
-        L.x0, L.xb0, L.k_c, L.v_c = x0.data_ptr(), xb0.data_ptr(), k_c.data_ptr(), v_c.data_ptr()
+        P = None
+        if pos:
+            P = MpfDecoderLayerPos()
+            P.qpos = second.data_ptr()
+            for n, o in zip(_SAVED_POS, offs[len(_SAVED):]):
+                setattr(P, n, base + o)
+        L.x0, L.xb0, L.k_c, L.v_c = x0.data_ptr(), (None if pos else second.data_ptr()), k_c.data_ptr(), v_c.data_ptr()
         L.mask_c = mask_c.data_ptr()
         L.mask_s = mask_s.data_ptr() if mask_s is not None else None
         L.x3, L.xb3 = x3.data_ptr(), xb3.data_ptr()
         L.Qt, L.N, L.H, L.S, L.ffn_dim, L.eps = Qt, N, nheads, S, F_, float(eps)
         if not k_c.is_contiguous():
             L.kv_row_stride, L.kv_img_stride = k_c.stride(0), k_c.stride(1)
-        sc_bytes, ws_bytes = _scratch_bytes(lib, Qt, N, nheads, S, F_)
+        sc_bytes, ws_bytes = _scratch_bytes(lib, Qt, N, nheads, S, F_, pos)
         stream = _lib.stream_ptr(dev)
         sc = _lib.scratch("decoder_scratch", dev, stream, sc_bytes)
         ws = _lib.scratch("attn", dev, stream, ws_bytes)
         L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
-        _lib.call("mpf_decoder_layer_forward", dev, ctypes.byref(L), stream)
-        ctx.save_for_backward(xb0, k_c, v_c, mask_c, mask_s, arena, *params)
+        if pos:
+            _lib.call("mpf_decoder_layer_pos_forward", dev, ctypes.byref(L), ctypes.byref(P), stream)
+        else:
+            _lib.call("mpf_decoder_layer_forward", dev, ctypes.byref(L), stream)
+        ctx.save_for_backward(second, k_c, v_c, mask_c, mask_s, arena, *params)
         ctx.layer = L
+        ctx.pos = P
         ctx.kv_pack = kv_pack
         ctx.dims = (Qt, N, E, S, F_, nheads)
         # x3 leaves twice (two aliases of one tensor): the next layer and the prediction heads both consume it, and their
@@ -236,17 +272,17 @@ class DecoderLayerFn(Function):
         return x3, xb3, x3.view(x3.shape)
 
     @staticmethod
-    def backward(ctx, g_x3, g_xb3, g_x3h=None):
+    def backward(ctx, pos, g_x3, g_xb3, g_x3h=None):
         if g_x3 is None:
             g_x3, g_x3h = g_x3h, None
         if g_x3 is None and g_xb3 is None:
             return (None,) * (9 + len(PARAM_NAMES))
         lib = _lib_checked()
         saved = ctx.saved_tensors
-        xb0, k_c = saved[0], saved[1]
+        k_c = saved[1]
         params = saved[6:]
         Qt, N, E, S, F_, H = ctx.dims
-        dev = xb0.device
+        dev = k_c.device
         L = ctx.layer
         if g_x3 is not None:
             g_x3 = g_x3.to(torch.float32).contiguous()
@@ -255,7 +291,10 @@ class DecoderLayerFn(Function):
         if g_x3h is not None:
             g_x3h = g_x3h.to(torch.float32).contiguous()
         d_x0 = torch.empty((Qt, N, E), dtype=torch.float32, device=dev)
-        d_xb0 = torch.empty((Qt, N, E), dtype=torch.bfloat16, device=dev)
+        if pos:
+            d_second = torch.empty((Qt, E), dtype=torch.float32, device=dev)            # d_qpos, fully written by the call
+        else:
+            d_second = torch.empty((Qt, N, E), dtype=torch.bfloat16, device=dev)        # d_xb0
         G = MpfDecoderLayerGrad()
         if ctx.kv_pack is not None:       # our blocks of the packed dK / dV of the level, written in place
             (pk, jk), (pv, jv) = ctx.kv_pack
@@ -272,17 +311,22 @@ class DecoderLayerFn(Function):
         G.g_x3 = g_x3.data_ptr() if g_x3 is not None else None
         G.g_xb3 = g_xb3.data_ptr() if g_xb3 is not None else None
         G.g_x3_plus = g_x3h.data_ptr() if g_x3h is not None else None
-        G.d_x0, G.d_xb0, G.d_k_c, G.d_v_c = d_x0.data_ptr(), d_xb0.data_ptr(), d_k.data_ptr(), d_v.data_ptr()
+        G.d_x0, G.d_xb0, G.d_k_c, G.d_v_c = d_x0.data_ptr(), (None if pos else d_second.data_ptr()), d_k.data_ptr(), d_v.data_ptr()
         wbase = wg.data_ptr()
         for n, o in zip(_WGRADS, offs):
             setattr(G, n, wbase + 2 * o)
         G.d_ln = d_ln.data_ptr()
-        sc_bytes, ws_bytes = _scratch_bytes(lib, Qt, N, H, S, F_)
+        sc_bytes, ws_bytes = _scratch_bytes(lib, Qt, N, H, S, F_, pos)
         stream = _lib.stream_ptr(dev)
         sc = _lib.scratch("decoder_scratch", dev, stream, sc_bytes)
         ws = _lib.scratch("attn", dev, stream, ws_bytes)
         L.scratch, L.scratch_bytes, L.attn_ws, L.attn_ws_bytes = sc.data_ptr(), sc.numel(), ws.data_ptr(), ws.numel()
-        _lib.call("mpf_decoder_layer_backward", dev, ctypes.byref(L), ctypes.byref(G), stream)
+        if pos:
+            P = ctx.pos
+            P.d_qpos = d_second.data_ptr()
+            _lib.call("mpf_decoder_layer_pos_backward", dev, ctypes.byref(L), ctypes.byref(P), ctypes.byref(G), stream)
+        else:
+            _lib.call("mpf_decoder_layer_backward", dev, ctypes.byref(L), ctypes.byref(G), stream)
         grads, wi, li = [], 0, 0
         lns = d_ln.unbind(0)
         for ln in _IS_LN:
@@ -293,13 +337,45 @@ class DecoderLayerFn(Function):
                 s_ = wshapes[wi]
                 grads.append(wg.as_strided(s_, _contig_strides(s_), offs[wi]))      # (one view op instead of slice + view)
                 wi += 1
-        return (d_x0, d_xb0, d_k, d_v, None, None, None, None, None, *grads)
+        return (d_x0, d_second, d_k, d_v, None, None, None, None, None, *grads)
+
+
+class DecoderLayerFn(Function):
+    @staticmethod
+    def forward(ctx, x0, xb0, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, *params):
+        return _LayerNode.forward(ctx, False, x0, xb0, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, params)
+
+    @staticmethod
+    def backward(ctx, g_x3, g_xb3, g_x3h=None):
+        return _LayerNode.backward(ctx, False, g_x3, g_xb3, g_x3h)
+
+
+class DecoderLayerPosFn(Function):
+    """the layer with query positions: qpos fp32 [Qt, 256] in place of xb0, d_qpos in place of d_xb0"""
+
+    @staticmethod
+    def forward(ctx, x0, qpos, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, *params):
+        return _LayerNode.forward(ctx, True, x0, qpos, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, params)
+
+    @staticmethod
+    def backward(ctx, g_x3, g_xb3, g_x3h=None):
+        return _LayerNode.backward(ctx, True, g_x3, g_xb3, g_x3h)
 
 
 def decoder_layer(x0, xb0, k_c, v_c, mask_c, mask_s, nheads, eps, params, kv_pack=None):
     """(x3 fp32, xb3 bf16, x3 again) = one decoder layer; ``params``: the 22 tensors of PARAM_NAMES.  The third result is an
-    alias of the first for a second consumer (see DecoderLayerFn.forward).  ``kv_pack`` = the
+    alias of the first for a second consumer (see _LayerNode.forward).  ``kv_pack`` = the
     ``split_cols`` handles of k_c and v_c when they are column blocks of a level's packed projection."""
     if not x0.is_cuda:
         raise RuntimeError("mp_former_amd decoder layer runs on the GPU only (no CPU fallback)")
     return DecoderLayerFn.apply(x0, xb0, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, *params)
+
+
+def decoder_layer_pos(x0, qpos, k_c, v_c, mask_c, mask_s, nheads, eps, params, kv_pack=None):
+    """``decoder_layer`` with learned query positions ``qpos`` fp32 [Qt, 256] (the clip decoder, video_mask2former_transformer_
+    decoder.py:415, :421): the cross-attention query is projected from x0 + qpos, the self-attention query and key from
+    x1 + qpos, its value from x1; the operand copy xb0 has no reader and is not an input.  Gradients for x0, qpos, k_c, v_c and
+    the parameters."""
+    if not x0.is_cuda:
+        raise RuntimeError("mp_former_amd decoder layer runs on the GPU only (no CPU fallback)")
+    return DecoderLayerPosFn.apply(x0, qpos, k_c, v_c, mask_c, mask_s, nheads, eps, kv_pack, *params)

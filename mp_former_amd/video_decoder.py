@@ -21,10 +21,14 @@ module is built from the image decoder's parts (transformer_decoder.py), which i
   * the mask predictions of all layers are ONE parent [B, L * Q, T, h, w]; layer l is the slice [:, l * Q:(l + 1) * Q], which
     ``video_losses.clip_planes`` / ``MapSet`` address in place.
 
-Every layer runs op by op (one autograd node per op, the native attention / small-GEMM / residual-LayerNorm kernels under bf16
-autocast); the one-call native layer of the image decoder has no query-position operand.  GPU only.
+A layer takes one of two routes (``last_layer_route()`` names the one taken): 'native' — the whole layer is ONE autograd node
+whose forward / backward are single native calls (decoder_layer.decoder_layer_pos: the image decoder's one-call layer with a
+query-position operand) — under bf16 autocast with 256 channels and 8 heads unless MPF_FUSED_DECODER=0; 'ops' — ``_layer_by_ops``,
+one autograd node per op on the same attention / small-GEMM / residual-LayerNorm kernels — everywhere else (fp32, other widths).
+The module attribute ``fused_layers`` (None = that rule, True / False = forced) switches routes in one process.  GPU only.
 """
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -32,10 +36,20 @@ from torch import nn
 
 from . import _lib
 from .attention import attention_core
+from .decoder_layer import decoder_layer_pos
 from .pixel_decoder import _ConvNorm, _c2_xavier_fill
 from .resln import res_ln
 from .transformer_decoder import (MLP, CrossAttentionLayer, FFNLayer, MultiScaleMaskedTransformerDecoderMaskDN as _ImageDecoder,
                                   SelfAttentionLayer, linear, pool_features)
+
+
+_last_layer_route = None
+
+
+def last_layer_route():
+    """'native' (one call per layer, decoder_layer_pos) | 'ops' (_layer_by_ops): the route of the most recent decoder layer
+    (None before the first)"""
+    return _last_layer_route
 
 
 class PositionEmbeddingSine3D(nn.Module):
@@ -188,6 +202,7 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
         self.mask_embed = MLP(hidden_dim, hidden_dim, mask_dim, 3)
         self.factored_masks = False      # (read by the shared batched heads: the clip criterion takes materialised maps)
         self.mask_log = None             # tests: a list here receives the attention mask made after every layer, the last included
+        self.fused_layers = None         # None: the rule of ``_one_call_layers``; True / False: that route (tests, the bench tool)
 
     @classmethod
     def from_config(cls, cfg, in_channels, mask_classification):
@@ -263,7 +278,40 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
                     W[pre + "linear2.weight"], W[pre + "linear2.bias"])
         return post_norm(self.transformer_ffn_layers[i].norm, output, t2)
 
+    def _one_call_layers(self, W, amp, adt, channels):
+        """Does a layer run as ONE native call (decoder_layer_pos)?  By default under the image decoder's conditions: bf16
+        autocast (the weights then arrive as bf16 row blocks), 256 channels, 8 heads, post-norm, MPF_FUSED_DECODER not 0.
+        ``fused_layers`` = True / False forces a route; True where the native layer cannot run is an error, not a fallback."""
+        # (post-norm holds by construction: the attention / FFN modules refuse normalize_before)
+        can = (amp and adt == torch.bfloat16 and channels == 256 and self.num_heads == 8
+               and isinstance(W["transformer_cross_attention_layers.0.multihead_attn.in_proj_weight"], tuple))
+        want = getattr(self, "fused_layers", None)
+        if want is None:
+            return can and os.environ.get("MPF_FUSED_DECODER", "1") != "0"
+        if want and not can:
+            raise RuntimeError("fused_layers=True: the one-call decoder layer needs bf16 autocast, 256 channels, 8 heads, post-norm")
+        return bool(want)
+
+    def _layer_native(self, W, i, output, qpos, k_c, v_c, kv_pack, attn_mask):
+        """One decoder layer with query positions as one autograd node whose forward / backward are single native calls
+        (decoder_layer.decoder_layer_pos): the kernels and rounding points of ``_layer_by_ops``, issued from C++.
+        -> (x3 fp32, xb3 bf16, x3 again for the prediction heads)"""
+        ca = f"transformer_cross_attention_layers.{i}.multihead_attn."
+        sa = f"transformer_self_attention_layers.{i}.self_attn."
+        ff = f"transformer_ffn_layers.{i}."
+        cw, cb = W[ca + "in_proj_weight"], W[ca + "in_proj_bias"]
+        sw, sb = W[sa + "in_proj_weight"], W[sa + "in_proj_bias"]
+        n1, n2, n3 = (self.transformer_cross_attention_layers[i].norm, self.transformer_self_attention_layers[i].norm,
+                      self.transformer_ffn_layers[i].norm)
+        return decoder_layer_pos(
+            output, qpos, k_c, v_c, attn_mask, None, self.num_heads, n1.eps,
+            (cw[0], cb[0], W[ca + "out_proj.weight"], W[ca + "out_proj.bias"], n1.weight, n1.bias,
+             sw[0], sb[0], sw[1], sb[1], sw[2], sb[2], W[sa + "out_proj.weight"], W[sa + "out_proj.bias"], n2.weight, n2.bias,
+             W[ff + "linear1.weight"], W[ff + "linear1.bias"], W[ff + "linear2.weight"], W[ff + "linear2.bias"],
+             n3.weight, n3.bias), kv_pack)
+
     def forward(self, x, mask_features, mask=None):
+        global _last_layer_route
         assert len(x) == self.num_feature_levels
         del mask                                           # :382-383
         if not mask_features.is_cuda or not all(xi.is_cuda for xi in x):
@@ -320,15 +368,24 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
         # the key / value projections of the layers that share a level as one GEMM each (autocast: the weights arrive as row blocks)
         batched = amp and isinstance(W["transformer_cross_attention_layers.0.multihead_attn.in_proj_weight"], tuple)
         kv = self._kv_batched(W, kin, src) if batched else None
+        fused = self._one_call_layers(W, amp, adt, output.shape[-1])
+        qpos2 = self.query_embed.weight.float() if fused else None      # [Q, C], passed to every layer: autograd sums the d_qpos
+        _last_layer_route = "native" if fused else "ops"
         for i in range(self.num_layers):
             level = i % nlev
             if kv is not None:
-                (k_c, _), (v_c, _) = kv[i]
+                (k_c, pk), (v_c, pv) = kv[i]
             else:
                 w, b = self._in_proj(W, f"transformer_cross_attention_layers.{i}.multihead_attn.")
-                k_c, v_c = linear(kin[level], w[1], b[1]), linear(src[level], w[2], b[2])
-            output, xb = self._layer_by_ops(W, i, output, xb, qpos, k_c, v_c, attn_mask, post_norm, cast)
-            streams.append(output)
+                k_c, v_c, pk, pv = linear(kin[level], w[1], b[1]), linear(src[level], w[2], b[2]), None, None
+            if fused:
+                kv_pack = (pk, pv) if pk is not None and pv is not None else None
+                # (the third result: a second alias of the stream for the prediction heads, decoder_layer._LayerNode)
+                output, xb, out_heads = self._layer_native(W, i, output, qpos2, k_c, v_c, kv_pack, attn_mask)
+            else:
+                output, xb = self._layer_by_ops(W, i, output, xb, qpos, k_c, v_c, attn_mask, post_norm, cast)
+                out_heads = output
+            streams.append(out_heads)
             nxt = (i + 1) % nlev
             if i + 1 < self.num_layers or log is not None:       # (the reference makes the mask after the last layer too, unused)
                 attn_mask = self._clip_attn_mask(W, output, mf5, size_list[nxt], pooled[nxt])

@@ -7,11 +7,14 @@ reference's layer loop (video_mask2former_transformer_decoder.py:370-461) on the
 
     python tools/bench_video_decoder.py [--shape train|eval|both] [--iters 20] [--json out.json]
 
-Routes: "native" = the module as it ships (every layer op by op on the native attention / small-GEMM / residual-LayerNorm kernels,
-clip-inputs kernel, fused mask head, batched key / value projections and prediction heads); "torch" = ``reference_forward`` below:
-nn.MultiheadAttention per attention, the [B, Q, T, H/4, W/4] logits map resized and thresholded per layer, the bool mask repeated
-for the heads.  Times are medians of device-event intervals around whole calls, after a warm-up of the same shape; launches are
-the device kernels one forward enqueues, counted by the profiler in a pass of its own (not timed)."""
+Routes: "ops" = the module with every layer op by op (``fused_layers = False``: one autograd node per op on the native attention /
+small-GEMM / residual-LayerNorm kernels; clip-inputs kernel, fused mask head, batched key / value projections and prediction
+heads); "native" = native, one call per layer (``fused_layers = True``: the same kernels issued by decoder_layer.decoder_layer_pos,
+one autograd node per layer); "torch" = ``reference_forward`` below: nn.MultiheadAttention per attention, the
+[B, Q, T, H/4, W/4] logits map resized and thresholded per layer, the bool mask repeated for the heads.  The routes ALTERNATE call
+by call in one process (after 3 warm calls each), so that they see the same clocks; times are medians (min, max) of device-event
+intervals around whole calls; launches are the device kernels one forward enqueues, counted by the profiler in a pass of its own
+(not timed)."""
 import argparse
 import json
 import os
@@ -94,7 +97,14 @@ def seeds_for(out, dev):
 
 
 def step_fn(route, m, xs, mf, training):
-    fwd = (lambda: m(xs, mf)) if route == "native" else (lambda: reference_forward(m, xs, mf))
+    def module_forward():
+        m.fused_layers = route == "native"
+        try:
+            return m(xs, mf)
+        finally:
+            m.fused_layers = None
+
+    fwd = module_forward if route in ("ops", "native") else (lambda: reference_forward(m, xs, mf))
     seeds = []
 
     def forward():
@@ -123,20 +133,26 @@ def step_fn(route, m, xs, mf, training):
     return step, forward_only
 
 
-def timed(fn, iters):
-    for _ in range(3):
-        fn()
+def timed(fns, iters):
+    """{route: fn} -> {route: (median, min, max) ms}: 3 warm calls each, then ``iters`` rounds in which the routes take turns"""
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
+    ts = {r: [] for r in fns}
     for _ in range(iters):
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    ts.sort()
-    return ts[len(ts) // 2], ts[0], ts[-1]
+        for r, fn in fns.items():
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[r].append(e0.elapsed_time(e1))
+    out = {}
+    for r, t in ts.items():
+        t.sort()
+        out[r] = (t[len(t) // 2], t[0], t[-1])
+    return out
 
 
 def count_launches(fn):
@@ -158,7 +174,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="both", choices=["train", "eval", "both"])
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--routes", default="native,torch")
+    ap.add_argument("--routes", default="ops,native,torch")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -176,9 +192,10 @@ def main():
         xs, mf = make_inputs(sp["B"], sp["T"], dev)
         if sp["training"]:
             xs, mf = [x.requires_grad_(True) for x in xs], mf.requires_grad_(True)
-        for route in args.routes.split(","):
-            step, forward_only = step_fn(route, m, xs, mf, sp["training"])
-            med, lo, hi = timed(step, args.iters)
+        fns = {route: step_fn(route, m, xs, mf, sp["training"]) for route in args.routes.split(",")}
+        times = timed({route: step for route, (step, _) in fns.items()}, args.iters)
+        for route, (_, forward_only) in fns.items():
+            med, lo, hi = times[route]
             launches = count_launches(forward_only)
             r = {"shape": shape, "B": sp["B"], "T": sp["T"], "route": route, "what": "forward+backward" if sp["training"] else "forward",
                  "ms_median": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3), "iters": args.iters,
