@@ -1220,6 +1220,14 @@ int mpf_upsample2x_cl_backward(const float* gy, int64_t gy_bs, int N, int Ht, in
  *   (mask + dice part) for G groups = (decoder output, image): queries q = 0..Q-1 of group g are the rows
  *   embed + embed_first[g] + q * embed_row_stride; coords [G][P][2] (x, y) in [0,1]; tsamp [tsamp_rows][P] = the
  *   ground-truth masks sampled at the group's points, rows t_first[g] .. + t_count[g].  Tmax <= 128.  Deterministic.
+ * mpf_match_cost_fused_clip: the same cost for clips (mask2former_video/modeling/matcher.py:113-148).  Group g = (decoder
+ *   output, clip); frame f of its map is the channel-last plane at features + group_clip[g] * feat_clip_stride +
+ *   f * feat_frame_stride (both strides multiples of 8 elements, feat_frame_stride >= h*w*256; the gap is never read).
+ *   coords[g] ([P][2]) is used for EVERY frame; a footprint corner outside a frame's plane weighs zero and is never taken from
+ *   the neighbouring frame.  tsamp rows are F*P floats, frame-major.  The sums run over all F*P samples:
+ *     cost[g][q][t] = w_mask (sum softplus(x) - sum x t) / (F P) + w_dice (1 - (2 sum s t + 1) / (sum s + sum t + 1)).
+ *   Tmax <= 128 (MPF_E_SHAPE); G <= 65535, F <= 65535, F*P < 2^31 (MPF_E_TOO_LARGE).  Deterministic; with F = 1 the cost is
+ *   mpf_match_cost_fused's bit for bit.
  * mpf_pair_planes_forward: out[slot][h*w] (bf16) = embed row of slot . features of its image, for the slots
  *   slot_first[b] .. + slot_count[b] of image b; the row of a slot is embed + row_off[pair_of_slot ? pair_of_slot[slot] : slot].
  *   All index arrays are DEVICE memory (row_off is written by the device assignment solver).  h*w % 4 == 0.
@@ -1235,6 +1243,12 @@ int mpf_match_cost_fused(const void* embed, const int64_t* embed_first, int64_t 
                          int64_t feat_img_stride, const int32_t* group_image, int h, int w, int channels, const float* coords,
                          const float* tsamp, int tsamp_rows, const int32_t* t_first, const int32_t* t_count, float* cost, int G,
                          int Q, int Tmax, int P, float w_mask, float w_dice, void* workspace, size_t workspace_bytes, void* stream);
+size_t mpf_match_cost_fused_clip_workspace_bytes(int G, int Q, int Tmax, int P, int F, int tsamp_rows);
+int mpf_match_cost_fused_clip(const void* embed, const int64_t* embed_first, int64_t embed_row_stride, const void* features,
+                              int64_t feat_clip_stride, int64_t feat_frame_stride, const int32_t* group_clip, int h, int w,
+                              int channels, const float* coords, const float* tsamp, int tsamp_rows, const int32_t* t_first,
+                              const int32_t* t_count, float* cost, int G, int Q, int Tmax, int P, int F, float w_mask, float w_dice,
+                              void* workspace, size_t workspace_bytes, void* stream);
 int mpf_pair_planes_forward(const void* embed, const int64_t* row_off, const int32_t* pair_of_slot, const int32_t* slot_first,
                             const int32_t* slot_count, const void* features, int64_t feat_img_stride, void* out, int N, int HW,
                             int channels, void* stream);

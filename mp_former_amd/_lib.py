@@ -40,6 +40,10 @@ SIGNATURES = {
     "mpf_match_cost_fused": (_c_int, [_c_vp, _c_vp, ctypes.c_int64, _c_vp, ctypes.c_int64, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int,
                                       _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, _c_vp,
                                       ctypes.c_size_t, _c_vp]),
+    "mpf_match_cost_fused_clip_workspace_bytes": (ctypes.c_size_t, [_c_int] * 6),
+    "mpf_match_cost_fused_clip": (_c_int, [_c_vp, _c_vp, ctypes.c_int64, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_int, _c_int, _c_int,
+                                           _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_float,
+                                           ctypes.c_float, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_pair_planes_forward": (_c_int, [_c_vp] * 6 + [ctypes.c_int64, _c_vp, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_pair_planes_backward_workspace_bytes": (ctypes.c_size_t, [_c_int] * 4),
     "mpf_pair_planes_backward": (_c_int, [_c_vp] * 7 + [ctypes.c_int64, _c_vp, ctypes.c_int64, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int,

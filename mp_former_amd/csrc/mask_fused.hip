@@ -14,6 +14,8 @@
 //     logits go through LDS to a (query, target-half) thread mapping that accumulates sum_p x t, sum_p sigmoid(x) t,
 //     sum_p softplus(x), sum_p sigmoid(x) over the workgroup's tiles in registers (fp32, matcher.py:20-62).  Partial sums
 //     per workgroup are reduced in a FIXED order by a second launch: no atomics, bit-reproducible costs.
+//     mpf_match_cost_fused_clip is the same kernel (CLIP instantiation) over the F frames of a clip at one shared point set
+//     (mask2former_video/modeling/matcher.py:113-148): the tiles of all frames, frame-major, are dealt to the workgroups.
 //
 //   * loss planes (mpf_pair_planes_forward).  Importance sampling draws 3 P = 37 632 DIFFERENT points per pair — more point
 //     evaluations than the plane has pixels — so for the ~500 (prediction, target) pairs of a step (of 2 280 rows) the plane
@@ -383,13 +385,16 @@ constexpr int kMQ = 128;          // queries per workgroup (8 row tiles)
 // LDS: [0, 16K) interpolated features, high planes [32 pt][512 B]; [16K, 32K) low planes; then X [128][33] f32; then TV
 constexpr int kOffLo = kMP * 512, kOffX = 2 * kMP * 512, kOffTV = kOffX + kMQ * 33 * 4;
 
-template <int TCH>
+// CLIP: the group's map is F frames (planes feat_fs elements apart) sampled at ONE point set; the workgroup's range runs over
+// the F * ceil(P / 32) tiles of all frames, frame-major, so a tile never straddles two frames: its plane, its clamped corner
+// indices and its cut at P are the frame's own, and tsamp rows are [F][P].  F = 1 is the image problem, tile for tile.
+template <int TCH, bool CLIP>
 __global__ __launch_bounds__(kT) void match_cost_fused_kernel(
     const __hip_bfloat16* __restrict__ embed, const int64_t* __restrict__ embed_first, int64_t embed_row_stride,
     const __hip_bfloat16* __restrict__ feat, int64_t feat_bs, const int32_t* __restrict__ group_image, int h, int w,
     const float* __restrict__ coords, const float* __restrict__ tsamp, const int32_t* __restrict__ t_first,
     const int32_t* __restrict__ t_count, float* __restrict__ part_qt, float* __restrict__ part_q, int G, int Q, int Tmax, int P,
-    int tiles_per_wg)
+    int tiles_per_wg, int64_t feat_fs, int F)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* sX = reinterpret_cast<float*>(smem + kOffX);
@@ -399,10 +404,11 @@ __global__ __launch_bounds__(kT) void match_cost_fused_kernel(
     const int Tn = t_count[g];
     if (Tn <= 0) return;
     const int T0 = t_first[g];
-    const __hip_bfloat16* fb = feat + (int64_t)group_image[g] * feat_bs;
+    const __hip_bfloat16* fg = feat + (int64_t)group_image[g] * feat_bs;
     const float2* cg = reinterpret_cast<const float2*>(coords) + (int64_t)g * P;
     const int ntiles = (P + kMP - 1) / kMP;
-    const int tile0 = blockIdx.x * tiles_per_wg, tile1 = min(tile0 + tiles_per_wg, ntiles);
+    const int tile0 = blockIdx.x * tiles_per_wg, tile1 = min(tile0 + tiles_per_wg, CLIP ? F * ntiles : ntiles);
+    const int64_t trow = CLIP ? (int64_t)F * P : (int64_t)P;          // length of a tsamp row
 
     // A fragments: the wave's two query tiles, all 8 contraction steps (embedding rows, register-resident)
     bf16x8 a[2][8];
@@ -422,7 +428,10 @@ __global__ __launch_bounds__(kT) void match_cost_fused_kernel(
     for (int j = 0; j < TCH; ++j) { ax[j] = 0.f; as_[j] = 0.f; }
 
     for (int tile = tile0; tile < tile1; ++tile) {
-        const int pbase = tile * kMP;
+        const int f = CLIP ? tile / ntiles : 0;                    // wave-uniform
+        const int pbase = (tile - f * ntiles) * kMP;
+        const __hip_bfloat16* fb = CLIP ? fg + (int64_t)f * feat_fs : fg;
+        const float* ts = CLIP ? tsamp + (int64_t)f * P : tsamp;
         // ---- gather role: thread = (point tid >> 3, 16-byte slots (tid & 7) + 8 j): four corner rows, fp32 interpolation
         {
             const int pt = tid >> 3, cl = tid & 7;
@@ -455,7 +464,7 @@ __global__ __launch_bounds__(kT) void match_cost_fused_kernel(
             for (int u = 0; u < TCH / 4; ++u) {
                 const int i = tid + u * kT;
                 const int pp = i & (kMP - 1), tt = i >> 5;
-                const float v = tsamp[(int64_t)(T0 + min(tt, Tn - 1)) * P + min(pbase + pp, P - 1)];
+                const float v = ts[(int64_t)(T0 + min(tt, Tn - 1)) * trow + min(pbase + pp, P - 1)];
                 sTV[pp * (2 * TCH) + tt] = (tt < Tn && pbase + pp < P) ? v : 0.f;
             }
 #pragma unroll
@@ -533,6 +542,7 @@ __global__ __launch_bounds__(kT) void match_cost_fused_kernel(
 }
 
 // cost[g][q][t] = w_mask (sum softplus(x) - sum x t) / P + w_dice (1 - (2 sum s t + 1) / (sum s + sum t + 1))   (matcher.py:20-62)
+// (P = number of samples of a row: F * P for a clip)
 __global__ __launch_bounds__(kT) void match_cost_reduce_kernel(const float* __restrict__ part_qt, const float* __restrict__ part_q,
                                                                const float* __restrict__ tsum, const int32_t* __restrict__ t_first,
                                                                const int32_t* __restrict__ t_count, float* __restrict__ cost, int nwg, int G,
@@ -555,10 +565,10 @@ __global__ __launch_bounds__(kT) void match_cost_reduce_kernel(const float* __re
 struct McGeom {
     int ntiles, tiles_per_wg, nwg, qgroups;
 };
-McGeom mc_geom(int G, int Q, int P)
+McGeom mc_geom(int G, int Q, int P, int F = 1)
 {
     McGeom m;
-    m.ntiles = (P + kMP - 1) / kMP;
+    m.ntiles = F * ((P + kMP - 1) / kMP);          // of all frames
     m.qgroups = (Q + kMQ - 1) / kMQ;
     // two workgroups fit a CU (208 VGPRs): ONE full round of 512 (768 workgroups = 1.5 rounds measured 8 % slower)
     const int want = std::max(1, 512 / std::max(1, G * m.qgroups));
@@ -568,20 +578,59 @@ McGeom mc_geom(int G, int Q, int P)
 }
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-template <int TCH>
+template <int TCH, bool CLIP>
 void launch_mc(dim3 grid, hipStream_t st, const __hip_bfloat16* embed, const int64_t* embed_first, int64_t ers, const __hip_bfloat16* feat,
                int64_t feat_bs, const int32_t* gi, int h, int w, const float* coords, const float* tsamp, const int32_t* t_first,
-               const int32_t* t_count, float* pqt, float* pq, int G, int Q, int Tmax, int P, int tpw)
+               const int32_t* t_count, float* pqt, float* pq, int G, int Q, int Tmax, int P, int tpw, int64_t feat_fs, int F)
 {
     const size_t lds = kOffTV + (size_t)kMP * 2 * TCH * 4;
     // > 64 KB of dynamic LDS needs the attribute; it is PER DEVICE, so it is set (and checked) on every launch like loss.hip does
     if (lds > 48 * 1024 &&
-        mpf::check(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_cost_fused_kernel<TCH>),
+        mpf::check(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_cost_fused_kernel<TCH, CLIP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                    "match_cost_fused: hipFuncSetAttribute") != 0)
         return;
-    hipLaunchKernelGGL(match_cost_fused_kernel<TCH>, grid, dim3(kT), lds, st, embed, embed_first, ers, feat, feat_bs, gi, h, w, coords, tsamp,
-                       t_first, t_count, pqt, pq, G, Q, Tmax, P, tpw);
+    hipLaunchKernelGGL((match_cost_fused_kernel<TCH, CLIP>), grid, dim3(kT), lds, st, embed, embed_first, ers, feat, feat_bs, gi, h, w, coords,
+                       tsamp, t_first, t_count, pqt, pq, G, Q, Tmax, P, tpw, feat_fs, F);
+}
+
+// the three launches of both entries: target row sums, per-workgroup partial sums, fixed-order fold
+template <bool CLIP>
+int mc_run(const void* embed, const int64_t* embed_first, int64_t embed_row_stride, const void* features, int64_t feat_bs, int64_t feat_fs,
+           const int32_t* group_image, int h, int w, const float* coords, const float* tsamp, int tsamp_rows, const int32_t* t_first,
+           const int32_t* t_count, float* cost, int G, int Q, int Tmax, int P, int F, float w_mask, float w_dice, void* workspace,
+           void* stream, const char* what)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const McGeom m = mc_geom(G, Q, P, F);
+    char* ws = (char*)workspace;
+    float* pqt = (float*)ws;
+    float* pq = (float*)(ws + align256((size_t)m.nwg * G * Q * Tmax * 2 * 4));
+    float* tsum = (float*)((char*)pq + align256((size_t)m.nwg * G * Q * 2 * 4));
+    const __hip_bfloat16* e = (const __hip_bfloat16*)embed;
+    const __hip_bfloat16* f = (const __hip_bfloat16*)features;
+    hipLaunchKernelGGL(tsamp_rowsum_kernel, dim3(tsamp_rows), dim3(kT), 0, st, tsamp, tsum, tsamp_rows, F * P);
+    const dim3 grid(m.nwg, G, m.qgroups);
+    const int need = (Tmax + 1) / 2;
+    mpf::prof_begin(st);
+    mpf::set_kernel("match_cost_fused_kernel");
+#define MPF_MC(TCH) launch_mc<TCH, CLIP>(grid, st, e, embed_first, embed_row_stride, f, feat_bs, group_image, h, w, coords, tsamp, t_first, \
+                                         t_count, pqt, pq, G, Q, Tmax, P, m.tiles_per_wg, feat_fs, F)
+    if (need <= 4) MPF_MC(4);
+    else if (need <= 8) MPF_MC(8);
+    else if (need <= 12) MPF_MC(12);
+    else if (need <= 16) MPF_MC(16);
+    else if (need <= 24) MPF_MC(24);
+    else if (need <= 32) MPF_MC(32);
+    else MPF_MC(64);
+#undef MPF_MC
+    // gathers: 4 corner rows of 512 B per point; flops: the two-plane product
+    mpf::prof_end("match_cost_fused_kernel", st, (double)G * m.qgroups * F * P * 2048.0 + (double)tsamp_rows * F * P * 4.0,
+                  2.0 * 2.0 * (double)G * Q * F * P * kC);
+    const int64_t n = (int64_t)G * Q * Tmax;
+    hipLaunchKernelGGL(match_cost_reduce_kernel, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, st, pqt, pq, tsum, t_first, t_count, cost,
+                       m.nwg, G, Q, Tmax, F * P, w_mask, w_dice);
+    return mpf::check(hipGetLastError(), what);
 }
 
 }  // namespace
@@ -610,36 +659,38 @@ extern "C" int mpf_match_cost_fused(const void* embed, const int64_t* embed_firs
     if (G > 65535 || (int64_t)G * Q * Tmax >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_fused: too many groups");
     if (workspace_bytes < mpf_match_cost_fused_workspace_bytes(G, Q, Tmax, P, tsamp_rows))
         return mpf::fail(MPF_E_SHAPE, "match_cost_fused: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const McGeom m = mc_geom(G, Q, P);
-    char* ws = (char*)workspace;
-    float* pqt = (float*)ws;
-    float* pq = (float*)(ws + align256((size_t)m.nwg * G * Q * Tmax * 2 * 4));
-    float* tsum = (float*)((char*)pq + align256((size_t)m.nwg * G * Q * 2 * 4));
-    const __hip_bfloat16* e = (const __hip_bfloat16*)embed;
-    const __hip_bfloat16* f = (const __hip_bfloat16*)features;
-    hipLaunchKernelGGL(tsamp_rowsum_kernel, dim3(tsamp_rows), dim3(kT), 0, st, tsamp, tsum, tsamp_rows, P);
-    const dim3 grid(m.nwg, G, m.qgroups);
-    const int need = (Tmax + 1) / 2;
-    mpf::prof_begin(st);
-    mpf::set_kernel("match_cost_fused_kernel");
-#define MPF_MC(TCH) launch_mc<TCH>(grid, st, e, embed_first, embed_row_stride, f, feat_img_stride, group_image, h, w, coords, tsamp, t_first, \
-                                   t_count, pqt, pq, G, Q, Tmax, P, m.tiles_per_wg)
-    if (need <= 4) MPF_MC(4);
-    else if (need <= 8) MPF_MC(8);
-    else if (need <= 12) MPF_MC(12);
-    else if (need <= 16) MPF_MC(16);
-    else if (need <= 24) MPF_MC(24);
-    else if (need <= 32) MPF_MC(32);
-    else MPF_MC(64);
-#undef MPF_MC
-    // gathers: 4 corner rows of 512 B per point; flops: the two-plane product
-    mpf::prof_end("match_cost_fused_kernel", st, (double)G * m.qgroups * P * 2048.0 + (double)tsamp_rows * P * 4.0,
-                  2.0 * 2.0 * (double)G * Q * P * kC);
-    const int64_t n = (int64_t)G * Q * Tmax;
-    hipLaunchKernelGGL(match_cost_reduce_kernel, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, st, pqt, pq, tsum, t_first, t_count, cost,
-                       m.nwg, G, Q, Tmax, P, w_mask, w_dice);
-    return mpf::check(hipGetLastError(), "mpf_match_cost_fused");
+    return mc_run<false>(embed, embed_first, embed_row_stride, features, feat_img_stride, 0, group_image, h, w, coords, tsamp, tsamp_rows, t_first,
+                         t_count, cost, G, Q, Tmax, P, 1, w_mask, w_dice, workspace, stream, "mpf_match_cost_fused");
+}
+
+extern "C" size_t mpf_match_cost_fused_clip_workspace_bytes(int G, int Q, int Tmax, int P, int F, int tsamp_rows)
+{
+    if (G <= 0 || Q <= 0 || Tmax <= 0 || P <= 0 || F <= 0 || tsamp_rows < 0 || (int64_t)F * P >= (1ll << 31)) return 0;
+    const McGeom m = mc_geom(G, Q, P, F);
+    return align256((size_t)m.nwg * G * Q * Tmax * 2 * 4) + align256((size_t)m.nwg * G * Q * 2 * 4) + align256((size_t)tsamp_rows * 4);
+}
+
+extern "C" int mpf_match_cost_fused_clip(const void* embed, const int64_t* embed_first, int64_t embed_row_stride, const void* features,
+                                         int64_t feat_clip_stride, int64_t feat_frame_stride, const int32_t* group_clip, int h, int w,
+                                         int channels, const float* coords, const float* tsamp, int tsamp_rows, const int32_t* t_first,
+                                         const int32_t* t_count, float* cost, int G, int Q, int Tmax, int P, int F, float w_mask,
+                                         float w_dice, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!embed || !embed_first || !features || !group_clip || !coords || !tsamp || !t_first || !t_count || !cost || !workspace)
+        return mpf::fail(MPF_E_NULL, "match_cost_fused_clip: NULL buffer");
+    if (channels != kC) return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: 256 channels only");
+    if (G <= 0 || Q <= 0 || Tmax <= 0 || P <= 0 || F <= 0 || h <= 0 || w <= 0 || tsamp_rows <= 0)
+        return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: bad sizes");
+    if (Tmax > 128) return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: at most 128 tubes per clip");
+    if ((embed_row_stride % 8) || (feat_clip_stride % 8) || (feat_frame_stride % 8))
+        return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: rows must be 16-byte aligned");
+    if (feat_frame_stride < (int64_t)h * w * kC) return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: frames overlap");
+    if (G > 65535 || F > 65535 || (int64_t)G * Q * Tmax >= (1ll << 31) || (int64_t)F * P >= (1ll << 31))
+        return mpf::fail(MPF_E_TOO_LARGE, "match_cost_fused_clip: too many groups, frames or samples");
+    if (workspace_bytes < mpf_match_cost_fused_clip_workspace_bytes(G, Q, Tmax, P, F, tsamp_rows))
+        return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: workspace too small");
+    return mc_run<true>(embed, embed_first, embed_row_stride, features, feat_clip_stride, feat_frame_stride, group_clip, h, w, coords, tsamp,
+                        tsamp_rows, t_first, t_count, cost, G, Q, Tmax, P, F, w_mask, w_dice, workspace, stream, "mpf_match_cost_fused_clip");
 }
 
 extern "C" int mpf_pair_planes_forward(const void* embed, const int64_t* row_off, const int32_t* pair_of_slot, const int32_t* slot_first,

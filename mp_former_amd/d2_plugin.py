@@ -209,12 +209,14 @@ def register_backbone(backbone_registry=None, backbone_base=None, shape_spec=Non
 register_backbone()     # (as register(): at import, a no-op without detectron2)
 
 
-def install_native_video_decoder(model):
+def install_native_video_decoder(model, factored_masks=False):
     """Replace ``model.sem_seg_head.predictor`` of a reference ``VideoMaskFormer`` — its torch
     ``VideoMultiScaleMaskedTransformerDecoder`` — by the native module (video_decoder.py) built from the old one's fields, with
     the old one's state dict loaded strictly, on its device and in its training mode.  Returns the new module.  Composes with
     ``install_native_video_inference`` and ``install_native_video_training`` in any order: those replace the eval branch of
-    ``forward`` and the criterion, this the module between the pixel decoder and them."""
+    ``forward`` and the criterion, this the module between the pixel decoder and them.
+    ``factored_masks``: in training the module hands ``pred_masks`` over as ``mask_fused.FactoredClipMasks`` and never writes the
+    [B, L * Q, T, h, w] maps.  Only the criterion of ``install_native_video_training`` reads that form: install both."""
     from .video_decoder import VideoMultiScaleMaskedTransformerDecoder
     old = model.sem_seg_head.predictor
     hidden = old.decoder_norm.normalized_shape[0]
@@ -228,6 +230,7 @@ def install_native_video_decoder(model):
     new.to(old.decoder_norm.weight.device)
     new.load_state_dict(old.state_dict(), strict=True)
     new.train(old.training)
+    new.factored_masks = bool(factored_masks)
     model.sem_seg_head.predictor = new
     return new
 
@@ -316,7 +319,8 @@ def install_native_video_training(model):
     ``VideoSetCriterion`` built from the old one's fields (matcher weights and points, ``num_classes``, ``weight_dict``,
     ``eos_coef``, ``losses`` and the three sampling parameters) and ``model.prepare_targets`` one that calls
     ``prepare_video_targets`` (bool masks, no float copy).  The training branch of ``forward`` (:190-203) runs on as it is; the
-    eval branch and ``install_native_video_inference`` are not touched.  Returns the new criterion."""
+    eval branch and ``install_native_video_inference`` are not touched.  The criterion takes ``pred_masks`` as tensors or as
+    the factors of ``install_native_video_decoder(model, factored_masks=True)``.  Returns the new criterion."""
     from .video_losses import VideoHungarianMatcher, VideoSetCriterion, prepare_video_targets
     old = model.criterion
     matcher = VideoHungarianMatcher(cost_class=old.matcher.cost_class, cost_mask=old.matcher.cost_mask,

@@ -9,6 +9,9 @@ the criterion a ``FactoredMasks`` (mask_embed rows + channel-last mask_features)
   * ``pair_planes``: the logits planes of the matched / mask-piloted (prediction, target) pairs only, as one MFMA launch over
     embedding rows gathered by the device assignment's indices, differentiable w.r.t. both factors (native backward);
   * ``full_product``: the same kernel over all rows — what a caller of the reference interface gets as ``pred_masks``.
+Clips (``FactoredClipMasks``, ``match_cost_fused_clip``): the mask features of a clip are one tall image [B, 256, T * h, w], so
+``pair_planes`` writes a tube's T frame planes back to back; the matching cost has its own entry, which pads every frame with
+zeros on its own and sums over the T * P samples of one shared point set.
 bf16, 256 channels, GPU only (no CPU or eager fallback: unsupported shapes are rejected by ``supported`` before use).
 """
 import numpy as np
@@ -164,6 +167,73 @@ class FactoredMasks:
     def row_offsets(self, b, q):
         """numpy int64: element offsets (from me.data_ptr()) of the embedding rows of (image b, row q of this view)."""
         return b * self.me.stride(0) + (self.q0 + q) * self.me.stride(1)
+
+
+class FactoredClipMasks(FactoredMasks):
+    """Rows [q0, q1) of every clip of ``einsum("bqc,btchw->bqthw", me, mf5)``, unevaluated: ``mf4`` is the clip's mask features
+    as ONE tall image [B, 256, T * h, w] (frame f = rows f * h .. (f + 1) * h), the form the clip decoder's product runs on.
+    Behaves like the [B, q1 - q0, T, h, w] tensor where the clip criterion touches it (shape, dim-1 slicing, detach);
+    anything else goes through ``materialize()``."""
+
+    def __init__(self, me, mf4, T, q0=0, q1=None):
+        super().__init__(me, mf4, q0, q1)
+        self.T = int(T)
+        if mf4.shape[2] % self.T:
+            raise RuntimeError(f"a tall image of {mf4.shape[2]} rows does not hold {self.T} frames")
+
+    @property
+    def shape(self):
+        return torch.Size((self.me.shape[0], self.q1 - self.q0, self.T, self.mf.shape[2] // self.T, self.mf.shape[3]))
+
+    def dim(self):
+        return 5
+
+    def same_factors(self, other):
+        return isinstance(other, FactoredClipMasks) and other.me is self.me and other.mf is self.mf and other.T == self.T
+
+    def __getitem__(self, idx):
+        if isinstance(idx, tuple) and len(idx) == 2 and idx[0] == slice(None) and isinstance(idx[1], slice):
+            a, b, step = idx[1].indices(self.q1 - self.q0)
+            if step == 1:
+                return FactoredClipMasks(self.me, self.mf, self.T, self.q0 + a, self.q0 + max(a, b))
+        return self.materialize()[idx]
+
+    def detach(self):
+        return FactoredClipMasks(self.me.detach(), self.mf.detach(), self.T, self.q0, self.q1)
+
+    def materialize(self):
+        me = self.me[:, self.q0:self.q1]
+        # (operands the native product does not take — a criterion handed factors it cannot use — go through the library)
+        prod = full_product(me, self.mf) if supported(me, self.mf) else torch.einsum("bqc,bchw->bqhw", me, self.mf)
+        return prod.view(self.shape)
+
+
+def match_cost_fused_clip(views, coords, tsamp, t_first, t_count, group_view, group_clip, Q, Tmax, w_mask, w_dice):
+    """Mask + dice matching cost of tubes (mask2former_video/modeling/matcher.py:113-148) of G groups from the factors -> fp32
+    [G, Q, Tmax].  views: FactoredClipMasks of one (me, mf4); group g = rows of views[group_view[g]] in clip group_clip[g];
+    coords [G, P, 2]: ONE point set for all frames of the group; tsamp [rows, T * P] frame-major."""
+    root = views[0]
+    me, mf, T = root.me, root.mf, root.T
+    dev = me.device
+    G, P = coords.shape[0], coords.shape[1]
+    h, W = mf.shape[2] // T, mf.shape[3]
+    # rows of T * P floats, however the sampler shaped them ([rows * T, P] per plane is the same memory)
+    if not tsamp.is_contiguous() or tsamp.numel() % (T * P):
+        raise RuntimeError(f"target samples of {tuple(tsamp.shape)} are not rows of {T} x {P}")
+    rows = tsamp.numel() // (T * P)
+    if int(np.max(np.asarray(t_first) + np.asarray(t_count))) > rows:
+        raise RuntimeError("a group's target rows lie outside the target samples")
+    first = np.array([views[v].row_offsets(int(b), 0) for v, b in zip(group_view, group_clip)], dtype=np.int64)
+    first_d = upload(first, dev)
+    i32 = upload(np.concatenate([group_clip, t_first, t_count]).astype(np.int32), dev)
+    cost = torch.zeros((G, Q, Tmax), dtype=torch.float32, device=dev)
+    st = _lib.stream_ptr(dev)
+    ws = _lib.scratch("match_cost_fused_clip", dev, st, _lib.lib().mpf_match_cost_fused_clip_workspace_bytes(G, Q, Tmax, P, T, rows))
+    _lib.call("mpf_match_cost_fused_clip", dev, me.data_ptr(), first_d.data_ptr(), me.stride(1), mf.data_ptr(), mf.stride(0),
+              h * W * mf.shape[1], i32[:G].data_ptr(), h, W, mf.shape[1], coords.data_ptr(), tsamp.data_ptr(), rows,
+              i32[G:2 * G].data_ptr(), i32[2 * G:].data_ptr(), cost.data_ptr(), G, Q, Tmax, P, T, float(w_mask), float(w_dice),
+              ws.data_ptr(), ws.numel(), st)
+    return cost
 
 
 def match_cost_fused(views, coords, tsamp, t_first, t_count, group_view, group_image, Q, Tmax, w_mask, w_dice):

@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, mask_fused
 from .attention import attention_core
 from .decoder_layer import decoder_layer_pos
 from .pixel_decoder import _ConvNorm, _c2_xavier_fill
@@ -200,7 +200,9 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
                 self.input_proj.append(nn.Sequential())
         self.class_embed = nn.Linear(hidden_dim, num_classes + 1)
         self.mask_embed = MLP(hidden_dim, hidden_dim, mask_dim, 3)
-        self.factored_masks = False      # (read by the shared batched heads: the clip criterion takes materialised maps)
+        # True: in training mode "pred_masks" are mask_fused.FactoredClipMasks (for mp_former_amd's VideoSetCriterion, which takes
+        # the matching cost and the matched tubes' planes from the factors); the [B, L * Q, T, h, w] maps are then never formed
+        self.factored_masks = False
         self.mask_log = None             # tests: a list here receives the attention mask made after every layer, the last included
         self.fused_layers = None         # None: the rule of ``_one_call_layers``; True / False: that route (tests, the bench tool)
 
@@ -394,6 +396,9 @@ class VideoMultiScaleMaskedTransformerDecoder(nn.Module):
         predictions_class, planes = self._heads_batched(W, streams, mf4)
         # the batched heads return dim-1 slices of ONE parent [B, L * Q, T * h, w]; seen per frame they are slices of
         # [B, L * Q, T, h, w], which clip_planes / MapSet address through that parent
-        predictions_mask = [m.view(bs, m.shape[1], t, h_m, w_m) for m in planes]
+        if isinstance(planes[0], mask_fused.FactoredMasks):      # factored_masks, training, operands the native product takes
+            predictions_mask = [mask_fused.FactoredClipMasks(m.me, m.mf, t, m.q0, m.q1) for m in planes]
+        else:
+            predictions_mask = [m.view(bs, m.shape[1], t, h_m, w_m) for m in planes]
         return {"pred_logits": predictions_class[-1], "pred_masks": predictions_mask[-1],
                 "aux_outputs": self._set_aux_loss(predictions_class, predictions_mask)}

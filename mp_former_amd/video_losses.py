@@ -10,6 +10,9 @@ kind: it sums over the F * P samples of ONE point set shared by every frame and 
     g * F + f; no float copy exists;
   * predictions: ``pred_masks`` [B, Q, F, h, w] is addressed in place as [B, Q * F, h, w] (``MapSet``): no gathered
     [M * F, 1, h, w] copy, and the gradient of the sums goes to it in one piece;
+  * predictions as factors (``mask_fused.FactoredClipMasks``, the clip decoder with ``factored_masks = True``): the matching
+    cost comes from (mask_embed, mask_features) directly (``mpf_match_cost_fused_clip``), and only the matched tubes get planes:
+    ``PairPlanes`` on the clip as one tall image writes a pair's F frame planes back to back, which ARE its (pair, frame) rows;
   * assignment: the device solver by default (lsa.py) — the step has no device->host copy; it reports per pair the tube and
     the element offset of the matched query's first frame, which are expanded to (pair, frame) rows on the device.
 """
@@ -23,8 +26,10 @@ from ._h2d import upload
 from .criterion import LossDict, SetCriterion, group_mask_losses, strided_stack
 from .dist import distributed, global_num_masks, global_num_masks_device
 from .lsa import MAX_DIM as LSA_MAX_DIM, lsa_assign
+from . import mask_fused
+from .mask_fused import FactoredClipMasks, PairPlanes, match_cost_fused_clip
 from .matcher import GTMasks, HungarianMatcher
-from .point_sample import MapSet, MaskLossSums, match_cost_clip, sample_select_uncertain
+from .point_sample import MapSet, MaskLossSums, MaskLossSumsPlanes, match_cost_clip, sample_select_uncertain
 
 
 def prepare_video_targets(frame_masks, frame_ids, classes, padded_hw):
@@ -46,7 +51,9 @@ def prepare_video_targets(frame_masks, frame_ids, classes, padded_hw):
 
 def clip_planes(pred_masks):
     """[B, Q, F, h, w] -> the same memory as [B, Q * F, h, w] where the strides allow it (a query-slice view of a larger tensor
-    does), a copy otherwise: frame f of query q is row q * F + f."""
+    does), a copy otherwise: frame f of query q is row q * F + f.  Factors are evaluated first."""
+    if isinstance(pred_masks, FactoredClipMasks):
+        pred_masks = pred_masks.materialize()
     B, Q, Fr, h, w = pred_masks.shape
     return pred_masks.reshape(B, Q * Fr, h, w)
 
@@ -94,8 +101,6 @@ class VideoHungarianMatcher(HungarianMatcher):
         Fr = gt.F
         if outs[0]["pred_masks"].shape[2] != Fr:
             raise RuntimeError(f"pred_masks has {outs[0]['pred_masks'].shape[2]} frames, the targets {Fr}")
-        if mapset is None:
-            mapset = MapSet([clip_planes(o["pred_masks"]) for o in outs])
         Tt, Tmax = gt.total, gt.tmax
         counts = np.asarray(gt.counts, dtype=np.int64)
         firsts = np.asarray(gt.offsets[:-1], dtype=np.int64)
@@ -103,6 +108,19 @@ class VideoHungarianMatcher(HungarianMatcher):
         n_planes = Tt * Fr
         gt_offs = np.tile(np.arange(n_planes, dtype=np.int64) * (gt.H * gt.W), L)
         gcrow = (np.repeat(np.arange(L), n_planes) * B + np.tile(gt.image_of_row, L)).astype(np.int32)
+        masks = [o["pred_masks"] for o in outs]
+        if (mapset is None and not self.reference_amp_rounding and Tmax <= 128
+                and all(isinstance(m, FactoredClipMasks) and m.same_factors(masks[0]) for m in masks)
+                and mask_fused.supported(masks[0].me, masks[0].mf)):
+            # the maps are kept as (mask_embed, mask_features): cost straight from the factors (csrc/mask_fused.hip)
+            tsamp = self._gt_samples(gt, upload(gt_offs, dev), coords, upload(gcrow, dev), dev)
+            l_idx, b_idx = np.meshgrid(np.arange(L), np.arange(B), indexing="ij")
+            l_idx, b_idx = l_idx.reshape(-1), b_idx.reshape(-1)
+            C = match_cost_fused_clip(masks, coords, tsamp, l_idx * Tt + firsts[b_idx], counts[b_idx], l_idx, b_idx, Q, Tmax,
+                                      self.cost_mask, self.cost_dice).view(L, B, Q, Tmax)
+            return self._add_class_cost(C, outs, targets, gt)
+        if mapset is None:
+            mapset = MapSet([clip_planes(m) for m in masks])
         l_idx, b_idx, q_idx = np.meshgrid(np.arange(L), np.arange(B), np.arange(Q), indexing="ij")
         l_idx, b_idx, q_idx = l_idx.reshape(-1), b_idx.reshape(-1), q_idx.reshape(-1)
         pred_offs = mapset.offsets(l_idx, b_idx, q_idx * Fr)                # frame 0 of every (output, clip, query)
@@ -138,8 +156,18 @@ class VideoSetCriterion(SetCriterion):
         num_masks = global_num_masks_device(n_local, dev) if distributed() else global_num_masks(n_local, dev)
 
         gt = GTTubes(targets)
-        ms = MapSet([clip_planes(o["pred_masks"]) for o in outs])
-        hw = ms.h * ms.w
+        # the clip decoder's training path may hand the predictions over as their factors (mask_fused.FactoredClipMasks):
+        # matching cost and loss planes are then produced from (mask_embed, mask_features) and no [B, Q, F, h, w] map exists;
+        # factors this route cannot take (mixed, more than 128 tubes in a clip, unsupported operands) are evaluated here
+        masks = [o["pred_masks"] for o in outs]
+        fm = masks[0] if isinstance(masks[0], FactoredClipMasks) else None
+        if fm is not None and not (all(fm.same_factors(m) for m in masks) and gt.tmax <= 128 and mask_fused.supported(fm.me, fm.mf)):
+            fm = None
+        if fm is None and any(isinstance(m, FactoredClipMasks) for m in masks):
+            masks = [m.materialize() if isinstance(m, FactoredClipMasks) else m for m in masks]
+            outs = [{"pred_logits": o["pred_logits"], "pred_masks": m} for o, m in zip(outs, masks)]
+        ms = MapSet([clip_planes(m) for m in masks]) if fm is None else None
+        hw = h * w
 
         # ---- stage 1: all matchings (device solver, or MPF_DEVICE_LSA=0 / a large problem: one D2H copy + SciPy) ----------------
         tags = ["match" + s for s in suffixes]
@@ -194,21 +222,46 @@ class VideoSetCriterion(SetCriterion):
 
         # ---- index arrays of the pairs -> device; the solver fills them; then one row per (pair, frame) ------------------------
         tc_main_d = torch.full((L, B, Q), K, dtype=torch.int64, device=dev) if dev_lsa else None
+        planes = None
         if n_pairs:
-            p_offs = ms.offsets(ti, bi, qi * Fr)                            # frame 0 of the matched query
-            g_offs = ms.grad_offsets(ti, bi, qi * Fr)
-            if not dev_lsa:
-                assert len(np.unique(g_offs)) == n_pairs, "a prediction tube is paired twice in one step"
+            if fm is not None:
+                # factors: pair i = embedding row p_offs[i] (elements from mask_embed's base) -> slot[i] of a compact
+                # [pairs, F * h * w] tensor produced AFTER the assignment: the pair's F frame planes back to back
+                q0s = np.array([m.q0 for m in masks], dtype=np.int64)
+                p_offs = bi * fm.me.stride(0) + (q0s[ti] + qi) * fm.me.stride(1)
+                slot, s_first, s_count = self._slot_layout(bi, B)
+                g_offs = slot * (Fr * hw)
+                # (a pair's slot does not depend on the matched query)
+                q_stride, g_stride = np.full(n_pairs, fm.me.stride(1), dtype=np.int64), 0
+                if not dev_lsa:
+                    # mpf_pair_planes_backward WRITES the d_embed row of a slot (include/mpformer_hip.h): rows must be distinct
+                    assert len(np.unique(p_offs)) == n_pairs, "an embedding row is paired twice in one step"
+            else:
+                p_offs = ms.offsets(ti, bi, qi * Fr)                        # frame 0 of the matched query
+                g_offs = ms.grad_offsets(ti, bi, qi * Fr)
+                q_stride, g_stride = ms.s1[ms.base_of[ti]] * Fr, Fr * hw    # a query is F planes further on
+                if not dev_lsa:
+                    assert len(np.unique(g_offs)) == n_pairs, "a prediction tube is paired twice in one step"
             up = upload(np.concatenate([p_offs, g_offs]), dev)
             pair_pred, pair_grad = up[:n_pairs], up[n_pairs:]
             pair_tube = upload(tube.astype(np.int32), dev)
             if dev_lsa and problems:
                 pr = np.asarray(problems, dtype=np.int64)
                 pos = pr[:, 4]
-                pr[:, 6], pr[:, 7] = p_offs[pos], ms.s1[ms.base_of[ti[pos]]] * Fr      # a query is F planes further on
-                pr[:, 8], pr[:, 9] = g_offs[pos], Fr * hw
-                lsa_assign(C, pr, n_pairs, want_rows=False, scatter_dst=tc_main_d, scatter_src=labels_dev,
-                           into={"cols": pair_tube, "a": pair_pred, "b": pair_grad})
+                pr[:, 6], pr[:, 7] = p_offs[pos], q_stride[pos]
+                pr[:, 8], pr[:, 9] = g_offs[pos], g_stride
+                into = {"cols": pair_tube, "a": pair_pred}
+                if fm is None:
+                    into["b"] = pair_grad
+                lsa_assign(C, pr, n_pairs, want_rows=False, scatter_dst=tc_main_d, scatter_src=labels_dev, into=into)
+            if fm is not None:
+                inv = np.zeros(n_pairs, dtype=np.int32)
+                inv[slot] = np.arange(n_pairs, dtype=np.int32)
+                i32 = upload(np.concatenate([inv, s_first, s_count]), dev)
+                planes = PairPlanes.apply(fm.me, fm.mf, pair_pred, i32[:n_pairs], i32[n_pairs:n_pairs + B], i32[n_pairs + B:],
+                                          n_pairs, int(s_count.max()))
+                ms = MapSet([planes.view(1, n_pairs * Fr, h, w)])
+                pair_pred = pair_grad               # from here on a pair is addressed by its planes
             fr = torch.arange(Fr, dtype=torch.int64, device=dev)
             pred_offs = (pair_pred[:, None] + fr * hw).reshape(-1)           # row = pair * F + frame (criterion.py:154-155)
             grad_offs = (pair_grad[:, None] + fr * hw).reshape(-1)
@@ -223,7 +276,10 @@ class VideoSetCriterion(SetCriterion):
                     coords = sample_select_uncertain(ms, pred_offs, coords_over, num_uncertain, P)
                     if P - num_uncertain > 0:
                         coords[:, num_uncertain:] = _rng.rand_cat(rand_parts, dev)
-                sums = MaskLossSums.apply(ms, pred_offs, grad_offs, gt, gt_rows, coords, *ms.bases)
+                if planes is not None:
+                    sums = MaskLossSumsPlanes.apply(ms, pred_offs, gt, gt_rows, coords, planes)
+                else:
+                    sums = MaskLossSums.apply(ms, pred_offs, grad_offs, gt, gt_rows, coords, *ms.bases)
                 if torch.is_tensor(num_masks):
                     norm = num_masks * upload([1.0] * L, dev, torch.float32)
                 else:
@@ -233,7 +289,10 @@ class VideoSetCriterion(SetCriterion):
                 # no tube anywhere: sums over empty sets (still consume the draws for RNG parity)
                 _rng.rand_cat(over_parts, dev)
                 _rng.rand_cat(rand_parts, dev)
-                zero = sum(o["pred_masks"].sum() * 0.0 for o in outs).float()
+                if fm is not None:
+                    zero = (fm.me.sum() * 0.0 + fm.mf.sum() * 0.0).float()
+                else:
+                    zero = sum(m.sum() * 0.0 for m in masks).float()
                 g_mask = g_dice = zero.expand(L)
             losses.add_group(["loss_mask" + s_ for s_ in suffixes], g_mask)
             losses.add_group(["loss_dice" + s_ for s_ in suffixes], g_dice)
