@@ -1520,6 +1520,31 @@ int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, const int* ar
                               size_t workspace_bytes, void* stream);
 
 /*
+ * Instance boxes from masks and bbox AP on the device (csrc/seg_box.hip, csrc/seg_ap.hip).  The reference's instance_inference
+ * returns pred_boxes as zeros and says "Uncomment the following to get boxes from masks (this is slow)"
+ * (mask2former/maskformer_model.py:393-395: BitMasks(mask_pred > 0).get_bounding_boxes()); on packed bits the box of a mask costs
+ * one read of 1/8 byte per pixel.
+ *   mpf_seg_bits_boxes:    bits uint64 [M, nwords] in the layout above (p = x * H + y, zero at and past H * W) -> boxes int32
+ *                          [M, 4] = (x0, y0, x1, y1) with x0 = min x, y0 = min y, x1 = max x + 1, y1 = max y + 1 over the set
+ *                          pixels (Detectron2's BitMasks.get_bounding_boxes); an empty mask gives (0, 0, 0, 0).  Bits at or past
+ *                          H * W are not looked at.  H * W < 2^31 and M <= 65535 (else MPF_E_TOO_LARGE); M == 0 launches nothing.
+ *                          Integer only, one writer per box, no atomics: bitwise reproducible.
+ *   mpf_seg_ap_match_box:  mpf_seg_ap_match with boxes in place of the three count arrays: dt_box float64 [D, 4] (score order) and
+ *                          gt_box float64 [G, 4], both XYWH as a COCO json holds them.  A pair's IoU is pycocotools' bbIou in
+ *                          double: w = min(dx + dw, gx + gw) - max(dx, gx), h likewise; w <= 0 or h <= 0: IoU 0; else i = w * h,
+ *                          u = dw * dh for a crowd ground truth under crowd_rule 0, else dw * dh + gw * gh - i; IoU = i / u.
+ *                          Every operation is rounded on its own (no FMA contraction), so a host restatement in IEEE double
+ *                          gives the same bits.  An unmatched detection is tested against the ranges with dw * dh (the "area"
+ *                          COCO's loadRes gives a bbox result); gt_area is the caller's.  Everything else, the records included,
+ *                          as mpf_seg_ap_match; dt_box NULL with D > 0 or gt_box NULL with G > 0: MPF_E_NULL.
+ */
+int mpf_seg_bits_boxes(const uint64_t* bits, int M, int H, int W, int* boxes /* [M, 4] */, void* stream);
+int mpf_seg_ap_match_box(const double* dt_box /* [D,4] xywh, score order */, const double* gt_box /* [G,4] xywh */, int D, int G,
+                         const float* dt_score, const int* dt_cat, const int* gt_cat, const int* gt_crowd, const double* gt_area,
+                         const double* iou_thrs, int Tn, const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image,
+                         int64_t* records, int64_t* npig, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Video instance segmentation (csrc/seg_video.hip, csrc/seg_ap.hip): the eval branch of the reference's VideoMaskFormer
  * (mask2former_video/video_maskformer_model.py:204-287: forward's else branch and inference_video) and its YouTube-VIS score
  * (mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py).  At test time a whole video is one clip: masks [Q, F, h, w], fp32

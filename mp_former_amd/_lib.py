@@ -240,6 +240,9 @@ SIGNATURES = {
     "mpf_seg_mask_boundary": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "mpf_seg_ap_match_boundary": (_c_int, [_c_vp] * 6 + [_c_int, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp] + [_c_int] * 5
                                   + [_c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "mpf_seg_bits_boxes": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_ap_match_box": (_c_int, [_c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 6 + [_c_int, _c_vp] + [_c_int] * 5
+                             + [_c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_seg_video_bits": (_c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64] + [_c_int] * 11 + [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
     "mpf_seg_tube_areas": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_vp]),
     "mpf_seg_ap_match_tube": (_c_int, [_c_vp, _c_vp, _c_vp, _c_int, _c_int] + [_c_vp] * 7 + [_c_int, _c_vp] + [_c_int] * 5

@@ -14,12 +14,15 @@
 //   seg_ap_match_kernel      one thread per (category, area range, IoU threshold): the loop of evaluateVid over the category's first
 //                            maxDet detections and its ground truths, non-ignored first; sets the "matched" / "ignored" bit of its
 //                            setting in the detections' records and adds the non-ignored ground truths to npig[k][a].
-//                            <true> (mpf_seg_ap_match_boundary): a second set of counts, those of the masks' boundaries
+//                            The loop exists once; where a pair's IoU comes from is its template parameter:
+//                            <ApCounts> reads the mask counts alone.  dt_area != NULL (mpf_seg_ap_match_tube): a video.  The counts are
+//                            those of tubes (the frames' packed words concatenated: popcount(a & b) is the tube intersection, area_a +
+//                            area_b - inter iou_seq's union, :203-217) and the ranges test avg_area on both sides (:283, :330).
+//                            <ApBoundary> (mpf_seg_ap_match_boundary): a second set of counts, those of the masks' boundaries
 //                            (seg_boundary.hip), and a pair's IoU is the smaller of the two (boundary-iou-api's computeBoundaryIoU,
-//                            which the reference's tools/evaluate_coco_boundary_ap.py runs); <false> reads the mask counts alone.
-//                            dt_area != NULL (mpf_seg_ap_match_tube): a video.  The counts are those of tubes (the frames' packed words
-//                            concatenated: popcount(a & b) is the tube intersection, area_a + area_b - inter iou_seq's union, :203-217)
-//                            and the ranges test avg_area on both sides (:283, :330); the same <false> instance otherwise
+//                            which the reference's tools/evaluate_coco_boundary_ap.py runs).
+//                            <ApBoxes> (mpf_seg_ap_match_box): XYWH float64 boxes and pycocotools' bbIou, the "bbox" task of COCO
+//                            (boxes of packed masks: seg_box.hip)
 //
 // Exactness: counts are integers; iou = (double)inter / (double)union is the correctly rounded quotient of two integers below 2^53, as
 // python's float / float of the same integers is; the thresholds are the float64 values the host computed (np.linspace), uploaded as
@@ -119,15 +122,68 @@ __device__ __forceinline__ double ap_iou(int inter, int area_d, int area_g, bool
     return (double)inter / (double)uni;
 }
 
-// kBoundary: a second set of counts (the masks' boundaries, csrc/seg_boundary.hip) and the pair's IoU is the smaller of the two
+// The IoU sources of seg_ap_match_kernel: iou(d, g, crowd, crowd_rule) of a pair and det_area(d), the area the ranges test for an
+// unmatched detection.
+// ApCounts: the integer counts of mpf_seg_mask_pairs; dt_area != NULL (tubes): avg_area, not the IoU's pixel count
+struct ApCounts {
+    const int* __restrict__ inter;
+    const int* __restrict__ area_d;
+    const int* __restrict__ area_g;
+    const double* __restrict__ dt_area;
+    int G;
+    __device__ __forceinline__ double iou(int d, int g, bool crowd, int crowd_rule) const
+    {
+        return ap_iou(inter[(int64_t)d * G + g], area_d[d], area_g[g], crowd, crowd_rule);
+    }
+    __device__ __forceinline__ double det_area(int d) const { return dt_area ? dt_area[d] : (double)area_d[d]; }
+};
+
+// ApBoundary: a second set of counts (the masks' boundaries, csrc/seg_boundary.hip) and the pair's IoU is the smaller of the two
 // (boundary-iou-api, COCOeval.computeBoundaryIoU); areas and ranges stay the masks'
-template <bool kBoundary>
-__global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restrict__ inter, const int* __restrict__ area_d,
-                                                            const int* __restrict__ area_g, const int* __restrict__ inter_b,
-                                                            const int* __restrict__ area_db, const int* __restrict__ area_gb, int D, int G,
-                                                            const int* __restrict__ dt_cat, const int* __restrict__ gt_cat,
-                                                            const int* __restrict__ gt_crowd, const double* __restrict__ gt_area,
-                                                            const double* __restrict__ dt_area, const double* __restrict__ thrs, int Tn,
+struct ApBoundary {
+    ApCounts mask, bnd;
+    __device__ __forceinline__ double iou(int d, int g, bool crowd, int crowd_rule) const
+    {
+        return fmin(mask.iou(d, g, crowd, crowd_rule), bnd.iou(d, g, crowd, crowd_rule));
+    }
+    __device__ __forceinline__ double det_area(int d) const { return mask.det_area(d); }
+};
+
+// ApBoxes: XYWH float64 boxes and pycocotools' bbIou (maskApi.c) in its operation order.  Every product, sum and quotient is rounded
+// on its own: the two bodies are compiled with contraction off (`#pragma clang fp contract(off)`; hipcc's default would fuse
+// gw * gh + da and (da + ga) - w * h into v_fma_f64, and the __dmul_rn family of this ROCm's headers are plain operators that fuse
+// the same way), so a host restatement in IEEE double gives the same bits and no ">= threshold" decision differs by rounding.  An
+// unmatched detection is tested with w * h, the "area" COCO's loadRes gives a bbox result.
+struct ApBoxes {
+    const double* __restrict__ dt_box;
+    const double* __restrict__ gt_box;
+    __device__ __forceinline__ double iou(int d, int g, bool crowd, int crowd_rule) const
+    {
+#pragma clang fp contract(off)
+        const double dx = dt_box[4 * (int64_t)d], dy = dt_box[4 * (int64_t)d + 1], dw = dt_box[4 * (int64_t)d + 2], dh = dt_box[4 * (int64_t)d + 3];
+        const double gx = gt_box[4 * (int64_t)g], gy = gt_box[4 * (int64_t)g + 1], gw = gt_box[4 * (int64_t)g + 2], gh = gt_box[4 * (int64_t)g + 3];
+        const double w = fmin(dx + dw, gx + gw) - fmax(dx, gx);
+        const double h = fmin(dy + dh, gy + gh) - fmax(dy, gy);
+        if (w <= 0.0 || h <= 0.0) return 0.0;
+        const double i = w * h, da = dw * dh;
+        if (crowd && crowd_rule == 0) return i / da;
+        const double ga = gw * gh;
+        const double s = da + ga;
+        const double u = s - i;
+        return i / u;
+    }
+    __device__ __forceinline__ double det_area(int d) const
+    {
+#pragma clang fp contract(off)
+        const double w = dt_box[4 * (int64_t)d + 2], h = dt_box[4 * (int64_t)d + 3];
+        return w * h;
+    }
+};
+
+template <class Iou>
+__global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const Iou src, int D, int G, const int* __restrict__ dt_cat,
+                                                            const int* __restrict__ gt_cat, const int* __restrict__ gt_crowd,
+                                                            const double* __restrict__ gt_area, const double* __restrict__ thrs, int Tn,
                                                             const double* __restrict__ rngs, int A, int K, int max_det, int crowd_rule,
                                                             unsigned long long* __restrict__ rec, long long* __restrict__ npig,
                                                             unsigned char* __restrict__ gtm_all)
@@ -163,8 +219,7 @@ __global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restric
                 if (ig != pass) continue;
                 if (gtm[g] && !crowd) continue;                         // :312
                 if (m > -1 && m_ig == 0 && ig == 1) { stop = true; break; }     // :315
-                double v = ap_iou(inter[(int64_t)d * G + g], area_d[d], area_g[g], crowd, crowd_rule);
-                if constexpr (kBoundary) v = fmin(v, ap_iou(inter_b[(int64_t)d * G + g], area_db[d], area_gb[g], crowd, crowd_rule));
+                const double v = src.iou(d, g, crowd, crowd_rule);
                 if (v < best) continue;                                 // :318: equality takes the later ground truth
                 best = v;
                 m = g;
@@ -176,7 +231,7 @@ __global__ __launch_bounds__(kApT) void seg_ap_match_kernel(const int* __restric
             ignored = m_ig != 0;
             atomicOr(&rec[(int64_t)kApRec * d + 2], bit);
         } else {
-            const double da = dt_area ? dt_area[d] : (double)area_d[d];     // tubes: avg_area, not the IoU's pixel count
+            const double da = src.det_area(d);
             ignored = da < lo || da > hi;                               // :330-331
         }
         if (ignored) atomicOr(&rec[(int64_t)kApRec * d + 3], bit);
@@ -238,13 +293,20 @@ extern "C" size_t mpf_seg_ap_workspace_bytes(int G, int A, int Tn)
     return (size_t)A * Tn * G;
 }
 
-// the body of the three entries; boundary: the three boundary counts are checked and seg_ap_match_kernel<true> runs; dt_area (tubes,
-// else NULL): the area the ranges test for an unmatched detection, where the images' entries take the pixel count area_d
-static int ap_match(const char* where, bool boundary, const int* inter, const int* area_d, const int* area_g, const int* inter_b,
-                    const int* area_db, const int* area_gb, int D, int G, const float* dt_score, const int* dt_cat, const int* gt_cat,
-                    const int* gt_crowd, const double* gt_area, const double* dt_area, const double* iou_thrs, int Tn,
-                    const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig,
-                    void* workspace, size_t workspace_bytes, void* stream)
+// What a pair's IoU is computed from: the counts of mpf_seg_mask_pairs (inter [D, G], area_d [D], area_g [G]), with the boundaries'
+// counts as a second set (boundary), or XYWH boxes (box: dt_box [D, 4], gt_box [G, 4]).  dt_area (tubes, else NULL): the area the
+// ranges test for an unmatched detection, where the images' entries take the pixel count area_d
+struct ApSource {
+    bool boundary = false, box = false;
+    const int *inter = nullptr, *area_d = nullptr, *area_g = nullptr, *inter_b = nullptr, *area_db = nullptr, *area_gb = nullptr;
+    const double *dt_area = nullptr, *dt_box = nullptr, *gt_box = nullptr;
+};
+
+// the body of the four entries: one argument check, one records kernel, one workspace rule, one record format
+static int ap_match(const char* where, const ApSource& s, int D, int G, const float* dt_score, const int* dt_cat, const int* gt_cat,
+                    const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn, const double* area_rngs, int A, int K,
+                    int max_det, int crowd_rule, int image, int64_t* records, int64_t* npig, void* workspace, size_t workspace_bytes,
+                    void* stream)
 {
     if (D < 0 || G < 0 || K <= 0 || A <= 0 || Tn <= 0 || max_det <= 0 || image < 0)
         return mpf::fail(MPF_E_SHAPE, "seg_ap_match: need D, G >= 0, K, A, Tn, max_det > 0 and image >= 0");
@@ -252,29 +314,40 @@ static int ap_match(const char* where, bool boundary, const int* inter, const in
     if (crowd_rule != 0 && crowd_rule != 1) return mpf::fail(MPF_E_SHAPE, "seg_ap_match: crowd_rule is 0 (coco) or 1 (union)");
     if ((int64_t)D * G >= (1ll << 31) || (int64_t)K * A * Tn >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "seg_ap_match: too large");
     if (!iou_thrs || !area_rngs || !npig) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL settings or counters");
-    if (D && (!area_d || !dt_score || !dt_cat || !records)) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL detection buffer");
-    if (G && (!area_g || !gt_cat || !gt_crowd || !gt_area || !workspace)) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL ground-truth buffer");
-    if (D && G && !inter) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL pair counts");
-    if (boundary && D && G && (!inter_b || !area_db || !area_gb)) return mpf::fail(MPF_E_NULL, "seg_ap_match_boundary: NULL boundary counts");
+    const void* of_d = s.box ? (const void*)s.dt_box : (const void*)s.area_d;
+    const void* of_g = s.box ? (const void*)s.gt_box : (const void*)s.area_g;
+    if (D && (!of_d || !dt_score || !dt_cat || !records)) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL detection buffer");
+    if (G && (!of_g || !gt_cat || !gt_crowd || !gt_area || !workspace)) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL ground-truth buffer");
+    if (!s.box && D && G && !s.inter) return mpf::fail(MPF_E_NULL, "seg_ap_match: NULL pair counts");
+    if (s.boundary && D && G && (!s.inter_b || !s.area_db || !s.area_gb)) return mpf::fail(MPF_E_NULL, "seg_ap_match_boundary: NULL boundary counts");
     if (workspace_bytes < (size_t)A * Tn * G) return mpf::fail(MPF_E_SHAPE, "seg_ap_match: workspace smaller than mpf_seg_ap_workspace_bytes");
     if (D == 0 && G == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
+    // the launch as mpf_last_kernel reports it; the profiler's name is the part after the records kernel
+    static constexpr char kRecordsPlus[] = "seg_ap_records_kernel+";
+    const char* launched = s.box ? "seg_ap_records_kernel+seg_ap_match_kernel<box>"
+                         : s.boundary ? "seg_ap_records_kernel+seg_ap_match_kernel<boundary>" : "seg_ap_records_kernel+seg_ap_match_kernel";
+    const char* name = launched + sizeof(kRecordsPlus) - 1;
     mpf::prof_begin(st);
-    mpf::set_kernel(boundary ? "seg_ap_records_kernel+seg_ap_match_kernel<boundary>" : "seg_ap_records_kernel+seg_ap_match_kernel");
+    mpf::set_kernel(launched);
     if (D)
         hipLaunchKernelGGL(seg_ap_records_kernel, dim3((unsigned)((D + kApT - 1) / kApT)), dim3(kApT), 0, st, dt_score, dt_cat, D, image,
                            (unsigned long long*)records);
     const int n = K * A * Tn;
     const dim3 grid((unsigned)((n + kApT - 1) / kApT));
-    if (boundary)
-        hipLaunchKernelGGL(seg_ap_match_kernel<true>, grid, dim3(kApT), 0, st, inter, area_d, area_g, inter_b, area_db, area_gb, D, G, dt_cat,
-                           gt_cat, gt_crowd, gt_area, dt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
-                           (long long*)npig, (unsigned char*)workspace);
+    auto launch = [&](auto src) {
+        hipLaunchKernelGGL(seg_ap_match_kernel<decltype(src)>, grid, dim3(kApT), 0, st, src, D, G, dt_cat, gt_cat, gt_crowd, gt_area, iou_thrs,
+                           Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records, (long long*)npig,
+                           (unsigned char*)workspace);
+    };
+    const ApCounts mask{s.inter, s.area_d, s.area_g, s.dt_area, G};
+    if (s.box)
+        launch(ApBoxes{s.dt_box, s.gt_box});
+    else if (s.boundary)
+        launch(ApBoundary{mask, ApCounts{s.inter_b, s.area_db, s.area_gb, nullptr, G}});
     else
-        hipLaunchKernelGGL(seg_ap_match_kernel<false>, grid, dim3(kApT), 0, st, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_cat,
-                           gt_cat, gt_crowd, gt_area, dt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, (unsigned long long*)records,
-                           (long long*)npig, (unsigned char*)workspace);
-    mpf::prof_end(boundary ? "seg_ap_match_kernel<boundary>" : "seg_ap_match_kernel", st, (boundary ? 8.0 : 4.0) * D * G + 32.0 * D);
+        launch(mask);
+    mpf::prof_end(name, st, s.box ? 32.0 * ((double)D + G) + 32.0 * D : (s.boundary ? 8.0 : 4.0) * D * G + 32.0 * D);
     return mpf::check(hipGetLastError(), where);
 }
 
@@ -283,9 +356,10 @@ extern "C" int mpf_seg_ap_match(const int* inter, const int* area_d, const int* 
                                 int Tn, const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
                                 int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return ap_match("mpf_seg_ap_match", false, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_score, dt_cat, gt_cat, gt_crowd,
-                    gt_area, nullptr, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace, workspace_bytes,
-                    stream);
+    ApSource s;
+    s.inter = inter, s.area_d = area_d, s.area_g = area_g;
+    return ap_match("mpf_seg_ap_match", s, D, G, dt_score, dt_cat, gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det,
+                    crowd_rule, image, records, npig, workspace, workspace_bytes, stream);
 }
 
 // one video: the counts are those of the tubes (the frames' words concatenated), gt_area / dt_area their avg_area (mpf_seg_tube_areas)
@@ -296,9 +370,10 @@ extern "C" int mpf_seg_ap_match_tube(const int* inter, const int* area_d, const 
                                      size_t workspace_bytes, void* stream)
 {
     if (D > 0 && !dt_area) return mpf::fail(MPF_E_NULL, "seg_ap_match_tube: NULL dt_area");
-    return ap_match("mpf_seg_ap_match_tube", false, inter, area_d, area_g, nullptr, nullptr, nullptr, D, G, dt_score, dt_cat, gt_cat, gt_crowd,
-                    gt_area, dt_area, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace, workspace_bytes,
-                    stream);
+    ApSource s;
+    s.inter = inter, s.area_d = area_d, s.area_g = area_g, s.dt_area = dt_area;
+    return ap_match("mpf_seg_ap_match_tube", s, D, G, dt_score, dt_cat, gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det,
+                    crowd_rule, image, records, npig, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, const int* area_g, const int* inter_b, const int* area_db,
@@ -307,7 +382,22 @@ extern "C" int mpf_seg_ap_match_boundary(const int* inter, const int* area_d, co
                                          const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
                                          int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return ap_match("mpf_seg_ap_match_boundary", true, inter, area_d, area_g, inter_b, area_db, area_gb, D, G, dt_score, dt_cat, gt_cat,
-                    gt_crowd, gt_area, nullptr, iou_thrs, Tn, area_rngs, A, K, max_det, crowd_rule, image, records, npig, workspace,
-                    workspace_bytes, stream);
+    ApSource s;
+    s.boundary = true;
+    s.inter = inter, s.area_d = area_d, s.area_g = area_g, s.inter_b = inter_b, s.area_db = area_db, s.area_gb = area_gb;
+    return ap_match("mpf_seg_ap_match_boundary", s, D, G, dt_score, dt_cat, gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K,
+                    max_det, crowd_rule, image, records, npig, workspace, workspace_bytes, stream);
+}
+
+// boxes in place of the counts: XYWH float64, the detections' in score order
+extern "C" int mpf_seg_ap_match_box(const double* dt_box, const double* gt_box, int D, int G, const float* dt_score, const int* dt_cat,
+                                    const int* gt_cat, const int* gt_crowd, const double* gt_area, const double* iou_thrs, int Tn,
+                                    const double* area_rngs, int A, int K, int max_det, int crowd_rule, int image, int64_t* records,
+                                    int64_t* npig, void* workspace, size_t workspace_bytes, void* stream)
+{
+    ApSource s;
+    s.box = true;
+    s.dt_box = dt_box, s.gt_box = gt_box;
+    return ap_match("mpf_seg_ap_match_box", s, D, G, dt_score, dt_cat, gt_cat, gt_crowd, gt_area, iou_thrs, Tn, area_rngs, A, K, max_det,
+                    crowd_rule, image, records, npig, workspace, workspace_bytes, stream);
 }

@@ -256,15 +256,17 @@ def native_eval_forward(model, batched_inputs, cfg, image_list_cls=None, instanc
                        cfg)
 
 
-def install_native_inference(model, image_list_cls=None, semantic_labels=False, instance_masks="dense", instance_bits=False):
+def install_native_inference(model, image_list_cls=None, semantic_labels=False, instance_masks="dense", instance_bits=False,
+                             instance_boxes=False):
     """Route the eval branch of a reference ``MaskFormer`` instance through ``native_eval_forward``; training is unchanged.
-    ``semantic_labels`` / ``instance_masks``: the evaluation-form results of inference.InferenceConfig (the model has no such
-    attributes; the defaults give the reference's own result dicts).  ``instance_bits``: the model returns only "instances", as
-    packed masks (inference.instance_bits), the form ``InstanceAPEvaluator`` consumes without a dense mask.  Returns the
-    inference.InferenceConfig in use."""
+    ``semantic_labels`` / ``instance_masks`` / ``instance_boxes``: the evaluation-form results of inference.InferenceConfig (the
+    model has no such attributes; the defaults give the reference's own result dicts, ``pred_boxes`` zeros among them).
+    ``instance_bits``: the model returns only "instances", as packed masks (inference.instance_bits), the form
+    ``InstanceAPEvaluator`` consumes without a dense mask.  Returns the inference.InferenceConfig in use."""
     import dataclasses
     from .inference import InferenceConfig
-    cfg = dataclasses.replace(InferenceConfig.from_maskformer(model), semantic_labels=semantic_labels, instance_masks=instance_masks)
+    cfg = dataclasses.replace(InferenceConfig.from_maskformer(model), semantic_labels=semantic_labels, instance_masks=instance_masks,
+                              instance_boxes=bool(instance_boxes))
     train_forward = model.forward
 
     def forward(batched_inputs):
@@ -537,8 +539,12 @@ class InstanceAPEvaluator:
     masks are packed and matched on the device, one record per detection and score crosses to the host at ``evaluate``.  Writes no
     file and needs neither detectron2, pycocotools nor boundary_iou.
 
-    iou_types: any of "segm", "boundary"; one ``InstanceAP`` per type (``self.aps``), the masks of an image packed once and their
-    pair intersections counted once for all of them.  ``evaluate`` returns one key per type.
+    iou_types: any of "segm", "boundary", "bbox"; one ``InstanceAP`` per type (``self.aps``), the masks of an image packed once and
+    their pair intersections counted once for all of them.  ``evaluate`` returns one key per type.  "bbox" (COCOEvaluator's task of
+    that name) takes the detections' boxes from ``"boxes"`` (inference.instance_bits with ``instance_boxes``) or ``pred_boxes``
+    where the prediction carries them, the ground truth's from ``gt_boxes`` (a tensor or an object with ``.tensor``), all XYXY; a
+    side without boxes gets those of its masks (inference.mask_boxes).  ``pred_boxes`` of a model installed without
+    ``instance_boxes`` are the reference's placeholder, all zero on the host: they count as absent and the masks' boxes are scored.
 
     Predictions: ``outputs[i]["instances"]`` with dense ``pred_masks`` [T, H, W], ``scores`` and ``pred_classes`` (packed here), or
     the dict of inference.instance_bits where the model was installed with ``install_native_inference(..., instance_bits=True)``.
@@ -568,6 +574,19 @@ class InstanceAPEvaluator:
             return default
         return getattr(inst, name, default)
 
+    def _xywh(self, boxes, placeholder_is_absent=False):
+        """XYXY boxes (a tensor or an object with ``.tensor``) -> XYWH float64 on the evaluator's device; None stays None.
+        ``placeholder_is_absent``: host boxes that are all zero are the reference's placeholder (``Boxes(torch.zeros(T, 4))``, what
+        a model installed without ``instance_boxes`` returns), not boxes: None, so that the masks' boxes are scored.  Only host
+        tensors are looked at: reading a device tensor here would stall the loop, and real boxes are not all zero."""
+        from .inference import boxes_xyxy_to_xywh
+        if boxes is None:
+            return None
+        boxes = getattr(boxes, "tensor", boxes)
+        if placeholder_is_absent and not boxes.is_cuda and not bool(boxes.any()):
+            return None
+        return boxes_xyxy_to_xywh(boxes.to(self.ap.device))
+
     def process(self, inputs, outputs):
         import torch
         from .inference import mask_pair_counts, pack_masks
@@ -590,8 +609,14 @@ class InstanceAPEvaluator:
             args = (dt_bits, self._field(pred, "scores"), self._field(pred, "pred_classes"), pack_masks(gm.to(dev)),
                     self._field(gt, "gt_classes"), torch.zeros(G, dtype=torch.int32) if crowd is None else crowd,
                     self._field(gt, "gt_areas"))
-            counts = mask_pair_counts(args[0], args[3])      # once for every type
-            for ap in self.aps.values():
+            counts = None
+            for t, ap in self.aps.items():
+                if t == "bbox":
+                    dt_boxes = self._xywh(self._field(pred, "boxes", self._field(pred, "pred_boxes")), placeholder_is_absent=True)
+                    ap.update(*args, size=size, dt_boxes=dt_boxes, gt_boxes=self._xywh(self._field(gt, "gt_boxes")))
+                    continue
+                if counts is None:
+                    counts = mask_pair_counts(args[0], args[3])      # once for every type that counts pixels
                 ap.update(*args, size=size, pair_counts=counts)
 
     def evaluate(self):

@@ -8,6 +8,10 @@ The per-pixel work runs on the device; what stays on the host is the panoptic se
 entries), fed by ONE device-to-host copy of the per-query area counters.  CPU tensors and other dtypes raise: there is
 no torch fallback.
 
+``InferenceConfig.instance_boxes`` (off by default: the reference's zeros) fills ``pred_boxes`` with the bounding boxes of the
+instance masks, which the reference leaves commented out as slow (maskformer_model.py:393-395): ``mask_boxes`` reads them off
+the packed bits (csrc/seg_box.hip), and ``InstanceAP(iou_type="bbox")`` scores COCO's box AP on them.
+
 For an evaluation loop the largest results can be had in the form their consumers use (both off by default):
 * ``InferenceConfig.semantic_labels``: ``"sem_seg_labels"`` int32 [H, W] (the argmax every evaluator takes) instead of the
   fp32 [K, H, W] ``"sem_seg"``, which is then never written; ``SemSegConfusion`` accumulates the (K+1) x (K+1) counts of mIoU
@@ -53,6 +57,7 @@ class InferenceConfig:
     thing_ids: frozenset = field(default_factory=frozenset)     # contiguous ids of the thing classes
     semantic_labels: bool = False       # "sem_seg_labels" int32 [H, W] instead of "sem_seg" fp32 [K, H, W]
     instance_masks: str = "dense"       # "dense": pred_masks fp32 [T, H, W]; "rle": pred_masks_rle (uncompressed COCO RLE)
+    instance_boxes: bool = False        # pred_boxes = the masks' bounding boxes (maskformer_model.py:393-395) instead of zeros
 
     def __post_init__(self):
         self.thing_ids = frozenset(int(i) for i in self.thing_ids)
@@ -271,6 +276,18 @@ def _instance_selection(view, img, cfg, thing_lut):
     return scores, labels[order], query[order].contiguous()
 
 
+def _instance_boxes(view, query, T):
+    """The bounding boxes int32 [T, 4] (XYXY) of the sorted entries' masks: their packed bits (``mpf_seg_instance_bits``, the ``m > 0``
+    decision of the dense masks and of the run lengths) go to scratch and ``mask_boxes`` reads them."""
+    (H, W), dev = view.out, view.dev
+    if not T:
+        return torch.zeros((0, 4), dtype=torch.int32, device=dev)
+    nwords = (H * W + 63) // 64
+    bits = _lib.scratch("seg_infer.box_bits", dev, view.stream, 8 * T * nwords)[:8 * T * nwords].view(torch.int64).view(T, nwords)
+    _lib.call("mpf_seg_instance_bits", dev, *view.args(), query.data_ptr(), T, bits.data_ptr(), view.stream)
+    return mask_boxes(bits, (H, W))
+
+
 def _instances(view, img, cfg, thing_lut):
     (H, W), dev = view.out, view.dev
     scores, labels, query = _instance_selection(view, img, cfg, thing_lut)
@@ -283,7 +300,7 @@ def _instances(view, img, cfg, thing_lut):
         result.pred_masks = torch.empty((T, H, W), dtype=torch.float32, device=dev)
         if T:
             _lib.call("mpf_seg_instance_masks", dev, *view.args(), query.data_ptr(), T, result.pred_masks.data_ptr(), view.stream)
-    result.pred_boxes = Boxes(torch.zeros(T, 4))
+    result.pred_boxes = Boxes(_instance_boxes(view, query, T).float() if cfg.instance_boxes else torch.zeros(T, 4))
     result.scores = scores
     result.pred_classes = labels
     return result
@@ -344,7 +361,8 @@ def postprocess(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, c
     -> list of dicts with "sem_seg" [K, height, width], "panoptic_seg" (ids int32 [height, width], segments_info) and
     "instances" (pred_masks [T, height, width] 0/1 fp32, pred_boxes zeros, scores, pred_classes), per the *_on flags.
     cfg.semantic_labels: "sem_seg_labels" int32 [height, width] in place of "sem_seg"; cfg.instance_masks == "rle":
-    instances.pred_masks_rle (list of T {"size", "counts"} dicts) in place of pred_masks."""
+    instances.pred_masks_rle (list of T {"size", "counts"} dicts) in place of pred_masks; cfg.instance_boxes: pred_boxes fp32
+    [T, 4] XYXY on the device, the bounding boxes of the masks (``mask_boxes``), in place of the zeros."""
     out = []
     for view, img, thing_lut in _images("postprocess", pred_logits, pred_masks, image_sizes, padded_hw, output_sizes, cfg):
         res = {}
@@ -371,7 +389,7 @@ def instance_bits(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes,
     """The "instances" of ``postprocess`` (same arguments) with their masks as packed bits, for ``InstanceAP``: per image a dict
     with "bits" int64 [T, nwords] on the device (position p = x * H + y, 64 per word, bit b of word j = position 64 j + b, zero at
     and past H * W), "size" (H, W), "scores" and "pred_classes".  Selection, scores and order are those of ``postprocess``; the
-    dense [T, H, W] masks are never written."""
+    dense [T, H, W] masks are never written.  cfg.instance_boxes: also "boxes" int32 [T, 4], ``mask_boxes`` of the bits."""
     if not cfg.instance_on:
         raise ValueError("instance_bits needs instance_on")
     out = []
@@ -382,7 +400,10 @@ def instance_bits(pred_logits, pred_masks, image_sizes, padded_hw, output_sizes,
         bits = torch.empty((T, (H * W + 63) // 64), dtype=torch.int64, device=view.dev)
         if T:
             _lib.call("mpf_seg_instance_bits", view.dev, *view.args(), query.data_ptr(), T, bits.data_ptr(), view.stream)
-        out.append({"bits": bits, "size": (H, W), "scores": scores, "pred_classes": labels})
+        res = {"bits": bits, "size": (H, W), "scores": scores, "pred_classes": labels}
+        if cfg.instance_boxes:
+            res["boxes"] = mask_boxes(bits, (H, W))
+        out.append(res)
     return out
 
 
@@ -917,7 +938,7 @@ def mask_pair_counts(a_bits, b_bits):
     return inter, area_a, area_b
 
 
-AP_IOU_TYPES = ("segm", "boundary")
+AP_IOU_TYPES = ("segm", "boundary", "bbox")
 
 
 def boundary_dilation(H, W, dilation_ratio=0.02):
@@ -955,6 +976,30 @@ def mask_boundaries(bits, size, dilation_ratio=0.02, d=None):
     return out
 
 
+def mask_boxes(bits, size):
+    """Packed masks int64 [M, nwords] of an image of ``size`` (H, W), or tubes int64 [T, F, nwords] -> their bounding boxes int32
+    [M, 4] (or [T, F, 4]) on the device, XYXY as Detectron2's ``BitMasks.get_bounding_boxes`` gives them (the call the reference's
+    instance_inference leaves commented out, maskformer_model.py:393-395): (min x, min y, max x + 1, max y + 1) over the set
+    pixels, (0, 0, 0, 0) for an empty mask.  One read of the words, one launch."""
+    if not bits.is_cuda:
+        raise RuntimeError("mask_boxes: Not implemented on the CPU (device tensors only)")
+    tubes = bits.dim() == 3
+    flat = _bits_arg(bits.flatten(0, 1) if tubes else bits, "bits")
+    H, W = _bits_size(flat, size, "mask_boxes")
+    dev = flat.device
+    boxes = torch.empty((flat.shape[0], 4), dtype=torch.int32, device=dev)
+    if flat.shape[0]:
+        _lib.call("mpf_seg_bits_boxes", dev, flat.data_ptr(), flat.shape[0], H, W, boxes.data_ptr(), _lib.stream_ptr(dev))
+    return boxes.view(bits.shape[0], bits.shape[1], 4) if tubes else boxes
+
+
+def boxes_xyxy_to_xywh(boxes):
+    """[N, 4] (x0, y0, x1, y1) of any dtype -> float64 [N, 4] (x, y, w, h), the form a COCO json holds and
+    ``InstanceAP(iou_type="bbox")`` takes."""
+    b = boxes.to(torch.float64).reshape(-1, 4)
+    return torch.cat([b[:, :2], b[:, 2:] - b[:, :2]], dim=1)
+
+
 class InstanceAP:
     """The per-image part of the COCO mask evaluation (``COCOeval.evaluateImg``; the reference carries the same body as
     ``evaluateVid`` in mask2former_video/data_video/datasets/ytvis_api/ytvoseval.py:267-345) on the device, and its ``accumulate`` /
@@ -969,7 +1014,9 @@ class InstanceAP:
 
     iou_type: "segm" = mask AP; "boundary" = Boundary AP as tools/evaluate_coco_boundary_ap.py computes it with boundary-iou-api: a
     pair's IoU is min(mask IoU, IoU of the two masks' boundaries), the boundaries ``mask_boundaries`` with ``dilation_ratio``;
-    area ranges, matching, accumulate and summarize are the same.
+    area ranges, matching, accumulate and summarize are the same.  "bbox" = COCO's box AP: a pair's IoU is pycocotools' ``bbIou`` of
+    two XYWH float64 boxes (``mpf_seg_ap_match_box``, every operation rounded on its own: an IEEE double restatement gives the same
+    bits), the boxes given to ``update`` or derived from the masks with ``mask_boxes``; an unmatched detection's area is w * h.
 
     tubes: the YouTube-VIS form of the same file (``TubeAP``): a "mask" is a tube int64 [F, nwords], the packed words of its frames,
     an image a video.  The IoU is ``iou_seq`` (:203-217): the frames' words concatenated, a frame without annotation all-zero words.
@@ -982,7 +1029,7 @@ class InstanceAP:
     def __init__(self, num_classes, iou_thrs=None, area_rngs=None, max_dets=(1, 10, 100), crowd_rule=None, device="cuda:0",
                  iou_type="segm", dilation_ratio=0.02, tubes=False):
         if iou_type not in AP_IOU_TYPES:
-            raise ValueError(f"iou_type must be 'segm' or 'boundary', got {iou_type!r}")
+            raise ValueError(f"iou_type must be 'segm', 'boundary' or 'bbox', got {iou_type!r}")
         self.tubes = bool(tubes)
         if self.tubes and iou_type != "segm":
             raise ValueError("tubes=True evaluates mask tubes: iou_type must be 'segm'")
@@ -1043,7 +1090,7 @@ class InstanceAP:
         return t
 
     def update(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas=None, size=None, pair_counts=None,
-               dt_frame_area=None, gt_frame_area=None):
+               dt_frame_area=None, gt_frame_area=None, dt_boxes=None, gt_boxes=None):
         """One image.  dt_bits int64 [D, nwords] and gt_bits int64 [G, nwords] packed masks on the device (``instance_bits`` /
         ``pack_masks``), scores [D], classes [D], gt_classes [G], gt_crowd [G] (0 / 1), gt_areas [G] or None (= the pixel counts).
         The detections may come in any order: they are sorted by score, descending and stable (the reference's mergesort of -score).
@@ -1053,9 +1100,18 @@ class InstanceAP:
         (``pack_masks`` of the frames; a frame without annotation all zero); dt_frame_area int32 [D, F] / gt_frame_area int32 [G, F]
         where the caller has them (``postprocess_video`` returns the detections'), else counted here; gt_areas [G] replaces the ground
         truths' avg_area.
+        iou_type="bbox": dt_boxes [D, 4] / gt_boxes [G, 4], XYWH float64 as a COCO json holds them (host or device).  A side given as
+        None is derived on the device from its bits (``boxes_xyxy_to_xywh(mask_boxes(bits, size))``; size is then required); a side
+        whose boxes are given may pass its bits as None.  gt_areas None: the pixel counts where gt_bits is given, else w * h.
         No device-to-host copy."""
         if self.device.type != "cuda":
             raise RuntimeError("InstanceAP: Not implemented on the CPU (device tensors only)")
+        if self.iou_type == "bbox":
+            if dt_frame_area is not None or gt_frame_area is not None:
+                raise ValueError("InstanceAP.update: frame areas belong to tubes=True")
+            return self._update_bbox(dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas, size, dt_boxes, gt_boxes)
+        if dt_boxes is not None or gt_boxes is not None:
+            raise ValueError("InstanceAP.update: boxes belong to iou_type='bbox'")
         if self.tubes:
             dt_tubes, gt_tubes = _tubes_arg(dt_bits, "dt_bits"), _tubes_arg(gt_bits, "gt_bits")
             if dt_tubes.shape[0] and gt_tubes.shape[0] and dt_tubes.shape[1:] != gt_tubes.shape[1:]:
@@ -1080,7 +1136,6 @@ class InstanceAP:
             if tuple(inter.shape) != (D, G) or area_d.numel() != D or area_g.numel() != G or inter.dtype != torch.int32:
                 raise ValueError(f"pair_counts are not the int32 counts of {D} x {G} masks")
         self._buffers()
-        dev = self.device
         scores = self._small(scores, D, torch.float32, "scores")
         classes = self._small(classes, D, torch.int32, "classes")
         gt_cat = self._small(gt_classes, G, torch.int32, "gt_classes")
@@ -1108,6 +1163,17 @@ class InstanceAP:
             tube_gt_area = None
         own_area = area_g.double() if tube_gt_area is None else tube_gt_area
         gt_area = own_area if gt_areas is None else self._small(gt_areas, G, torch.float64, "gt_areas")
+        counts = (_lib.ptr(inter) if D and G else None, area_d.data_ptr() if D else None, area_g.data_ptr() if G else None)
+        if boundary:
+            counts += (_lib.ptr(inter_b) if D and G else None, area_db.data_ptr() if D else None, area_gb.data_ptr() if G else None)
+        entry = "mpf_seg_ap_match_tube" if self.tubes else "mpf_seg_ap_match_boundary" if boundary else "mpf_seg_ap_match"
+        areas = (gt_area.data_ptr() if G else None,) + ((dt_area.data_ptr() if D else None,) if self.tubes else ())
+        self._match(entry, counts, D, G, scores, classes, gt_cat, crowd, areas, image)
+
+    def _match(self, entry, source, D, G, scores, classes, gt_cat, crowd, areas, image):
+        """The launch every IoU type ends in: ``source`` = the leading pointers of ``entry`` (counts or boxes), ``areas`` = gt_area
+        (and the tubes' dt_area); the detections in score order.  The records of the D detections are appended."""
+        dev = self.device
         if self._n + D > self._rec.shape[0]:                # grow by doubling; the old buffer stays valid for the queued launches
             grown = torch.empty((max(2 * self._rec.shape[0], self._n + D), _AP_REC), dtype=torch.int64, device=dev)
             grown[:self._n] = self._rec[:self._n]
@@ -1116,17 +1182,58 @@ class InstanceAP:
         Tn, A = self.iou_thrs.size, self.area_rngs.shape[0]
         ws = _lib.scratch("seg_ap.gt_marks", dev, stream, max(1, _lib.lib().mpf_seg_ap_workspace_bytes(G, A, Tn)))
         sp = self._settings.data_ptr()
-        counts = (_lib.ptr(inter) if D and G else None, area_d.data_ptr() if D else None, area_g.data_ptr() if G else None)
-        if boundary:
-            counts += (_lib.ptr(inter_b) if D and G else None, area_db.data_ptr() if D else None, area_gb.data_ptr() if G else None)
-        entry = "mpf_seg_ap_match_tube" if self.tubes else "mpf_seg_ap_match_boundary" if boundary else "mpf_seg_ap_match"
-        areas = (gt_area.data_ptr() if G else None,) + ((dt_area.data_ptr() if D else None,) if self.tubes else ())
-        _lib.call(entry, dev, *counts,
+        _lib.call(entry, dev, *source,
                   D, G, scores.data_ptr() if D else None, classes.data_ptr() if D else None,
                   gt_cat.data_ptr() if G else None, crowd.data_ptr() if G else None, *areas, sp, Tn, sp + 8 * Tn,
                   A, self.num_classes, self.max_dets[-1], AP_CROWD_RULES[self.crowd_rule], image,
                   self._rec.data_ptr() + 8 * _AP_REC * self._n, self._npig.data_ptr(), ws.data_ptr(), ws.numel(), stream)
         self._n += D
+
+    def _update_bbox(self, dt_bits, scores, classes, gt_bits, gt_classes, gt_crowd, gt_areas, size, dt_boxes, gt_boxes):
+        """``update`` of iou_type="bbox": a side's boxes are those given (XYWH) or ``mask_boxes`` of its bits"""
+        dev = self.device
+
+        def checked(bits, boxes, what):                     # -> (bits, how many), before anything is uploaded or launched
+            if bits is not None:
+                bits = _bits_arg(bits, f"{what}_bits")
+                if bits.device != dev:
+                    raise RuntimeError(f"{what}_bits on {bits.device}, the records on {dev}")
+            if boxes is None:
+                if bits is None:
+                    raise ValueError(f"InstanceAP.update: iou_type='bbox' needs {what}_boxes or {what}_bits")
+                if size is None:
+                    raise ValueError(f"InstanceAP.update: iou_type='bbox' derives {what}_boxes from the bits and needs size=(H, W)")
+                _bits_size(bits, size, "InstanceAP.update")
+                return bits, bits.shape[0]
+            if bits is not None and bits.shape[0] != len(boxes):
+                raise ValueError(f"{len(boxes)} {what}_boxes for {bits.shape[0]} masks")
+            return bits, len(boxes)
+
+        def xywh(bits, boxes, n, what):
+            if boxes is None:
+                return boxes_xyxy_to_xywh(mask_boxes(bits, size))
+            return self._small(boxes, 4 * n, torch.float64, f"{what}_boxes").view(n, 4)
+        (dt_bits, D), (gt_bits, G) = checked(dt_bits, dt_boxes, "dt"), checked(gt_bits, gt_boxes, "gt")
+        dt_box, gt_box = xywh(dt_bits, dt_boxes, D, "dt"), xywh(gt_bits, gt_boxes, G, "gt")
+        self._buffers()
+        scores = self._small(scores, D, torch.float32, "scores")
+        classes = self._small(classes, D, torch.int32, "classes")
+        gt_cat = self._small(gt_classes, G, torch.int32, "gt_classes")
+        crowd = self._small(gt_crowd, G, torch.int32, "gt_crowd")
+        if gt_areas is not None:
+            gt_area = self._small(gt_areas, G, torch.float64, "gt_areas")
+        elif gt_bits is not None:                           # as "segm": the pixel counts
+            gt_area = mask_pair_counts(gt_bits, gt_bits.new_empty((0, gt_bits.shape[1])))[1].double() if G else gt_box.new_empty(0)
+        else:
+            gt_area = (gt_box[:, 2] * gt_box[:, 3]).contiguous()
+        image = self._images
+        self._images += 1
+        if D == 0 and G == 0:
+            return
+        scores, order = scores.sort(descending=True, stable=True)
+        classes, dt_box = classes[order].contiguous(), dt_box[order].contiguous()
+        self._match("mpf_seg_ap_match_box", (dt_box.data_ptr() if D else None, gt_box.data_ptr() if G else None), D, G, scores, classes,
+                    gt_cat, crowd, (gt_area.data_ptr() if G else None,), image)
 
     # ---- host side ----
     def stats(self):
