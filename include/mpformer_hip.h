@@ -1587,6 +1587,40 @@ int mpf_seg_bits_rle_write(const uint64_t* bits, const void* workspace, size_t w
                            const int64_t* offsets, int64_t total, uint32_t* pos, uint32_t* counts, void* stream);
 
 /*
+ * COCO ground truth to packed bits on the device (csrc/seg_codec.hip): the three forms a COCO or YouTube-VIS json holds a
+ * segmentation in (polygons, uncompressed RLE, compressed RLE once its string is decoded) become bits uint64 [M, nwords] in the
+ * layout above (p = x * H + y, zero at and past H * W), which is COCO's own column-major order.  pycocotools' rleFrPoly ends with
+ * "sort the boundary positions, take differences, merge zero-length runs": the mask at position p is the parity of the number of
+ * boundary positions <= p, and a run-length decode is the same with a boundary at every cumulative count.  So both sources write
+ * TOGGLE PLANES, uint64 [R, nwords] with one bit XOR-ed per boundary position, and one pass fills them.
+ *   mpf_seg_poly_toggles:  the rings of a batch of objects: xy double [sum K_r, 2] (x, y), ring_off int64 [R + 1] (first vertex of
+ *                          every ring, then the total) -> planes [R, nwords], zeroed by the call.  Per ring, rleFrPoly (scale 5):
+ *                          X[j] = (int)(5 x_j + .5), Y likewise, the ring closed; per edge the dense points of its major axis, from
+ *                          the edge's original start to its end, the minor coordinate (int)(start + s t + .5) with s the slope, all in
+ *                          IEEE double with every operation rounded on its own; over the concatenated points, for every i >= 1 with
+ *                          u[i] != u[i-1]: xd = (u[i] < u[i-1] ? u[i] : u[i] - 1), xd = (xd + .5) / 5 - .5, skipped unless an integer
+ *                          in [0, W - 1]; yd = min(v[i], v[i-1]), yd = (yd + .5) / 5 - .5 clamped to [0, H] (H, not H - 1), rounded
+ *                          up; position xd * H + yd is toggled unless it is >= H * W.  A ring may have any number of vertices (the
+ *                          kernel stages mpf_seg_poly_stage_edges() edges at a time); a ring of no vertex leaves its plane zero.
+ *                          The coordinates must satisfy |5 c + .5| < 2^31 (the caller's check: they are device memory).
+ *   mpf_seg_rle_toggles:   counts uint32 (the masks' run lengths concatenated, each starting with its run of zeros), off int64
+ *                          [M + 1] -> planes [M, nwords], zeroed by the call: a toggle at every cumulative count < H * W.  Zero-length
+ *                          runs anywhere cancel by themselves.
+ *   mpf_seg_toggles_fill:  planes [R, nwords], plane_obj int32 [R] NON-DECREASING (the object of every plane) -> bits [M, nwords]:
+ *                          the prefix XOR of every plane along the linear bit order, OR-ed over the planes of one object (a COCO
+ *                          multi-polygon annotation is the union of its rings: rleMerge, intersect = 0).  An object without a plane
+ *                          is all zero (R == 0: planes and plane_obj may be NULL).  bits must not overlap planes.
+ *   mpf_seg_unpack_masks:  bits [M, nwords] -> masks uint8 [M, H, W] row-major, 0 / 1: the inverse of mpf_seg_pack_masks.
+ * H * W < 2^31; M <= 65535 for _fill and _unpack, R (and the M of _rle_toggles) < 2^24, else MPF_E_TOO_LARGE; a count of 0 launches
+ * nothing.  Integer XOR atomics and single writers only: bitwise reproducible, whatever the order of rings or launch geometry.
+ */
+int mpf_seg_poly_stage_edges(void);
+int mpf_seg_poly_toggles(const double* xy, const int64_t* ring_off, int R, int H, int W, uint64_t* planes, void* stream);
+int mpf_seg_rle_toggles(const uint32_t* counts, const int64_t* off, int M, int H, int W, uint64_t* planes, void* stream);
+int mpf_seg_toggles_fill(const uint64_t* planes, const int* plane_obj, int R, int M, int H, int W, uint64_t* bits, void* stream);
+int mpf_seg_unpack_masks(const uint64_t* bits, int M, int H, int W, uint8_t* masks, void* stream);
+
+/*
  * Shifted-window attention core of the Swin backbone (bf16 MFMA tiles; head_dim 32): per (image, window, head)
  *   out = softmax(scale * q k^T + table[index(i, j), head] + shift_mask(i, j)) v
  * — WindowAttention.forward between its qkv and proj Linears (mask2former/modeling/backbone/swin.py:131-171) together with the

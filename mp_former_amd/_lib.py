@@ -250,6 +250,11 @@ SIGNATURES = {
     "mpf_seg_bits_rle_workspace_bytes": (ctypes.c_size_t, [_c_int] * 3),
     "mpf_seg_bits_rle_count": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_seg_bits_rle_write": (_c_int, [_c_vp, _c_vp, ctypes.c_size_t, _c_int, _c_int, _c_int, _c_vp, ctypes.c_int64, _c_vp, _c_vp, _c_vp]),
+    "mpf_seg_poly_stage_edges": (_c_int, []),
+    "mpf_seg_poly_toggles": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_rle_toggles": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_toggles_fill": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_seg_unpack_masks": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
 }
 
 

@@ -356,9 +356,13 @@ class YTVISEvaluatorHIP:
     the video's ground-truth tubes: ``gt_masks`` dense [G, F, H, W] (any of ``pack_masks``' dtypes; a frame without annotation all
     zero) or packed int64 [G, F, nwords], ``gt_classes`` [G], optional ``gt_iscrowd`` [G].
     ``evaluate()`` -> {"segm": {AP, AP50, AP75, APs, APm, APl, AR1, AR10, AP-{name}...}} (ytvis_eval.py:205).
-    ``results_json(video_id, output)``: the submission entries of ``instances_to_coco_json_video`` (:256-293) from the "rle" form.
-    Their "counts" are uncompressed run lengths (column-major, starting with the zeros); compressing them to the COCO string
-    (pycocotools' ``frPyObjects``) is the caller's, as with the image route's ``pred_masks_rle``."""
+    In place of ``gt_masks`` the ground truth may carry ``"segmentations"``, [G][F] entries as a YouTube-VIS json holds them
+    (``None`` for a frame without annotation, an RLE dict with a list or a string, or a polygon list) at the prediction's size:
+    inference.segmentation_bits decodes them on the device, no dense mask exists on the host.
+    ``results_json(video_id, output, compressed=False)``: the submission entries of ``instances_to_coco_json_video`` (:256-293)
+    from the "rle" form.  Their "counts" are uncompressed run lengths (column-major, starting with the zeros);
+    ``compressed=True`` makes them the COCO strings a submission file holds (inference.rle_compress, pycocotools' ``frPyObjects``).
+    The image route's ``pred_masks_rle`` go through ``compress_rles`` of this module."""
 
     def __init__(self, num_classes, class_names=None, device="cuda:0", **ap_options):
         from .inference import TubeAP
@@ -383,10 +387,21 @@ class YTVISEvaluatorHIP:
         F, nwords = dt_bits.shape[1:]
         H, W = outputs["size"]
         gt = inputs[0]["instances"]
-        gm = gt["gt_masks"]
-        gm = getattr(gm, "tensor", gm).to(dev)
-        G = gm.shape[0]
-        if G == 0:
+        segs = gt.get("segmentations") if isinstance(gt, dict) and "gt_masks" not in gt else None
+        if segs is not None:                                 # as the json holds them: decoded on the device, never dense on the host
+            from .inference import segmentation_bits
+            G = len(segs)
+            if any(len(tube) != F for tube in segs):
+                raise ValueError(f"segmentations must be [G][{F}], one entry (or None) per frame of the prediction")
+            gm = None
+            gt_bits = segmentation_bits([s for tube in segs for s in tube], (H, W), device=dev).view(G, F, nwords)
+        else:
+            gm = gt["gt_masks"]
+            gm = getattr(gm, "tensor", gm).to(dev)
+            G = gm.shape[0]
+        if gm is None:
+            pass
+        elif G == 0:
             gt_bits = dt_bits.new_empty((0, F, nwords))
         elif gm.dim() == 4:
             if tuple(gm.shape[1:]) != (F, H, W):
@@ -402,11 +417,19 @@ class YTVISEvaluatorHIP:
         return {"segm": self.ap.results(self.class_names)}
 
     @staticmethod
-    def results_json(video_id, output):
+    def results_json(video_id, output, compressed=False):
         if "pred_masks_rle" not in output:
             raise ValueError("YTVISEvaluatorHIP.results_json takes the 'rle' form of postprocess_video")
+        tubes = [compress_rles(segms) for segms in output["pred_masks_rle"]] if compressed else output["pred_masks_rle"]
         return [{"video_id": video_id, "score": s, "category_id": l, "segmentations": segms}
-                for s, l, segms in zip(output["pred_scores"], output["pred_labels"], output["pred_masks_rle"])]
+                for s, l, segms in zip(output["pred_scores"], output["pred_labels"], tubes)]
+
+
+def compress_rles(rles):
+    """Uncompressed RLE dicts (the image route's ``pred_masks_rle``, a tube of the video route's, ``inference.bits_rle``) -> the
+    dicts a COCO results json holds, "counts" the compressed string (inference.rle_compress); a ``None`` entry stays ``None``."""
+    from .inference import rle_compress
+    return [None if r is None else rle_compress(r) for r in rles]
 
 
 def is_hflip(tfm):
@@ -549,10 +572,16 @@ class InstanceAPEvaluator:
     Predictions: ``outputs[i]["instances"]`` with dense ``pred_masks`` [T, H, W], ``scores`` and ``pred_classes`` (packed here), or
     the dict of inference.instance_bits where the model was installed with ``install_native_inference(..., instance_bits=True)``.
     Ground truth: ``inputs[i]["instances"]`` with ``gt_masks`` (a [G, H, W] tensor or an object with ``.tensor``) and ``gt_classes``
-    at the prediction's size; optional ``gt_iscrowd`` and ``gt_areas`` (missing: no crowd, the pixel counts)."""
+    at the prediction's size; optional ``gt_iscrowd`` and ``gt_areas`` (missing: no crowd, the pixel counts).
+    An input without ``"instances"`` may carry ``"annotations"`` instead, the COCO dicts of the image as the json holds them
+    (``segmentation`` as polygons, RLE or compressed RLE at the prediction's size, ``category_id``, optional ``iscrowd``, ``area``,
+    ``bbox``): inference.segmentation_bits decodes them on the device, ``area`` / ``bbox`` (XYWH) are used where every annotation of
+    the image has them, and ``dataset_id_to_contiguous`` (a dict; None: identity) maps the category ids."""
 
-    def __init__(self, num_classes, class_names=None, device="cuda:0", iou_types=("segm",), dilation_ratio=0.02, **ap_options):
+    def __init__(self, num_classes, class_names=None, device="cuda:0", iou_types=("segm",), dilation_ratio=0.02,
+                 dataset_id_to_contiguous=None, **ap_options):
         from .inference import InstanceAP
+        self.dataset_id_to_contiguous = None if dataset_id_to_contiguous is None else dict(dataset_id_to_contiguous)
         iou_types = tuple(iou_types)
         if not iou_types or len(set(iou_types)) != len(iou_types):
             raise ValueError(f"iou_types must list each wanted type once, got {iou_types!r}")
@@ -589,15 +618,20 @@ class InstanceAPEvaluator:
 
     def process(self, inputs, outputs):
         import torch
-        from .inference import mask_pair_counts, pack_masks
+        from .inference import pack_masks
         dev = self.ap.device
         for inp, out in zip(inputs, outputs):
-            pred, gt = out["instances"], inp["instances"]
+            pred = out["instances"]
             if isinstance(pred, dict) and "bits" in pred:
                 dt_bits, size = pred["bits"], tuple(pred["size"])
             else:
                 masks = self._field(pred, "pred_masks")
                 dt_bits, size = pack_masks(masks.to(dev)), tuple(masks.shape[-2:])
+            if "instances" not in inp and "annotations" in inp:
+                args, gt_boxes = self._annotation_args(inp["annotations"], size)
+                self._update(pred, (dt_bits, self._field(pred, "scores"), self._field(pred, "pred_classes")) + args, size, gt_boxes)
+                continue
+            gt = inp["instances"]
             gm = self._field(gt, "gt_masks")
             gm = getattr(gm, "tensor", gm)
             if gm.shape[0] == 0:                             # an image without annotations, whatever shape its empty tensor has
@@ -609,15 +643,41 @@ class InstanceAPEvaluator:
             args = (dt_bits, self._field(pred, "scores"), self._field(pred, "pred_classes"), pack_masks(gm.to(dev)),
                     self._field(gt, "gt_classes"), torch.zeros(G, dtype=torch.int32) if crowd is None else crowd,
                     self._field(gt, "gt_areas"))
-            counts = None
-            for t, ap in self.aps.items():
-                if t == "bbox":
-                    dt_boxes = self._xywh(self._field(pred, "boxes", self._field(pred, "pred_boxes")), placeholder_is_absent=True)
-                    ap.update(*args, size=size, dt_boxes=dt_boxes, gt_boxes=self._xywh(self._field(gt, "gt_boxes")))
-                    continue
-                if counts is None:
-                    counts = mask_pair_counts(args[0], args[3])      # once for every type that counts pixels
-                ap.update(*args, size=size, pair_counts=counts)
+            self._update(pred, args, size, self._xywh(self._field(gt, "gt_boxes")))
+
+    def _update(self, pred, args, size, gt_boxes):
+        """one image into every type's InstanceAP: args as ``InstanceAP.update`` takes them, gt_boxes XYWH or None"""
+        from .inference import mask_pair_counts
+        counts = None
+        for t, ap in self.aps.items():
+            if t == "bbox":
+                dt_boxes = self._xywh(self._field(pred, "boxes", self._field(pred, "pred_boxes")), placeholder_is_absent=True)
+                ap.update(*args, size=size, dt_boxes=dt_boxes, gt_boxes=gt_boxes)
+                continue
+            if counts is None:
+                counts = mask_pair_counts(args[0], args[3])      # once for every type that counts pixels
+            ap.update(*args, size=size, pair_counts=counts)
+
+    def _annotation_args(self, annotations, size):
+        """COCO annotation dicts of one image -> the ground-truth arguments of ``InstanceAP.update`` (bits, classes, crowd, areas) and
+        the XYWH boxes: the segmentations decoded on the device at the prediction's size, "area" / "bbox" used where EVERY annotation
+        has them (else the pixel counts / the masks' boxes), "category_id" mapped through ``dataset_id_to_contiguous``."""
+        import torch
+        from .inference import segmentation_bits
+        dev = self.ap.device
+        ids = self.dataset_id_to_contiguous
+        for a in annotations:
+            if ids is not None and a["category_id"] not in ids:
+                raise ValueError(f"category_id {a['category_id']} is not in dataset_id_to_contiguous")
+        classes = torch.tensor([a["category_id"] if ids is None else ids[a["category_id"]] for a in annotations], dtype=torch.int64)
+        crowd = torch.tensor([int(a.get("iscrowd", 0)) for a in annotations], dtype=torch.int32)
+        G = len(annotations)
+        areas = torch.tensor([float(a["area"]) for a in annotations], dtype=torch.float64) \
+            if G and all("area" in a for a in annotations) else None
+        boxes = torch.tensor([[float(v) for v in a["bbox"]] for a in annotations], dtype=torch.float64).reshape(G, 4).to(dev) \
+            if G and all("bbox" in a for a in annotations) else None
+        bits = segmentation_bits([a["segmentation"] for a in annotations], size, device=dev)
+        return (bits, classes, crowd, areas), boxes
 
     def evaluate(self):
         return {t: ap.results(self.class_names) for t, ap in self.aps.items()}

@@ -17,7 +17,11 @@ For an evaluation loop the largest results can be had in the form their consumer
   fp32 [K, H, W] ``"sem_seg"``, which is then never written; ``SemSegConfusion`` accumulates the (K+1) x (K+1) counts of mIoU
   from such label maps on the device.
 * ``InferenceConfig.instance_masks = "rle"``: ``pred_masks_rle`` (uncompressed COCO run lengths) instead of the fp32
-  [T, H, W] ``pred_masks``; only the run lengths cross to the host.
+  [T, H, W] ``pred_masks``; only the run lengths cross to the host (``rle_compress`` makes them the strings a COCO json holds).
+
+The ground-truth side of such a loop reads a COCO / YouTube-VIS json without pycocotools and without a dense mask on the host:
+``polygon_bits``, ``rle_bits`` and ``segmentation_bits`` turn polygons, uncompressed and compressed RLE into the packed bits the
+scoring classes take (csrc/seg_codec.hip); ``unpack_masks`` / ``polygon_masks`` give dense targets on the device.
 
 ``SemanticTTA`` is the reference's semantic test-time augmentation (mask2former/test_time_augmentation.py): the mean of the
 views' "sem_seg", flipped views mirrored back, accumulated view by view in one [K, H, W] buffer on the device.
@@ -998,6 +1002,241 @@ def boxes_xyxy_to_xywh(boxes):
     ``InstanceAP(iou_type="bbox")`` takes."""
     b = boxes.to(torch.float64).reshape(-1, 4)
     return torch.cat([b[:, :2], b[:, 2:] - b[:, :2]], dim=1)
+
+
+# ---- COCO ground truth to packed bits: polygons and run lengths ------------------------------------------------------------------
+def rle_to_string(counts):
+    """pycocotools' ``rleToString``: run lengths -> the COCO "counts" string.  From the third count on the difference to the count
+    two places back is stored, in groups of 5 bits, lowest first, bit 0x20 = "more follows", characters offset by 48.  Byte-serial
+    and a few hundred bytes long: host work."""
+    cnts = [int(c) for c in counts]
+    out = []
+    for i, c in enumerate(cnts):
+        if c < 0:
+            raise ValueError(f"counts must be non-negative, got {c}")
+        x = c - (cnts[i - 2] if i > 2 else 0)
+        more = True
+        while more:
+            g = x & 0x1f
+            x >>= 5                                          # arithmetic: a negative difference ends in -1
+            more = (x != -1) if g & 0x10 else (x != 0)
+            if more:
+                g |= 0x20
+            out.append(chr(g + 48))
+    return "".join(out)
+
+
+def rle_from_string(s):
+    """pycocotools' ``rleFrString``: the COCO "counts" string (str or bytes) -> the run lengths, a list of ints."""
+    data = s.encode("ascii") if isinstance(s, str) else bytes(s)
+    cnts = []
+    p, n = 0, len(data)
+    while p < n:
+        x, k, more = 0, 0, True
+        while more:
+            if p >= n:
+                raise ValueError("counts string ends inside a number")
+            g = data[p] - 48
+            if not 0 <= g < 64:
+                raise ValueError(f"counts string holds {chr(data[p])!r}: not a character of the COCO encoding")
+            x |= (g & 0x1f) << (5 * k)
+            more = bool(g & 0x20)
+            p += 1
+            k += 1
+            if not more and g & 0x10:
+                x |= -1 << (5 * k)                           # sign-extend
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x)
+    return cnts
+
+
+def rle_compress(rle):
+    """An uncompressed RLE dict {"size", "counts": list} (what ``bits_rle`` and the "rle" forms give) -> the dict a COCO json holds,
+    "counts" the string of ``rle_to_string``."""
+    return {"size": [int(rle["size"][0]), int(rle["size"][1])], "counts": rle_to_string(rle["counts"])}
+
+
+_NP2T = {np.dtype(np.float64): torch.float64, np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32}
+
+
+def _codec_device(device, what):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{what}: Not implemented on the CPU (device tensors only)")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _codec_size(size, what):
+    if size is None or len(size) != 2:
+        raise ValueError(f"{what}: size must be (H, W), got {size!r}")
+    H, W = int(size[0]), int(size[1])
+    if H <= 0 or W <= 0 or H * W >= 1 << 31:
+        raise ValueError(f"{what}: need H, W > 0 and H * W < 2^31, got {H} x {W}")
+    return H, W
+
+
+def _stage(dev, arrays):
+    """numpy arrays -> their device copies through ONE pinned staging buffer: one host-to-device copy, every array 8-byte aligned"""
+    offs, n = [], 0
+    for a in arrays:
+        offs.append(n)
+        n += (a.nbytes + 7) // 8 * 8
+    host = np.zeros(max(n, 8), dtype=np.uint8)
+    for a, o in zip(arrays, offs):
+        host[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    d = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    return [d[o:o + a.nbytes].view(_NP2T[a.dtype]) if a.nbytes else torch.empty(0, dtype=_NP2T[a.dtype], device=dev)
+            for a, o in zip(arrays, offs)]
+
+
+def _ring_arrays(polygons, what):
+    """the checked rings of a list of objects -> (xy float64 [V, 2], ring_off int64 [R + 1], ring_obj int32 [R])"""
+    rings, ring_obj = [], []
+    for m, obj in enumerate(polygons):
+        if not isinstance(obj, (list, tuple)):
+            raise ValueError(f"{what}: object {m} must be a list of rings [x0, y0, x1, y1, ...], got {type(obj).__name__}")
+        for ring in obj:
+            a = np.asarray(ring, dtype=np.float64).reshape(-1)
+            if a.size % 2:
+                raise ValueError(f"{what}: object {m} has a ring of odd length {a.size}")
+            if a.size < 6:
+                raise ValueError(f"{what}: object {m} has a ring of {a.size} numbers: a polygon needs at least 6 (3 vertices)")
+            if not np.isfinite(a).all():
+                raise ValueError(f"{what}: object {m} has a non-finite coordinate")
+            if (np.abs(5.0 * a + 0.5) >= 2.0 ** 31).any():
+                raise ValueError(f"{what}: object {m} has a coordinate c with |5 c + .5| >= 2^31")
+            rings.append(a)
+            ring_obj.append(m)
+    ring_off = np.zeros(len(rings) + 1, dtype=np.int64)
+    if rings:
+        ring_off[1:] = np.cumsum([r.size // 2 for r in rings])
+    xy = np.concatenate(rings) if rings else np.zeros(0, dtype=np.float64)
+    return xy, ring_off, np.asarray(ring_obj, dtype=np.int32)
+
+
+def _rle_arrays(rles, H, W, what):
+    """the checked run lengths of a list of RLE dicts of one size -> (counts uint32 as int32 bits, off int64 [M + 1]); (H, W) None:
+    taken from the first dict -> also (H, W)"""
+    runs = []
+    for m, r in enumerate(rles):
+        if not isinstance(r, dict) or "size" not in r or "counts" not in r:
+            raise ValueError(f"{what}: entry {m} must be a dict with \"size\" and \"counts\"")
+        sz = (int(r["size"][0]), int(r["size"][1]))
+        if H is None:
+            H, W = _codec_size(sz, what)
+        if sz != (H, W):
+            raise ValueError(f"{what}: entry {m} has size {sz[0]} x {sz[1]}, expected {H} x {W}")
+        c = r["counts"]
+        c = rle_from_string(c) if isinstance(c, (str, bytes, bytearray)) else [int(v) for v in c]
+        if any(v < 0 for v in c):
+            raise ValueError(f"{what}: entry {m} has a negative count")
+        if sum(c) != H * W:
+            raise ValueError(f"{what}: the counts of entry {m} sum to {sum(c)}, not H * W = {H * W}")
+        runs.append(np.asarray(c, dtype=np.int64))
+    off = np.zeros(len(runs) + 1, dtype=np.int64)
+    if runs:
+        off[1:] = np.cumsum([r.size for r in runs])
+    counts = (np.concatenate(runs) if runs else np.zeros(0, dtype=np.int64)).astype(np.uint32).view(np.int32)
+    return counts, off, (H, W)
+
+
+def _toggle_fill(dev, H, W, M, poly, poly_obj, rle, rle_obj):
+    """bits int64 [M, nwords] from the toggle planes of both sources: poly = (xy, ring_off), rle = (counts, off), *_obj the object of
+    every plane (int32).  The polygon planes come first, so the caller numbers the objects so that (poly_obj, rle_obj) is
+    non-decreasing.  One host-to-device copy, one toggle launch per source kind, one fill."""
+    nwords = (H * W + 63) // 64
+    bits = torch.empty((M, nwords), dtype=torch.int64, device=dev)
+    if M == 0:
+        return bits
+    Rp, Rr = len(poly_obj), len(rle_obj)
+    stream = _lib.stream_ptr(dev)
+    planes = torch.empty((Rp + Rr, nwords), dtype=torch.int64, device=dev)
+    xy, ring_off, counts, off, plane_obj = _stage(dev, [poly[0], poly[1], rle[0], rle[1], np.concatenate([poly_obj, rle_obj]).astype(np.int32)])
+    if Rp:
+        _lib.call("mpf_seg_poly_toggles", dev, xy.data_ptr(), ring_off.data_ptr(), Rp, H, W, planes.data_ptr(), stream)
+    if Rr:
+        _lib.call("mpf_seg_rle_toggles", dev, counts.data_ptr(), off.data_ptr(), Rr, H, W, planes[Rp:].data_ptr(), stream)
+    _lib.call("mpf_seg_toggles_fill", dev, planes.data_ptr() if Rp + Rr else None, plane_obj.data_ptr() if Rp + Rr else None, Rp + Rr, M, H, W,
+              bits.data_ptr(), stream)
+    return bits
+
+
+_NO_POLY = (np.zeros(0, dtype=np.float64), np.zeros(1, dtype=np.int64))
+_NO_RLE = (np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int64))
+_NO_OBJ = np.zeros(0, dtype=np.int32)
+
+
+def polygon_bits(polygons, size, device="cuda"):
+    """COCO polygon segmentations -> packed bits int64 [M, nwords] on the device, as pycocotools' ``frPyObjects`` + ``merge`` decide
+    them (``rleFrPoly`` per ring, the union of an object's rings).  ``polygons``: a list over objects, each a list of rings
+    [x0, y0, x1, y1, ...] (the "segmentation" list of a COCO annotation; an object without a ring is empty); ``size`` (H, W).
+    Only the vertices cross to the device: vertices, ring offsets and the ring -> object table in one staging buffer, one copy.
+    ValueError on a ring of odd length, of fewer than 6 numbers (detectron2's filter), with a non-finite coordinate or with
+    |5 c + .5| >= 2^31."""
+    H, W = _codec_size(size, "polygon_bits")
+    xy, ring_off, ring_obj = _ring_arrays(polygons, "polygon_bits")
+    dev = _codec_device(device, "polygon_bits")
+    return _toggle_fill(dev, H, W, len(polygons), (xy, ring_off), ring_obj, _NO_RLE, _NO_OBJ)
+
+
+def rle_bits(rles, size=None, device="cuda"):
+    """COCO RLE segmentations {"size": [H, W], "counts": list | str | bytes} -> packed bits int64 [M, nwords] on the device
+    (pycocotools' ``rleDecode``, never dense: COCO's column-major order is the packed layout's).  Strings are decoded on the host
+    (``rle_from_string``); only the run lengths cross.  Checked on the host before anything is launched: all sizes equal (and equal
+    to ``size`` where given; an empty list needs it), every mask's counts summing to H * W."""
+    H, W = _codec_size(size, "rle_bits") if size is not None else (None, None)
+    if H is None and not len(rles):
+        raise ValueError("rle_bits: size must be given for an empty list")
+    counts, off, (H, W) = _rle_arrays(rles, H, W, "rle_bits")
+    dev = _codec_device(device, "rle_bits")
+    return _toggle_fill(dev, H, W, len(rles), _NO_POLY, _NO_OBJ, (counts, off), np.arange(len(rles), dtype=np.int32))
+
+
+def segmentation_bits(segms, size, device="cuda"):
+    """A mixed list of COCO segmentations -> packed bits int64 [M, nwords] on the device, in input order (pycocotools' ``annToRLE``
+    without the dense mask): an entry is a polygon list, an RLE dict with a list, or one with a string, or None (all zero: a
+    YouTube-VIS frame without annotation).  One toggle-plane batch per source kind, one fill, one host-to-device copy (a second,
+    of M indices, where both kinds occur: the rows are then put back in input order)."""
+    H, W = _codec_size(size, "segmentation_bits")
+    poly_idx = [i for i, s in enumerate(segms) if isinstance(s, (list, tuple))]
+    rle_idx = [i for i, s in enumerate(segms) if isinstance(s, dict)]
+    for i, s in enumerate(segms):
+        if s is not None and not isinstance(s, (list, tuple, dict)):
+            raise ValueError(f"segmentation_bits: entry {i} is a {type(s).__name__}: expected polygons, an RLE dict or None")
+    xy, ring_off, ring_obj = _ring_arrays([segms[i] for i in poly_idx], "segmentation_bits")
+    counts, off, _ = _rle_arrays([segms[i] for i in rle_idx], H, W, "segmentation_bits")
+    dev = _codec_device(device, "segmentation_bits")
+    M = len(segms)
+    if not poly_idx or not rle_idx:                          # one kind: its objects keep their places, the others have no plane
+        return _toggle_fill(dev, H, W, M, (xy, ring_off), np.asarray(poly_idx, dtype=np.int32)[ring_obj] if poly_idx else _NO_OBJ,
+                            (counts, off), np.asarray(rle_idx, dtype=np.int32))
+    # both kinds: polygons first, then run lengths (plane_obj non-decreasing), and the rows put back in input order
+    part = _toggle_fill(dev, H, W, len(poly_idx) + len(rle_idx), (xy, ring_off), ring_obj, (counts, off),
+                        len(poly_idx) + np.arange(len(rle_idx), dtype=np.int32))
+    bits = part.new_zeros((M, part.shape[1]))
+    bits[_stage(dev, [np.asarray(poly_idx + rle_idx, dtype=np.int64)])[0]] = part
+    return bits
+
+
+def unpack_masks(bits, size, dtype=torch.bool):
+    """Packed bits int64 [M, nwords] of ``size`` (H, W) -> dense masks [M, H, W] on the device, row-major, bool (default), uint8 or
+    float32: the inverse of ``pack_masks``, for consumers that want dense targets."""
+    bits = _bits_arg(bits, "bits")
+    H, W = _bits_size(bits, size, "unpack_masks")
+    if dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise TypeError(f"dtype must be bool, uint8 or float32, got {dtype}")
+    M, dev = bits.shape[0], bits.device
+    out = torch.empty((M, H, W), dtype=torch.uint8, device=dev)
+    if M:
+        _lib.call("mpf_seg_unpack_masks", dev, bits.data_ptr(), M, H, W, out.data_ptr(), _lib.stream_ptr(dev))
+    return out.view(torch.bool) if dtype == torch.bool else out.to(dtype)
+
+
+def polygon_masks(polygons, size, dtype=torch.bool, device="cuda"):
+    """COCO polygons -> dense masks [M, H, W] on the device: the device form of the training mappers' ``convert_coco_poly_to_mask``
+    / detectron2's ``polygons_to_bitmask`` (``polygon_bits``, then ``unpack_masks``); only the vertices cross."""
+    return unpack_masks(polygon_bits(polygons, size, device=device), size, dtype=dtype)
 
 
 class InstanceAP:
