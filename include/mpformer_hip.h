@@ -1649,6 +1649,59 @@ int mpf_win_attn_backward(const void* qkv, const float* table, const void* out, 
                           int Hp, int Wp, int heads, int head_dim, int ws, int shift, float scale, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/*
+ * Training input on the device (csrc/img_resample.hip): the image half of large-scale jitter — horizontal flip, resize, fixed
+ * crop, pad — for a batch of decoded uint8 HWC images in ONE launch, with the values of PIL's 8-bit bilinear resize
+ * (ImagingResample, triangle filter: detectron2's ResizeTransform.apply_image for uint8), and optionally the model's
+ * (x - pixel_mean) / pixel_std and the zero canvas of ImageList.from_tensors on top.  Only the crop window is computed.
+ *
+ * One record per image, all int32 but the pointer:
+ *   src, src_stride, src_h, src_w   the source: uint8 [H, W, 3] on the device, rows src_stride bytes apart (>= 3 W)
+ *   flip                            1: the source is read at column W - 1 - x (PIL on the mirrored image)
+ *   out_h, out_w                    the resized size (h', w'), never materialised
+ *   off_y, off_x                    the crop origin inside the resized image
+ *   crop_h, crop_w                  the crop size (Sh, Sw)
+ *   valid_h, valid_w                min(resized - origin, crop size): where resized pixels exist
+ *   tile_h                          output rows per workgroup, 1 .. 32: the caller picks the largest whose tiles tap at most
+ *                                   mpf_img_resample_span_rows() source rows each (the rows held in LDS)
+ *   ksize_x, ksize_y                taps stored per output column / row
+ *   xk_off, xb_off, yk_off, yb_off  offsets, in int32 elements, into the table buffer: coefficients [valid, ksize] and
+ *                                   (first source index, tap count) pairs [valid, 2] of the crop window's columns and rows
+ * The tables are PIL's: per axis with input size in and output size out, scale = in / out, fs = max(scale, 1), support = fs; for
+ * output xx, center = (xx + .5) scale, first = max((int)(center - support + .5), 0), count = min((int)(center + support + .5), in)
+ * - first, weights max(0, 1 - |(x + first - center + .5) / fs|) normalised by their sum in double, k = (int)(.5 + w 2^22).  A pass
+ * is clip(((1 << 21) + sum pixel * k) >> 22, 0, 255); the horizontal pass runs first and its uint8 result feeds the vertical one.
+ *
+ * out [B, 3, Hc, Wc] with the canvas (Hc, Wc) >= every crop size, from one integer v per element (the resampled value inside the
+ * valid extent, pad_value in the rest of the crop rectangle): MPF_U8 v; MPF_F32 (v - mean[c]) / std[c] with IEEE subtraction and
+ * division (bit-equal to the two torch operations); MPF_BF16 that rounded to nearest even.  Outside the crop rectangle: 0.
+ * mean / std: three host floats each (NULL for MPF_U8).
+ *
+ * recs_host / tab_host are the host copies of recs_dev / tab_dev (the caller's staging buffer, tab_len int32 elements): every
+ * record and every tap range is checked against them before the launch, so nothing read on the device can leave the source image,
+ * the tables or LDS.  NULL buffer: MPF_E_NULL; dtype: MPF_E_DTYPE; a source / resized ratio above mpf_img_resample_max_ratio() (64)
+ * on an axis, a canvas smaller than a crop, an inconsistent record or table: MPF_E_SHAPE; B > 65535 or a source of 2^31 bytes:
+ * MPF_E_TOO_LARGE.  B == 0 launches nothing.  Integer arithmetic and single writers: bitwise reproducible.
+ */
+typedef struct MpfResampleRecord {
+    const void* src;
+    int32_t src_stride, src_h, src_w, flip;
+    int32_t out_h, out_w, off_y, off_x;
+    int32_t crop_h, crop_w, valid_h, valid_w;
+    int32_t tile_h, ksize_x, ksize_y, xk_off;
+    int32_t xb_off, yk_off, yb_off, reserved;
+} MpfResampleRecord;
+/* taps stored per output of an axis, (int)ceil(max(in / out, 1)) * 2 + 1 (0 for non-positive sizes), and the tables of the outputs
+ * first .. first + count of that axis, coef int32 [count, ksize] and bounds int32 [count, 2], computed on the HOST in double as
+ * above (PIL's precompute_coeffs and normalize_coeffs_8bpc) into host memory: the caller's staging buffer. */
+int mpf_img_resample_ksize(int in_size, int out_size);
+int mpf_img_resample_tables(int in_size, int out_size, int first, int count, int32_t* coef, int32_t* bounds);
+int mpf_img_resample_span_rows(void);
+int mpf_img_resample_max_ratio(void);
+int mpf_img_resample(const MpfResampleRecord* recs_host, const MpfResampleRecord* recs_dev, const int32_t* tab_host,
+                     const int32_t* tab_dev, int64_t tab_len, int B, void* out, int dtype, int Hc, int Wc, int pad_value,
+                     const float* mean, const float* std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

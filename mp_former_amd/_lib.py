@@ -255,6 +255,12 @@ SIGNATURES = {
     "mpf_seg_rle_toggles": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "mpf_seg_toggles_fill": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
     "mpf_seg_unpack_masks": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_img_resample_ksize": (_c_int, [_c_int, _c_int]),
+    "mpf_img_resample_tables": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "mpf_img_resample_span_rows": (_c_int, []),
+    "mpf_img_resample_max_ratio": (_c_int, []),
+    "mpf_img_resample": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_int,
+                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _c_vp]),
 }
 
 

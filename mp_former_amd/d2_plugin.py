@@ -23,6 +23,10 @@ detectron2's ``Registry`` interface).  The construction convention of the regist
 The backbone is selected the same way from detectron2's ``BACKBONE_REGISTRY`` (``MODEL.BACKBONE.NAME``): ``register_backbone()``
 adds ``D2SwinTransformerHIP`` (swin.py, native shifted-window attention) there; the override is
 ``MODEL.BACKBONE.NAME D2SwinTransformerHIP``.
+
+The training input of the COCO-instance configuration can be formed on the device as well: ``COCOInstanceLSJDeviceMapper`` is the
+worker side of the reference's LSJ mapper (it only reads the image and draws the geometry) and ``install_native_lsj`` the model
+side (augment.py: one resample launch and one polygon pass per batch).
 """
 import functools
 
@@ -681,3 +685,99 @@ class InstanceAPEvaluator:
 
     def evaluate(self):
         return {t: ap.results(self.class_names) for t, ap in self.aps.items()}
+
+
+def _read_image_default():
+    """detectron2's ``detection_utils.read_image`` where importable, else PIL's decode to RGB (BGR on request)"""
+    try:
+        from detectron2.data.detection_utils import read_image
+        return read_image
+    except ImportError:
+        def read_image(file_name, format=None):
+            import numpy as np
+            from PIL import Image
+            with Image.open(file_name) as im:
+                a = np.asarray(im.convert("RGB"))
+            return a[:, :, ::-1] if format == "BGR" else a
+        return read_image
+
+
+class COCOInstanceLSJDeviceMapper:
+    """The worker side of the reference's ``COCOInstanceNewBaselineDatasetMapper``
+    (mask2former/data/dataset_mappers/coco_instance_new_baseline_dataset_mapper.py) when large-scale jitter runs on the device
+    (augment.py): it reads the image, DRAWS the geometry (flip, scale, crop, in the reference's order from ``numpy.random``) and
+    returns the dict with ``"image_raw"`` (uint8 [H, W, 3]), ``"lsj"`` (``augment.LSJParams``) and the non-crowd ``"annotations"``
+    without keypoints.  No resize and no rasterisation on the worker: ``install_native_lsj`` forms the batch on the model's device.
+    ``cls(cfg, is_train)`` reads ``cfg.INPUT`` as the reference's ``from_config`` does."""
+
+    @_configurable
+    def __init__(self, is_train=True, *, image_size, min_scale, max_scale, random_flip, image_format, read_image=None):
+        if not is_train:
+            raise ValueError("COCOInstanceLSJDeviceMapper: only training augmentation, as the reference's build_transform_gen")
+        if random_flip not in ("horizontal", "none"):
+            raise ValueError(f"COCOInstanceLSJDeviceMapper: random_flip must be 'horizontal' or 'none', got {random_flip!r}")
+        self.is_train, self.image_size, self.min_scale, self.max_scale = bool(is_train), image_size, float(min_scale), float(max_scale)
+        self.random_flip, self.image_format = random_flip, image_format
+        self.read_image = read_image or _read_image_default()
+
+    @classmethod
+    def from_config(cls, cfg, is_train=True):
+        return {"is_train": is_train, "image_size": cfg.INPUT.IMAGE_SIZE, "min_scale": cfg.INPUT.MIN_SCALE,
+                "max_scale": cfg.INPUT.MAX_SCALE, "random_flip": cfg.INPUT.RANDOM_FLIP, "image_format": cfg.INPUT.FORMAT}
+
+    def __call__(self, dataset_dict):
+        import numpy as np
+        import torch
+        from .augment import draw_lsj
+        d = {k: v for k, v in dataset_dict.items() if k != "annotations"}
+        image = np.ascontiguousarray(self.read_image(dataset_dict["file_name"], format=self.image_format))
+        if image.ndim != 3 or image.shape[2] != 3 or image.dtype != np.uint8:
+            raise ValueError(f"COCOInstanceLSJDeviceMapper: expected a uint8 [H, W, 3] image, got {image.dtype} {image.shape}")
+        for key, n in (("height", image.shape[0]), ("width", image.shape[1])):
+            if key in d and d[key] != n:
+                raise ValueError(f"COCOInstanceLSJDeviceMapper: {dataset_dict['file_name']} has {key} {n}, the dataset says {d[key]}")
+        d["image_raw"] = torch.from_numpy(image)
+        d["lsj"] = draw_lsj(image.shape[0], image.shape[1], image_size=self.image_size, min_scale=self.min_scale,
+                            max_scale=self.max_scale, flip=self.random_flip == "horizontal", rng=np.random)
+        if "annotations" in dataset_dict:
+            d["annotations"] = [{k: v for k, v in a.items() if k != "keypoints"} for a in dataset_dict["annotations"]
+                                if a.get("iscrowd", 0) == 0]
+        return d
+
+
+def native_lsj_inputs(batched_inputs, device):
+    """The dicts of ``COCOInstanceLSJDeviceMapper`` -> copies with ``"image"`` (uint8 [3, S, S] on ``device``) and ``"instances"``
+    (``gt_classes``, ``gt_masks`` bool [T, S, S], ``gt_boxes``, ``image_size``), as the reference's mapper would have left them: one
+    resample launch and one polygon pass for the batch (augment.lsj_batch)."""
+    from .augment import lsj_batch
+    from .inference import _structures
+    Boxes, Instances = _structures()
+    images, targets = lsj_batch(batched_inputs, device=device)
+    out = []
+    for x, image, t in zip(batched_inputs, images, targets):
+        p = x["lsj"]
+        d = {k: v for k, v in x.items() if k not in ("image_raw", "annotations")}
+        d["image"] = image[:, :p.crop[0], :p.crop[1]]
+        inst = Instances(tuple(p.crop))
+        inst.gt_classes = t["labels"]
+        inst.gt_masks = t["masks"]
+        inst.gt_boxes = Boxes(t["boxes"])
+        d["instances"] = inst
+        out.append(d)
+    return out
+
+
+def install_native_lsj(model):
+    """Route the training branch of a model fed by ``COCOInstanceLSJDeviceMapper`` through ``native_lsj_inputs``: ``forward`` forms
+    the batch on the model's device and hands the usual dicts ("image", "instances") on, so the model's own normalisation and
+    ``prepare_targets`` run unchanged.  Eval mode is passed through untouched.  Works without detectron2 (the ``Instances``
+    stand-in of inference.py)."""
+    inner = model.forward
+
+    def forward(batched_inputs):
+        if not model.training:
+            return inner(batched_inputs)
+        return inner(native_lsj_inputs(batched_inputs, model.device))
+
+    model.forward = forward
+    return forward
