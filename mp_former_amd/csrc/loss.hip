@@ -12,15 +12,17 @@
 // the BYTE ground-truth mask directly at the sampled corners and emits four sums per (prediction,
 // target) pair; the backward scatters d(loss)/d(logit) to the four corners with fp32 atomics.
 // All of it is HBM/L2-latency bound gather work: one thread per point, coalesced coordinate reads.
+//
+// The kernels come first, then the ten entry points on loss_host.h: an entry fills one LossProblem, runs loss_check, asks the route
+// function which kernel serves it, names that kernel and launches it, once per argument list (with_map_type and mpf::with_bool choose
+// the element type and the byte / bit form of the masks), and through launch_lds where the kernel takes dynamic LDS.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#include "mpf_common.h"
+#include "loss_host.h"
 
 namespace {
-
-constexpr int kThreads = 256;
 
 __device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }
 __device__ __forceinline__ float ld(const __hip_bfloat16* p, int64_t i) { return __bfloat162float(p[i]); }
@@ -265,185 +267,6 @@ __global__ __launch_bounds__(1024) void mask_loss_bwd_band_kernel(
     for (int k = threadIdx.x; k < cells; k += 1024) dst[k] = (TG)((float)band[k] * inv);
 }
 
-int check_common(const void* a, const void* b, const void* c, const void* d, int n, int P, int h, int w)
-{
-    if (!a || !b || !c || !d) return mpf::fail(MPF_E_NULL, "point-sample: NULL buffer");
-    if (n < 0 || P <= 0 || h <= 0 || w <= 0) return mpf::fail(MPF_E_SHAPE, "point-sample: bad sizes");
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int mpf_point_sample(const void* src, int src_dtype, int h, int w, const int64_t* rows,
-                                const float* coords, const int32_t* coord_rows, float* out, int n, int P,
-                                void* stream)
-{
-    if (int e = check_common(src, rows, coords, out, n, P, h, w)) return e;
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n > 65535) return mpf::fail(MPF_E_TOO_LARGE, "loss kernels: more than 65535 rows in one launch (grid.y)");
-    dim3 grid((P + kThreads - 1) / kThreads, n);
-    mpf::prof_begin(st);
-    if (src_dtype == MPF_F32) {
-        mpf::set_kernel("point_sample_kernel<float>");
-        hipLaunchKernelGGL(point_sample_kernel<float>, grid, dim3(kThreads), 0, st, (const float*)src, h, w,
-                           rows, coords, coord_rows, out, n, P);
-    } else if (src_dtype == MPF_BF16) {
-        mpf::set_kernel("point_sample_kernel<bf16>");
-        hipLaunchKernelGGL(point_sample_kernel<__hip_bfloat16>, grid, dim3(kThreads), 0, st,
-                           (const __hip_bfloat16*)src, h, w, rows, coords, coord_rows, out, n, P);
-    } else if (src_dtype == MPF_U8) {
-        mpf::set_kernel("point_sample_kernel<u8>");
-        hipLaunchKernelGGL(point_sample_kernel<uint8_t>, grid, dim3(kThreads), 0, st, (const uint8_t*)src, h, w,
-                           rows, coords, coord_rows, out, n, P);
-    } else if (src_dtype == MPF_BITS) {        // rows[] are PIXEL indices of the planes' first pixel
-        mpf::set_kernel("point_sample_bits_kernel");
-        hipLaunchKernelGGL(point_sample_bits_kernel, grid, dim3(kThreads), 0, st, (const uint32_t*)src, h, w,
-                           rows, coords, coord_rows, out, n, P);
-    } else {
-        return mpf::fail(MPF_E_DTYPE, "mpf_point_sample: dtype must be MPF_F32, MPF_BF16, MPF_U8 or MPF_BITS");
-    }
-    mpf::prof_end(mpf_last_kernel(), st, (double)n * P * (8.0 + 4.0 + 16.0));
-    return mpf::check(hipGetLastError(), "mpf_point_sample");
-}
-
-// defined further down (needs the LDS sampling helpers): returns false if the LDS variant does not apply
-static bool launch_mask_loss_fwd_lds(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows, const void* gt, bool bits,
-                                     int H, int W, const int32_t* gt_rows, const float* coords, float* partial, int n, int P, int chunks,
-                                     hipStream_t st, int* err);
-
-extern "C" int mpf_pack_mask_bits(const uint8_t* masks, void* bits, int64_t n_pixels, void* stream)
-{
-    if (!masks || !bits) return mpf::fail(MPF_E_NULL, "pack_mask_bits: NULL buffer");
-    if (n_pixels < 0 || n_pixels % 32 != 0) return mpf::fail(MPF_E_SHAPE, "pack_mask_bits: pixel count must be a multiple of 32");
-    if (n_pixels == 0) return 0;
-    const int64_t nwords = n_pixels / 32;
-    const int blocks = (int)((nwords + kThreads - 1) / kThreads < 4096 ? (nwords + kThreads - 1) / kThreads : 4096);
-    mpf::set_kernel("pack_mask_bits_kernel");
-    hipLaunchKernelGGL(pack_mask_bits_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, masks, (uint32_t*)bits, nwords);
-    return mpf::check(hipGetLastError(), "mpf_pack_mask_bits");
-}
-
-extern "C" int mpf_mask_loss_forward(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows,
-                                     const void* gt, int gt_dtype, int H, int W, const int32_t* gt_rows,
-                                     const float* coords, float* partial, int n, int P, int chunks,
-                                     void* stream)
-{
-    if (int e = check_common(pred, pred_rows, coords, partial, n, P, h, w)) return e;
-    if (!gt || !gt_rows) return mpf::fail(MPF_E_NULL, "mask_loss_forward: NULL buffer");
-    if (H <= 0 || W <= 0 || chunks <= 0) return mpf::fail(MPF_E_SHAPE, "mask_loss_forward: bad sizes");
-    if (gt_dtype != MPF_U8 && gt_dtype != MPF_BITS) return mpf::fail(MPF_E_DTYPE, "mask_loss_forward: gt dtype must be MPF_U8 or MPF_BITS");
-    if (gt_dtype == MPF_BITS && ((int64_t)H * W) % 32 != 0) return mpf::fail(MPF_E_SHAPE, "mask_loss_forward: bit-packed masks need H*W % 32 == 0");
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n > 65535) return mpf::fail(MPF_E_TOO_LARGE, "loss kernels: more than 65535 rows in one launch (grid.y)");
-    dim3 grid(chunks, n);
-    const bool bits = gt_dtype == MPF_BITS;
-    mpf::prof_begin(st);
-    {
-        int err = 0;
-        if (launch_mask_loss_fwd_lds(pred, pred_dtype, h, w, pred_rows, gt, bits, H, W, gt_rows, coords, partial, n, P, chunks, st, &err)) {
-            if (err) return err;
-            mpf::prof_end(mpf_last_kernel(), st, (double)n * ((double)h * w * 2.0 + P * (8.0 + 4.0)));
-            return mpf::check(hipGetLastError(), "mpf_mask_loss_forward");
-        }
-    }
-    if (pred_dtype == MPF_F32) {
-        mpf::set_kernel("mask_loss_fwd_kernel<float>");
-        if (bits) hipLaunchKernelGGL((mask_loss_fwd_kernel<float, true>), grid, dim3(kThreads), 0, st, (const float*)pred, h, w,
-                                     pred_rows, gt, H, W, gt_rows, coords, partial, n, P, chunks);
-        else hipLaunchKernelGGL((mask_loss_fwd_kernel<float, false>), grid, dim3(kThreads), 0, st, (const float*)pred, h, w,
-                                pred_rows, gt, H, W, gt_rows, coords, partial, n, P, chunks);
-    } else if (pred_dtype == MPF_BF16) {
-        mpf::set_kernel("mask_loss_fwd_kernel<bf16>");
-        if (bits) hipLaunchKernelGGL((mask_loss_fwd_kernel<__hip_bfloat16, true>), grid, dim3(kThreads), 0, st,
-                                     (const __hip_bfloat16*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords, partial, n, P, chunks);
-        else hipLaunchKernelGGL((mask_loss_fwd_kernel<__hip_bfloat16, false>), grid, dim3(kThreads), 0, st,
-                                (const __hip_bfloat16*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords, partial, n, P, chunks);
-    } else {
-        return mpf::fail(MPF_E_DTYPE, "mpf_mask_loss_forward: pred dtype must be MPF_F32 or MPF_BF16");
-    }
-    mpf::prof_end(mpf_last_kernel(), st, (double)n * P * (8.0 + 16.0 + 4.0));
-    return mpf::check(hipGetLastError(), "mpf_mask_loss_forward");
-}
-
-extern "C" int mpf_mask_loss_backward(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows,
-                                      const uint8_t* gt, int H, int W, const int32_t* gt_rows,
-                                      const float* coords, const float* grad_sums, float* grad_pred,
-                                      const int64_t* grad_offs, int n, int P, void* stream)
-{
-    if (int e = check_common(pred, pred_rows, coords, grad_pred, n, P, h, w)) return e;
-    if (!gt || !gt_rows || !grad_sums || !grad_offs) return mpf::fail(MPF_E_NULL, "mask_loss_backward: NULL buffer");
-    if (H <= 0 || W <= 0) return mpf::fail(MPF_E_SHAPE, "mask_loss_backward: bad sizes");
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n > 65535) return mpf::fail(MPF_E_TOO_LARGE, "loss kernels: more than 65535 rows in one launch (grid.y)");
-    dim3 grid((P + kThreads * 4 - 1) / (kThreads * 4), n);
-    mpf::prof_begin(st);
-    if (pred_dtype == MPF_F32) {
-        mpf::set_kernel("mask_loss_bwd_kernel<float>");
-        hipLaunchKernelGGL(mask_loss_bwd_kernel<float>, grid, dim3(kThreads), 0, st, (const float*)pred, h, w,
-                           pred_rows, gt, H, W, gt_rows, coords, grad_sums, grad_pred, grad_offs, n, P);
-    } else if (pred_dtype == MPF_BF16) {
-        mpf::set_kernel("mask_loss_bwd_kernel<bf16>");
-        hipLaunchKernelGGL(mask_loss_bwd_kernel<__hip_bfloat16>, grid, dim3(kThreads), 0, st,
-                           (const __hip_bfloat16*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords, grad_sums,
-                           grad_pred, grad_offs, n, P);
-    } else {
-        return mpf::fail(MPF_E_DTYPE, "mpf_mask_loss_backward: pred dtype must be MPF_F32 or MPF_BF16");
-    }
-    mpf::prof_end(mpf_last_kernel(), st, (double)n * P * (8.0 + 16.0 + 4.0 + 32.0));
-    return mpf::check(hipGetLastError(), "mpf_mask_loss_backward");
-}
-
-extern "C" int mpf_mask_loss_backward_dense(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows,
-                                            const void* gt, int gt_dtype, int H, int W, const int32_t* gt_rows, const float* coords,
-                                            const float* grad_sums, void* grad, int grad_dtype, const int64_t* grad_offs,
-                                            int n, int P, void* stream)
-{
-    if (int e = check_common(pred, pred_rows, coords, grad, n, P, h, w)) return e;
-    if (!gt || !gt_rows || !grad_sums || !grad_offs) return mpf::fail(MPF_E_NULL, "mask_loss_backward_dense: NULL buffer");
-    if (n == 0) return 0;
-    if (grad_dtype != pred_dtype) return mpf::fail(MPF_E_DTYPE, "mask_loss_backward_dense: gradient dtype must equal the map dtype");
-    if (gt_dtype != MPF_U8 && gt_dtype != MPF_BITS) return mpf::fail(MPF_E_DTYPE, "mask_loss_backward_dense: gt dtype must be MPF_U8 or MPF_BITS");
-    if (gt_dtype == MPF_BITS && ((int64_t)H * W) % 32 != 0) return mpf::fail(MPF_E_SHAPE, "mask_loss_backward_dense: bit-packed masks need H*W % 32 == 0");
-    const bool bits = gt_dtype == MPF_BITS;
-    hipStream_t st = (hipStream_t)stream;
-    // horizontal bands of at most 128 KiB of 32-bit accumulators
-    const int max_rows = (128 * 1024) / (4 * w);
-    if (max_rows < 2) return mpf::fail(MPF_E_TOO_LARGE, "mask_loss_backward_dense: plane rows wider than 16384");
-    const int nb = (h + max_rows - 1) / max_rows;
-    const int band_rows = (h + nb - 1) / nb;
-    const size_t lds = (size_t)band_rows * w * 4;
-    if (n > 65535) return mpf::fail(MPF_E_TOO_LARGE, "loss kernels: more than 65535 rows in one launch (grid.y)");
-    const dim3 grid(nb, n);
-    mpf::prof_begin(st);
-    if (pred_dtype == MPF_F32) {
-        mpf::set_kernel("mask_loss_bwd_band_kernel<float>");
-        const void* fn = bits ? (const void*)mask_loss_bwd_band_kernel<float, float, true> : (const void*)mask_loss_bwd_band_kernel<float, float, false>;
-        if (int e = mpf::check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute")) return e;
-        if (bits) hipLaunchKernelGGL((mask_loss_bwd_band_kernel<float, float, true>), grid, dim3(1024), lds, st, (const float*)pred, h, w,
-                                     pred_rows, gt, H, W, gt_rows, coords, grad_sums, (float*)grad, grad_offs, n, P, band_rows);
-        else hipLaunchKernelGGL((mask_loss_bwd_band_kernel<float, float, false>), grid, dim3(1024), lds, st, (const float*)pred, h, w,
-                                pred_rows, gt, H, W, gt_rows, coords, grad_sums, (float*)grad, grad_offs, n, P, band_rows);
-    } else if (pred_dtype == MPF_BF16) {
-        mpf::set_kernel("mask_loss_bwd_band_kernel<bf16>");
-        const void* fn = bits ? (const void*)mask_loss_bwd_band_kernel<__hip_bfloat16, __hip_bfloat16, true>
-                              : (const void*)mask_loss_bwd_band_kernel<__hip_bfloat16, __hip_bfloat16, false>;
-        if (int e = mpf::check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute")) return e;
-        if (bits) hipLaunchKernelGGL((mask_loss_bwd_band_kernel<__hip_bfloat16, __hip_bfloat16, true>), grid, dim3(1024), lds, st,
-                                     (const __hip_bfloat16*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords, grad_sums,
-                                     (__hip_bfloat16*)grad, grad_offs, n, P, band_rows);
-        else hipLaunchKernelGGL((mask_loss_bwd_band_kernel<__hip_bfloat16, __hip_bfloat16, false>), grid, dim3(1024), lds, st,
-                                (const __hip_bfloat16*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords, grad_sums,
-                                (__hip_bfloat16*)grad, grad_offs, n, P, band_rows);
-    } else {
-        return mpf::fail(MPF_E_DTYPE, "mpf_mask_loss_backward_dense: pred dtype must be MPF_F32 or MPF_BF16");
-    }
-    mpf::prof_end(mpf_last_kernel(), st, (double)n * P * (8.0 + 16.0 + 4.0) + (double)n * h * w * 2.0);
-    return mpf::check(hipGetLastError(), "mpf_mask_loss_backward_dense");
-}
-
 // ================================================================================================
 // Importance selection: per row keep the k points with the SMALLEST |logit| (= the most uncertain,
 // uncertainty = -|logit|, criterion.py:73-87 + detectron2 get_uncertain_point_coords_with_randomness)
@@ -451,10 +274,6 @@ extern "C" int mpf_mask_loss_backward_dense(const void* pred, int pred_dtype, in
 // non-negative floats) with an LDS histogram, then an order-preserving compaction — replaces
 // torch.topk (a full sort of 37632 keys per row) + gather.
 // ================================================================================================
-namespace {
-
-constexpr int kSelThreads = 1024;
-
 __device__ __forceinline__ int block_excl_scan_1024(int v, int* red, int* total)
 {
     // exclusive scan of one int per thread over 1024 threads (16 waves)
@@ -560,8 +379,6 @@ __global__ __launch_bounds__(kSelThreads) void select_uncertain_kernel(
 // ================================================================================================
 constexpr int kTT = 8;
 
-__host__ __device__ __forceinline__ int clip_partial_floats(int Tmax) { return 2 + 3 * Tmax; }
-
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(kThreads) void match_cost_kernel(
     const T* __restrict__ pred, int h, int w, const int64_t* __restrict__ pred_offs,
@@ -648,20 +465,6 @@ __global__ __launch_bounds__(kThreads) void match_cost_clip_fold_kernel(
 
 }  // namespace
 
-extern "C" int mpf_select_uncertain(const float* vals, const float* coords_in, float* coords_out,
-                                    int n, int M, int k, int P_out, void* stream)
-{
-    if (!vals || !coords_in || !coords_out) return mpf::fail(MPF_E_NULL, "select_uncertain: NULL buffer");
-    if (n < 0 || M <= 0 || k < 0 || k > M || P_out < k) return mpf::fail(MPF_E_SHAPE, "select_uncertain: bad sizes");
-    if (n == 0 || k == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    mpf::prof_begin(st);
-    mpf::set_kernel("select_uncertain_kernel");
-    hipLaunchKernelGGL(select_uncertain_kernel, dim3(n), dim3(kSelThreads), 0, st, vals, coords_in, coords_out, M, k, P_out);
-    mpf::prof_end(mpf_last_kernel(), st, (double)n * M * 12.0 * 2 + (double)n * k * 8.0);
-    return mpf::check(hipGetLastError(), "mpf_select_uncertain");
-}
-
 // ------------------------------------------------------------------------------------------------
 // Matching cost with the prediction plane staged in LDS.  The samples of a row are 4 x P random 2-byte
 // gathers from a 128 KB plane — from L2 that is the whole cost of the kernel above; from LDS it is
@@ -670,8 +473,6 @@ extern "C" int mpf_select_uncertain(const float* vals, const float* coords_in, f
 // samples and their sigmoids stay in registers, PT points per thread), then the target samples are
 // streamed ONCE for the G rows.  fp32 throughout; block reductions by wave shuffles + one LDS pass.
 // ------------------------------------------------------------------------------------------------
-constexpr int kMcThreads = 1024;
-
 // global -> LDS copy of a plane by a 1024-thread workgroup: all loads of a thread are issued before its
 // first LDS store (a load-store-load-store loop exposes one memory latency per 16 KiB)
 template <int THREADS = 1024>
@@ -1045,187 +846,200 @@ __global__ __launch_bounds__(kMcThreads) void mask_loss_fwd_lds_kernel(
     }
 }
 
-static bool launch_mask_loss_fwd_lds(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows, const void* gt, bool bits,
-                                     int H, int W, const int32_t* gt_rows, const float* coords, float* partial, int n, int P, int chunks,
-                                     hipStream_t st, int* err)
+// ---- entry points (loss_host.h: record, check, routes, launcher) ------------------------------------------------------------------
+namespace {
+
+using bf16 = __hip_bfloat16;
+
+// loss_begin: the profiler's start and the name of the kernel the route chose; loss_done: unless the launcher failed (e), the
+// profiler's record of that launch and its status
+hipStream_t loss_begin(void* stream, const char* kernel)
 {
-    const int plane_bytes = h * w * 2;
-    if (pred_dtype != MPF_BF16 || plane_bytes % 16 != 0 || plane_bytes > 128 * 1024 || chunks > 256) return false;
-    const size_t lds = (size_t)plane_bytes + (kMcThreads / 64) * 4 * sizeof(float);
-    const void* fn = bits ? (const void*)mask_loss_fwd_lds_kernel<true> : (const void*)mask_loss_fwd_lds_kernel<false>;
-    *err = mpf::check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute");
-    if (*err) return true;
-    mpf::set_kernel("mask_loss_fwd_lds_kernel");
-    if (bits) hipLaunchKernelGGL(mask_loss_fwd_lds_kernel<true>, dim3(n), dim3(kMcThreads), lds, st, (const __hip_bfloat16*)pred, h, w,
-                                 pred_rows, gt, H, W, gt_rows, coords, partial, P, chunks, plane_bytes);
-    else hipLaunchKernelGGL(mask_loss_fwd_lds_kernel<false>, dim3(n), dim3(kMcThreads), lds, st, (const __hip_bfloat16*)pred, h, w,
-                            pred_rows, gt, H, W, gt_rows, coords, partial, P, chunks, plane_bytes);
-    return true;
+    mpf::prof_begin((hipStream_t)stream);
+    mpf::set_kernel(kernel);
+    return (hipStream_t)stream;
+}
+int loss_done(const char* who, hipStream_t st, double bytes, int e = 0)
+{
+    if (e) return e;
+    mpf::prof_end(mpf_last_kernel(), st, bytes);
+    return mpf::check(hipGetLastError(), who);
 }
 
-// 512 threads x 25 points: the samples of 4 rows stay in registers without spilling (1024 threads leave
-// 128 VGPRs per lane: 180 spilled registers and 2.6x the time)
-// F == 0: the image form.  F >= 1 (mpf_match_cost_clip): per-frame sums into `partial`, any G >= 2 (the workgroups of a run
-// handle its tail), planes of at most 128 KiB.
-template <typename T>
-static bool launch_match_cost_lds(const T* pred, int h, int w, const int64_t* pred_offs, const float* coords,
-                                  const int32_t* coord_rows, const float* tsamp, const int32_t* t_first, const int32_t* t_count,
-                                  float* cost, int n_rows, int Tmax, int P, float w_mask, float w_dice, int G, hipStream_t st,
-                                  int* err, int F = 0, int64_t stride_f = 0, float* partial = nullptr)
+// both forms of the matching cost: p.F == 0 is the image form (no workspace, the kernels write the cost themselves)
+int match_cost(const char* who, const LossProblem& p, const void* pred, const int64_t* pred_offs, const float* coords, const int32_t* coord_rows,
+               const float* tsamp, const int32_t* t_first, const int32_t* t_count, float* cost, float w_mask, float w_dice, float* partial, void* stream)
 {
-    constexpr int THREADS = 512, PT = 25;
-    const int plane_bytes = h * w * (int)sizeof(T);
-    constexpr int GQ = 2;                      // rows per workgroup (4 would need ~300 registers per lane)
-    if (plane_bytes % 16 != 0 || P > PT * THREADS) return false;
-    if (F ? (G < 2 || n_rows % G != 0 || plane_bytes > 128 * 1024) : (G % GQ != 0 || plane_bytes > 136 * 1024 || n_rows % GQ != 0))
-        return false;
-    constexpr int NV = 2 * GQ * 4 + 4;
-    const size_t lds = (size_t)plane_bytes + (THREADS / 64) * NV * sizeof(float);
-    auto kfn = F ? match_cost_lds_kernel<T, GQ, PT, THREADS, true> : match_cost_lds_kernel<T, GQ, PT, THREADS, false>;
-    *err = mpf::check(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute");
-    if (*err) return true;
-    const dim3 grid = F ? dim3((n_rows / G) * ((G + GQ - 1) / GQ), F) : dim3(n_rows / GQ);
-    hipLaunchKernelGGL(kfn, grid, dim3(THREADS), lds, st, pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first,
-                       t_count, cost, n_rows, Tmax, P, w_mask, w_dice, plane_bytes, stride_f, partial, G);
-    return true;
+    const LossRoute route = match_cost_route(p);
+    const bool lds = route == LossRoute::lds;
+    const char* const names[2][2] = {{p.pick("match_cost_kernel<float>", "match_cost_kernel<bf16>"), "match_cost_lds_kernel<bf16>"},
+                                     {p.pick("match_cost_clip_kernel<float>", "match_cost_clip_kernel<bf16>"), "match_cost_clip_lds_kernel<bf16>"}};
+    hipStream_t st = loss_begin(stream, names[p.F > 0][lds]);
+    int e = 0;
+    mpf::with_bool(p.F > 0, [&](auto clip) { with_map_type(p.dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        constexpr bool CLIP = decltype(clip)::value;
+        if (lds)
+            e = launch_lds<match_cost_lds_kernel<bf16, kCostRows, kCostPT, kCostThreads, CLIP>>(
+                p.cost_lds_grid(), kCostThreads, p.cost_lds(), st, (const bf16*)pred, p.h, p.w, pred_offs, coords, coord_rows, tsamp, t_first,
+                t_count, cost, p.n, p.Tmax, p.P, w_mask, w_dice, (int)p.plane_bytes(), p.stride_f, partial, p.G);
+        else
+            e = launch_lds<match_cost_kernel<T, CLIP>, kDefaultLds>(
+                p.cost_grid(), kThreads, p.xs_bytes(), st, (const T*)pred, p.h, p.w, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost,
+                p.Tmax, p.P, w_mask, w_dice, p.stride_f, partial);
+    }); });
+    if (e || !p.F) return loss_done(who, st, p.bytes(route), e);
+    if (int e2 = mpf::check(hipGetLastError(), who)) return e2;
+    hipLaunchKernelGGL(match_cost_clip_fold_kernel, p.fold_grid(), dim3(kThreads), 0, st, partial, t_count, cost, p.n, p.F, p.Tmax, p.P,
+                       w_mask, w_dice);
+    return loss_done(who, st, p.bytes());
 }
 
-extern "C" int mpf_match_cost(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs,
-                              const float* coords, const int32_t* coord_rows, const float* tsamp,
-                              const int32_t* t_first, const int32_t* t_count, float* cost,
+}  // namespace
+
+extern "C" int mpf_point_sample(const void* src, int src_dtype, int h, int w, const int64_t* rows, const float* coords, const int32_t* coord_rows,
+                                float* out, int n, int P, void* stream)
+{
+    const LossProblem p(LossEntry::point_sample, src_dtype, h, w, n, P);
+    if (int e = loss_check("mpf_point_sample", p, {src, rows, coords, out}); e || p.empty()) return e;
+    const bool bits = src_dtype == MPF_BITS;                                  // rows[] are then PIXEL indices of the planes' first pixel
+    hipStream_t st = loss_begin(stream, bits ? "point_sample_bits_kernel" : src_dtype == MPF_U8 ? "point_sample_kernel<u8>"
+                                                                          : p.pick("point_sample_kernel<float>", "point_sample_kernel<bf16>"));
+    const dim3 grid = p.sample_grid(), block(kThreads);
+    if (bits)
+        hipLaunchKernelGGL(point_sample_bits_kernel, grid, block, 0, st, (const uint32_t*)src, h, w, rows, coords, coord_rows, out, n, P);
+    else
+        with_map_type<true>(src_dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL(point_sample_kernel<T>, grid, block, 0, st, (const T*)src, h, w, rows, coords, coord_rows, out, n, P);
+        });
+    return loss_done("mpf_point_sample", st, p.bytes());
+}
+
+extern "C" int mpf_pack_mask_bits(const uint8_t* masks, void* bits, int64_t n_pixels, void* stream)
+{
+    if (mpf::any_null({masks, bits})) return mpf::failf(MPF_E_NULL, "pack_mask_bits", "NULL buffer");
+    if (n_pixels < 0 || n_pixels % 32 != 0) return mpf::failf(MPF_E_SHAPE, "pack_mask_bits", "pixel count must be a multiple of 32");
+    if (n_pixels == 0) return 0;
+    const int64_t nwords = n_pixels / 32, want = (nwords + kThreads - 1) / kThreads;
+    mpf::set_kernel("pack_mask_bits_kernel");
+    hipLaunchKernelGGL(pack_mask_bits_kernel, dim3((int)(want < 4096 ? want : 4096)), dim3(kThreads), 0, (hipStream_t)stream, masks,
+                       (uint32_t*)bits, nwords);
+    return mpf::check(hipGetLastError(), "mpf_pack_mask_bits");
+}
+
+extern "C" int mpf_mask_loss_forward(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows, const void* gt, int gt_dtype, int H,
+                                     int W, const int32_t* gt_rows, const float* coords, float* partial, int n, int P, int chunks, void* stream)
+{
+    LossProblem p(LossEntry::forward, pred_dtype, h, w, n, P);
+    p.H = H; p.W = W; p.gt_dtype = gt_dtype; p.chunks = chunks;
+    if (int e = loss_check("mpf_mask_loss_forward", p, {pred, pred_rows, coords, partial}, {gt, gt_rows}); e || p.empty()) return e;
+    const LossRoute route = mask_loss_fwd_route(p);
+    const bool lds = route == LossRoute::lds;
+    hipStream_t st = loss_begin(stream, lds ? "mask_loss_fwd_lds_kernel" : p.pick("mask_loss_fwd_kernel<float>", "mask_loss_fwd_kernel<bf16>"));
+    int e = 0;
+    with_map_type(pred_dtype, [&](auto t) { mpf::with_bool(p.bits(), [&](auto b) {
+        using T = typename decltype(t)::type;
+        constexpr bool BITS = decltype(b)::value;
+        if (lds)
+            e = launch_lds<mask_loss_fwd_lds_kernel<BITS>>(dim3(n), kMcThreads, p.fwd_lds(), st, (const bf16*)pred, h, w, pred_rows, gt, H, W,
+                                                          gt_rows, coords, partial, P, chunks, (int)p.plane_bytes());
+        else
+            hipLaunchKernelGGL((mask_loss_fwd_kernel<T, BITS>), p.fwd_grid(), dim3(kThreads), 0, st, (const T*)pred, h, w, pred_rows, gt, H, W,
+                               gt_rows, coords, partial, n, P, chunks);
+    }); });
+    return loss_done("mpf_mask_loss_forward", st, p.bytes(route), e);
+}
+
+extern "C" int mpf_mask_loss_backward(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows, const uint8_t* gt, int H, int W,
+                                      const int32_t* gt_rows, const float* coords, const float* grad_sums, float* grad_pred,
+                                      const int64_t* grad_offs, int n, int P, void* stream)
+{
+    LossProblem p(LossEntry::backward, pred_dtype, h, w, n, P);
+    p.H = H; p.W = W;
+    const int bad = loss_check("mpf_mask_loss_backward", p, {pred, pred_rows, coords, grad_pred}, {gt, gt_rows, grad_sums, grad_offs});
+    if (bad || p.empty()) return bad;
+    hipStream_t st = loss_begin(stream, p.pick("mask_loss_bwd_kernel<float>", "mask_loss_bwd_kernel<bf16>"));
+    with_map_type(pred_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(mask_loss_bwd_kernel<T>, p.bwd_grid(), dim3(kThreads), 0, st, (const T*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords,
+                           grad_sums, grad_pred, grad_offs, n, P);
+    });
+    return loss_done("mpf_mask_loss_backward", st, p.bytes());
+}
+
+extern "C" int mpf_mask_loss_backward_dense(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_rows, const void* gt, int gt_dtype,
+                                            int H, int W, const int32_t* gt_rows, const float* coords, const float* grad_sums, void* grad,
+                                            int grad_dtype, const int64_t* grad_offs, int n, int P, void* stream)
+{
+    LossProblem p(LossEntry::backward_dense, pred_dtype, h, w, n, P);
+    p.H = H; p.W = W; p.gt_dtype = gt_dtype; p.grad_dtype = grad_dtype;
+    const int bad = loss_check("mpf_mask_loss_backward_dense", p, {pred, pred_rows, coords, grad}, {gt, gt_rows, grad_sums, grad_offs});
+    if (bad || p.empty()) return bad;
+    hipStream_t st = loss_begin(stream, p.pick("mask_loss_bwd_band_kernel<float>", "mask_loss_bwd_band_kernel<bf16>"));
+    int e = 0;
+    with_map_type(pred_dtype, [&](auto t) { mpf::with_bool(p.bits(), [&](auto b) {
+        using T = typename decltype(t)::type;
+        e = launch_lds<mask_loss_bwd_band_kernel<T, T, decltype(b)::value>>(
+            p.band_grid(), kBandThreads, p.band_lds(), st, (const T*)pred, h, w, pred_rows, gt, H, W, gt_rows, coords, grad_sums, (T*)grad,
+            grad_offs, n, P, p.band_rows());
+    }); });
+    return loss_done("mpf_mask_loss_backward_dense", st, p.bytes(), e);
+}
+
+extern "C" int mpf_select_uncertain(const float* vals, const float* coords_in, float* coords_out, int n, int M, int k, int P_out, void* stream)
+{
+    LossProblem p(LossEntry::select, MPF_F32, 1, 1, n);
+    p.M = M; p.k = k; p.P_out = P_out;
+    if (int e = loss_check("mpf_select_uncertain", p, {vals, coords_in, coords_out}); e || p.empty()) return e;
+    hipStream_t st = loss_begin(stream, "select_uncertain_kernel");
+    hipLaunchKernelGGL(select_uncertain_kernel, dim3(n), dim3(kSelThreads), 0, st, vals, coords_in, coords_out, M, k, P_out);
+    return loss_done("mpf_select_uncertain", st, p.bytes());
+}
+
+extern "C" int mpf_sample_select_uncertain(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs, const float* coords_in,
+                                           float* coords_out, int n, int M, int k, int P_out, void* stream)
+{
+    LossProblem p(LossEntry::sample_select, pred_dtype, h, w, n);
+    p.M = M; p.k = k; p.P_out = P_out;
+    if (int e = loss_check("mpf_sample_select_uncertain", p, {pred, pred_offs, coords_in, coords_out}); e || p.empty()) return e;
+    hipStream_t st = loss_begin(stream, "sample_select_kernel<bf16>");
+    int e = 0;
+    mpf::with_int_of<16, 37, 40>(sample_select_pt(M), [&](auto pt) {
+        constexpr int PT = decltype(pt)::value;
+        e = launch_lds<sample_select_kernel<bf16, PT>>(dim3(n), kMcThreads, p.select_lds(PT), st, (const bf16*)pred, h, w, pred_offs, coords_in,
+                                                       coords_out, M, k, P_out, (int)p.plane_bytes());
+    });
+    return loss_done("mpf_sample_select_uncertain", st, p.bytes(), e);
+}
+
+extern "C" int mpf_match_cost(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs, const float* coords,
+                              const int32_t* coord_rows, const float* tsamp, const int32_t* t_first, const int32_t* t_count, float* cost,
                               int n_rows, int Tmax, int P, float w_mask, float w_dice, int rows_per_group, void* stream)
 {
-    if (!pred || !pred_offs || !coords || !coord_rows || !tsamp || !t_first || !t_count || !cost)
-        return mpf::fail(MPF_E_NULL, "match_cost: NULL buffer");
-    if (n_rows < 0 || Tmax <= 0 || P <= 0 || h <= 0 || w <= 0) return mpf::fail(MPF_E_SHAPE, "match_cost: bad sizes");
-    if ((size_t)P * 4 > 150 * 1024) return mpf::fail(MPF_E_TOO_LARGE, "match_cost: more than 38400 points per row");
-    if (n_rows == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    mpf::prof_begin(st);
-    if (pred_dtype == MPF_BF16 && rows_per_group >= 2 && rows_per_group % 2 == 0) {
-        int err = 0;
-        mpf::set_kernel("match_cost_lds_kernel<bf16>");
-        if (launch_match_cost_lds((const __hip_bfloat16*)pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost,
-                                  n_rows, Tmax, P, w_mask, w_dice, rows_per_group, st, &err)) {
-            if (err) return err;
-            mpf::prof_end(mpf_last_kernel(), st, (double)n_rows * ((double)h * w * 2.0 + P * 8.0 / 4 + P * 4.0 * Tmax / 4));
-            return mpf::check(hipGetLastError(), "mpf_match_cost");
-        }
-    }
-    // the generic kernel keeps the row's P logits in dynamic LDS: above 32 KiB the limit is raised, as in mpf_match_cost_clip (once per
-    // device and size, not per launch: the matcher on materialised maps comes through here with 12544 points for every step)
-    const size_t xs_bytes = (size_t)P * 4;
-    if (pred_dtype == MPF_F32) {
-        mpf::set_kernel("match_cost_kernel<float>");
-        auto kfn = match_cost_kernel<float, false>;
-        static mpf::LdsAttr attr;
-        if (xs_bytes > 32 * 1024)
-            if (int e = mpf::ensure_dynamic_lds((const void*)kfn, xs_bytes, attr)) return e;
-        hipLaunchKernelGGL(kfn, dim3(n_rows), dim3(kThreads), xs_bytes, st, (const float*)pred, h, w,
-                           pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, (int64_t)0,
-                           (float*)nullptr);
-    } else if (pred_dtype == MPF_BF16) {
-        mpf::set_kernel("match_cost_kernel<bf16>");
-        auto kfn = match_cost_kernel<__hip_bfloat16, false>;
-        static mpf::LdsAttr attr;
-        if (xs_bytes > 32 * 1024)
-            if (int e = mpf::ensure_dynamic_lds((const void*)kfn, xs_bytes, attr)) return e;
-        hipLaunchKernelGGL(kfn, dim3(n_rows), dim3(kThreads), xs_bytes, st,
-                           (const __hip_bfloat16*)pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first, t_count,
-                           cost, Tmax, P, w_mask, w_dice, (int64_t)0, (float*)nullptr);
-    } else {
-        return mpf::fail(MPF_E_DTYPE, "mpf_match_cost: pred dtype must be MPF_F32 or MPF_BF16");
-    }
-    mpf::prof_end(mpf_last_kernel(), st, (double)n_rows * P * (8.0 + 16.0 + 4.0 * Tmax));
-    return mpf::check(hipGetLastError(), "mpf_match_cost");
+    LossProblem p(LossEntry::cost, pred_dtype, h, w, n_rows, P);
+    p.Tmax = Tmax; p.G = rows_per_group;
+    if (int e = loss_check("mpf_match_cost", p, {pred, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost}); e || p.empty()) return e;
+    return match_cost("mpf_match_cost", p, pred, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost, w_mask, w_dice, nullptr, stream);
 }
 
 extern "C" size_t mpf_match_cost_clip_workspace_bytes(int n_rows, int F, int Tmax)
 {
-    if (n_rows <= 0 || F <= 0 || Tmax <= 0) return 0;
-    return (size_t)n_rows * F * clip_partial_floats(Tmax) * sizeof(float);
+    LossProblem p(LossEntry::cost_clip, MPF_BF16, 1, 1, n_rows);
+    p.F = F; p.Tmax = Tmax;
+    return p.workspace_bytes();
 }
 
 extern "C" int mpf_match_cost_clip(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs, int F, int64_t stride_f,
-                                   const float* coords, const int32_t* coord_rows, const float* tsamp,
-                                   const int32_t* t_first, const int32_t* t_count, float* cost,
-                                   int n_rows, int Tmax, int P, float w_mask, float w_dice, int rows_per_group,
-                                   void* workspace, size_t workspace_bytes, void* stream)
+                                   const float* coords, const int32_t* coord_rows, const float* tsamp, const int32_t* t_first,
+                                   const int32_t* t_count, float* cost, int n_rows, int Tmax, int P, float w_mask, float w_dice,
+                                   int rows_per_group, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!pred || !pred_offs || !coords || !coord_rows || !tsamp || !t_first || !t_count || !cost)
-        return mpf::fail(MPF_E_NULL, "match_cost_clip: NULL buffer");
-    if (n_rows < 0 || Tmax <= 0 || P <= 0 || h <= 0 || w <= 0 || F <= 0 || rows_per_group <= 0)
-        return mpf::fail(MPF_E_SHAPE, "match_cost_clip: bad sizes");
-    if (stride_f < (int64_t)h * w && F > 1) return mpf::fail(MPF_E_SHAPE, "match_cost_clip: the frames of a row overlap (stride_f < h * w)");
-    if (pred_dtype != MPF_F32 && pred_dtype != MPF_BF16) return mpf::fail(MPF_E_DTYPE, "mpf_match_cost_clip: pred dtype must be MPF_F32 or MPF_BF16");
-    // per FRAME, as in mpf_match_cost: the generic kernel keeps one frame's logits in LDS, never the F * P of a tube
-    if ((size_t)P * 4 > 150 * 1024) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_clip: more than 38400 points per frame");
-    if (F > 65535) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_clip: more than 65535 frames (grid.y)");
-    if ((int64_t)n_rows * Tmax > (int64_t)kThreads * 0x7fffffff) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_clip: cost matrix too large");
-    if (n_rows == 0) return 0;
-    if (!workspace) return mpf::fail(MPF_E_NULL, "match_cost_clip: NULL workspace");
-    if (workspace_bytes < mpf_match_cost_clip_workspace_bytes(n_rows, F, Tmax))
-        return mpf::fail(MPF_E_SHAPE, "match_cost_clip: workspace too small (mpf_match_cost_clip_workspace_bytes)");
-    hipStream_t st = (hipStream_t)stream;
+    LossProblem p(LossEntry::cost_clip, pred_dtype, h, w, n_rows, P);
+    p.F = F; p.stride_f = stride_f; p.Tmax = Tmax; p.G = rows_per_group;
+    const int bad = loss_check("mpf_match_cost_clip", p, {pred, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost}, {}, workspace, workspace_bytes);
+    if (bad || p.empty()) return bad;
     float* partial = (float*)workspace;
-    const size_t xs_bytes = (size_t)P * 4;
-    mpf::prof_begin(st);
-    bool done = false;
-    if (pred_dtype == MPF_BF16 && rows_per_group >= 2) {
-        int err = 0;
-        mpf::set_kernel("match_cost_clip_lds_kernel<bf16>");
-        done = launch_match_cost_lds((const __hip_bfloat16*)pred, h, w, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost,
-                                     n_rows, Tmax, P, w_mask, w_dice, rows_per_group, st, &err, F, stride_f, partial);
-        if (err) return err;
-    }
-    if (!done && pred_dtype == MPF_F32) {
-        mpf::set_kernel("match_cost_clip_kernel<float>");
-        auto kfn = match_cost_kernel<float, true>;
-        if (xs_bytes > 32 * 1024)
-            if (int e = mpf::check(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs_bytes), "hipFuncSetAttribute")) return e;
-        hipLaunchKernelGGL(kfn, dim3(n_rows, F), dim3(kThreads), xs_bytes, st, (const float*)pred, h, w, pred_offs, coords, coord_rows,
-                           tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, stride_f, partial);
-    } else if (!done) {
-        mpf::set_kernel("match_cost_clip_kernel<bf16>");
-        auto kfn = match_cost_kernel<__hip_bfloat16, true>;
-        if (xs_bytes > 32 * 1024)
-            if (int e = mpf::check(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs_bytes), "hipFuncSetAttribute")) return e;
-        hipLaunchKernelGGL(kfn, dim3(n_rows, F), dim3(kThreads), xs_bytes, st, (const __hip_bfloat16*)pred, h, w, pred_offs, coords,
-                           coord_rows, tsamp, t_first, t_count, cost, Tmax, P, w_mask, w_dice, stride_f, partial);
-    }
-    if (int e = mpf::check(hipGetLastError(), "mpf_match_cost_clip")) return e;
-    const int64_t cells = (int64_t)n_rows * Tmax;
-    hipLaunchKernelGGL(match_cost_clip_fold_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, partial,
-                       t_count, cost, n_rows, F, Tmax, P, w_mask, w_dice);
-    mpf::prof_end(mpf_last_kernel(), st, (double)n_rows * F * ((double)h * w * 2.0 + P * 8.0 / 2 + P * 4.0 * Tmax / 2));
-    return mpf::check(hipGetLastError(), "mpf_match_cost_clip");
+    return match_cost("mpf_match_cost_clip", p, pred, pred_offs, coords, coord_rows, tsamp, t_first, t_count, cost, w_mask, w_dice, partial, stream);
 }
 
-extern "C" int mpf_sample_select_uncertain(const void* pred, int pred_dtype, int h, int w, const int64_t* pred_offs,
-                                           const float* coords_in, float* coords_out, int n, int M, int k, int P_out,
-                                           void* stream)
-{
-    if (!pred || !pred_offs || !coords_in || !coords_out) return mpf::fail(MPF_E_NULL, "sample_select_uncertain: NULL buffer");
-    if (n < 0 || M <= 0 || k < 0 || k > M || k > P_out || h <= 0 || w <= 0) return mpf::fail(MPF_E_SHAPE, "sample_select_uncertain: bad sizes");
-    if (n == 0 || k == 0) return 0;
-    const int plane_bytes = h * w * 2;
-    if (pred_dtype != MPF_BF16) return mpf::fail(MPF_E_DTYPE, "sample_select_uncertain: bf16 maps only (use mpf_point_sample + mpf_select_uncertain)");
-    if (plane_bytes % 16 != 0 || plane_bytes > 128 * 1024 || M > 40 * kMcThreads)
-        return mpf::fail(MPF_E_TOO_LARGE, "sample_select_uncertain: plane larger than 128 KiB or more than 40960 candidates");
-    hipStream_t st = (hipStream_t)stream;
-    // keys per thread: 37 covers the shipped 3 x 12544 candidates without register spills; 40 is the general cap
-    const int PT = M <= 16 * kMcThreads ? 16 : (M <= 37 * kMcThreads ? 37 : 40);
-    const size_t lds = (size_t)plane_bytes + (256 + 2 * PT * 16 + 8) * sizeof(int);
-    const void* fn = PT == 16 ? (const void*)sample_select_kernel<__hip_bfloat16, 16>
-                              : (PT == 37 ? (const void*)sample_select_kernel<__hip_bfloat16, 37> : (const void*)sample_select_kernel<__hip_bfloat16, 40>);
-    if (int e = mpf::check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute")) return e;
-    mpf::prof_begin(st);
-    mpf::set_kernel("sample_select_kernel<bf16>");
-#define MPF_SS_LAUNCH(PTV)                                                                                                        \
-    hipLaunchKernelGGL((sample_select_kernel<__hip_bfloat16, PTV>), dim3(n), dim3(kMcThreads), lds, st, (const __hip_bfloat16*)pred, h, w, \
-                       pred_offs, coords_in, coords_out, M, k, P_out, plane_bytes)
-    if (PT == 16) MPF_SS_LAUNCH(16); else if (PT == 37) MPF_SS_LAUNCH(37); else MPF_SS_LAUNCH(40);
-#undef MPF_SS_LAUNCH
-    mpf::prof_end(mpf_last_kernel(), st, (double)n * ((double)plane_bytes + M * 8.0 + k * 16.0));
-    return mpf::check(hipGetLastError(), "mpf_sample_select_uncertain");
-}
