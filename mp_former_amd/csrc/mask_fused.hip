@@ -29,20 +29,14 @@
 //     two adjacent rows, v_perm_b32 pairs, 4-byte LDS stores into a [column][64 k] image whose 16-byte slots are XOR-swizzled
 //     so that both the stores (2 x 32 lanes, 32 banks) and the ds_read_b128 fragment reads (MI355X_MICROARCH.md: four
 //     non-contiguous 16-lane groups, 64 banks) are conflict-free.
-#include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
-#include <stdint.h>
 
-#include <algorithm>
-
-#include "mpf_common.h"
+#include "mask_fused_host.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-constexpr int kC = 256;           // mask dimension (contraction length of the product)
-constexpr int kT = 256;
 
 __device__ __forceinline__ unsigned pack_bf16(float a, float b)
 {
@@ -380,11 +374,7 @@ __global__ __launch_bounds__(kT) void tsamp_rowsum_kernel(const float* __restric
     if (tid == 0) tsum[row] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-constexpr int kMP = 32;           // points per tile
-constexpr int kMQ = 128;          // queries per workgroup (8 row tiles)
-// LDS: [0, 16K) interpolated features, high planes [32 pt][512 B]; [16K, 32K) low planes; then X [128][33] f32; then TV
-constexpr int kOffLo = kMP * 512, kOffX = 2 * kMP * 512, kOffTV = kOffX + kMQ * 33 * 4;
-
+// (tile constants kMP, kMQ and the LDS offsets kOffLo, kOffX, kOffTV: mask_fused_host.h)
 // CLIP: the group's map is F frames (planes feat_fs elements apart) sampled at ONE point set; the workgroup's range runs over
 // the F * ceil(P / 32) tiles of all frames, frame-major, so a tile never straddles two frames: its plane, its clamped corner
 // indices and its cut at P are the frame's own, and tsamp rows are [F][P].  F = 1 is the image problem, tile for tile.
@@ -562,75 +552,46 @@ __global__ __launch_bounds__(kT) void match_cost_reduce_kernel(const float* __re
     cost[i] = w_mask * (sp - sx) / (float)P + w_dice * (1.f - (2.f * sst + 1.f) / (ss + st + 1.f));
 }
 
-struct McGeom {
-    int ntiles, tiles_per_wg, nwg, qgroups;
-};
-McGeom mc_geom(int G, int Q, int P, int F = 1)
+// ---- host: the record, its check and its layouts are mask_fused_host.h; here every kernel's argument list is written once -----------
+// launch of a kernel that is named (mpf_last_kernel) and logged by the profiler
+template <class K, class... A>
+void launch_named(const char* name, K kernel, dim3 grid, size_t lds, hipStream_t st, double bytes, double flops, A... args)
 {
-    McGeom m;
-    m.ntiles = F * ((P + kMP - 1) / kMP);          // of all frames
-    m.qgroups = (Q + kMQ - 1) / kMQ;
-    // two workgroups fit a CU (208 VGPRs): ONE full round of 512 (768 workgroups = 1.5 rounds measured 8 % slower)
-    const int want = std::max(1, 512 / std::max(1, G * m.qgroups));
-    m.tiles_per_wg = (m.ntiles + want - 1) / want;
-    m.nwg = (m.ntiles + m.tiles_per_wg - 1) / m.tiles_per_wg;
-    return m;
-}
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <int TCH, bool CLIP>
-void launch_mc(dim3 grid, hipStream_t st, const __hip_bfloat16* embed, const int64_t* embed_first, int64_t ers, const __hip_bfloat16* feat,
-               int64_t feat_bs, const int32_t* gi, int h, int w, const float* coords, const float* tsamp, const int32_t* t_first,
-               const int32_t* t_count, float* pqt, float* pq, int G, int Q, int Tmax, int P, int tpw, int64_t feat_fs, int F)
-{
-    const size_t lds = kOffTV + (size_t)kMP * 2 * TCH * 4;
-    // > 64 KB of dynamic LDS needs the attribute; it is PER DEVICE, so it is set (and checked) on every launch like loss.hip does
-    if (lds > 48 * 1024 &&
-        mpf::check(hipFuncSetAttribute(reinterpret_cast<const void*>(&match_cost_fused_kernel<TCH, CLIP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                   "match_cost_fused: hipFuncSetAttribute") != 0)
-        return;
-    hipLaunchKernelGGL((match_cost_fused_kernel<TCH, CLIP>), grid, dim3(kT), lds, st, embed, embed_first, ers, feat, feat_bs, gi, h, w, coords,
-                       tsamp, t_first, t_count, pqt, pq, G, Q, Tmax, P, tpw, feat_fs, F);
-}
-
-// the three launches of both entries: target row sums, per-workgroup partial sums, fixed-order fold
-template <bool CLIP>
-int mc_run(const void* embed, const int64_t* embed_first, int64_t embed_row_stride, const void* features, int64_t feat_bs, int64_t feat_fs,
-           const int32_t* group_image, int h, int w, const float* coords, const float* tsamp, int tsamp_rows, const int32_t* t_first,
-           const int32_t* t_count, float* cost, int G, int Q, int Tmax, int P, int F, float w_mask, float w_dice, void* workspace,
-           void* stream, const char* what)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const McGeom m = mc_geom(G, Q, P, F);
-    char* ws = (char*)workspace;
-    float* pqt = (float*)ws;
-    float* pq = (float*)(ws + align256((size_t)m.nwg * G * Q * Tmax * 2 * 4));
-    float* tsum = (float*)((char*)pq + align256((size_t)m.nwg * G * Q * 2 * 4));
-    const __hip_bfloat16* e = (const __hip_bfloat16*)embed;
-    const __hip_bfloat16* f = (const __hip_bfloat16*)features;
-    hipLaunchKernelGGL(tsamp_rowsum_kernel, dim3(tsamp_rows), dim3(kT), 0, st, tsamp, tsum, tsamp_rows, F * P);
-    const dim3 grid(m.nwg, G, m.qgroups);
-    const int need = (Tmax + 1) / 2;
     mpf::prof_begin(st);
-    mpf::set_kernel("match_cost_fused_kernel");
-#define MPF_MC(TCH) launch_mc<TCH, CLIP>(grid, st, e, embed_first, embed_row_stride, f, feat_bs, group_image, h, w, coords, tsamp, t_first, \
-                                         t_count, pqt, pq, G, Q, Tmax, P, m.tiles_per_wg, feat_fs, F)
-    if (need <= 4) MPF_MC(4);
-    else if (need <= 8) MPF_MC(8);
-    else if (need <= 12) MPF_MC(12);
-    else if (need <= 16) MPF_MC(16);
-    else if (need <= 24) MPF_MC(24);
-    else if (need <= 32) MPF_MC(32);
-    else MPF_MC(64);
-#undef MPF_MC
-    // gathers: 4 corner rows of 512 B per point; flops: the two-plane product
-    mpf::prof_end("match_cost_fused_kernel", st, (double)G * m.qgroups * F * P * 2048.0 + (double)tsamp_rows * F * P * 4.0,
-                  2.0 * 2.0 * (double)G * Q * F * P * kC);
-    const int64_t n = (int64_t)G * Q * Tmax;
-    hipLaunchKernelGGL(match_cost_reduce_kernel, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, st, pqt, pq, tsum, t_first, t_count, cost,
-                       m.nwg, G, Q, Tmax, F * P, w_mask, w_dice);
-    return mpf::check(hipGetLastError(), what);
+    mpf::set_kernel(name);
+    hipLaunchKernelGGL(kernel, grid, dim3(kT), lds, st, args...);
+    mpf::prof_end(name, st, bytes, flops);
+}
+
+// both cost entries: the check, then three launches: target row sums, per-workgroup partial sums, fixed-order fold
+int run_cost(const char* who, const MaskFusedProblem& p, const void* embed, const int64_t* embed_first, const void* features,
+             const int32_t* group_image, const float* coords, const float* tsamp, const int32_t* t_first, const int32_t* t_count, float* cost,
+             float w_mask, float w_dice, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (int e = mask_fused_check(who, p, {embed, embed_first, features, group_image, coords, tsamp, t_first, t_count, cost}, workspace,
+                                 workspace_bytes))
+        return e;
+    hipStream_t st = (hipStream_t)stream;
+    const CostWs ws = p.cost_ws();
+    float *pqt = (float*)workspace, *pq = (float*)((char*)workspace + ws.part_q), *tsum = (float*)((char*)workspace + ws.tsum);
+    hipLaunchKernelGGL(tsamp_rowsum_kernel, p.rowsum_grid(), dim3(kT), 0, st, tsamp, tsum, p.tsamp_rows, (int)p.samples());
+    int err = 0;
+    mpf::with_bool(p.clip(), [&](auto clip) {
+        mpf::with_int_of<4, 8, 12, 16, 24, 32, 64>(p.tch(), [&](auto tch) {
+            constexpr auto K = match_cost_fused_kernel<decltype(tch)::value, decltype(clip)::value>;
+            // every chunk width takes more dynamic LDS (50 688 .. 66 048 bytes) than a kernel gets unasked: the limit is raised once
+            // per (kernel, device)
+            static mpf::LdsAttr attr;
+            if ((err = mpf::ensure_dynamic_lds((const void*)K, p.cost_lds(), attr))) return;
+            launch_named("match_cost_fused_kernel", K, p.cost_grid(), p.cost_lds(), st, p.cost_bytes(), p.cost_flops(), (const __hip_bfloat16*)embed,
+                         embed_first, p.embed_row_stride, (const __hip_bfloat16*)features, p.feat_stride, group_image, p.h, p.w, coords, tsamp,
+                         t_first, t_count, pqt, pq, p.G, p.Q, p.Tmax, p.P, (int)p.tiles_per_wg(), p.feat_frame_stride, p.F);
+        });
+    });
+    if (err) return err;          // nothing wrote the partial sums: no fold
+    hipLaunchKernelGGL(match_cost_reduce_kernel, p.fold_grid(), dim3(kT), 0, st, pqt, pq, tsum, t_first, t_count, cost, (int)p.nwg(), p.G, p.Q,
+                       p.Tmax, (int)p.samples(), w_mask, w_dice);
+    return mpf::check(hipGetLastError(), who);
 }
 
 }  // namespace
@@ -640,9 +601,14 @@ int mc_run(const void* embed, const int64_t* embed_first, int64_t embed_row_stri
 // --------------------------------------------------------------------------------------------------------------------
 extern "C" size_t mpf_match_cost_fused_workspace_bytes(int G, int Q, int Tmax, int P, int tsamp_rows)
 {
-    if (G <= 0 || Q <= 0 || Tmax <= 0 || P <= 0 || tsamp_rows < 0) return 0;
-    const McGeom m = mc_geom(G, Q, P);
-    return align256((size_t)m.nwg * G * Q * Tmax * 2 * 4) + align256((size_t)m.nwg * G * Q * 2 * 4) + align256((size_t)tsamp_rows * 4);
+    return mpf_match_cost_fused_clip_workspace_bytes(G, Q, Tmax, P, 1, tsamp_rows);
+}
+
+extern "C" size_t mpf_match_cost_fused_clip_workspace_bytes(int G, int Q, int Tmax, int P, int F, int tsamp_rows)
+{
+    MaskFusedProblem p{MaskFusedEntry::cost_clip};
+    p.G = G; p.Q = Q; p.Tmax = Tmax; p.P = P; p.F = F; p.tsamp_rows = tsamp_rows;
+    return p.cost_ws().total;
 }
 
 extern "C" int mpf_match_cost_fused(const void* embed, const int64_t* embed_first, int64_t embed_row_stride, const void* features,
@@ -650,24 +616,11 @@ extern "C" int mpf_match_cost_fused(const void* embed, const int64_t* embed_firs
                                     const float* tsamp, int tsamp_rows, const int32_t* t_first, const int32_t* t_count, float* cost, int G,
                                     int Q, int Tmax, int P, float w_mask, float w_dice, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!embed || !embed_first || !features || !group_image || !coords || !tsamp || !t_first || !t_count || !cost || !workspace)
-        return mpf::fail(MPF_E_NULL, "match_cost_fused: NULL buffer");
-    if (channels != kC) return mpf::fail(MPF_E_SHAPE, "match_cost_fused: 256 channels only");
-    if (G <= 0 || Q <= 0 || Tmax <= 0 || P <= 0 || h <= 0 || w <= 0 || tsamp_rows <= 0) return mpf::fail(MPF_E_SHAPE, "match_cost_fused: bad sizes");
-    if (Tmax > 128) return mpf::fail(MPF_E_SHAPE, "match_cost_fused: at most 128 targets per image");
-    if ((embed_row_stride % 8) || (feat_img_stride % 8)) return mpf::fail(MPF_E_SHAPE, "match_cost_fused: rows must be 16-byte aligned");
-    if (G > 65535 || (int64_t)G * Q * Tmax >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "match_cost_fused: too many groups");
-    if (workspace_bytes < mpf_match_cost_fused_workspace_bytes(G, Q, Tmax, P, tsamp_rows))
-        return mpf::fail(MPF_E_SHAPE, "match_cost_fused: workspace too small");
-    return mc_run<false>(embed, embed_first, embed_row_stride, features, feat_img_stride, 0, group_image, h, w, coords, tsamp, tsamp_rows, t_first,
-                         t_count, cost, G, Q, Tmax, P, 1, w_mask, w_dice, workspace, stream, "mpf_match_cost_fused");
-}
-
-extern "C" size_t mpf_match_cost_fused_clip_workspace_bytes(int G, int Q, int Tmax, int P, int F, int tsamp_rows)
-{
-    if (G <= 0 || Q <= 0 || Tmax <= 0 || P <= 0 || F <= 0 || tsamp_rows < 0 || (int64_t)F * P >= (1ll << 31)) return 0;
-    const McGeom m = mc_geom(G, Q, P, F);
-    return align256((size_t)m.nwg * G * Q * Tmax * 2 * 4) + align256((size_t)m.nwg * G * Q * 2 * 4) + align256((size_t)tsamp_rows * 4);
+    MaskFusedProblem p{MaskFusedEntry::cost};
+    p.channels = channels; p.G = G; p.Q = Q; p.Tmax = Tmax; p.P = P; p.h = h; p.w = w; p.tsamp_rows = tsamp_rows;
+    p.embed_row_stride = embed_row_stride; p.feat_stride = feat_img_stride;
+    return run_cost("mpf_match_cost_fused", p, embed, embed_first, features, group_image, coords, tsamp, t_first, t_count, cost, w_mask, w_dice,
+                    workspace, workspace_bytes, stream);
 }
 
 extern "C" int mpf_match_cost_fused_clip(const void* embed, const int64_t* embed_first, int64_t embed_row_stride, const void* features,
@@ -676,62 +629,31 @@ extern "C" int mpf_match_cost_fused_clip(const void* embed, const int64_t* embed
                                          const int32_t* t_count, float* cost, int G, int Q, int Tmax, int P, int F, float w_mask,
                                          float w_dice, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!embed || !embed_first || !features || !group_clip || !coords || !tsamp || !t_first || !t_count || !cost || !workspace)
-        return mpf::fail(MPF_E_NULL, "match_cost_fused_clip: NULL buffer");
-    if (channels != kC) return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: 256 channels only");
-    if (G <= 0 || Q <= 0 || Tmax <= 0 || P <= 0 || F <= 0 || h <= 0 || w <= 0 || tsamp_rows <= 0)
-        return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: bad sizes");
-    if (Tmax > 128) return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: at most 128 tubes per clip");
-    if ((embed_row_stride % 8) || (feat_clip_stride % 8) || (feat_frame_stride % 8))
-        return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: rows must be 16-byte aligned");
-    if (feat_frame_stride < (int64_t)h * w * kC) return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: frames overlap");
-    if (G > 65535 || F > 65535 || (int64_t)G * Q * Tmax >= (1ll << 31) || (int64_t)F * P >= (1ll << 31))
-        return mpf::fail(MPF_E_TOO_LARGE, "match_cost_fused_clip: too many groups, frames or samples");
-    if (workspace_bytes < mpf_match_cost_fused_clip_workspace_bytes(G, Q, Tmax, P, F, tsamp_rows))
-        return mpf::fail(MPF_E_SHAPE, "match_cost_fused_clip: workspace too small");
-    return mc_run<true>(embed, embed_first, embed_row_stride, features, feat_clip_stride, feat_frame_stride, group_clip, h, w, coords, tsamp,
-                        tsamp_rows, t_first, t_count, cost, G, Q, Tmax, P, F, w_mask, w_dice, workspace, stream, "mpf_match_cost_fused_clip");
+    MaskFusedProblem p{MaskFusedEntry::cost_clip};
+    p.channels = channels; p.G = G; p.Q = Q; p.Tmax = Tmax; p.P = P; p.F = F; p.h = h; p.w = w; p.tsamp_rows = tsamp_rows;
+    p.embed_row_stride = embed_row_stride; p.feat_stride = feat_clip_stride; p.feat_frame_stride = feat_frame_stride;
+    return run_cost("mpf_match_cost_fused_clip", p, embed, embed_first, features, group_clip, coords, tsamp, t_first, t_count, cost, w_mask, w_dice,
+                    workspace, workspace_bytes, stream);
 }
 
 extern "C" int mpf_pair_planes_forward(const void* embed, const int64_t* row_off, const int32_t* pair_of_slot, const int32_t* slot_first,
                                        const int32_t* slot_count, const void* features, int64_t feat_img_stride, void* out, int N, int HW,
                                        int channels, void* stream)
 {
-    if (!embed || !row_off || !slot_first || !slot_count || !features || !out) return mpf::fail(MPF_E_NULL, "pair_planes_forward: NULL buffer");
-    if (channels != kC) return mpf::fail(MPF_E_SHAPE, "pair_planes_forward: 256 channels only");
-    if (N <= 0 || N > 65535 || HW <= 0 || (HW % 4) || (feat_img_stride % 8)) return mpf::fail(MPF_E_SHAPE, "pair_planes_forward: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    mpf::prof_begin(st);
-    mpf::set_kernel("pair_planes_fwd_kernel");
-    hipLaunchKernelGGL(pair_planes_fwd_kernel, dim3((HW + 127) / 128, N), dim3(kT), 0, st, (const __hip_bfloat16*)embed, row_off, pair_of_slot,
-                       slot_first, slot_count, (const __hip_bfloat16*)features, feat_img_stride, (__hip_bfloat16*)out, HW);
-    mpf::prof_end("pair_planes_fwd_kernel", st, 2.0 * (double)N * HW * kC);
+    MaskFusedProblem p{MaskFusedEntry::planes_fwd};
+    p.channels = channels; p.N = N; p.HW = HW; p.feat_stride = feat_img_stride;
+    if (int e = mask_fused_check("mpf_pair_planes_forward", p, {embed, row_off, slot_first, slot_count, features, out})) return e;
+    launch_named("pair_planes_fwd_kernel", pair_planes_fwd_kernel, p.fwd_grid(), 0, (hipStream_t)stream, p.fwd_bytes(), 0.0,
+                 (const __hip_bfloat16*)embed, row_off, pair_of_slot, slot_first, slot_count, (const __hip_bfloat16*)features, feat_img_stride,
+                 (__hip_bfloat16*)out, HW);
     return mpf::check(hipGetLastError(), "mpf_pair_planes_forward");
 }
 
-namespace {
-struct PbGeom {
-    int KP, KS, px_per_chunk, mgroups;
-};
-PbGeom pb_geom(int N, int HW, int max_count)
-{
-    PbGeom p;
-    p.KP = std::max(64, (max_count + 63) / 64 * 64);
-    p.mgroups = std::max(1, (max_count + 127) / 128);
-    // pixel chunks: enough workgroups to fill the chip, at most 64 partial planes; a chunk is a multiple of 64 pixels
-    int ks = std::max(1, std::min(64, 512 / std::max(1, N * p.mgroups)));
-    while (ks > 1 && (HW % (ks * 64))) --ks;
-    p.KS = ks;
-    p.px_per_chunk = HW / ks;
-    return p;
-}
-}  // namespace
-
 extern "C" size_t mpf_pair_planes_backward_workspace_bytes(int N, int HW, int total_slots, int max_count)
 {
-    if (N <= 0 || HW <= 0 || total_slots <= 0 || max_count <= 0) return 0;
-    const PbGeom p = pb_geom(N, HW, max_count);
-    return align256((size_t)N * kC * p.KP * 2) + align256((size_t)p.KS * total_slots * kC * 4) + align256((size_t)total_slots * 4);
+    MaskFusedProblem p{MaskFusedEntry::planes_bwd};
+    p.N = N; p.HW = HW; p.total_slots = total_slots; p.max_count = max_count;
+    return p.pair_bwd_ws().total;
 }
 
 // grad_planes [total_slots, HW] bf16 (rows outside the images' slot ranges are ignored) ->
@@ -742,45 +664,33 @@ extern "C" int mpf_pair_planes_backward(const void* grad_planes, const void* emb
                                         void* d_features, int64_t dfeat_img_stride, void* d_embed, int d_embed_dtype, int N, int HW, int channels,
                                         int total_slots, int max_count, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!grad_planes || !embed || !row_off || !slot_first || !slot_count || !features || !workspace)
-        return mpf::fail(MPF_E_NULL, "pair_planes_backward: NULL buffer");
-    if (channels != kC) return mpf::fail(MPF_E_SHAPE, "pair_planes_backward: 256 channels only");
-    if (N <= 0 || N > 65535 || HW <= 0 || (HW % 128) || total_slots <= 0 || max_count <= 0 || (feat_img_stride % 8) || (dfeat_img_stride % 8))
-        return mpf::fail(MPF_E_SHAPE, "pair_planes_backward: bad sizes (HW must be a multiple of 128)");
-    if (d_embed && d_embed_dtype != MPF_BF16 && d_embed_dtype != MPF_F32) return mpf::fail(MPF_E_DTYPE, "pair_planes_backward: d_embed bf16 or f32");
-    if (workspace_bytes < mpf_pair_planes_backward_workspace_bytes(N, HW, total_slots, max_count))
-        return mpf::fail(MPF_E_SHAPE, "pair_planes_backward: workspace too small");
+    MaskFusedProblem p{MaskFusedEntry::planes_bwd};
+    p.channels = channels; p.N = N; p.HW = HW; p.total_slots = total_slots; p.max_count = max_count; p.feat_stride = feat_img_stride;
+    p.dfeat_stride = dfeat_img_stride; p.d_features = d_features; p.d_embed = d_embed; p.d_embed_dtype = d_embed_dtype;
+    if (int e = mask_fused_check("mpf_pair_planes_backward", p, {grad_planes, embed, row_off, slot_first, slot_count, features}, workspace,
+                                 workspace_bytes))
+        return e;
     hipStream_t st = (hipStream_t)stream;
-    const PbGeom p = pb_geom(N, HW, max_count);
-    char* ws = (char*)workspace;
-    __hip_bfloat16* Et = (__hip_bfloat16*)ws;
-    float* part = (float*)(ws + align256((size_t)N * kC * p.KP * 2));
-    int32_t* valid = (int32_t*)((char*)part + align256((size_t)p.KS * total_slots * kC * 4));
+    const PairBwdWs ws = p.pair_bwd_ws();
     const __hip_bfloat16* G = (const __hip_bfloat16*)grad_planes;
-    const __hip_bfloat16* e = (const __hip_bfloat16*)embed;
-    const __hip_bfloat16* f = (const __hip_bfloat16*)features;
-    if (d_features) {
-        hipLaunchKernelGGL(pair_embed_transpose_kernel, dim3(p.KP / 32, N), dim3(kT), 0, st, e, row_off, pair_of_slot, slot_first, slot_count, Et, p.KP);
-        mpf::prof_begin(st);
-        mpf::set_kernel("pair_planes_dfeat_kernel");
-        hipLaunchKernelGGL(pair_planes_dfeat_kernel, dim3(HW / 128, N), dim3(kT), 0, st, G, Et, p.KP, slot_first, slot_count,
-                           (__hip_bfloat16*)d_features, dfeat_img_stride, HW);
-        mpf::prof_end("pair_planes_dfeat_kernel", st, 2.0 * (double)N * HW * kC + 2.0 * (double)total_slots * HW, 2.0 * (double)total_slots * HW * kC);
+    __hip_bfloat16* Et = (__hip_bfloat16*)workspace;
+    float* part = (float*)((char*)workspace + ws.part);
+    int32_t* valid = (int32_t*)((char*)workspace + ws.valid);
+    if (p.d_features) {
+        hipLaunchKernelGGL(pair_embed_transpose_kernel, p.transpose_grid(), dim3(kT), 0, st, (const __hip_bfloat16*)embed, row_off, pair_of_slot,
+                           slot_first, slot_count, Et, (int)p.KP());
+        launch_named("pair_planes_dfeat_kernel", pair_planes_dfeat_kernel, p.dfeat_grid(), 0, st, p.dfeat_bytes(), p.bwd_flops(), G, Et, (int)p.KP(),
+                     slot_first, slot_count, (__hip_bfloat16*)d_features, dfeat_img_stride, HW);
     }
-    if (d_embed) {
-        hipLaunchKernelGGL(slot_valid_kernel, dim3((total_slots + kT - 1) / kT), dim3(kT), 0, st, slot_first, slot_count, N, total_slots, valid);
-        mpf::prof_begin(st);
-        mpf::set_kernel("pair_planes_dembed_kernel");
-        hipLaunchKernelGGL(pair_planes_dembed_kernel, dim3(p.KS, p.mgroups, N), dim3(kT), 0, st, G, f, feat_img_stride, slot_first, slot_count, part,
-                           total_slots, HW, p.px_per_chunk);
-        mpf::prof_end("pair_planes_dembed_kernel", st, 2.0 * (double)N * HW * kC * p.mgroups + 2.0 * (double)total_slots * HW,
-                      2.0 * (double)total_slots * HW * kC);
-        if (d_embed_dtype == MPF_BF16)
-            hipLaunchKernelGGL(pair_dembed_reduce_kernel<__hip_bfloat16>, dim3(total_slots), dim3(kT), 0, st, part, p.KS, total_slots, row_off,
-                               pair_of_slot, valid, (__hip_bfloat16*)d_embed);
-        else
-            hipLaunchKernelGGL(pair_dembed_reduce_kernel<float>, dim3(total_slots), dim3(kT), 0, st, part, p.KS, total_slots, row_off, pair_of_slot,
-                               valid, (float*)d_embed);
+    if (p.d_embed) {
+        hipLaunchKernelGGL(slot_valid_kernel, p.valid_grid(), dim3(kT), 0, st, slot_first, slot_count, N, total_slots, valid);
+        launch_named("pair_planes_dembed_kernel", pair_planes_dembed_kernel, p.dembed_grid(), 0, st, p.dembed_bytes(), p.bwd_flops(), G,
+                     (const __hip_bfloat16*)features, feat_img_stride, slot_first, slot_count, part, total_slots, HW, p.px_per_chunk());
+        mpf::with_bool(d_embed_dtype == MPF_BF16, [&](auto bf16) {
+            using OT = std::conditional_t<decltype(bf16)::value, __hip_bfloat16, float>;
+            hipLaunchKernelGGL(pair_dembed_reduce_kernel<OT>, p.reduce_grid(), dim3(kT), 0, st, part, p.KS(), total_slots, row_off, pair_of_slot,
+                               valid, (OT*)d_embed);
+        });
     }
     return mpf::check(hipGetLastError(), "mpf_pair_planes_backward");
 }

@@ -208,13 +208,31 @@ class FactoredClipMasks(FactoredMasks):
         return prod.view(self.shape)
 
 
+def _match_cost(entry, scratch_owner, ws_bytes, views, coords, tsamp, rows, t_first, t_count, group_view, group_index, Q, Tmax, w_mask, w_dice,
+                hw, strides, frames):
+    """What the two matching-cost entries share: the groups' row offsets, the packed int32 upload, the cost buffer and the call.
+    ``strides``: of the features, as the entry takes them; ``frames``: () or (T,); the workspace of ``ws_bytes`` is the scratch
+    buffer of ``scratch_owner``, or a fresh tensor when that is None."""
+    me, mf = views[0].me, views[0].mf
+    dev = me.device
+    G, P = coords.shape[0], coords.shape[1]
+    first = np.array([views[v].row_offsets(int(b), 0) for v, b in zip(group_view, group_index)], dtype=np.int64)
+    first_d = upload(first, dev)
+    i32 = upload(np.concatenate([group_index, t_first, t_count]).astype(np.int32), dev)
+    cost = torch.zeros((G, Q, Tmax), dtype=torch.float32, device=dev)
+    st = _lib.stream_ptr(dev)
+    ws = _lib.scratch(scratch_owner, dev, st, ws_bytes) if scratch_owner else torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.call(entry, dev, me.data_ptr(), first_d.data_ptr(), me.stride(1), mf.data_ptr(), *strides, i32[:G].data_ptr(), *hw, mf.shape[1],
+              coords.data_ptr(), tsamp.data_ptr(), rows, i32[G:2 * G].data_ptr(), i32[2 * G:].data_ptr(), cost.data_ptr(), G, Q, Tmax, P, *frames,
+              float(w_mask), float(w_dice), ws.data_ptr(), ws.numel(), st)
+    return cost
+
+
 def match_cost_fused_clip(views, coords, tsamp, t_first, t_count, group_view, group_clip, Q, Tmax, w_mask, w_dice):
     """Mask + dice matching cost of tubes (mask2former_video/modeling/matcher.py:113-148) of G groups from the factors -> fp32
     [G, Q, Tmax].  views: FactoredClipMasks of one (me, mf4); group g = rows of views[group_view[g]] in clip group_clip[g];
     coords [G, P, 2]: ONE point set for all frames of the group; tsamp [rows, T * P] frame-major."""
-    root = views[0]
-    me, mf, T = root.me, root.mf, root.T
-    dev = me.device
+    mf, T = views[0].mf, views[0].T
     G, P = coords.shape[0], coords.shape[1]
     h, W = mf.shape[2] // T, mf.shape[3]
     # rows of T * P floats, however the sampler shaped them ([rows * T, P] per plane is the same memory)
@@ -223,36 +241,16 @@ def match_cost_fused_clip(views, coords, tsamp, t_first, t_count, group_view, gr
     rows = tsamp.numel() // (T * P)
     if int(np.max(np.asarray(t_first) + np.asarray(t_count))) > rows:
         raise RuntimeError("a group's target rows lie outside the target samples")
-    first = np.array([views[v].row_offsets(int(b), 0) for v, b in zip(group_view, group_clip)], dtype=np.int64)
-    first_d = upload(first, dev)
-    i32 = upload(np.concatenate([group_clip, t_first, t_count]).astype(np.int32), dev)
-    cost = torch.zeros((G, Q, Tmax), dtype=torch.float32, device=dev)
-    st = _lib.stream_ptr(dev)
-    ws = _lib.scratch("match_cost_fused_clip", dev, st, _lib.lib().mpf_match_cost_fused_clip_workspace_bytes(G, Q, Tmax, P, T, rows))
-    _lib.call("mpf_match_cost_fused_clip", dev, me.data_ptr(), first_d.data_ptr(), me.stride(1), mf.data_ptr(), mf.stride(0),
-              h * W * mf.shape[1], i32[:G].data_ptr(), h, W, mf.shape[1], coords.data_ptr(), tsamp.data_ptr(), rows,
-              i32[G:2 * G].data_ptr(), i32[2 * G:].data_ptr(), cost.data_ptr(), G, Q, Tmax, P, T, float(w_mask), float(w_dice),
-              ws.data_ptr(), ws.numel(), st)
-    return cost
+    ws_bytes = _lib.lib().mpf_match_cost_fused_clip_workspace_bytes(G, Q, Tmax, P, T, rows)
+    return _match_cost("mpf_match_cost_fused_clip", "match_cost_fused_clip", ws_bytes, views, coords, tsamp, rows, t_first, t_count, group_view,
+                       group_clip, Q, Tmax, w_mask, w_dice, (h, W), (mf.stride(0), h * W * mf.shape[1]), (T,))
 
 
 def match_cost_fused(views, coords, tsamp, t_first, t_count, group_view, group_image, Q, Tmax, w_mask, w_dice):
     """Mask + dice matching cost (matcher.py:105-147) of G groups from the factors -> fp32 [G, Q, Tmax].
     views: FactoredMasks of one (me, mf); group g = rows of views[group_view[g]] in image group_image[g] (numpy int arrays);
     coords [G, P, 2]; tsamp [rows, P]; t_first / t_count numpy int [G]."""
-    root = views[0]
-    me, mf = root.me, root.mf
-    dev = me.device
-    G, P = coords.shape[0], coords.shape[1]
-    H, W = mf.shape[2:]
-    first = np.array([views[v].row_offsets(int(b), 0) for v, b in zip(group_view, group_image)], dtype=np.int64)
-    first_d = upload(first, dev)
-    i32 = upload(np.concatenate([group_image, t_first, t_count]).astype(np.int32), dev)
-    cost = torch.zeros((G, Q, Tmax), dtype=torch.float32, device=dev)
-    lib = _lib.lib()
-    ws = torch.empty(lib.mpf_match_cost_fused_workspace_bytes(G, Q, Tmax, P, tsamp.shape[0]), dtype=torch.uint8, device=dev)
-    _lib.call("mpf_match_cost_fused", dev, me.data_ptr(), first_d.data_ptr(), me.stride(1), mf.data_ptr(), mf.stride(0), i32[:G].data_ptr(),
-              H, W, mf.shape[1], coords.data_ptr(), tsamp.data_ptr(), tsamp.shape[0], i32[G:2 * G].data_ptr(),
-              i32[2 * G:].data_ptr(), cost.data_ptr(), G, Q, Tmax, P, float(w_mask), float(w_dice),
-              ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
-    return cost
+    mf, rows = views[0].mf, tsamp.shape[0]
+    ws_bytes = _lib.lib().mpf_match_cost_fused_workspace_bytes(coords.shape[0], Q, Tmax, coords.shape[1], rows)
+    return _match_cost("mpf_match_cost_fused", None, ws_bytes, views, coords, tsamp, rows, t_first, t_count, group_view, group_image, Q, Tmax,
+                       w_mask, w_dice, tuple(mf.shape[2:]), (mf.stride(0),), ())
