@@ -896,6 +896,51 @@ int mpf_gemm3_conv3x3_wgrad(const float* dy, const float* x, float* c_part, floa
                             int rows_per_split, void* stream);
 
 /*
+ * bf16 weight gradients of several stride-1 convolutions of channel-last bf16 activations in grouped launches (the bottleneck
+ * convolutions of one stage of the bench backbone, detectron2 BottleneckBlock with STRIDE_IN_1X1 False under
+ * configs/coco/instance-segmentation/Base-COCO-InstanceSegmentation.yaml:2-15, whose FrozenBatchNorm scale is folded into the
+ * weight).  Item i:
+ *   out_i[co * out_stride_co + ci * out_stride_ci + tap * out_stride_tap]
+ *       = float(bf16_rn(sum_r dy_i[r][co] * x_i[r shifted by the tap][ci])) * scale_i[co]
+ *   kind MPF_CONV_WGRAD_1X1: one tap, no shift (out_stride_tap unused);
+ *   kind MPF_CONV_WGRAD_3X3: stride 1, zero padding 1, R = images * H * W rows, tap = ky * 3 + kx reads the row at image offset
+ *     (ky - 1, kx - 1), rows off the image contribute nothing; W % 8 == 0, Cin % 128 == 0.
+ * dy [R, Cout] and x [R, Cin] are bf16 with row strides ld_dy / ld_x (elements), out is fp32, Cin % 4 == 0.  The sum over the rows
+ * is accumulated in fp32 per split of rows_per_split rows (% 32 == 0; items of one call may differ in R and in rows_per_split),
+ * the splits are summed in ascending order (bit-reproducible), the sum is rounded to bf16 (the value a bf16 weight gradient
+ * holds) and scaled in fp32.  ws_offset (bytes, % 16 == 0): the item's own slice of `workspace`, ceil(R / rows_per_split) *
+ * Cout * taps * Cin floats.  items: HOST array of any length; every MPF_CONV_WGRAD_GROUP_MAX items (fewer when that divides
+ * the items more evenly: mpf_conv_wgrad_plan's `launch`) take one product launch and one reduce launch.  Nothing is launched
+ * when an item fails a check.
+ *
+ * mpf_conv_wgrad_plan (host only, launches nothing): rows_per_split, workspace slice, splits and workgroups of every item so that
+ * the (tile, split) workgroups of a launch contract about the same number of rows, fill whole rounds of `slots` workgroup slots
+ * (0: two per compute unit of the current device) and an item's partial sums stay below its operand bytes.  rows_per_split,
+ * ws_offset and the other fields of `items` are read only; the caller copies the plan into the items.
+ */
+#define MPF_CONV_WGRAD_GROUP_MAX 12
+#define MPF_CONV_WGRAD_1X1 0
+#define MPF_CONV_WGRAD_3X3 1
+typedef struct MpfConvWgradItem {
+    const void* dy;
+    int64_t ld_dy;
+    const void* x;
+    int64_t ld_x;
+    const float* scale;
+    float* out;
+    int64_t out_stride_co, out_stride_ci, out_stride_tap;
+    int64_t ws_offset;
+    int R, Cout, Cin, kind, H, W, rows_per_split, reserved;
+} MpfConvWgradItem;
+typedef struct MpfConvWgradPlan {
+    int64_t ws_offset, ws_bytes;
+    int rows_per_split, nsplit, tiles, launch;      /* tiles: workgroups of the item (output tiles x splits) */
+} MpfConvWgradPlan;
+int mpf_conv_wgrad_group_max(void);
+int mpf_conv_wgrad_plan(const MpfConvWgradItem* items, int n_items, int slots, MpfConvWgradPlan* plans, size_t* workspace_bytes);
+int mpf_conv_wgrad_bf16_grouped(const MpfConvWgradItem* items, int n_items, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * mpf_gemm3_tn with a bf16 A operand and / or a bf16 result (a_dtype / c_dtype = MPF_F32 | MPF_BF16; no second addend / gate /
  * row-periodic addend): a bf16 activation (a backbone feature map under autocast, the bf16 gradient of mask_features) is
  * exactly its own first plane, so it enters the fp32 GEMM without a cast pass and at three products per K step; a bf16

@@ -111,6 +111,9 @@ SIGNATURES = {
     "mpf_gemm3_conv3x3_h2": (_c_int, [_c_vp] * 7 + [_c_int] * 6 + [_c_vp]),
     "mpf_gemm3_conv3x3_wgrad_h2": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_gemm3_nt_grouped": (_c_int, [_c_vp, _c_int, _c_int, _c_int, ctypes.c_int64, _c_vp]),
+    "mpf_conv_wgrad_group_max": (_c_int, []),
+    "mpf_conv_wgrad_plan": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, ctypes.POINTER(ctypes.c_size_t)]),
+    "mpf_conv_wgrad_bf16_grouped": (_c_int, [_c_vp, _c_int, _c_vp, ctypes.c_size_t, _c_vp]),
     "mpf_small_gemm_bf16": (_c_int, [_c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_vp, _c_vp,
                                      ctypes.c_int64, _c_vp, ctypes.c_int64, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mpf_encoder_fields": (_c_int, []),

@@ -2,7 +2,11 @@
 strides 4/8/16/32, channels 256/512/1024/2048; detectron2 `build_resnet_backbone` layout with
 STRIDE_IN_1X1 False and FrozenBN, configs/coco/instance-segmentation/Base-COCO-InstanceSegmentation.yaml:2-15).
 Stock PyTorch-ROCm ops (MIOpen convolutions) — the backbone is outside the native hot path
-('backbone stays stock PyTorch-ROCm')."""
+('backbone stays stock PyTorch-ROCm') — except the weight gradients of the stride-1 convolutions,
+which run as grouped native launches per stage (MPF_BACKBONE_WGRAD)."""
+import ctypes
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -171,13 +175,21 @@ def max_pool_3x3_s2(x):
 def conv_bn(conv, bn, x, folded=None, res=None, relu=True, fork=False):
     """relu?(FrozenBN(conv(x)) + res) with the fixed per-channel scale folded into the convolution
     weight (w' = w * scale: same function, same gradient wrt w) and shift / residual / ReLU as ONE
-    element-wise pass over the activation instead of MIOpen's bias kernel + add + ReLU."""
+    element-wise pass over the activation instead of MIOpen's bias kernel + add + ReLU.
+    folded = (w', shift) of the stage's _FoldCast, or (w', shift, record, index) when the stage defers its weight gradients to
+    the native grouped launches (see _WgradRecord)."""
+    y = None
     if folded is not None:
-        w, shift = folded
+        w, shift = folded[0], folded[1]
+        if len(folded) == 4:
+            kind = _wgrad_kind(conv, x, w)
+            if kind is not None:
+                y = _ConvDeferredWgrad.apply(x, w, folded[2], folded[3], kind)
     else:
         scale, shift = bn.scale_bias()
         w = conv.weight * scale.view(-1, 1, 1, 1)
-    y = F.conv2d(x, w, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+    if y is None:
+        y = F.conv2d(x, w, None, conv.stride, conv.padding, conv.dilation, conv.groups)
     return bias_act_fork(y, shift, res) if fork else bias_act(y, shift, res, relu)
 
 
@@ -223,12 +235,170 @@ def _grouped_scale_cast(srcs, scales, out_dtype):
     return [out[o:o + n].as_strided(shp, std) for o, n, shp, std in views]
 
 
+# ---- weight gradients of the stride-1 convolutions on the native grouped launches (csrc/gemm3_conv_wgrad.h) ------------------
+# MPF_BACKBONE_WGRAD=native (default): an eligible convolution's backward computes only dX through the library and leaves
+# (dY, x) in its stage's record; the stage's _FoldCast.backward turns all of them into fp32 * scale gradients with one product
+# launch and one reduce launch per MPF_CONV_WGRAD_GROUP_MAX items.  miopen: every weight gradient through the library.
+_WGRAD_ROUTES = ("native", "miopen")
+_wgrad_route = os.environ.get("MPF_BACKBONE_WGRAD", "native")
+if _wgrad_route not in _WGRAD_ROUTES:
+    raise ValueError(f"MPF_BACKBONE_WGRAD={_wgrad_route!r}: expected one of {_WGRAD_ROUTES}")
+_CW_1X1, _CW_3X3 = 0, 1          # MPF_CONV_WGRAD_1X1 / _3X3
+
+
+def set_wgrad_route(route):
+    """Select the weight-gradient route of the forwards that follow ("native" | "miopen") -> the previous route."""
+    global _wgrad_route
+    if route not in _WGRAD_ROUTES:
+        raise ValueError(f"wgrad route {route!r}: expected one of {_WGRAD_ROUTES}")
+    prev, _wgrad_route = _wgrad_route, route
+    return prev
+
+
+class _WgradRecord:
+    """What the convolutions of one stage leave for the stage's _FoldCast.backward: index in the stage -> (dY, x, kind)."""
+    __slots__ = ("items",)
+
+    def __init__(self):
+        self.items = {}
+
+
+def _wgrad_kind(conv, x, w):
+    """_CW_* of a convolution whose weight gradient the grouped launch takes (bf16 channels_last input, stride 1, 1x1 or an
+    eligible 3x3), else None: the present path"""
+    if not (torch.is_grad_enabled() and w.requires_grad and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        return None
+    if conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or x.shape[1] % 4 != 0:
+        return None
+    if conv.kernel_size == (1, 1) and conv.padding == (0, 0):
+        return _CW_1X1
+    if conv.kernel_size == (3, 3) and conv.padding == (1, 1) and x.shape[1] % 128 == 0 and x.shape[3] % 8 == 0:
+        return _CW_3X3
+    return None
+
+
+_placeholders = {}
+
+
+def _placeholder(w):
+    """a tensor of w's shape and dtype without memory of its own: stands in for a deferred weight gradient on its way through
+    autograd to _FoldCast.backward, which never reads it"""
+    key = (w.device, w.dtype)
+    z = _placeholders.get(key)
+    if z is None:
+        z = _placeholders[key] = torch.zeros((), dtype=w.dtype, device=w.device)
+    return z.expand(w.shape)
+
+
+class _ConvDeferredWgrad(torch.autograd.Function):
+    """F.conv2d (stride 1; padding 0 for 1x1, 1 for 3x3) whose backward takes dX from the library and hands (dY, x) to the
+    stage's record instead of computing dW."""
+
+    @staticmethod
+    def forward(ctx, x, w, rec, idx, kind):
+        ctx.save_for_backward(x, w)
+        ctx.rec, ctx.idx, ctx.kind = rec, idx, kind
+        return F.conv2d(x, w, None, 1, 1 if kind == _CW_3X3 else 0)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # a dY in another layout or dtype: this convolution's gradient through the library after all (a real gradient)
+        deferred = need_w and gy.dtype == torch.bfloat16 and gy.is_contiguous(memory_format=torch.channels_last)
+        gx = gw = None
+        if need_x or (need_w and not deferred):
+            pad = [1, 1] if ctx.kind == _CW_3X3 else [0, 0]
+            gx, gw, _ = torch.ops.aten.convolution_backward(gy, x, w, None, [1, 1], pad, [1, 1], False, [0, 0], 1,
+                                                            [need_x, need_w and not deferred, False])
+        if deferred:
+            ctx.rec.items[ctx.idx] = (gy, x, ctx.kind)
+            gw = _placeholder(w)
+        return gx, gw, None, None, None
+
+
+class _CwItem(ctypes.Structure):        # MpfConvWgradItem
+    _fields_ = [("dy", ctypes.c_void_p), ("ld_dy", ctypes.c_int64), ("x", ctypes.c_void_p), ("ld_x", ctypes.c_int64),
+                ("scale", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_stride_co", ctypes.c_int64),
+                ("out_stride_ci", ctypes.c_int64), ("out_stride_tap", ctypes.c_int64), ("ws_offset", ctypes.c_int64),
+                ("R", ctypes.c_int), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int), ("kind", ctypes.c_int), ("H", ctypes.c_int),
+                ("W", ctypes.c_int), ("rows_per_split", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class _CwPlan(ctypes.Structure):        # MpfConvWgradPlan
+    _fields_ = [("ws_offset", ctypes.c_int64), ("ws_bytes", ctypes.c_int64), ("rows_per_split", ctypes.c_int),
+                ("nsplit", ctypes.c_int), ("tiles", ctypes.c_int), ("launch", ctypes.c_int)]
+
+
+def conv_wgrad_plan(items, slots=0, device=torch.device("cpu")):
+    """mpf_conv_wgrad_plan over a ctypes array of _CwItem -> (list of _CwPlan, workspace bytes); copies rows_per_split and the
+    workspace slices into the items.  slots = 0: two per compute unit of `device` (a host function: nothing is launched)."""
+    n = len(items)
+    plans = (_CwPlan * n)()
+    ws = ctypes.c_size_t(0)
+    _lib.call("mpf_conv_wgrad_plan", device, items, n, slots, plans, ctypes.byref(ws))
+    for it, pl in zip(items, plans):
+        it.rows_per_split, it.ws_offset = pl.rows_per_split, pl.ws_offset
+    return list(plans), ws.value
+
+
+def conv_wgrad_item(R, Cout, Cin, kind, H=0, W=0, out_strides=None):
+    """one _CwItem of the given problem; out_strides = (co, ci, tap) in elements, default: k = tap * Cin + ci contiguous (the
+    [Cout, Cin, 1, 1] layout, or channels_last [Cout, Cin, 3, 3])"""
+    taps = 9 if kind == _CW_3X3 else 1
+    sco, sci, stap = out_strides if out_strides is not None else (taps * Cin, 1, Cin)
+    return _CwItem(None, Cout, None, Cin, None, None, sco, sci, stap, 0, R, Cout, Cin, kind, H, W, 0, 0)
+
+
+_cw_layouts = {}
+
+
+def _conv_wgrad_grouped(entries, scales):
+    """[float(bf16(dW_i)) * scale_i] for the recorded (dY, x, kind) of one stage: views of one fp32 buffer, [Cout, Cin, 1, 1]
+    contiguous or [Cout, Cin, 3, 3] channels_last (the order the kernels produce).  Shapes, plan and layout are computed once
+    per stage; per call only the pointers enter the item table."""
+    dev = entries[0][0].device
+    key = (dev, _lib.option_generation()) + tuple((gy.shape, x.shape[1], kind) for gy, x, kind in entries)
+    lay = _cw_layouts.get(key)
+    if lay is None:
+        arr = (_CwItem * len(entries))()
+        views, tot = [], 0
+        for i, (gy, x, kind) in enumerate(entries):
+            N, Cout, H, W = gy.shape
+            Cin = x.shape[1]
+            arr[i] = conv_wgrad_item(N * H * W, Cout, Cin, kind, H, W)
+            shape = (Cout, Cin, 3, 3) if kind == _CW_3X3 else (Cout, Cin, 1, 1)
+            stride = (9 * Cin, 1, 3 * Cin, Cin) if kind == _CW_3X3 else (Cin, 1, 1, 1)
+            views.append((tot, Cout * Cin * shape[2] * shape[3], shape, stride))
+            tot += (views[-1][1] + 63) & ~63
+        _, ws_bytes = conv_wgrad_plan(arr, 0, dev)
+        if len(_cw_layouts) > 64:
+            _cw_layouts.clear()
+        lay = _cw_layouts[key] = (arr, ws_bytes, views, tot)
+    arr, ws_bytes, views, tot = lay
+    stream = _lib.stream_ptr(dev)
+    out = torch.empty(tot, dtype=torch.float32, device=dev)
+    ws = _lib.scratch("conv_wgrad", dev, stream, ws_bytes)
+    base = out.data_ptr()
+    for it, (gy, x, _), sc, (off, _, _, _) in zip(arr, entries, scales, views):
+        assert sc.dtype == torch.float32 and sc.is_contiguous() and sc.numel() == it.Cout
+        it.dy, it.x, it.scale, it.out = gy.data_ptr(), x.data_ptr(), sc.data_ptr(), base + 4 * off
+    _lib.call("mpf_conv_wgrad_bf16_grouped", dev, arr, len(entries), ws.data_ptr(), ws.numel(), stream)
+    return [out[o:o + n].as_strided(shp, std) for o, n, shp, std in views]
+
+
 class _FoldCast(torch.autograd.Function):
     """All folded conv weights of a stage in ONE launch: w'_i = w_i * scale_i, cast to the autocast dtype;
-    the backward casts the gradients back to fp32 and multiplies by scale_i, also in one launch."""
+    the backward casts the gradients back to fp32 and multiplies by scale_i, also in one launch.  With a _WgradRecord in front
+    of the weights, the backward first turns what the stage's convolutions recorded into their gradients (grouped native
+    launches) and casts only the rest."""
 
     @staticmethod
     def forward(ctx, dtype, scales, *weights):
+        ctx.rec = None
+        if weights and isinstance(weights[0], _WgradRecord):
+            ctx.rec, weights = weights[0], weights[1:]
         ctx.scales = scales
         ws = [p.detach() for p in weights]
         native = (ws[0].is_cuda and all(w.dtype == torch.float32 and _dense(w) for w in ws)
@@ -245,14 +415,33 @@ class _FoldCast(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        if ctx.native and all(g is not None and g.dtype == grads[0].dtype for g in grads) \
+        rec = ctx.rec
+        if rec is None:
+            return (None, None, *_FoldCast._cast_back(ctx.native, grads, ctx.scales))
+        deferred, rec.items = rec.items, {}
+        if not deferred:
+            return (None, None, None, *_FoldCast._cast_back(ctx.native, grads, ctx.scales))
+        out = [None] * len(grads)
+        idx = list(deferred)
+        for i, g in zip(idx, _conv_wgrad_grouped([deferred[i] for i in idx], [ctx.scales[i] for i in idx])):
+            out[i] = g
+        rest = [i for i in range(len(grads)) if i not in deferred]
+        if rest:
+            for i, g in zip(rest, _FoldCast._cast_back(ctx.native, [grads[i] for i in rest], [ctx.scales[i] for i in rest])):
+                out[i] = g
+        return (None, None, None, *out)
+
+    @staticmethod
+    def _cast_back(native, grads, scales):
+        """the library's gradients of the folded weights -> fp32 * scale"""
+        if native and all(g is not None and g.dtype == grads[0].dtype for g in grads) \
                 and grads[0].dtype in (torch.float32, torch.bfloat16):
             gs = [g if _dense(g) else g.contiguous() for g in grads]
-            return (None, None, *_grouped_scale_cast(gs, ctx.scales, torch.float32))
+            return _grouped_scale_cast(gs, scales, torch.float32)
         g32 = [torch.empty_like(g, dtype=torch.float32) for g in grads]
         torch._foreach_copy_(g32, list(grads))
-        torch._foreach_mul_(g32, [s_.view(-1, 1, 1, 1) for s_ in ctx.scales])
-        return (None, None, *g32)
+        torch._foreach_mul_(g32, [s_.view(-1, 1, 1, 1) for s_ in scales])
+        return g32
 
 
 _PAIR_NAMES = (("conv1", "norm1"), ("conv2", "norm2"), ("conv3", "norm3"), ("shortcut", "shortcut_norm"))
@@ -330,7 +519,12 @@ class ResNet50(nn.Module):
         the stage has been back-propagated and DDP can start all-reducing them under the earlier stages."""
         sb = [bn.scale_bias() for _, bn in pairs]
         scales = [s_ for s_, _ in sb]
-        ws = _FoldCast.apply(dtype, scales, *[c.weight for c, _ in pairs])
+        weights = [c.weight for c, _ in pairs]
+        if _wgrad_route == "native" and dtype == torch.bfloat16 and torch.is_grad_enabled():
+            rec = _WgradRecord()            # the stage's deferred weight gradients: filled and emptied in backward
+            ws = _FoldCast.apply(dtype, scales, rec, *weights)
+            return [(w, b_, rec, i) for i, (w, (_, b_)) in enumerate(zip(ws, sb))]
+        ws = _FoldCast.apply(dtype, scales, *weights)
         return [(w, b_) for w, (_, b_) in zip(ws, sb)]
 
     def forward(self, x):

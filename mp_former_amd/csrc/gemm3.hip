@@ -1145,7 +1145,7 @@ __device__ __forceinline__ void gemm3_nt_tile(const G3N& p, const int tile)
     static_assert(!(H2 && (BF || A16 || B16)), "fp16 x 2 form: fp32 operands only");
     constexpr int NJ = BN / 32;
     constexpr int kBKc = BN * 16;
-    constexpr int kPl = H2 ? 2 : 3;
+    constexpr int kPl = BF ? 1 : H2 ? 2 : 3;                 // planes of the LDS image (bf16 operands are their own plane 0)
     constexpr int kAbytes = kPl * 4 * kAKc;
     constexpr int kBunits = 4 * BN;                          // (k-chunk, column) units of the B tile
     __shared__ __attribute__((aligned(16))) unsigned char lds[kAbytes + kPl * 4 * kBKc];
@@ -2390,4 +2390,6 @@ extern "C" int mpf_gemm3_nt_reduce(const float* c_part, int64_t c_numel, const f
                        c_numel, s_part, s_numel, nsplit, c_out, s_out);
     return mpf::check(hipGetLastError(), "mpf_gemm3_nt_reduce");
 }
+
+#include "gemm3_conv_wgrad.h"
 
