@@ -1702,7 +1702,10 @@ int mpf_win_attn_backward(const void* qkv, const float* table, const void* out, 
  *
  * One record per image, all int32 but the pointer:
  *   src, src_stride, src_h, src_w   the source: uint8 [H, W, 3] on the device, rows src_stride bytes apart (>= 3 W)
- *   flip                            1: the source is read at column W - 1 - x (PIL on the mirrored image)
+ *   flip                            1: the source is read at column W - 1 - x (PIL on the mirrored image): resize(flip(x))
+ *   flip_out                        (last word) 1: valid column x of the output takes the value of valid column valid_w - 1 - x:
+ *                                   flip(resize(x)), the order of the semantic mapper (mask_former_semantic_dataset_mapper.py:
+ *                                   ResizeShortestEdge, the crop, then RandomFlip); the pad stays at the bottom right.  0: as before
  *   out_h, out_w                    the resized size (h', w'), never materialised
  *   off_y, off_x                    the crop origin inside the resized image
  *   crop_h, crop_w                  the crop size (Sh, Sw)
@@ -1734,7 +1737,7 @@ typedef struct MpfResampleRecord {
     int32_t out_h, out_w, off_y, off_x;
     int32_t crop_h, crop_w, valid_h, valid_w;
     int32_t tile_h, ksize_x, ksize_y, xk_off;
-    int32_t xb_off, yk_off, yb_off, reserved;
+    int32_t xb_off, yk_off, yb_off, flip_out;
 } MpfResampleRecord;
 /* taps stored per output of an axis, (int)ceil(max(in / out, 1)) * 2 + 1 (0 for non-positive sizes), and the tables of the outputs
  * first .. first + count of that axis, coef int32 [count, ksize] and bounds int32 [count, 2], computed on the HOST in double as
@@ -1746,6 +1749,66 @@ int mpf_img_resample_max_ratio(void);
 int mpf_img_resample(const MpfResampleRecord* recs_host, const MpfResampleRecord* recs_dev, const int32_t* tab_host,
                      const int32_t* tab_dev, int64_t tab_len, int B, void* out, int dtype, int Hc, int Wc, int pad_value,
                      const float* mean, const float* std, void* stream);
+
+/*
+ * Training input from label maps (csrc/label_input.hip): the panoptic and the semantic ground truth of the reference's
+ * COCOPanopticNewBaselineDatasetMapper (mask2former/data/dataset_mappers/coco_panoptic_new_baseline_dataset_mapper.py:139-165:
+ * transforms.apply_segmentation, rgb2id, one `pan_seg_gt == id` plane per segment, BitMasks) and MaskFormerSemanticDatasetMapper
+ * (mask_former_semantic_dataset_mapper.py:137-183: the transforms on sem_seg, F.pad with the ignore label, np.unique, one
+ * `sem_seg_gt == class_id` plane per class), with detectron2's RandomCrop_CategoryAreaConstraint (np.unique on up to ten candidate
+ * windows) in between.  All results are integers.
+ *
+ * One record per image, all int32 but the pointer:
+ *   src, src_stride, src_h, src_w   the source map on the device, rows src_stride BYTES apart
+ *   kind                            MPF_LABEL_U8: uint8 [H, W]; MPF_LABEL_I32: int32 [H, W]; MPF_LABEL_RGB: uint8 [H, W, 3] read as the
+ *                                   id R + 256 G + 65536 B (panopticapi's rgb2id)
+ *   flip_in                         1: the source is read at column W - 1 - x (large-scale jitter flips before the resize)
+ *   flip_out                        1: valid column x of the result is valid column valid_w - 1 - x (the semantic mapper flips the
+ *                                   crop); mpf_label_window_counts ignores it (a mirrored window holds the same labels)
+ *   out_h, out_w                    the resized size, never materialised
+ *   off_y, off_x, crop_h, crop_w, valid_h, valid_w   as MpfResampleRecord (mpf_label_resample only)
+ *   xt_off, yt_off                  offsets, in int32 elements, into the table buffer: the SOURCE index of every column / row.
+ *                                   mpf_label_resample: of the crop window (valid_w / valid_h entries, entry i = resized index
+ *                                   off + i); mpf_label_window_counts: of the whole axis (out_w / out_h entries)
+ * The tables carry the nearest-neighbour rule (PIL's for the panoptic PNG, torch's for the float64 semantic map): the host makes
+ * them, the kernels gather.  recs_host / tab_host / win_host are the host copies of the device buffers (the caller's staging
+ * buffer, tab_len int32 elements): every record, table entry and window is checked against them before a launch, so nothing read
+ * on the device can leave a source map.  All launches go to `stream`.
+ *
+ * mpf_label_resample        out int32 [B, Hc, Wc]: the source id inside the valid extent, pad_id everywhere else on the canvas (the
+ *                           rest of the crop rectangle included: FixedSizeCrop pads the panoptic PNG with 255 = id 0xFFFFFF, the
+ *                           semantic mapper pads with the ignore label).  One launch, one writer per element.
+ * mpf_label_window_counts   win int32 [B, tries, 4] = (y0, x0, h, w) in resized coordinates -> counts int32 [B, tries, K + 1]
+ *                           (cleared here): per window the number of pixels of each label 0 .. K-1; labels equal to ignore_label
+ *                           are skipped, every other label outside 0 .. K-1 is counted in slot K (the caller raises on it).
+ *                           Integer atomics: independent of order.  tries 1 .. mpf_label_counts_max_tries() (16), K 1 ..
+ *                           mpf_label_counts_max_classes() (1024), else MPF_E_SHAPE.
+ * mpf_label_bits            one image: map int32, the H x W region at `map` with rows row_stride ELEMENTS apart, and ids_host [T]
+ *                           (HOST memory; passed to the kernel by value) -> bits int64 [T, nwords] in the layout of
+ *                           mpf_seg_pack_masks (p = x H + y) and areas int32 [T], both cleared here: row t is `map == ids[t]`.  The
+ *                           map is read once whatever T is; an id not present gives a zero row, equal ids equal rows.  T == 0
+ *                           launches nothing; T > mpf_label_bits_max_ids() (255): MPF_E_TOO_LARGE (the caller splits the list).
+ * NULL buffer: MPF_E_NULL; kind: MPF_E_DTYPE; inconsistent record, table or window: MPF_E_SHAPE; B > 65535, a source of 2^31 bytes,
+ * a canvas or map of 2^31 elements: MPF_E_TOO_LARGE.  B == 0 launches nothing.  Bitwise reproducible.
+ */
+enum { MPF_LABEL_U8 = 0, MPF_LABEL_I32 = 1, MPF_LABEL_RGB = 2 };
+typedef struct MpfLabelRecord {
+    const void* src;
+    int32_t src_stride, src_h, src_w, kind;
+    int32_t flip_in, flip_out, out_h, out_w;
+    int32_t off_y, off_x, crop_h, crop_w;
+    int32_t valid_h, valid_w, xt_off, yt_off;
+} MpfLabelRecord;
+int mpf_label_counts_max_classes(void);
+int mpf_label_counts_max_tries(void);
+int mpf_label_bits_max_ids(void);
+int mpf_label_resample(const MpfLabelRecord* recs_host, const MpfLabelRecord* recs_dev, const int32_t* tab_host,
+                       const int32_t* tab_dev, int64_t tab_len, int B, int32_t* out, int Hc, int Wc, int pad_id, void* stream);
+int mpf_label_window_counts(const MpfLabelRecord* recs_host, const MpfLabelRecord* recs_dev, const int32_t* tab_host,
+                            const int32_t* tab_dev, int64_t tab_len, const int32_t* win_host, const int32_t* win_dev, int B,
+                            int tries, int K, int ignore_label, int32_t* counts, void* stream);
+int mpf_label_bits(const int32_t* map, int64_t row_stride, int H, int W, const int32_t* ids_host, int T, int64_t* bits,
+                   int32_t* areas, void* stream);
 
 #ifdef __cplusplus
 }

@@ -264,6 +264,13 @@ SIGNATURES = {
     "mpf_img_resample_max_ratio": (_c_int, []),
     "mpf_img_resample": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_int,
                                   ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _c_vp]),
+    "mpf_label_counts_max_classes": (_c_int, []),
+    "mpf_label_counts_max_tries": (_c_int, []),
+    "mpf_label_bits_max_ids": (_c_int, []),
+    "mpf_label_resample": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp]),
+    "mpf_label_window_counts": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp,
+                                         _c_vp]),
+    "mpf_label_bits": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
 }
 
 

@@ -114,6 +114,142 @@ def draw_lsj(h, w, image_size=1024, min_scale=0.1, max_scale=2.0, flip=True, rng
     return lsj_params(h, w, do_flip, scale, u, image_size)
 
 
+# ---- label maps: the nearest-neighbour rules, the semantic mapper's draws and crop rule ---------------------------------------------
+def nearest_table_pil(in_size, out_size):
+    """The source index PIL's ``Image.resize(..., NEAREST)`` reads for each of ``out_size`` outputs of an axis of ``in_size`` -> int32
+    [out_size]: detectron2's ``ResizeTransform.apply_segmentation`` on a uint8 array (the panoptic PNG).  ``ImagingScaleAffine``
+    starts a double at ``0.5 * in / out`` and ADDS ``in / out`` once per output; the index is the C truncation of the running sum
+    (which differs from ``(int)((x + 0.5) * in / out)`` where the accumulated rounding crosses an integer)."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f"nearest_table_pil: sizes must be positive, got {in_size}, {out_size}")
+    step = in_size / out_size
+    steps = np.full(out_size, step, dtype=np.float64)
+    steps[0] = 0.0 + step * 0.5
+    acc = np.cumsum(steps)                                   # sequential double additions, as the C loop's ``xo += a[0]``
+    # PIL leaves an output whose coordinate falls outside the source untouched; after the clamp below none does
+    return np.minimum(acc.astype(np.int64), in_size - 1).astype(np.int32)
+
+
+_TORCH_NEAREST = {}
+
+
+def nearest_table_torch(in_size, out_size):
+    """The source index ``F.interpolate(mode="nearest")`` reads on a float64 CPU tensor -> int32 [out_size]: the route detectron2's
+    ``ResizeTransform`` takes for the reference's semantic mapper, which converts the label map to ``double`` first.  Taken from torch
+    itself (an ``arange`` of the axis interpolated as a [1, 1, 1, in] tensor), so it is the installed torch's rule by construction;
+    the rule is the same on either axis and inside a 2-D map."""
+    key = (int(in_size), int(out_size))
+    if key[0] <= 0 or key[1] <= 0:
+        raise ValueError(f"nearest_table_torch: sizes must be positive, got {key[0]}, {key[1]}")
+    t = _TORCH_NEAREST.get(key)
+    if t is None:
+        src = torch.arange(key[0], dtype=torch.float64).view(1, 1, 1, key[0])
+        t = torch.nn.functional.interpolate(src, size=(1, key[1]), mode="nearest").view(-1).to(torch.int32).numpy()
+        if len(_TORCH_NEAREST) > 4096:
+            _TORCH_NEAREST.clear()
+        _TORCH_NEAREST[key] = t
+    return t
+
+
+def draw_shortest_edge(h, w, short_edge_length, max_size, sample_style="range", rng=np.random):
+    """``ResizeShortestEdge.get_transform``: the draw (``"range"``: ``rng.randint(min, max + 1)``; ``"choice"``:
+    ``rng.choice(list)``), then ``shortest_edge_size`` -> (h', w').  A drawn size of 0 keeps the image, as detectron2's NoOp."""
+    if isinstance(short_edge_length, int):
+        short_edge_length = (short_edge_length, short_edge_length)
+    if sample_style == "range":
+        if len(short_edge_length) != 2:
+            raise ValueError(f"draw_shortest_edge: 'range' needs (min, max), got {short_edge_length!r}")
+        size = rng.randint(short_edge_length[0], short_edge_length[1] + 1)
+    elif sample_style == "choice":
+        size = rng.choice(list(short_edge_length))
+    else:
+        raise ValueError(f"draw_shortest_edge: sample_style must be 'range' or 'choice', got {sample_style!r}")
+    if size == 0:
+        return int(h), int(w)
+    return shortest_edge_size(h, w, int(size), max_size)
+
+
+def crop_size_absolute(crop_size, image_size):
+    """``RandomCrop.get_crop_size`` for ``CROP.TYPE == "absolute"``: (min(ch, h), min(cw, w))"""
+    return min(int(crop_size[0]), int(image_size[0])), min(int(crop_size[1]), int(image_size[1]))
+
+
+def crop_size(crop_type, crop_size, image_size):
+    """The crop size of ``CROP.TYPE``; only ``"absolute"`` is built, the others raise NotImplementedError naming the type"""
+    if crop_type == "absolute":
+        return crop_size_absolute(crop_size, image_size)
+    raise NotImplementedError(f"INPUT.CROP.TYPE {crop_type!r}: only 'absolute' is implemented on the device path")
+
+
+def choose_category_crop(counts, tries, single_category_max_area):
+    """detectron2's ``RandomCrop_CategoryAreaConstraint`` acceptance rule on integer counts.  ``counts`` [tries, K]: per candidate
+    window the pixel count of every non-ignored label.  For try i, cnt = the non-zero counts; the first i with ``len(cnt) > 1 and
+    cnt.max() < cnt.sum() * single_category_max_area`` is taken, the last try if none passes.  With ``single_category_max_area >=
+    1.0`` there is one draw and no test -> the index of the chosen try."""
+    if single_category_max_area >= 1.0:
+        return 0
+    counts = np.asarray(counts)
+    tries = int(tries)
+    if counts.ndim != 2 or tries < 1 or counts.shape[0] < tries:
+        raise ValueError(f"choose_category_crop: counts must be [tries, K] with tries >= 1, got {counts.shape} for {tries} tries")
+    for i in range(tries):
+        cnt = counts[i][counts[i] > 0]
+        if len(cnt) > 1 and np.max(cnt) < np.sum(cnt) * single_category_max_area:
+            return i
+    return tries - 1
+
+
+@dataclass(frozen=True)
+class SemSegParams:
+    """The geometry of one image of the semantic mapper, whose order is resize -> crop -> flip -> pad to ``size_divisibility``: the
+    flip mirrors the CROPPED image (the valid columns), after the resize."""
+    src: tuple          # (H, W) of the source
+    resized: tuple      # (h', w') of ResizeShortestEdge
+    offset: tuple       # (y0, x0) of the chosen crop window inside the resized image
+    crop: tuple         # (ch, cw) of the window
+    valid: tuple        # = crop: an absolute crop never leaves the resized image
+    flip: bool
+    canvas: tuple       # what the mapper pads to, at the bottom right
+
+
+@dataclass(frozen=True)
+class SemSegDraw:
+    """All a worker draws for one image of the semantic mapper: the resized size, the window size, every candidate origin (the
+    category-area rule picks one of them on the device side, from the counts) and the flip."""
+    src: tuple
+    resized: tuple
+    crop: tuple         # (ch, cw)
+    origins: tuple      # ((y0, x0), ...): ``tries`` candidates, one where the rule is off
+    flip: bool
+    canvas: tuple
+
+    def params(self, i):
+        return SemSegParams(self.src, self.resized, tuple(self.origins[i]), self.crop, self.crop, self.flip, self.canvas)
+
+
+CROP_TRIES = 10         # RandomCrop_CategoryAreaConstraint.get_transform: ``for _ in range(10)``
+
+
+def draw_semseg(h, w, short_edge_length, max_size, sample_style="range", crop=None, crop_type="absolute",
+                single_category_max_area=1.0, flip=True, size_divisibility=-1, rng=np.random):
+    """Draw for the reference's semantic mapper: the short edge, the crop origins (``randint(h' - ch + 1)`` then ``randint(w' - cw +
+    1)`` per try), the flip ``uniform() < 0.5``.  ``crop``: (ch, cw) or None (cropping disabled: the whole resized image is the one
+    window).  ALL ``CROP_TRIES`` origins are drawn up front where the category-area rule applies (``single_category_max_area < 1``):
+    the windows have the reference's distribution, but the reference stops drawing at the first accepted window, so the RNG stream
+    is consumed differently."""
+    rh, rw = draw_shortest_edge(h, w, short_edge_length, max_size, sample_style, rng)
+    if crop is None:
+        ch, cw, origins = rh, rw, ((0, 0),)
+    else:
+        ch, cw = crop_size(crop_type, crop, (rh, rw))
+        tries = 1 if single_category_max_area >= 1.0 else CROP_TRIES
+        origins = tuple((int(rng.randint(rh - ch + 1)), int(rng.randint(rw - cw + 1))) for _ in range(tries))
+    do_flip = bool(rng.uniform() < 0.5) if flip else False
+    canvas = (int(size_divisibility), int(size_divisibility)) if size_divisibility > 0 else (ch, cw)
+    return SemSegDraw((int(h), int(w)), (rh, rw), (ch, cw), origins, do_flip, canvas)
+
+
 def resize_params(h, w, size):
     """No flip, no crop: the whole resized image (the evaluation route)"""
     rh, rw = int(size[0]), int(size[1])
@@ -149,7 +285,10 @@ def _check_params(p, i):
 
 def resample_images(images, params, dtype=torch.uint8, mean=None, std=None, canvas=None, pad_value=128, device=None):
     """``images``: a list of uint8 [H, W, 3] tensors (host tensors are uploaded, device tensors are read in place, any row stride);
-    ``params``: their ``LSJParams`` -> [B, 3, Hc, Wc] on the device in ONE launch.  ``canvas`` (Hc, Wc) defaults to the largest crop.
+    ``params``: their ``LSJParams`` (a flip mirrors the source before the resize) or ``SemSegParams`` (a flip mirrors the valid
+    columns of the crop after it, and the pad value fills the record's own ``canvas``, as the semantic mapper pads to the size
+    divisibility) -> [B, 3, Hc, Wc] on the device in ONE launch.  ``canvas`` (Hc, Wc) defaults to the largest crop
+    (``SemSegParams``: the largest ``canvas``).
     uint8: PIL's value, ``pad_value`` in the rest of the crop rectangle.  float32 (needs ``mean`` and ``std``, three values each):
     ``(v - mean[c]) / std[c]`` bit-equal to the torch expression, 0 outside the crop rectangle; bfloat16: that rounded to nearest
     even.  ValueError before any device work for a non-uint8 or non-[H, W, 3] source, a canvas smaller than a crop, float output
@@ -172,11 +311,14 @@ def resample_images(images, params, dtype=torch.uint8, mean=None, std=None, canv
             raise ValueError(f"resample_images: image {i} is {tuple(im.shape[:2])} but its parameters say {tuple(p.src)}")
         _check_params(p, i)
     if canvas is None:
-        canvas = (max([p.crop[0] for p in params], default=1), max([p.crop[1] for p in params], default=1))
+        sizes = [p.canvas if isinstance(p, SemSegParams) else p.crop for p in params]
+        canvas = (max([c[0] for c in sizes], default=1), max([c[1] for c in sizes], default=1))
     Hc, Wc = int(canvas[0]), int(canvas[1])
     for i, p in enumerate(params):
         if p.crop[0] > Hc or p.crop[1] > Wc:
             raise ValueError(f"resample_images: the canvas {Hc} x {Wc} is smaller than the crop {p.crop[0]} x {p.crop[1]} of image {i}")
+        if isinstance(p, SemSegParams) and (p.canvas[0] > Hc or p.canvas[1] > Wc or p.crop[0] > p.canvas[0] or p.crop[1] > p.canvas[1]):
+            raise ValueError(f"resample_images: image {i}: the crop {p.crop} must fit its canvas {p.canvas}, and that the batch's {Hc} x {Wc}")
     mean_c = std_c = None
     if dtype != torch.uint8:
         mean_v = [float(v) for v in torch.as_tensor(mean).reshape(-1).tolist()]
@@ -219,9 +361,14 @@ def resample_images(images, params, dtype=torch.uint8, mean=None, std=None, canv
         _lib.call("mpf_img_resample_tables", dev, p.src[0], p.resized[0], p.offset[0], p.valid[0], base + 4 * offs[2], base + 4 * offs[3])
         yb = host[nrec + offs[3]:nrec + offs[3] + 2 * p.valid[0]].reshape(-1, 2)
         addr = im.data_ptr()
+        # LSJ mirrors the source, then crops; the semantic mapper mirrors the cropped result and pads it to ITS canvas with the pad
+        # value: the record's pad rectangle is then that canvas
+        sem = isinstance(p, SemSegParams)
+        flip_in, flip_out = (0, int(p.flip)) if sem else (int(p.flip), 0)
+        rect = p.canvas if sem else p.crop
         recs[b] = (_i32(addr), _i32(addr >> 32),
-                   im.stride(0), p.src[0], p.src[1], int(p.flip), p.resized[0], p.resized[1], p.offset[0], p.offset[1],
-                   p.crop[0], p.crop[1], p.valid[0], p.valid[1], _tile_h(yb), kx, ky, offs[0], offs[1], offs[2], offs[3], 0)
+                   im.stride(0), p.src[0], p.src[1], flip_in, p.resized[0], p.resized[1], p.offset[0], p.offset[1],
+                   rect[0], rect[1], p.valid[0], p.valid[1], _tile_h(yb), kx, ky, offs[0], offs[1], offs[2], offs[3], flip_out)
     staged = pinned.to(dev, non_blocking=True)
     _lib.call("mpf_img_resample", dev, pinned.data_ptr(), staged.data_ptr(), pinned.data_ptr() + 4 * nrec, staged.data_ptr() + 4 * nrec,
               n, B, out.data_ptr(), _lib.DTYPE[dtype], Hc, Wc, int(pad_value), mean_c, std_c, _lib.stream_ptr(dev))

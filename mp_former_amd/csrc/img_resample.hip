@@ -11,7 +11,9 @@
 //   img_resample_kernel   one workgroup per (image, output tile of tile_h x kTileW of the canvas).  Horizontal pass: for the source
 //                         rows the tile's output rows tap (at most kSpanRows: the host picks tile_h per image so that this holds)
 //                         and the tile's valid columns, three channels per thread, from the HWC source (read mirrored with the flip
-//                         flag: equal to PIL on the flipped image) into LDS as uint8 [row][channel][kTileW].  Vertical pass out of
+//                         flag: equal to PIL on the flipped image; with flip_out the valid columns take the tables of their mirror
+//                         column instead: the crop of the resize, flipped, which reads another window of the source than the crop
+//                         of the flipped resize unless the crop is centred) into LDS as uint8 [row][channel][kTileW].  Vertical pass out of
 //                         LDS, lanes along the output row, into the three channel planes of [B, 3, Hc, Wc]: the value inside the
 //                         valid extent, the pad value in the rest of the crop rectangle, zero in the rest of the canvas; as uint8,
 //                         as (v - mean[c]) / std[c] in fp32 (IEEE subtraction and division: bit-equal to torch's), or that rounded to
@@ -73,8 +75,9 @@ __global__ __launch_bounds__(kResT) void img_resample_kernel(const Rec* __restri
         const unsigned char* __restrict__ src = (const unsigned char*)r.src;
         for (int i = threadIdx.x; i < span * nvc; i += kResT) {
             const int s = i / nvc, j = i - s * nvc;
-            const int x0 = xb[2 * (ox0 + j)], n = xb[2 * (ox0 + j) + 1];
-            const int* __restrict__ k = xk + (int64_t)(ox0 + j) * r.ksize_x;
+            const int tx = r.flip_out ? r.valid_w - 1 - (ox0 + j) : ox0 + j;       // the table column: mirrored inside the valid extent
+            const int x0 = xb[2 * tx], n = xb[2 * tx + 1];
+            const int* __restrict__ k = xk + (int64_t)tx * r.ksize_x;
             const unsigned char* __restrict__ row = src + (int64_t)(r_lo + s) * r.src_stride;
             int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
             for (int t = 0; t < n; ++t) {
@@ -150,6 +153,7 @@ int check_record(const Rec& r, const int* tab, int64_t tab_len, int Hc, int Wc)
         r.off_y + r.valid_h > r.out_h || r.off_x + r.valid_w > r.out_w)
         return bad("the valid extent must lie inside the crop and the resized image");
     if (r.tile_h < 1 || r.tile_h > kMaxTileH) return bad("tile_h outside 1 .. 32");
+    if (r.flip_out < 0 || r.flip_out > 1) return bad("flip_out must be 0 or 1");
     if (int e = check_axis(tab, tab_len, r.xk_off, r.xb_off, r.ksize_x, r.valid_w, r.src_w)) return e;
     if (int e = check_axis(tab, tab_len, r.yk_off, r.yb_off, r.ksize_y, r.valid_h, r.src_h)) return e;
     for (int y0 = 0; y0 < r.valid_h; y0 += r.tile_h) {       // (tap ranges do not move backwards: the last row of a tile ends last)

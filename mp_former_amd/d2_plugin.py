@@ -781,3 +781,219 @@ def install_native_lsj(model):
 
     model.forward = forward
     return forward
+
+
+# ---- panoptic and semantic training input from label maps (label_input.py) ------------------------------------------------------------
+def _read_worker_image(read_image, dataset_dict, image_format, who):
+    import numpy as np
+    image = np.ascontiguousarray(read_image(dataset_dict["file_name"], format=image_format))
+    if image.ndim != 3 or image.shape[2] != 3 or image.dtype != np.uint8:
+        raise ValueError(f"{who}: expected a uint8 [H, W, 3] image, got {image.dtype} {image.shape}")
+    for key, n in (("height", image.shape[0]), ("width", image.shape[1])):
+        if key in dataset_dict and dataset_dict[key] != n:
+            raise ValueError(f"{who}: {dataset_dict['file_name']} has {key} {n}, the dataset says {dataset_dict[key]}")
+    return image
+
+
+def _read_label_default():
+    """detectron2's ``read_image(path)`` without a format where importable (the file's own mode), else PIL's decode as it is"""
+    try:
+        from detectron2.data.detection_utils import read_image
+        return read_image
+    except ImportError:
+        def read_label(file_name):
+            import numpy as np
+            from PIL import Image
+            with Image.open(file_name) as im:
+                return np.asarray(im)
+        return read_label
+
+
+class COCOPanopticLSJDeviceMapper:
+    """The worker side of the reference's ``COCOPanopticNewBaselineDatasetMapper``
+    (mask2former/data/dataset_mappers/coco_panoptic_new_baseline_dataset_mapper.py) when the augmentation runs on the device: it
+    reads the image and the panoptic PNG, DRAWS the geometry as ``COCOInstanceLSJDeviceMapper`` does and returns the dict with
+    ``"image_raw"`` and ``"pan_raw"`` (uint8 [H, W, 3] each), ``"lsj"`` (``augment.LSJParams``) and ``"segments_info"``.  No resize
+    and no mask on the worker: two decoded images cross instead of up to a hundred dense planes."""
+
+    @_configurable
+    def __init__(self, is_train=True, *, image_size, min_scale, max_scale, random_flip, image_format, read_image=None):
+        if not is_train:
+            raise ValueError("COCOPanopticLSJDeviceMapper: only training augmentation, as the reference's build_transform_gen")
+        if random_flip == "vertical":
+            raise NotImplementedError("INPUT.RANDOM_FLIP 'vertical': only the horizontal flip is implemented on the device path")
+        if random_flip not in ("horizontal", "none"):
+            raise ValueError(f"COCOPanopticLSJDeviceMapper: random_flip must be 'horizontal' or 'none', got {random_flip!r}")
+        self.is_train, self.image_size, self.min_scale, self.max_scale = bool(is_train), image_size, float(min_scale), float(max_scale)
+        self.random_flip, self.image_format = random_flip, image_format
+        self.read_image = read_image or _read_image_default()
+
+    @classmethod
+    def from_config(cls, cfg, is_train=True):
+        return {"is_train": is_train, "image_size": cfg.INPUT.IMAGE_SIZE, "min_scale": cfg.INPUT.MIN_SCALE,
+                "max_scale": cfg.INPUT.MAX_SCALE, "random_flip": cfg.INPUT.RANDOM_FLIP, "image_format": cfg.INPUT.FORMAT}
+
+    def __call__(self, dataset_dict):
+        import numpy as np
+        import torch
+        from .augment import draw_lsj
+        who = "COCOPanopticLSJDeviceMapper"
+        d = {k: v for k, v in dataset_dict.items() if k not in ("annotations", "pan_seg_file_name")}
+        image = _read_worker_image(self.read_image, dataset_dict, self.image_format, who)
+        d["image_raw"] = torch.from_numpy(image)
+        d["lsj"] = draw_lsj(image.shape[0], image.shape[1], image_size=self.image_size, min_scale=self.min_scale,
+                            max_scale=self.max_scale, flip=self.random_flip == "horizontal", rng=np.random)
+        if "pan_seg_file_name" in dataset_dict:
+            pan = np.ascontiguousarray(self.read_image(dataset_dict["pan_seg_file_name"], format="RGB"))
+            if pan.dtype != np.uint8 or pan.shape != image.shape:
+                raise ValueError(f"{who}: the panoptic PNG must be uint8 {image.shape}, got {pan.dtype} {pan.shape}")
+            d["pan_raw"] = torch.from_numpy(pan)
+            d["segments_info"] = list(dataset_dict["segments_info"])
+        return d
+
+
+class SemanticDeviceMapper:
+    """The worker side of the reference's ``MaskFormerSemanticDatasetMapper``
+    (mask2former/data/dataset_mappers/mask_former_semantic_dataset_mapper.py) when the augmentation runs on the device: it reads the
+    image and the label map and DRAWS (``augment.draw_semseg``: the short edge, the crop origins, the flip) and returns the dict
+    with ``"image_raw"`` (uint8 [H, W, 3]), ``"sem_seg_raw"`` (uint8 [H, W]; int32 for a map with labels above 255) and
+    ``"semseg"`` (``augment.SemSegDraw``).  All ten candidate origins of ``RandomCrop_CategoryAreaConstraint`` are drawn up front,
+    because the counts that decide between them are taken on the device: the windows have the reference's distribution, but its RNG
+    stream is consumed differently (the reference stops drawing at the first accepted window)."""
+
+    @_configurable
+    def __init__(self, is_train=True, *, min_size, max_size, sampling, crop_enabled, crop_type, crop_size, single_category_max_area,
+                 color_aug_ssd, image_format, ignore_label, size_divisibility, num_classes, read_image=None, read_label=None):
+        if not is_train:
+            raise ValueError("SemanticDeviceMapper: only training, as the reference's mapper asserts")
+        if color_aug_ssd:
+            raise NotImplementedError("INPUT.COLOR_AUG_SSD: its saturation and hue steps are OpenCV's 8-bit HSV tables, which are not "
+                                      "pinned; not implemented on the device path")
+        if crop_enabled and crop_type != "absolute":
+            raise NotImplementedError(f"INPUT.CROP.TYPE {crop_type!r}: only 'absolute' is implemented on the device path")
+        self.is_train = True
+        self.min_size = (min_size,) if isinstance(min_size, int) else tuple(min_size)
+        self.max_size, self.sampling = int(max_size), sampling
+        self.crop = (int(crop_size[0]), int(crop_size[1])) if crop_enabled else None
+        self.crop_type, self.single_category_max_area = crop_type, float(single_category_max_area)
+        self.image_format, self.ignore_label, self.size_divisibility = image_format, int(ignore_label), int(size_divisibility)
+        self.num_classes = int(num_classes)
+        self.read_image = read_image or _read_image_default()
+        self.read_label = read_label or _read_label_default()
+
+    @classmethod
+    def from_config(cls, cfg, is_train=True):
+        try:
+            from detectron2.data import MetadataCatalog
+            ignore_label = MetadataCatalog.get(cfg.DATASETS.TRAIN[0]).ignore_label
+        except ImportError:
+            ignore_label = cfg.MODEL.SEM_SEG_HEAD.IGNORE_VALUE
+        return {"is_train": is_train, "min_size": cfg.INPUT.MIN_SIZE_TRAIN, "max_size": cfg.INPUT.MAX_SIZE_TRAIN,
+                "sampling": cfg.INPUT.MIN_SIZE_TRAIN_SAMPLING, "crop_enabled": cfg.INPUT.CROP.ENABLED, "crop_type": cfg.INPUT.CROP.TYPE,
+                "crop_size": cfg.INPUT.CROP.SIZE, "single_category_max_area": cfg.INPUT.CROP.SINGLE_CATEGORY_MAX_AREA,
+                "color_aug_ssd": cfg.INPUT.COLOR_AUG_SSD, "image_format": cfg.INPUT.FORMAT, "ignore_label": ignore_label,
+                "size_divisibility": cfg.INPUT.SIZE_DIVISIBILITY, "num_classes": cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES}
+
+    def __call__(self, dataset_dict):
+        import numpy as np
+        import torch
+        from .augment import draw_semseg
+        who = "SemanticDeviceMapper"
+        if "annotations" in dataset_dict:
+            raise ValueError("Semantic segmentation dataset should not have 'annotations'.")
+        if "sem_seg_file_name" not in dataset_dict:
+            raise ValueError("Cannot find 'sem_seg_file_name' for semantic segmentation dataset {}.".format(dataset_dict["file_name"]))
+        d = {k: v for k, v in dataset_dict.items() if k != "sem_seg_file_name"}
+        image = _read_worker_image(self.read_image, dataset_dict, self.image_format, who)
+        sem = np.asarray(self.read_label(dataset_dict["sem_seg_file_name"]))
+        if sem.ndim != 2 or sem.shape != image.shape[:2] or sem.dtype.kind not in "iu":
+            raise ValueError(f"{who}: the label map must be an integer {image.shape[:2]} array, got {sem.dtype} {sem.shape}")
+        sem = np.ascontiguousarray(sem if sem.dtype == np.uint8 else sem.astype(np.int32))
+        d["image_raw"], d["sem_seg_raw"] = torch.from_numpy(image), torch.from_numpy(sem)
+        d["semseg"] = draw_semseg(image.shape[0], image.shape[1], self.min_size, self.max_size, self.sampling, crop=self.crop,
+                                  crop_type=self.crop_type, single_category_max_area=self.single_category_max_area, flip=True,
+                                  size_divisibility=self.size_divisibility, rng=np.random)
+        return d
+
+
+class MaskFormerPanopticDeviceMapper:
+    """ADE20K panoptic (the reference's ``MaskFormerPanopticDatasetMapper``): a composition of the semantic geometry and the
+    panoptic targets that is not built yet."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("MaskFormerPanopticDatasetMapper (ADE20K panoptic) is not implemented on the device path")
+
+
+def _instances(size, t):
+    from .inference import _structures
+    Boxes, Instances = _structures()
+    inst = Instances(tuple(size))
+    inst.gt_classes = t["labels"]
+    inst.gt_masks = t["masks"]
+    inst.gt_boxes = Boxes(t["boxes"])
+    return inst
+
+
+def native_panoptic_inputs(batched_inputs, device):
+    """The dicts of ``COCOPanopticLSJDeviceMapper`` -> copies with ``"image"`` (uint8 [3, S, S] on ``device``) and ``"instances"``
+    (``gt_classes``, ``gt_masks`` bool [T, S, S], ``gt_boxes``), as the reference's mapper would have left them: one image launch,
+    one label launch and one mask launch per image (label_input.panoptic_lsj_batch); no host wait."""
+    from .label_input import panoptic_lsj_batch
+    with_gt = all("pan_raw" in x for x in batched_inputs)
+    if not with_gt:
+        raise ValueError("native_panoptic_inputs: every input needs 'pan_raw' and 'segments_info' (a training batch)")
+    images, targets = panoptic_lsj_batch(batched_inputs, device=device)
+    out = []
+    for x, image, t in zip(batched_inputs, images, targets):
+        p = x["lsj"]
+        d = {k: v for k, v in x.items() if k not in ("image_raw", "pan_raw")}
+        d["image"] = image[:, :p.crop[0], :p.crop[1]]
+        d["instances"] = _instances(p.crop, t)
+        out.append(d)
+    return out
+
+
+def native_semantic_inputs(batched_inputs, device, num_classes, ignore_label, single_category_max_area=1.0):
+    """The dicts of ``SemanticDeviceMapper`` -> copies with ``"image"`` (uint8 [3, Hc, Wc] on ``device``, padded to the size
+    divisibility with 128), ``"sem_seg"`` (int64 [Hc, Wc], padded with the ignore label) and ``"instances"`` (one mask per class
+    present), as the reference's mapper would have left them (label_input.semantic_batch: one host wait, for the window counts)."""
+    from .label_input import semantic_batch
+    images, targets = semantic_batch(batched_inputs, num_classes, ignore_label, single_category_max_area, device=device)
+    out = []
+    for x, image, t in zip(batched_inputs, images, targets):
+        Hc, Wc = t["params"].canvas
+        d = {k: v for k, v in x.items() if k not in ("image_raw", "sem_seg_raw")}
+        d["image"] = image[:, :Hc, :Wc]
+        d["sem_seg"] = t["sem_seg"]
+        d["instances"] = _instances((Hc, Wc), t)
+        out.append(d)
+    return out
+
+
+def _install_inputs(model, make):
+    inner = model.forward
+
+    def forward(batched_inputs):
+        if not model.training:
+            return inner(batched_inputs)
+        return inner(make(batched_inputs))
+
+    model.forward = forward
+    return forward
+
+
+def install_native_panoptic_lsj(model):
+    """As ``install_native_lsj`` for a model fed by ``COCOPanopticLSJDeviceMapper``: the training branch gets the usual dicts
+    ("image", "instances") formed on the model's device; eval mode is passed through untouched."""
+    return _install_inputs(model, lambda batch: native_panoptic_inputs(batch, model.device))
+
+
+def install_native_semantic_input(model, mapper=None, *, num_classes=None, ignore_label=None, single_category_max_area=None):
+    """As ``install_native_lsj`` for a model fed by ``SemanticDeviceMapper``: pass the mapper (its ``num_classes``, ``ignore_label``
+    and ``single_category_max_area`` are used) or the three values.  Eval mode is passed through untouched."""
+    if mapper is None and (num_classes is None or ignore_label is None):
+        raise ValueError("install_native_semantic_input: pass the SemanticDeviceMapper, or num_classes and ignore_label")
+    K = mapper.num_classes if num_classes is None else num_classes
+    ignore = mapper.ignore_label if ignore_label is None else ignore_label
+    area = (mapper.single_category_max_area if mapper is not None else 1.0) if single_category_max_area is None else single_category_max_area
+    return _install_inputs(model, lambda batch: native_semantic_inputs(batch, model.device, K, ignore, area))
