@@ -883,7 +883,8 @@ int mpf_gemm3_nt_grouped(const MpfNtItem* items, int n_items, int R, int rows_pe
  *   w_planes = mpf_gemm3_split of the [Cout][9*Cin] matrix W2[co][(ky*3+kx)*Cin + ci] = W[co][ci][ky][kx].
  *   transposed != 0: the input gradient dx = conv_transpose(dy, W): call with x := dy (Cin := Cout of the forward),
  *   w_planes = split of W2t[ci][(ky*3+kx)*Cout + co] = W[co][ci][ky][kx]; the taps are then walked with the opposite sign.
- * Cin % 32 == 0, Cout % 4 == 0.
+ * Cin % 32 == 0, Cout % 4 == 0; n_img*H*W*Cin and n_img*H*W*Cout below 2^31 (32-bit element offsets), else MPF_E_TOO_LARGE.
+ * A tap off the image is selected away, not multiplied by zero: a non-finite pixel reaches its 3x3 neighbourhood only.
  */
 int mpf_gemm3_conv3x3(const float* x, const void* w_planes, const float* bias, float* y, int n_img, int H, int W, int Cin,
                       int Cout, int transposed, void* stream);

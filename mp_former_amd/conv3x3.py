@@ -1,7 +1,10 @@
 """The 3x3 / stride 1 / padding 1 fp32 convolution of the FPN output stage (msdeformattn.py:272-281) on the split-bf16
 GEMM: forward and input gradient are ONE GEMM each with K = 9 * Cin over channel-last planes (``mpf_gemm3_conv3x3``:
-the A rows of a K step are read at the tap's (dy, dx) shift, taps off the image contribute zeros); the weight
-gradient stays MIOpen's (``aten.convolution_backward``), which is already at the rate the NT kernel would reach.
+the A rows of a K step are read at the tap's (dy, dx) shift, taps off the image contribute zeros).  The weight and
+bias gradients are native as well where the image is W % 8 == 0 and Cin % 128 == 0 (``_wgrad_native``: the NT kernel's
+convolution mode ``mpf_gemm3_conv3x3_wgrad`` over row splits + the fixed-order sum of the splits; channel counts that
+are multiples of 256 take the fp16 x 2 form on 256 x 256 tiles); any other width or channel count falls back to
+``aten.convolution_backward`` for those two gradients only.
 Shapes outside the kernel (channel counts, alignment) keep the library convolution."""
 
 import torch

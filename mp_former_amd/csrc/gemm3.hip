@@ -670,11 +670,12 @@ __device__ __forceinline__ void g3_tn_tile(const G3& p, unsigned char* lds, cons
         /* (temporaries, not writes into ra[]: a float4 array written under a condition goes to scratch) */ \
         float4 w0_ = ra[0], w1_ = ra[1], w2_ = ra[2], w3_ = ra[3];                           \
         if constexpr (CV) {                                                                  \
-            const float s0_ = (vm & 1) ? 1.f : 0.f, s1_ = (vm & 2) ? 1.f : 0.f;              \
-            w0_ = make_float4(w0_.x * s0_, w0_.y * s0_, w0_.z * s0_, w0_.w * s0_);           \
-            w1_ = make_float4(w1_.x * s0_, w1_.y * s0_, w1_.z * s0_, w1_.w * s0_);           \
-            w2_ = make_float4(w2_.x * s1_, w2_.y * s1_, w2_.z * s1_, w2_.w * s1_);           \
-            w3_ = make_float4(w3_.x * s1_, w3_.y * s1_, w3_.z * s1_, w3_.w * s1_);           \
+            /* selected, not multiplied by 0: the clamped neighbour row may hold Inf / NaN */ \
+            const bool v0_ = (vm & 1) != 0, v1_ = (vm & 2) != 0;                             \
+            w0_ = make_float4(v0_ ? w0_.x : 0.f, v0_ ? w0_.y : 0.f, v0_ ? w0_.z : 0.f, v0_ ? w0_.w : 0.f); \
+            w1_ = make_float4(v0_ ? w1_.x : 0.f, v0_ ? w1_.y : 0.f, v0_ ? w1_.z : 0.f, v0_ ? w1_.w : 0.f); \
+            w2_ = make_float4(v1_ ? w2_.x : 0.f, v1_ ? w2_.y : 0.f, v1_ ? w2_.z : 0.f, v1_ ? w2_.w : 0.f); \
+            w3_ = make_float4(v1_ ? w3_.x : 0.f, v1_ ? w3_.y : 0.f, v1_ ? w3_.z : 0.f, v1_ ? w3_.w : 0.f); \
         }                                                                                    \
         if constexpr (A2) {                                                                  \
             w0_ = add4(w0_, ra2[0]); w1_ = add4(w1_, ra2[1]); w2_ = add4(w2_, ra2[2]); w3_ = add4(w3_, ra2[3]); \
@@ -958,11 +959,12 @@ __global__ __launch_bounds__(kThreads, 2) void gemm3_tn2_kernel(G3 p)
         uint4 h, m, l;                                                                       \
         float4 w0_ = ra[0], w1_ = ra[1], w2_ = ra[2], w3_ = ra[3];                           \
         if constexpr (CV) {                                                                  \
-            const float s0_ = (vm & 1) ? 1.f : 0.f, s1_ = (vm & 2) ? 1.f : 0.f;              \
-            w0_ = make_float4(w0_.x * s0_, w0_.y * s0_, w0_.z * s0_, w0_.w * s0_);           \
-            w1_ = make_float4(w1_.x * s0_, w1_.y * s0_, w1_.z * s0_, w1_.w * s0_);           \
-            w2_ = make_float4(w2_.x * s1_, w2_.y * s1_, w2_.z * s1_, w2_.w * s1_);           \
-            w3_ = make_float4(w3_.x * s1_, w3_.y * s1_, w3_.z * s1_, w3_.w * s1_);           \
+            /* selected, not multiplied by 0: the clamped neighbour row may hold Inf / NaN */ \
+            const bool v0_ = (vm & 1) != 0, v1_ = (vm & 2) != 0;                             \
+            w0_ = make_float4(v0_ ? w0_.x : 0.f, v0_ ? w0_.y : 0.f, v0_ ? w0_.z : 0.f, v0_ ? w0_.w : 0.f); \
+            w1_ = make_float4(v0_ ? w1_.x : 0.f, v0_ ? w1_.y : 0.f, v0_ ? w1_.z : 0.f, v0_ ? w1_.w : 0.f); \
+            w2_ = make_float4(v1_ ? w2_.x : 0.f, v1_ ? w2_.y : 0.f, v1_ ? w2_.z : 0.f, v1_ ? w2_.w : 0.f); \
+            w3_ = make_float4(v1_ ? w3_.x : 0.f, v1_ ? w3_.y : 0.f, v1_ ? w3_.z : 0.f, v1_ ? w3_.w : 0.f); \
         }                                                                                    \
         if constexpr (F16) {                                                                 \
             split8h(w0_, w1_, sc_a, &h, &l);                                                 \
@@ -1931,7 +1933,8 @@ int g3_conv_impl(const float* x, const void* w_planes, const float* bias, float*
     if (n_img <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 != 0 || Cout % 4 != 0)
         return mpf::fail(MPF_E_SHAPE, "gemm3_conv3x3: Cin must be a multiple of 32, Cout of 4");
     const int64_t M64 = (int64_t)n_img * H * W;
-    if (M64 >= (1ll << 31) / 4 || M64 * Cin >= (1ll << 40)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_conv3x3: image too large");
+    // the kernels form 32-bit element offsets into x (row * Cin + ...) and y (row * Cout + ...)
+    if (M64 * Cin >= (1ll << 31) || M64 * Cout >= (1ll << 31)) return mpf::fail(MPF_E_TOO_LARGE, "gemm3_conv3x3: image too large");
     G3 p;
     if (int rc = g3_fill(p, "gemm3_conv3x3: constants", x, Cin, w_planes, bias, Cout, (int)M64, Cout, 9 * Cin)) return rc;
     p.c = y;
