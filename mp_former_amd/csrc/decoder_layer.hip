@@ -11,12 +11,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "mpf_common.h"
 
 namespace {
 
 constexpr int kE = 256;
 constexpr int kMaxDw = 8;        // weight-gradient problems per layer (6 with packed in-projection gradients — 7 with query positions — 8 without)
+constexpr int kMaxOperands = 16;  // their distinct operands (14, 15 with query positions): what one mpf_transpose_group_bf16 launch takes
 
 struct Carve {
     char* p;
@@ -26,7 +29,7 @@ struct Carve {
     T* take(size_t count)
     {
         T* r = reinterpret_cast<T*>(p + used);
-        used += (count * sizeof(T) + 255) & ~size_t(255);
+        used += mpf::align256(count * sizeof(T));
         return r;
     }
 };
@@ -87,13 +90,10 @@ BwdScratch bwd_scratch(void* base, int Qt, int N, int H, int F, int S, bool pos)
     b.ds_a = c.take<float>(R * kE);
     b.ds_b = c.take<float>(R * kE);
     b.delta = c.take<float>((size_t)N * H * Qt);
-    {
-        const size_t ca = mpf_attn_bwd_aux_bytes(Qt, S, N, H, N), sa = mpf_attn_bwd_aux_bytes(Qt, Qt, N, H, 1);
-        b.aux_bytes = ca > sa ? ca : sa;
-        b.aux = c.take<char>(b.aux_bytes);
-    }
+    b.aux_bytes = std::max(mpf_attn_bwd_aux_bytes(Qt, S, N, H, N), mpf_attn_bwd_aux_bytes(Qt, Qt, N, H, 1));
+    b.aux = c.take<char>(b.aux_bytes);
     b.tbuf = c.take<uint16_t>((size_t)(2 * F + (pos ? 14 : 13) * kE) * ((R + 31) / 32 * 32));
-    b.ln_ws_bytes = (mpf_res_ln256_backward_workspace_bytes((int)R) + 255) & ~size_t(255);
+    b.ln_ws_bytes = mpf::align256(mpf_res_ln256_backward_workspace_bytes((int)R));
     b.ln_ws = c.take<char>(3 * b.ln_ws_bytes);
     b.dxq0 = pos ? c.take<uint16_t>(R * kE) : nullptr;       // (behind everything else: the layout without positions is unchanged)
     b.dxq1 = pos ? c.take<uint16_t>(R * kE) : nullptr;
@@ -109,13 +109,12 @@ int check_layer(const MpfDecoderLayer* L, const char* who, const MpfDecoderLayer
         return mpf::fail(MPF_E_NULL, "decoder_layer: NULL buffer in MpfDecoderLayerPos");
     if (L->Qt <= 0 || L->N <= 0 || L->S <= 0 || L->ffn_dim <= 0 || L->H * 32 != kE || L->ffn_dim % 32)
         return mpf::fail(MPF_E_SHAPE, "decoder_layer: needs H * 32 == 256 channels, positive sizes, ffn_dim % 32 == 0");
-    const void* need[] = {L->ca_wq, L->ca_bq, L->ca_wo, L->ca_bo, L->ca_gamma, L->ca_beta, L->sa_wq, L->sa_bq, L->sa_wk, L->sa_bk,
-                          L->sa_wv, L->sa_bv, L->sa_wo, L->sa_bo, L->sa_gamma, L->sa_beta, L->ff_w1, L->ff_b1, L->ff_w2, L->ff_b2,
-                          L->ff_gamma, L->ff_beta, L->x0, P ? L->x0 : L->xb0, L->k_c, L->v_c, L->mask_c, L->q_c, L->kT_c, L->o_c, L->lse_c,
-                          L->s1, L->mean1, L->rstd1, L->xb1, L->q_s, L->k_s, L->v_s, L->kT_s, L->o_s, L->lse_s, L->s2, L->mean2,
-                          L->rstd2, L->xb2, L->h, L->s3, L->mean3, L->rstd3, L->scratch, L->attn_ws};
-    for (const void* q : need)
-        if (!q) return mpf::fail(MPF_E_NULL, "decoder_layer: NULL buffer in MpfDecoderLayer");
+    if (mpf::any_null({L->ca_wq, L->ca_bq, L->ca_wo, L->ca_bo, L->ca_gamma, L->ca_beta, L->sa_wq, L->sa_bq, L->sa_wk, L->sa_bk,
+                       L->sa_wv, L->sa_bv, L->sa_wo, L->sa_bo, L->sa_gamma, L->sa_beta, L->ff_w1, L->ff_b1, L->ff_w2, L->ff_b2,
+                       L->ff_gamma, L->ff_beta, L->x0, P ? L->x0 : L->xb0, L->k_c, L->v_c, L->mask_c, L->q_c, L->kT_c, L->o_c, L->lse_c,
+                       L->s1, L->mean1, L->rstd1, L->xb1, L->q_s, L->k_s, L->v_s, L->kT_s, L->o_s, L->lse_s, L->s2, L->mean2,
+                       L->rstd2, L->xb2, L->h, L->s3, L->mean3, L->rstd3, L->scratch, L->attn_ws}))
+        return mpf::fail(MPF_E_NULL, "decoder_layer: NULL buffer in MpfDecoderLayer");
     return 0;
 }
 
@@ -131,31 +130,23 @@ int lin_dx(const void* dy, const void* gate, const void* w, const void* acc, voi
     return mpf_small_gemm_bf16(dy, J, 1, gate, w, 1, Kin, nullptr, acc, Kin, dx, Kin, nullptr, R, Kin, J, 0, st);
 }
 
-// dw[J, Kin] = (dy gated)^T . x[R, Kin];  db[J] = column sums of (dy gated)
-int lin_dw(const void* dy, const void* gate, const void* x, void* dw, void* db, int R, int J, int Kin, void* st)
+// q | k | v of the self-attention stand side by side in memory (packed in_proj weight / bias, the three activation buffers, the
+// three gradient buffers, the three weight-gradient destinations): the three GEMMs of each kind become ONE blocked GEMM
+bool side_by_side(const void* q, const void* k, const void* v, size_t bytes)
 {
-    return mpf_small_gemm_bf16(dy, 1, J, gate, x, 1, Kin, nullptr, nullptr, 0, dw, Kin, db, J, Kin, R, 0, st);
+    return k == static_cast<const char*>(q) + bytes && v == static_cast<const char*>(q) + 2 * bytes;
 }
+constexpr size_t kWeightBytes = (size_t)kE * kE * 2, kBiasBytes = (size_t)kE * 2;
+size_t act_bytes(int R) { return (size_t)R * kE * 2; }
 
-// the same problem as a descriptor of the grouped launch
-MpfSmallGemmItem dw_item(const void* dy, const void* gate, const void* x, void* dw, void* db, int R, int J, int Kin, int a_blk = 0,
-                         int64_t a_bs = 0)
-{
-    MpfSmallGemmItem m;
-    m.a = dy; m.gate = gate; m.b = x; m.c = dw; m.rowsum_a = db;
-    m.a_rs = 1; m.a_ks = a_blk ? kE : J; m.a_bs = a_bs; m.b_rs = 1; m.b_ks = Kin; m.ldc = Kin;
-    m.a_blk = a_blk; m.I = J; m.J = Kin; m.Kc = R;
-    return m;
-}
-
-inline const char* at(const void* p, size_t bytes) { return static_cast<const char*>(p) + bytes; }
-
-// q | k | v of the self-attention stand side by side in memory (packed in_proj weight / bias, the three
-// activation buffers, the three gradient buffers): the three GEMMs of each kind become ONE blocked GEMM
 bool packed_weights(const MpfDecoderLayer* L)
 {
-    const size_t w = (size_t)kE * kE * 2, b = (size_t)kE * 2;
-    return L->sa_wk == at(L->sa_wq, w) && L->sa_wv == at(L->sa_wq, 2 * w) && L->sa_bk == at(L->sa_bq, b) && L->sa_bv == at(L->sa_bq, 2 * b);
+    return side_by_side(L->sa_wq, L->sa_wk, L->sa_wv, kWeightBytes) && side_by_side(L->sa_bq, L->sa_bk, L->sa_bv, kBiasBytes);
+}
+bool packed_acts(const MpfDecoderLayer* L, int R) { return side_by_side(L->q_s, L->k_s, L->v_s, act_bytes(R)); }
+bool packed_dw_dst(const MpfDecoderLayerGrad* G)
+{
+    return side_by_side(G->d_sa_wq, G->d_sa_wk, G->d_sa_wv, kWeightBytes) && side_by_side(G->d_sa_bq, G->d_sa_bk, G->d_sa_bv, kBiasBytes);
 }
 
 }  // namespace
@@ -213,40 +204,34 @@ int layer_forward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, void* s
     MPF_TRY(check_layer(L, "decoder_layer_forward: NULL layer", P, false));
     if (!L->x3 && !L->xb3) return mpf::fail(MPF_E_NULL, "decoder_layer_forward: no output buffer");
     const int Qt = L->Qt, N = L->N, H = L->H, S = L->S, F = L->ffn_dim, R = Qt * N;
-    if (L->scratch_bytes < fwd_scratch(nullptr, Qt, N, S).bytes)
-        return mpf::fail(MPF_E_SHAPE, "decoder_layer_forward: scratch too small");
     const FwdScratch f = fwd_scratch(L->scratch, Qt, N, S);
+    if (L->scratch_bytes < f.bytes) return mpf::fail(MPF_E_SHAPE, "decoder_layer_forward: scratch too small");
     const float scale = 0.17677669529663687f;       // 1 / sqrt(32)
+    // output projection + residual LayerNorm of an attention block: the row-local chain of row_chain.hip, or two launches
+    const auto proj_ln = [&](auto o, auto wo, auto bo, auto x_in, auto gamma, auto beta, auto s, auto x_out, auto xb, auto mean, auto rstd) {
+        if (g_row_chain) return mpf_lin256_res_ln_forward(o, wo, bo, x_in, gamma, beta, s, x_out, xb, mean, rstd, R, L->eps, st);
+        MPF_TRY(lin_fwd(o, wo, bo, f.t, R, kE, kE, 0, st));
+        return mpf_res_ln256_forward(x_in, f.t, MPF_BF16, gamma, beta, s, x_out, xb, mean, rstd, R, L->eps, nullptr, 0, nullptr, st);
+    };
     // cross-attention (:1784-1789) + post-norm
     if (P) MPF_TRY(mpf_qpos_operand_forward(L->x0, P->qpos, P->xq0, Qt, N, st));
     MPF_TRY(lin_fwd(P ? P->xq0 : L->xb0, L->ca_wq, L->ca_bq, L->q_c, R, kE, kE, 0, st));
     MPF_TRY(mpf_attn_transpose2_strided(L->k_c, L->v_c, L->kv_row_stride, L->kv_img_stride, L->kT_c, f.vT_c, S, S, N, kE, st));
     MPF_TRY(mpf_attn_forward_kv(L->q_c, L->k_c, L->kv_row_stride, L->kv_img_stride, f.vT_c, L->mask_c, 1, L->o_c, L->lse_c, Qt, S, N,
                                 H, 32, scale, L->attn_ws, L->attn_ws_bytes, st));
-    if (g_row_chain) {
-        MPF_TRY(mpf_lin256_res_ln_forward(L->o_c, L->ca_wo, L->ca_bo, L->x0, L->ca_gamma, L->ca_beta, L->s1, f.x1, L->xb1, L->mean1, L->rstd1,
-                                          R, L->eps, st));
-    } else {
-        MPF_TRY(lin_fwd(L->o_c, L->ca_wo, L->ca_bo, f.t, R, kE, kE, 0, st));
-        MPF_TRY(mpf_res_ln256_forward(L->x0, f.t, MPF_BF16, L->ca_gamma, L->ca_beta, L->s1, f.x1, L->xb1, L->mean1, L->rstd1, R,
-                                      L->eps, nullptr, 0, nullptr, st));
-    }
+    MPF_TRY(proj_ln(L->o_c, L->ca_wo, L->ca_bo, L->x0, L->ca_gamma, L->ca_beta, L->s1, f.x1, L->xb1, L->mean1, L->rstd1));
     // self-attention (:1791-1795) + post-norm
-    const size_t act = (size_t)R * kE * 2;
-    const bool packed = packed_weights(L) && L->k_s == at(L->q_s, act) && L->v_s == at(L->q_s, 2 * act);
-    const void* xqk = L->xb1;                         // operand of the query and key projections
+    const bool packed = packed_weights(L) && packed_acts(L, R);
+    const void* xqk = L->xb1;                        // operand of the query and key projections
     if (P) {
         MPF_TRY(mpf_qpos_operand_forward(f.x1, P->qpos, P->xq1, Qt, N, st));
         xqk = P->xq1;
     }
-    if (packed && !P) {
-        MPF_TRY(mpf_small_gemm_bf16_blocked(L->xb1, kE, 1, 0, 0, nullptr, L->sa_wq, kE, 1, L->sa_bq, nullptr, 0, L->q_s, kE, kE,
-                                            (int64_t)R * kE, nullptr, R, 3 * kE, kE, 0, st));
-    } else if (packed) {
-        // [q_s | k_s] = xq1 . [Wq | Wk]^T as one blocked GEMM, v_s = xb1 . Wv^T
+    if (packed) {
+        // [q_s | k_s | v_s] = xb1 . W_in^T as one blocked GEMM; with positions [q_s | k_s] = xq1 . [Wq | Wk]^T, v_s = xb1 . Wv^T
         MPF_TRY(mpf_small_gemm_bf16_blocked(xqk, kE, 1, 0, 0, nullptr, L->sa_wq, kE, 1, L->sa_bq, nullptr, 0, L->q_s, kE, kE,
-                                            (int64_t)R * kE, nullptr, R, 2 * kE, kE, 0, st));
-        MPF_TRY(lin_fwd(L->xb1, L->sa_wv, L->sa_bv, L->v_s, R, kE, kE, 0, st));
+                                            (int64_t)R * kE, nullptr, R, (P ? 2 : 3) * kE, kE, 0, st));
+        if (P) MPF_TRY(lin_fwd(L->xb1, L->sa_wv, L->sa_bv, L->v_s, R, kE, kE, 0, st));
     } else {
         MPF_TRY(lin_fwd(xqk, L->sa_wq, L->sa_bq, L->q_s, R, kE, kE, 0, st));
         MPF_TRY(lin_fwd(xqk, L->sa_wk, L->sa_bk, L->k_s, R, kE, kE, 0, st));
@@ -255,14 +240,7 @@ int layer_forward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, void* s
     MPF_TRY(mpf_attn_transpose2(L->k_s, L->v_s, L->kT_s, f.vT_s, Qt, Qt, N, kE, st));
     MPF_TRY(mpf_attn_forward(L->q_s, L->k_s, f.vT_s, L->mask_s, 0, L->o_s, L->lse_s, Qt, Qt, N, H, 32, scale, L->attn_ws,
                              L->attn_ws_bytes, st));
-    if (g_row_chain) {
-        MPF_TRY(mpf_lin256_res_ln_forward(L->o_s, L->sa_wo, L->sa_bo, f.x1, L->sa_gamma, L->sa_beta, L->s2, f.x2, L->xb2, L->mean2, L->rstd2,
-                                          R, L->eps, st));
-    } else {
-        MPF_TRY(lin_fwd(L->o_s, L->sa_wo, L->sa_bo, f.t, R, kE, kE, 0, st));
-        MPF_TRY(mpf_res_ln256_forward(f.x1, f.t, MPF_BF16, L->sa_gamma, L->sa_beta, L->s2, f.x2, L->xb2, L->mean2, L->rstd2, R,
-                                      L->eps, nullptr, 0, nullptr, st));
-    }
+    MPF_TRY(proj_ln(L->o_s, L->sa_wo, L->sa_bo, f.x1, L->sa_gamma, L->sa_beta, L->s2, f.x2, L->xb2, L->mean2, L->rstd2));
     // FFN (:1798-1800) + post-norm
     MPF_TRY(lin_fwd(L->xb2, L->ff_w1, L->ff_b1, L->h, R, F, kE, 1, st));
     MPF_TRY(lin_fwd(L->h, L->ff_w2, L->ff_b2, f.t, R, kE, F, 0, st));
@@ -271,190 +249,170 @@ int layer_forward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, void* s
     return 0;
 }
 
+// The weight gradients of a layer, stated once along the backward chain: the distinct [R, C] operands, in the order of their
+// transposed copies, and one problem per gradient,  dw[J, Kin] = (dy gated)^T . x,  db[J] = column sums of (dy gated).  They depend
+// only on buffers that the chain leaves alone (each dY in its own scratch buffer), so issue() runs after the chain.
+struct DwList {
+    struct Operand { const void *src, *gate; int C; } op[kMaxOperands];
+    struct Problem { int dy, x; void *dw, *db; int J, Kin, blocks; } pr[kMaxDw];
+    int nop = 0, npr = 0, lost = 0;          // lost: an operand or a problem that did not fit (refused by issue())
+    int operand(const void* src, int C = kE, const void* gate = nullptr) { if (nop == kMaxOperands) return lost = 1, 0; op[nop] = {src, gate, C}; return nop++; }
+    // blocks > 1: dy is that many [R, 256] operands stated one after the other, their buffers R * 256 elements apart, and dw / db
+    // the packed [blocks * 256, Kin] / [blocks * 256] destination
+    void add(int dy, int x, void* dw, void* db, int blocks = 1)
+    {
+        if (npr == kMaxDw) lost = 1;
+        else pr[npr++] = {dy, x, dw, db, blocks * op[dy].C, op[x].C, blocks};
+    }
+
+    // form = decoder_dw_group.  0: one launch per problem and 1: one grouped launch, both on the operands as they lie (both
+    // row-contiguous); 2: the weight gradients contract over the ROWS of dY and x: on transposed [C, Rp] copies (one grouped launch)
+    // both operands are contraction-contiguous, i.e. 16-byte fragment loads instead of eight 2-byte ones per fragment; same 32-row
+    // contraction steps on the same waves, zero padding: bit-identical to the row-contiguous form.  The copies of a blocked dy are
+    // adjacent [256, Rp] blocks by construction, one [blocks * 256, Rp] operand.
+    int issue(int form, int R, uint16_t* tbuf, void* st) const
+    {
+        if (lost) return mpf::fail(MPF_E_SHAPE, "decoder_layer_backward: more weight-gradient operands or problems than one launch takes");
+        const int Rp = (R + 31) / 32 * 32;
+        const uint16_t* copy[kMaxOperands];
+        if (form == 2) {
+            MpfTransposeItem tr[kMaxOperands];
+            for (int t = 0; t < nop; ++t) {
+                tr[t].src = op[t].src; tr[t].gate = op[t].gate; tr[t].dst = tbuf; tr[t].ld = op[t].C; tr[t].R = R; tr[t].C = op[t].C;
+                copy[t] = tbuf;
+                tbuf += (size_t)op[t].C * Rp;
+            }
+            MPF_TRY(mpf_transpose_group_bf16(tr, nop, Rp, st));
+        }
+        MpfSmallGemmItem it[kMaxDw];
+        for (int t = 0; t < npr; ++t) {
+            const Problem& p = pr[t];
+            MpfSmallGemmItem& m = it[t];
+            m.c = p.dw; m.rowsum_a = p.db; m.ldc = p.Kin; m.I = p.J; m.J = p.Kin;
+            if (form == 2) {
+                m.a = copy[p.dy]; m.gate = nullptr; m.b = copy[p.x];
+                m.a_rs = Rp; m.a_ks = 1; m.a_bs = 0; m.b_rs = Rp; m.b_ks = 1; m.a_blk = 0; m.Kc = Rp;
+            } else {
+                m.a = op[p.dy].src; m.gate = op[p.dy].gate; m.b = op[p.x].src;
+                m.a_rs = 1; m.a_ks = op[p.dy].C; m.a_bs = p.blocks > 1 ? (int64_t)R * kE : 0; m.b_rs = 1; m.b_ks = p.Kin;
+                m.a_blk = p.blocks > 1 ? kE : 0; m.Kc = R;
+            }
+        }
+        if (form) return mpf_small_gemm_bf16_group(it, npr, st);
+        for (int t = 0; t < npr; ++t)
+            MPF_TRY(mpf_small_gemm_bf16_blocked(it[t].a, it[t].a_rs, it[t].a_ks, it[t].a_blk, it[t].a_bs, it[t].gate, it[t].b, it[t].b_rs,
+                                                it[t].b_ks, nullptr, nullptr, 0, it[t].c, it[t].ldc, 0, 0, it[t].rowsum_a, it[t].I,
+                                                it[t].J, it[t].Kc, 0, st));
+        return 0;
+    }
+};
+
 // The backward of both forms (P as in layer_forward).
 int layer_backward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, const MpfDecoderLayerGrad* G, void* st)
 {
     MPF_TRY(check_layer(L, "decoder_layer_backward: NULL layer", P, true));
     if (!G) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: NULL grad");
     if (!G->g_x3 && !G->g_xb3) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: no upstream gradient");
-    const void* need[] = {G->d_x0, P ? (const void*)G->d_x0 : G->d_xb0,         // (d_xb0: no reader, no gradient with positions)
-                          G->d_k_c, G->d_v_c, G->d_ca_wq, G->d_ca_bq, G->d_ca_wo, G->d_ca_bo, G->d_sa_wq, G->d_sa_bq,
-                          G->d_sa_wk, G->d_sa_bk, G->d_sa_wv, G->d_sa_bv, G->d_sa_wo, G->d_sa_bo, G->d_ff_w1, G->d_ff_b1, G->d_ff_w2,
-                          G->d_ff_b2, G->d_ln};
-    for (const void* q : need)
-        if (!q) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: NULL buffer in MpfDecoderLayerGrad");
+    if (mpf::any_null({G->d_x0, P ? (const void*)G->d_x0 : G->d_xb0,         // (d_xb0: no reader, no gradient with positions)
+                       G->d_k_c, G->d_v_c, G->d_ca_wq, G->d_ca_bq, G->d_ca_wo, G->d_ca_bo, G->d_sa_wq, G->d_sa_bq, G->d_sa_wk, G->d_sa_bk,
+                       G->d_sa_wv, G->d_sa_bv, G->d_sa_wo, G->d_sa_bo, G->d_ff_w1, G->d_ff_b1, G->d_ff_w2, G->d_ff_b2, G->d_ln}))
+        return mpf::fail(MPF_E_NULL, "decoder_layer_backward: NULL buffer in MpfDecoderLayerGrad");
     const int Qt = L->Qt, N = L->N, H = L->H, S = L->S, F = L->ffn_dim, R = Qt * N;
     const int LqP = (Qt + 31) / 32 * 32;
-    if (L->scratch_bytes < bwd_scratch(nullptr, Qt, N, H, F, S, P != nullptr).bytes)
-        return mpf::fail(MPF_E_SHAPE, "decoder_layer_backward: scratch too small");
     const BwdScratch b = bwd_scratch(L->scratch, Qt, N, H, F, S, P != nullptr);
+    if (L->scratch_bytes < b.bytes) return mpf::fail(MPF_E_SHAPE, "decoder_layer_backward: scratch too small");
     const float scale = 0.17677669529663687f;
-    float* dln = G->d_ln;
+    // q | k | v as one problem.  dX needs the packed weight and adjacent gradient buffers.  dW needs adjacent destinations, and
+    // adjacent gradient buffers where it reads them as they lie (the transposed copies of dq | dk | dv are adjacent by construction)
+    const bool grads_packed = side_by_side(b.dq, b.dk_s, b.dv_s, act_bytes(R));
+    const bool dx_packed = packed_weights(L) && grads_packed;
+    const bool dw_packed = packed_dw_dst(G) && (g_dw_group == 2 || grads_packed);
     // LayerNorm parameter gradients: the three backward launches leave per-workgroup partial sums, ONE launch at the end of the
     // layer reduces them in a fixed order (no float atomics, nothing to zero)
     char* ln_part = static_cast<char*>(b.ln_ws);
-    // The weight gradients depend only on the dY buffers of the chain below (each kept in its own scratch buffer), so they
-    // are collected here and issued as ONE grouped launch after the chain.
-    MpfSmallGemmItem dw[kMaxDw];
-    int ndw = 0;
+    DwList W;
     // FFN block: x3 = LN(x2 + W2 relu(W1 xb2))
     if (G->g_x3_plus && !G->g_x3) return mpf::fail(MPF_E_NULL, "decoder_layer_backward: g_x3_plus without g_x3");
     MPF_TRY(mpf_res_ln256_backward_partial(L->s3, L->mean3, L->rstd3, L->ff_gamma, G->g_x3, G->g_xb3, G->g_x3_plus, b.ds_a, b.dt3, R,
                                            ln_part + 2 * b.ln_ws_bytes, b.ln_ws_bytes, st));
     MPF_TRY(lin_dx(b.dt3, nullptr, L->ff_w2, nullptr, b.dh, R, kE, F, st));
-    dw[ndw++] = dw_item(b.dt3, nullptr, L->h, G->d_ff_w2, G->d_ff_b2, R, kE, F);
+    const int dt3 = W.operand(b.dt3), h = W.operand(L->h, F);
+    W.add(dt3, h, G->d_ff_w2, G->d_ff_b2);
     MPF_TRY(lin_dx(b.dh, L->h, L->ff_w1, nullptr, b.dxb, R, F, kE, st));
-    dw[ndw++] = dw_item(b.dh, L->h, L->xb2, G->d_ff_w1, G->d_ff_b1, R, F, kE);
+    const int dh = W.operand(b.dh, F, L->h), xb2 = W.operand(L->xb2);
+    W.add(dh, xb2, G->d_ff_w1, G->d_ff_b1);
     // self-attention block: x2 = LN(x1 + Wo attn(Wq xb1, Wk xb1, Wv xb1))
     MPF_TRY(mpf_res_ln256_backward_partial(L->s2, L->mean2, L->rstd2, L->sa_gamma, b.ds_a, b.dxb, nullptr, b.ds_b, b.dt2, R,
                                            ln_part + b.ln_ws_bytes, b.ln_ws_bytes, st));
     MPF_TRY(lin_dx(b.dt2, nullptr, L->sa_wo, nullptr, b.dout, R, kE, kE, st));
-    dw[ndw++] = dw_item(b.dt2, nullptr, L->o_s, G->d_sa_wo, G->d_sa_bo, R, kE, kE);
+    const int dt2 = W.operand(b.dt2), o_s = W.operand(L->o_s);
+    W.add(dt2, o_s, G->d_sa_wo, G->d_sa_bo);
     MPF_TRY(mpf_attn_bwd_prep_aux(L->q_s, b.dout, L->o_s, L->lse_s, L->mask_s, 0, Qt, b.qT, b.doT, b.delta, b.aux, b.aux_bytes, Qt, LqP,
                                   N, H, st));
     MPF_TRY(mpf_attn_backward_kv_aux(L->q_s, L->k_s, L->v_s, 0, 0, L->kT_s, b.qT, b.dout, b.doT, L->mask_s, 0, L->lse_s, b.delta, b.dq,
                                      b.dk_s, b.dv_s, 0, 0, Qt, LqP, Qt, N, H, 32, scale, L->attn_ws, L->attn_ws_bytes, b.aux, st));
-    const size_t act = (size_t)R * kE * 2, wsz = (size_t)kE * kE * 2, bsz = (size_t)kE * 2;
-    const bool grads_packed = b.dk_s == at(b.dq, act) && b.dv_s == at(b.dq, 2 * act);
-    const void* xqk = P ? P->xq1 : L->xb1;          // operand of the query and key projections
-    if (packed_weights(L) && grads_packed && !P) {
-        // dxb = [dq | dk | dv] . W_in (contraction over the 768 packed outputs, blocked over the three buffers)
-        MPF_TRY(mpf_small_gemm_bf16_blocked(b.dq, kE, 1, kE, (int64_t)R * kE, nullptr, L->sa_wq, 1, kE, nullptr, nullptr, 0, b.dxb, kE,
-                                            0, 0, nullptr, R, kE, 3 * kE, 0, st));
-    } else if (packed_weights(L) && grads_packed) {
+    void* dxqk = P ? b.dxq1 : b.dxb;                      // gradient of the operand of the query and key projections
+    if (dx_packed) {
+        // dxb = [dq | dk | dv] . W_in (contraction over the 768 packed outputs, blocked over the three buffers); with positions
         // dxq1 = [dq | dk] . [Wq | Wk] (contraction over 512), dxb = dv . Wv
-        MPF_TRY(mpf_small_gemm_bf16_blocked(b.dq, kE, 1, kE, (int64_t)R * kE, nullptr, L->sa_wq, 1, kE, nullptr, nullptr, 0, b.dxq1, kE,
-                                            0, 0, nullptr, R, kE, 2 * kE, 0, st));
-        MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, nullptr, b.dxb, R, kE, kE, st));
-    } else if (P) {
-        MPF_TRY(lin_dx(b.dq, nullptr, L->sa_wq, nullptr, b.dxq1, R, kE, kE, st));
-        MPF_TRY(lin_dx(b.dk_s, nullptr, L->sa_wk, b.dxq1, b.dxq1, R, kE, kE, st));
-        MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, nullptr, b.dxb, R, kE, kE, st));
+        MPF_TRY(mpf_small_gemm_bf16_blocked(b.dq, kE, 1, kE, (int64_t)R * kE, nullptr, L->sa_wq, 1, kE, nullptr, nullptr, 0, dxqk, kE,
+                                            0, 0, nullptr, R, kE, (P ? 2 : 3) * kE, 0, st));
+        if (P) MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, nullptr, b.dxb, R, kE, kE, st));
     } else {
-        MPF_TRY(lin_dx(b.dq, nullptr, L->sa_wq, nullptr, b.dxb, R, kE, kE, st));
-        MPF_TRY(lin_dx(b.dk_s, nullptr, L->sa_wk, b.dxb, b.dxb, R, kE, kE, st));
-        MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, b.dxb, b.dxb, R, kE, kE, st));
+        MPF_TRY(lin_dx(b.dq, nullptr, L->sa_wq, nullptr, dxqk, R, kE, kE, st));
+        MPF_TRY(lin_dx(b.dk_s, nullptr, L->sa_wk, dxqk, dxqk, R, kE, kE, st));
+        MPF_TRY(lin_dx(b.dv_s, nullptr, L->sa_wv, P ? nullptr : b.dxb, b.dxb, R, kE, kE, st));
     }
-    const bool dw_packed = grads_packed && G->d_sa_wk == at(G->d_sa_wq, wsz) && G->d_sa_wv == at(G->d_sa_wq, 2 * wsz) &&
-                           G->d_sa_bk == at(G->d_sa_bq, bsz) && G->d_sa_bv == at(G->d_sa_bq, 2 * bsz);
+    const int dq = W.operand(b.dq), dk = W.operand(b.dk_s), dv = W.operand(b.dv_s), xb1 = W.operand(L->xb1);
+    const int xqk = P ? W.operand(P->xq1) : xb1;          // operand of the query and key projections
     if (dw_packed && !P) {
-        // dW_in [768, 256] = [dq | dk | dv]^T . xb1 and its 768 bias gradients as one problem (rows of A blocked)
-        dw[ndw++] = dw_item(b.dq, nullptr, L->xb1, G->d_sa_wq, G->d_sa_bq, R, 3 * kE, kE, kE, (int64_t)R * kE);
+        // dW_in [768, 256] = [dq | dk | dv]^T . xb1 and its 768 bias gradients as one problem
+        W.add(dq, xb1, G->d_sa_wq, G->d_sa_bq, 3);
     } else if (dw_packed) {
         // [dWq | dWk] [512, 256] = [dq | dk]^T . xq1 as one problem, dWv = dv^T . xb1
-        dw[ndw++] = dw_item(b.dq, nullptr, xqk, G->d_sa_wq, G->d_sa_bq, R, 2 * kE, kE, kE, (int64_t)R * kE);
-        dw[ndw++] = dw_item(b.dv_s, nullptr, L->xb1, G->d_sa_wv, G->d_sa_bv, R, kE, kE);
+        W.add(dq, xqk, G->d_sa_wq, G->d_sa_bq, 2);
+        W.add(dv, xb1, G->d_sa_wv, G->d_sa_bv);
     } else {
-        dw[ndw++] = dw_item(b.dq, nullptr, xqk, G->d_sa_wq, G->d_sa_bq, R, kE, kE);
-        dw[ndw++] = dw_item(b.dk_s, nullptr, xqk, G->d_sa_wk, G->d_sa_bk, R, kE, kE);
-        dw[ndw++] = dw_item(b.dv_s, nullptr, L->xb1, G->d_sa_wv, G->d_sa_bv, R, kE, kE);
+        W.add(dq, xqk, G->d_sa_wq, G->d_sa_bq);
+        W.add(dk, xqk, G->d_sa_wk, G->d_sa_bk);
+        W.add(dv, xb1, G->d_sa_wv, G->d_sa_bv);
     }
     // cross-attention block: x1 = LN(x0 + Wo attn(Wq xb0, k_c, v_c)); with positions the gradient of bf16(x1 + qpos) joins the
     // fp32 gradient of x1 first (the sum autograd forms for the stream's two consumers)
     if (P) MPF_TRY(mpf::bf16_rows_add256(b.dxq1, b.ds_b, R, st));
     MPF_TRY(mpf_res_ln256_backward_partial(L->s1, L->mean1, L->rstd1, L->ca_gamma, b.ds_b, b.dxb, nullptr, G->d_x0, b.dt1, R, ln_part,
                                            b.ln_ws_bytes, st));
-    MPF_TRY(mpf_ln_partial_reduce(ln_part, b.ln_ws_bytes, R, 3, dln, st));      // dln = [ca | sa | ff] x (dgamma, dbeta)
+    MPF_TRY(mpf_ln_partial_reduce(ln_part, b.ln_ws_bytes, R, 3, G->d_ln, st));      // d_ln = [ca | sa | ff] x (dgamma, dbeta)
     MPF_TRY(lin_dx(b.dt1, nullptr, L->ca_wo, nullptr, b.dout, R, kE, kE, st));
-    dw[ndw++] = dw_item(b.dt1, nullptr, L->o_c, G->d_ca_wo, G->d_ca_bo, R, kE, kE);
+    const int dt1 = W.operand(b.dt1), o_c = W.operand(L->o_c);
+    W.add(dt1, o_c, G->d_ca_wo, G->d_ca_bo);
     MPF_TRY(mpf_attn_bwd_prep_aux(L->q_c, b.dout, L->o_c, L->lse_c, L->mask_c, 1, S, b.qT, b.doT, b.delta, b.aux, b.aux_bytes, Qt, LqP, N,
                                   H, st));
     MPF_TRY(mpf_attn_backward_kv_aux(L->q_c, L->k_c, L->v_c, L->kv_row_stride, L->kv_img_stride, L->kT_c, b.qT, b.dout, b.doT, L->mask_c,
                                      1, L->lse_c, b.delta, b.dq_c, G->d_k_c, G->d_v_c, G->dkv_row_stride, G->dkv_img_stride, Qt, LqP, S,
                                      N, H, 32, scale, L->attn_ws, L->attn_ws_bytes, b.aux, st));
-    const void* xq_c = P ? P->xq0 : L->xb0;         // operand of the cross-attention's query projection
     MPF_TRY(lin_dx(b.dq_c, nullptr, L->ca_wq, nullptr, P ? b.dxq0 : G->d_xb0, R, kE, kE, st));
     // the gradient of bf16(x0 + qpos) goes to the fp32 stream, and with that of bf16(x1 + qpos) to the positions
     if (P) MPF_TRY(mpf_qpos_backward(b.dxq0, b.dxq1, G->d_x0, P->d_qpos, Qt, N, st));
-    dw[ndw++] = dw_item(b.dq_c, nullptr, xq_c, G->d_ca_wq, G->d_ca_bq, R, kE, kE);
-    if (g_dw_group == 2) {
-        // the weight gradients contract over the ROWS of dY and x: on transposed [C, Rp] copies (one grouped launch) both operands
-        // are contraction-contiguous, i.e. 16-byte fragment loads instead of eight 2-byte ones per fragment; same 32-row
-        // contraction steps on the same waves, zero padding: bit-identical to the row-contiguous form
-        const int Rp = (R + 31) / 32 * 32;
-        uint16_t* tp = b.tbuf;
-        MpfTransposeItem tr[16];
-        int ntr = 0;
-        auto tcopy = [&](const void* src, const void* gate, int C) {
-            uint16_t* dst = tp;
-            tr[ntr].src = src; tr[ntr].gate = gate; tr[ntr].dst = dst; tr[ntr].ld = C; tr[ntr].R = R; tr[ntr].C = C;
-            ++ntr;
-            tp += (size_t)C * Rp;
-            return dst;
-        };
-        const uint16_t* dt3T = tcopy(b.dt3, nullptr, kE);
-        const uint16_t* hT = tcopy(L->h, nullptr, F);
-        const uint16_t* dhT = tcopy(b.dh, L->h, F);
-        const uint16_t* xb2T = tcopy(L->xb2, nullptr, kE);
-        const uint16_t* dt2T = tcopy(b.dt2, nullptr, kE);
-        const uint16_t* osT = tcopy(L->o_s, nullptr, kE);
-        const uint16_t* dqT = tcopy(b.dq, nullptr, kE);          // dq | dk | dv: three consecutive [256, Rp] blocks = one [768, Rp]
-        tcopy(b.dk_s, nullptr, kE);
-        tcopy(b.dv_s, nullptr, kE);
-        const uint16_t* xb1T = tcopy(L->xb1, nullptr, kE);
-        const uint16_t* xqkT = P ? tcopy(P->xq1, nullptr, kE) : xb1T;
-        const uint16_t* dt1T = tcopy(b.dt1, nullptr, kE);
-        const uint16_t* ocT = tcopy(L->o_c, nullptr, kE);
-        const uint16_t* dqcT = tcopy(b.dq_c, nullptr, kE);
-        const uint16_t* xb0T = tcopy(xq_c, nullptr, kE);
-        MPF_TRY(mpf_transpose_group_bf16(tr, ntr, Rp, st));
-        auto titem = [&](const uint16_t* aT, const uint16_t* bT, void* dwp, void* dbp, int J, int Kin) {
-            MpfSmallGemmItem m;
-            m.a = aT; m.gate = nullptr; m.b = bT; m.c = dwp; m.rowsum_a = dbp;
-            m.a_rs = Rp; m.a_ks = 1; m.a_bs = 0; m.b_rs = Rp; m.b_ks = 1; m.ldc = Kin;
-            m.a_blk = 0; m.I = J; m.J = Kin; m.Kc = Rp;
-            return m;
-        };
-        MpfSmallGemmItem tw[kMaxDw];
-        int nt = 0;
-        tw[nt++] = titem(dt3T, hT, G->d_ff_w2, G->d_ff_b2, kE, F);
-        tw[nt++] = titem(dhT, xb2T, G->d_ff_w1, G->d_ff_b1, F, kE);
-        tw[nt++] = titem(dt2T, osT, G->d_sa_wo, G->d_sa_bo, kE, kE);
-        const bool tw_packed = G->d_sa_wk == at(G->d_sa_wq, wsz) && G->d_sa_wv == at(G->d_sa_wq, 2 * wsz) &&
-                               G->d_sa_bk == at(G->d_sa_bq, bsz) && G->d_sa_bv == at(G->d_sa_bq, 2 * bsz);
-        if (tw_packed && !P) {
-            tw[nt++] = titem(dqT, xb1T, G->d_sa_wq, G->d_sa_bq, 3 * kE, kE);
-        } else if (tw_packed) {
-            tw[nt++] = titem(dqT, xqkT, G->d_sa_wq, G->d_sa_bq, 2 * kE, kE);
-            tw[nt++] = titem(dqT + (size_t)2 * kE * Rp, xb1T, G->d_sa_wv, G->d_sa_bv, kE, kE);
-        } else {
-            tw[nt++] = titem(dqT, xqkT, G->d_sa_wq, G->d_sa_bq, kE, kE);
-            tw[nt++] = titem(dqT + (size_t)kE * Rp, xqkT, G->d_sa_wk, G->d_sa_bk, kE, kE);
-            tw[nt++] = titem(dqT + (size_t)2 * kE * Rp, xb1T, G->d_sa_wv, G->d_sa_bv, kE, kE);
-        }
-        tw[nt++] = titem(dt1T, ocT, G->d_ca_wo, G->d_ca_bo, kE, kE);
-        tw[nt++] = titem(dqcT, xb0T, G->d_ca_wq, G->d_ca_bq, kE, kE);
-        MPF_TRY(mpf_small_gemm_bf16_group(tw, nt, st));
-    } else if (g_dw_group) {
-        MPF_TRY(mpf_small_gemm_bf16_group(dw, ndw, st));
-    } else {
-        for (int t = 0; t < ndw; ++t)
-            MPF_TRY(mpf_small_gemm_bf16_blocked(dw[t].a, dw[t].a_rs, dw[t].a_ks, dw[t].a_blk, dw[t].a_bs, dw[t].gate, dw[t].b, dw[t].b_rs,
-                                                dw[t].b_ks, nullptr, nullptr, 0, dw[t].c, dw[t].ldc, 0, 0, dw[t].rowsum_a, dw[t].I,
-                                                dw[t].J, dw[t].Kc, 0, st));
-    }
-    return 0;
+    const int dq_c = W.operand(b.dq_c), xq_c = W.operand(P ? P->xq0 : L->xb0);      // (the operand of the cross-attention's query projection)
+    W.add(dq_c, xq_c, G->d_ca_wq, G->d_ca_bq);
+    return W.issue(g_dw_group, R, b.tbuf, st);
 }
 
 }  // namespace
 
 extern "C" int mpf_decoder_layer_forward(const MpfDecoderLayer* L, void* st) { return layer_forward(L, nullptr, st); }
 
-extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDecoderLayerGrad* G, void* st)
-{
-    return layer_backward(L, nullptr, G, st);
-}
+extern "C" int mpf_decoder_layer_backward(const MpfDecoderLayer* L, const MpfDecoderLayerGrad* G, void* st) { return layer_backward(L, nullptr, G, st); }
 
 extern "C" int mpf_decoder_layer_pos_forward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, void* st)
 {
-    if (!P) return mpf::fail(MPF_E_NULL, "decoder_layer_pos_forward: NULL position record");
-    return layer_forward(L, P, st);
+    return P ? layer_forward(L, P, st) : mpf::fail(MPF_E_NULL, "decoder_layer_pos_forward: NULL position record");
 }
 
 extern "C" int mpf_decoder_layer_pos_backward(const MpfDecoderLayer* L, const MpfDecoderLayerPos* P, const MpfDecoderLayerGrad* G, void* st)
 {
-    if (!P) return mpf::fail(MPF_E_NULL, "decoder_layer_pos_backward: NULL position record");
-    return layer_backward(L, P, G, st);
+    return P ? layer_backward(L, P, G, st) : mpf::fail(MPF_E_NULL, "decoder_layer_pos_backward: NULL position record");
 }
 
 // The attention mask of the NEXT layer from this layer's residual stream (mask2former_transformer_decoder.py:1869-1875 with the
@@ -466,17 +424,17 @@ extern "C" size_t mpf_next_attn_mask_scratch_bytes(int N, int Q)
 {
     if (N <= 0 || Q <= 0) return 0;
     const size_t rows = (size_t)N * Q;
-    return 3 * ((rows * kE * 2 + 255) & ~(size_t)255) + 2 * ((rows * 4 + 255) & ~(size_t)255);
+    return 3 * mpf::align256(rows * kE * 2) + 2 * mpf::align256(rows * 4);
 }
 
 extern "C" int mpf_next_attn_mask(const MpfNextMask* m, void* st)
 {
-    if (!m || !m->x || !m->ln_gamma || !m->ln_beta || !m->w0 || !m->w1 || !m->w2 || !m->pooled || !m->out || !m->flags || !m->scratch)
+    if (!m || mpf::any_null({m->x, m->ln_gamma, m->ln_beta, m->w0, m->w1, m->w2, m->pooled, m->out, m->flags, m->scratch}))
         return mpf::fail(MPF_E_NULL, "next_attn_mask: NULL buffer");
     if (m->N <= 0 || m->Q <= 0 || m->HW <= 0 || m->pad < 0) return mpf::fail(MPF_E_SHAPE, "next_attn_mask: bad sizes");
     if (m->scratch_bytes < mpf_next_attn_mask_scratch_bytes(m->N, m->Q)) return mpf::fail(MPF_E_SHAPE, "next_attn_mask: scratch too small");
     const int rows = m->N * m->Q;
-    const size_t act = ((size_t)rows * kE * 2 + 255) & ~(size_t)255, vec = ((size_t)rows * 4 + 255) & ~(size_t)255;
+    const size_t act = mpf::align256((size_t)rows * kE * 2), vec = mpf::align256((size_t)rows * 4);
     char* sc = static_cast<char*>(m->scratch);
     void* d16 = sc;                 // decoder_norm(x) in bf16; reused for the third layer's result
     void* e1 = sc + act;

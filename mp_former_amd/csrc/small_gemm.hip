@@ -21,7 +21,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "mpf_common.h"
+#include "small_gemm_host.h"
 
 namespace {
 
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void small_gemm_kernel(const SG p)
 // Several independent weight-gradient problems (both operands row-contiguous: dY and x read along their rows) in ONE
 // launch: the six dW GEMMs of a decoder layer's backward are 6-9 us each as launches of 16-128 blocks, mostly latency.
 // A block finds its problem from the running block counts; the tile width and the gate are per problem.
-constexpr int kGroupMax = 8;
+constexpr int kGroupMax = kSgGroupMax;
 struct SGGroup {
     SG it[kGroupMax];
     int first[kGroupMax + 1];        // first block of problem g (first[n] = grid size)
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void small_gemm_group_kernel(const SGGroup g)
 // Transposed, zero-padded copies of several bf16 matrices in one launch: src [R, C] (row stride ld) -> dst [C, Rp] (Rp >= R, a
 // multiple of 8; rows R .. Rp - 1 of the source read as zero), optionally gated: elements whose `gate` element (same addressing)
 // is <= 0 become zero (the ReLU backward of the FFN's hidden gradient).  64 x 64 tiles through LDS, 16-byte loads and stores.
-constexpr int kTrMax = 16;
+constexpr int kTrMax = kSgTrMax;
 struct TrItem {
     const u16* src;
     const u16* gate;
@@ -297,79 +297,18 @@ __global__ __launch_bounds__(256) void transpose_group_kernel(const TrGroup g)
     }
 }
 
-template <int NJ, bool AC, bool BC>
-void launch2(const SG& p, bool gate, bool mask, int blocks, hipStream_t st)
+// the kernels' descriptor of a checked, non-empty problem
+SG to_sg(const SmallGemmProblem& p)
 {
-    if (gate && mask)
-        small_gemm_kernel<NJ, AC, BC, true, true><<<blocks, 256, 0, st>>>(p);
-    else if (gate)
-        small_gemm_kernel<NJ, AC, BC, true, false><<<blocks, 256, 0, st>>>(p);
-    else if (mask)
-        small_gemm_kernel<NJ, AC, BC, false, true><<<blocks, 256, 0, st>>>(p);
-    else
-        small_gemm_kernel<NJ, AC, BC, false, false><<<blocks, 256, 0, st>>>(p);
-}
-
-template <int NJ>
-void launch(const SG& p, bool ac, bool bc, int blocks, hipStream_t st)
-{
-    const bool gate = p.gate != nullptr, mask = (p.Kc & 31) != 0;
-    if (ac && bc)
-        launch2<NJ, true, true>(p, gate, mask, blocks, st);
-    else if (ac)
-        launch2<NJ, true, false>(p, gate, mask, blocks, st);
-    else if (bc)
-        launch2<NJ, false, true>(p, gate, mask, blocks, st);
-    else
-        launch2<NJ, false, false>(p, gate, mask, blocks, st);
-}
-
-}  // namespace
-
-namespace {
-
-// validates one problem and fills its descriptor; *nj_out = the tile width chosen for it.  Returns 1 for an empty problem.
-int sg_fill(SG& p, int* nj_out, const void* a, int64_t a_rs, int64_t a_ks, int a_blk, int64_t a_bs, const void* gate, const void* b,
-            int64_t b_rs, int64_t b_ks, const void* bias, const void* c_in, int64_t ldcin, void* c, int64_t ldc, int c_blk,
-            int64_t c_bs, void* rowsum_a, int I, int J, int Kc, int relu, int* err)
-{
-    *err = 0;
-#define SG_FAIL(code, msg) { *err = mpf::fail(code, msg); return 0; }
-    if (a_blk < 0 || c_blk < 0 || (a_blk && a_blk % 32) || (c_blk && c_blk % 64) || (a_blk && a_ks == 1 && Kc % 32) ||
-        (c_blk && c_in))
-        SG_FAIL(MPF_E_SHAPE, "small_gemm_blocked: a_blk % 32, c_blk % 64 (and Kc % 32 for a blocked contraction) must be 0");
-    if (I < 0 || J < 0 || Kc < 0) SG_FAIL(MPF_E_SHAPE, "small_gemm: negative size");
-    if (I == 0 || J == 0) return 1;
-    if (!a || !b || !c) SG_FAIL(MPF_E_NULL, "small_gemm: a, b, c must not be null");
-    if (Kc == 0) SG_FAIL(MPF_E_SHAPE, "small_gemm: empty contraction");
-    const bool ac = a_ks == 1, bc = b_ks == 1;
-    if ((!ac && a_rs != 1) || (!bc && b_rs != 1))
-        SG_FAIL(MPF_E_SHAPE, "small_gemm: each operand needs a unit row or contraction stride");
-    if ((ac && (Kc % 8 || a_rs % 8 || ((uintptr_t)a & 15) || (gate && ((uintptr_t)gate & 15)))) ||
-        (bc && (Kc % 8 || b_rs % 8 || ((uintptr_t)b & 15))))
-        SG_FAIL(MPF_E_SHAPE, "small_gemm: contraction-contiguous operands need 16-B aligned rows, Kc % 8 == 0");
-    if (J % 4 || ldc % 4 || ((uintptr_t)c & 7) || (bias && ((uintptr_t)bias & 7)) ||
-        (c_in && (ldcin % 4 || ((uintptr_t)c_in & 7))))
-        SG_FAIL(MPF_E_SHAPE, "small_gemm: J and ldc must be multiples of 4 (8-B stores)");
-#undef SG_FAIL
-    p.a = static_cast<const u16*>(a);
-    p.gate = static_cast<const u16*>(gate);
-    p.b = static_cast<const u16*>(b);
-    p.bias = static_cast<const u16*>(bias);
-    p.cin = static_cast<const u16*>(c_in);
-    p.ldcin = ldcin;
-    p.c = static_cast<u16*>(c);
-    p.rowsum = static_cast<u16*>(rowsum_a);
-    p.a_rs = a_rs; p.a_ks = a_ks; p.b_rs = b_rs; p.b_ks = b_ks; p.ldc = ldc;
-    p.a_blk = a_blk; p.a_bs = a_bs; p.c_blk = c_blk; p.c_bs = c_bs;
-    p.I = I; p.J = J; p.Kc = Kc; p.relu = relu;
-    p.n_it = (I + 15) / 16;
-    // widest tile that still gives the chip >= 256 blocks
-    int nj = 4;
-    while (nj > 1 && (int64_t)p.n_it * ((J + 16 * nj - 1) / (16 * nj)) < 256) nj >>= 1;
-    p.n_waves = p.n_it * ((J + 16 * nj - 1) / (16 * nj));
-    *nj_out = nj;
-    return 0;
+    SG s;
+    s.a = static_cast<const u16*>(p.a); s.gate = static_cast<const u16*>(p.gate); s.b = static_cast<const u16*>(p.b);
+    s.bias = static_cast<const u16*>(p.bias); s.cin = static_cast<const u16*>(p.c_in);
+    s.c = static_cast<u16*>(p.c); s.rowsum = static_cast<u16*>(p.rowsum_a);
+    s.a_rs = p.a_rs; s.a_ks = p.a_ks; s.b_rs = p.b_rs; s.b_ks = p.b_ks; s.ldc = p.ldc; s.ldcin = p.ldcin;
+    s.a_bs = p.a_bs; s.c_bs = p.c_bs; s.a_blk = p.a_blk; s.c_blk = p.c_blk;
+    s.I = p.I; s.J = p.J; s.Kc = p.Kc; s.relu = p.relu;
+    s.n_it = (int)p.n_it(); s.n_waves = (int)p.n_waves();
+    return s;
 }
 
 }  // namespace
@@ -379,22 +318,21 @@ extern "C" int mpf_small_gemm_bf16_blocked(const void* a, int64_t a_rs, int64_t 
                                            int64_t ldcin, void* c, int64_t ldc, int c_blk, int64_t c_bs, void* rowsum_a, int I,
                                            int J, int Kc, int relu, void* stream)
 {
-    SG p;
-    int nj = 1, err = 0;
-    const int empty = sg_fill(p, &nj, a, a_rs, a_ks, a_blk, a_bs, gate, b, b_rs, b_ks, bias, c_in, ldcin, c, ldc, c_blk, c_bs, rowsum_a,
-                              I, J, Kc, relu, &err);
-    if (err) return err;
-    if (empty) return 0;
-    const bool ac = a_ks == 1, bc = b_ks == 1;
-    const int blocks = p.n_waves;
+    const SmallGemmProblem p{a, gate, b, bias, c_in, c, rowsum_a, a_rs, a_ks, a_bs, b_rs, b_ks, ldcin, ldc, c_bs, a_blk, c_blk, I, J, Kc, relu};
+    if (int e = small_gemm_check(p)) return e;
+    if (p.empty()) return 0;
+    const SG s = to_sg(p);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    using mpf::with_bool;
     mpf::prof_begin(st);
-    if (nj == 4) launch<4>(p, ac, bc, blocks, st);
-    else if (nj == 2) launch<2>(p, ac, bc, blocks, st);
-    else launch<1>(p, ac, bc, blocks, st);
+    mpf::with_int_of<1, 2, 4>(p.nj(), [&](auto NJ) { with_bool(p.ac(), [&](auto AC) { with_bool(p.bc(), [&](auto BC) {
+        with_bool(p.gated(), [&](auto GATE) { with_bool(p.masked(), [&](auto MASK) {
+            small_gemm_kernel<decltype(NJ)::value, decltype(AC)::value, decltype(BC)::value, decltype(GATE)::value, decltype(MASK)::value>
+                <<<(unsigned)s.n_waves, 256, 0, st>>>(s);
+        }); });
+    }); }); });
     mpf::set_kernel("small_gemm_kernel");
-    const double bytes = 2.0 * ((double)I * Kc * (gate ? 2 : 1) + (double)J * Kc + (double)I * J);
-    mpf::prof_end("small_gemm_kernel", st, bytes);
+    mpf::prof_end("small_gemm_kernel", st, p.bytes());
     return mpf::check(hipGetLastError(), "small_gemm launch");
 }
 
@@ -408,72 +346,37 @@ extern "C" int mpf_small_gemm_bf16(const void* a, int64_t a_rs, int64_t a_ks, co
 
 extern "C" int mpf_small_gemm_bf16_group(const MpfSmallGemmItem* items, int n_items, void* stream)
 {
-    if (n_items < 0 || n_items > kGroupMax) return mpf::fail(MPF_E_SHAPE, "small_gemm_group: at most 8 problems per launch");
-    if (n_items == 0) return 0;
-    if (!items) return mpf::fail(MPF_E_NULL, "small_gemm_group: NULL items");
+    SmallGemmGroupPlan plan;
+    if (int e = small_gemm_group_plan(plan, items, n_items)) return e;
+    if (plan.n == 0) return 0;
     SGGroup g;
-    g.n = 0;
-    g.first[0] = 0;
-    bool mask = false, contig = false;
-    double bytes = 0.0;
-    for (int t = 0; t < n_items; ++t) {
-        const MpfSmallGemmItem& m = items[t];
-        const bool ct_item = m.a_ks == 1 && m.b_ks == 1;
-        if (!ct_item && (m.a_rs != 1 || m.b_rs != 1))
-            return mpf::fail(MPF_E_SHAPE, "small_gemm_group: both operands row-contiguous (the weight-gradient form) or both contraction-contiguous");
-        if (t > 0 && ct_item != contig) return mpf::fail(MPF_E_SHAPE, "small_gemm_group: one operand form per group");
-        contig = ct_item;
-        if (ct_item && m.gate) return mpf::fail(MPF_E_SHAPE, "small_gemm_group: the gate belongs into the transposed copy (mpf_transpose_group_bf16)");
-        int nj = 1, err = 0;
-        const int empty = sg_fill(g.it[g.n], &nj, m.a, m.a_rs, m.a_ks, m.a_blk, m.a_bs, m.gate, m.b, m.b_rs, m.b_ks, nullptr, nullptr, 0,
-                                  m.c, m.ldc, 0, 0, m.rowsum_a, m.I, m.J, m.Kc, 0, &err);
-        if (err) return err;
-        if (empty) continue;
-        if (g.n > 0 && ((m.Kc & 31) != 0) != mask) return mpf::fail(MPF_E_SHAPE, "small_gemm_group: Kc % 32 must agree across the group");
-        mask = (m.Kc & 31) != 0;
-        g.nj[g.n] = nj;
-        g.first[g.n + 1] = g.first[g.n] + g.it[g.n].n_waves;
-        bytes += 2.0 * ((double)m.I * m.Kc * (m.gate ? 2 : 1) + (double)m.J * m.Kc + (double)m.I * m.J);
-        ++g.n;
-    }
-    if (g.n == 0) return 0;
-    for (int t = g.n; t < kGroupMax; ++t) { g.first[t + 1] = g.first[g.n]; g.nj[t] = 1; g.it[t] = g.it[0]; }
+    g.n = plan.n;
+    for (int t = 0; t < kGroupMax; ++t) { g.it[t] = to_sg(plan.it[t]); g.nj[t] = plan.nj[t]; }
+    for (int t = 0; t <= kGroupMax; ++t) g.first[t] = (int)plan.first[t];
     hipStream_t st = static_cast<hipStream_t>(stream);
     mpf::prof_begin(st);
-    if (contig) {
-        if (mask) small_gemm_group_kernel<true, true><<<g.first[g.n], 256, 0, st>>>(g);
-        else small_gemm_group_kernel<false, true><<<g.first[g.n], 256, 0, st>>>(g);
-    } else {
-        if (mask) small_gemm_group_kernel<true, false><<<g.first[g.n], 256, 0, st>>>(g);
-        else small_gemm_group_kernel<false, false><<<g.first[g.n], 256, 0, st>>>(g);
-    }
+    mpf::with_bool(plan.masked, [&](auto MASK) { mpf::with_bool(plan.contig, [&](auto CT) {
+        small_gemm_group_kernel<decltype(MASK)::value, decltype(CT)::value><<<(unsigned)g.first[g.n], 256, 0, st>>>(g);
+    }); });
     mpf::set_kernel("small_gemm_group_kernel");
-    mpf::prof_end("small_gemm_group_kernel", st, bytes);
+    mpf::prof_end("small_gemm_group_kernel", st, plan.bytes);
     return mpf::check(hipGetLastError(), "small_gemm_group launch");
 }
 
 extern "C" int mpf_transpose_group_bf16(const MpfTransposeItem* items, int n_items, int Rp, void* stream)
 {
-    if (n_items < 0 || n_items > kTrMax) return mpf::fail(MPF_E_SHAPE, "transpose_group: at most 16 matrices per launch");
-    if (n_items == 0) return 0;
-    if (!items) return mpf::fail(MPF_E_NULL, "transpose_group: NULL items");
-    if (Rp <= 0 || Rp % 8) return mpf::fail(MPF_E_SHAPE, "transpose_group: Rp must be a positive multiple of 8");
+    TransposeGroupPlan plan;
+    if (int e = transpose_group_plan(plan, items, n_items, Rp)) return e;
+    if (plan.n == 0) return 0;
     TrGroup g;
-    g.n = n_items; g.Rp = Rp; g.tiles_r = (Rp + 63) / 64;
-    int blocks = 0;
-    for (int t = 0; t < n_items; ++t) {
-        const MpfTransposeItem& m = items[t];
-        if (!m.src || !m.dst) return mpf::fail(MPF_E_NULL, "transpose_group: NULL matrix");
-        if (m.R <= 0 || m.R > Rp || m.C <= 0 || m.C % 8 || m.ld % 8 || ((uintptr_t)m.src & 15) || ((uintptr_t)m.dst & 15) ||
-            (m.gate && ((uintptr_t)m.gate & 15)))
-            return mpf::fail(MPF_E_SHAPE, "transpose_group: 0 < R <= Rp, C % 8 == 0, 16-byte aligned rows");
+    g.n = plan.n; g.Rp = Rp; g.tiles_r = (int)plan.tiles_r;
+    for (int t = 0; t < kTrMax; ++t) {       // (the unused slots repeat matrix 0 with an empty block range)
+        const MpfTransposeItem& m = items[t < plan.n ? t : 0];
         g.it[t].src = static_cast<const u16*>(m.src); g.it[t].gate = static_cast<const u16*>(m.gate); g.it[t].dst = static_cast<u16*>(m.dst);
-        g.it[t].ld = m.ld; g.it[t].R = m.R; g.it[t].C = m.C; g.it[t].first = blocks;
-        blocks += g.tiles_r * ((m.C + 63) / 64);
+        g.it[t].ld = m.ld; g.it[t].R = m.R; g.it[t].C = m.C; g.it[t].first = (int)plan.first[t < plan.n ? t : plan.n];
     }
-    for (int t = n_items; t < kTrMax; ++t) { g.it[t] = g.it[0]; g.it[t].first = blocks; }
     mpf::set_kernel("transpose_group_kernel");
-    transpose_group_kernel<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(g);
+    transpose_group_kernel<<<(unsigned)plan.blocks(), 256, 0, static_cast<hipStream_t>(stream)>>>(g);
     return mpf::check(hipGetLastError(), "transpose_group launch");
 }
 
@@ -682,34 +585,27 @@ __global__ __launch_bounds__(256) void tall_ws_bf16_kernel(const __bf16* __restr
 }
 
 int g_tall_ws_wgs = 0;      // mpf_set_option("tall_ws_wgs"): workgroups of the weight-stationary kernel (0 = one residency)
+int g_tall_ws = 1;          // mpf_set_option("tall_ws", 0): the fragment-per-wave kernel for every shape (A/B)
 
-template <int KS, int NB, int MB, int NBUF>
-int launch_tall_ws(const void* a, int64_t lda, const void* b, int64_t ldb, const void* bias, void* c, int64_t ldc, int M, int N,
-                   hipStream_t st)
+// the one launch expression of both tall kernels: the same parameter list up to `last`, which the caller states (K of the
+// fragment-per-wave kernel, the number of row tiles of the weight-stationary one)
+template <class Kernel>
+void tall_launch(Kernel kernel, const TallGemmProblem& p, const TallRoute& r, int last, hipStream_t st)
 {
-    const int ntiles = (M + MB * 16 - 1) / (MB * 16);
-    const unsigned gx = (unsigned)((N + 64 * NB - 1) / (64 * NB));
-    const size_t lds = (size_t)MB * 16 * KS * 64 * NBUF;
-    // the grid is exactly one residency (LDS: 160 KB per CU; registers: two workgroups), so that no workgroup starts after the
-    // others have walked their tiles
-    const unsigned per_cu = lds > 80 * 1024 ? 1u : 2u;
-    unsigned gy = (unsigned)(g_tall_ws_wgs ? g_tall_ws_wgs : mpf::cu_count() * (int)per_cu) / gx;
-    gy = gy < 1u ? 1u : (gy > (unsigned)ntiles ? (unsigned)ntiles : gy);
-    {
-        const void* fn = bias ? (const void*)tall_ws_bf16_kernel<KS, NB, MB, NBUF, true> : (const void*)tall_ws_bf16_kernel<KS, NB, MB, NBUF, false>;
-        static mpf::LdsAttr attr[2];       // (per instantiation of this launcher: with / without bias)
-        if (int e = mpf::ensure_dynamic_lds(fn, lds, attr[bias ? 1 : 0])) return e;
-    }
-    if (bias)
-        hipLaunchKernelGGL((tall_ws_bf16_kernel<KS, NB, MB, NBUF, true>), dim3(gx, gy), dim3(256), lds, st, (const __bf16*)a, lda,
-                           (const __bf16*)b, ldb, (const __bf16*)bias, (__bf16*)c, ldc, M, N, ntiles);
-    else
-        hipLaunchKernelGGL((tall_ws_bf16_kernel<KS, NB, MB, NBUF, false>), dim3(gx, gy), dim3(256), lds, st, (const __bf16*)a, lda,
-                           (const __bf16*)b, ldb, (const __bf16*)bias, (__bf16*)c, ldc, M, N, ntiles);
-    return 0;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r.gx, (unsigned)r.gy), dim3(256), r.lds, st, (const __bf16*)p.a, p.lda, (const __bf16*)p.b,
+                       p.ldb, (const __bf16*)p.bias, (__bf16*)p.c, p.ldc, p.M, p.N, last);
 }
 
-int g_tall_ws = 1;          // mpf_set_option("tall_ws", 0): the fragment-per-wave kernel for every shape (A/B)
+// the weight-stationary kernel of a route; its dynamic-LDS limit is raised once per instantiation, bias form and device
+template <int KS, bool BIAS>
+int tall_ws_launch(const TallGemmProblem& p, const TallRoute& r, hipStream_t st)
+{
+    const auto kernel = tall_ws_bf16_kernel<KS, KS == 8 ? 2 : 1, KS == 8 ? 4 : 2, 2, BIAS>;
+    static mpf::LdsAttr attr;
+    if (int e = mpf::ensure_dynamic_lds((const void*)kernel, r.lds, attr)) return e;
+    tall_launch(kernel, p, r, (int)r.ntiles, st);
+    return 0;
+}
 }  // namespace
 
 namespace mpf {
@@ -717,7 +613,6 @@ int set_small_gemm_option(const char* key, int v)
 {
     if (!strcmp(key, "tall_ws")) { g_tall_ws = v != 0; return 0; }
     if (!strcmp(key, "tall_ws_wgs")) { g_tall_ws_wgs = v; return 0; }
-
     return 1;
 }
 }  // namespace mpf
@@ -725,35 +620,22 @@ int set_small_gemm_option(const char* key, int v)
 extern "C" int mpf_tall_gemm_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, const void* bias, void* c, int64_t ldc, int M,
                                   int N, int K, void* stream)
 {
-    if (M == 0 || N == 0) return 0;
-    if (!a || !b || !c) return mpf::fail(MPF_E_NULL, "tall_gemm_bf16: NULL buffer");
-    if (M < 0 || N < 0 || K <= 0 || (K & 31)) return mpf::fail(MPF_E_SHAPE, "tall_gemm_bf16: K must be a positive multiple of 32");
-    if ((lda & 7) || (ldb & 7) || (ldc & 3) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 7))
-        return mpf::fail(MPF_E_SHAPE, "tall_gemm_bf16: 16-byte aligned operand rows, 8-byte aligned result rows");
-    const dim3 grid((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128));
-    if (grid.y > 65535u) return mpf::fail(MPF_E_TOO_LARGE, "tall_gemm_bf16: more than 65 535 row tiles");
+    const TallGemmProblem p{a, b, bias, c, lda, ldb, ldc, M, N, K};
+    if (p.empty()) return 0;
+    if (int e = tall_gemm_check(p)) return e;
+    // (the device is asked for its compute units only where the grid depends on them: one residency of the weight-stationary kernel)
+    const TallRoute r = p.route(g_tall_ws, p.weight_stationary(g_tall_ws) && !g_tall_ws_wgs ? mpf::cu_count() : 0, g_tall_ws_wgs);
+    if (int e = r.check()) return e;
     hipStream_t st = (hipStream_t)stream;
-    if (g_tall_ws && M >= 1024 && (K == 256 || K == 768)) {
-        mpf::prof_begin(st);
-        mpf::set_kernel("tall_ws_bf16_kernel");
-        int e;
-        // (measured at 32 768 rows: 64-row tiles x 2 buffers, 32-row tiles x 3 or 4 buffers all give 29-30 us for K = 256 and
-        // 35-38 us for K = 768: the copies are not what the kernel waits for — ablations: result stores 9 us of HBM write time,
-        // copies 3-8, MFMA phase 3 (K = 256) / 15 (K = 768: one 16-column block per wave reads the whole X tile from LDS))
-        if (K == 256) e = launch_tall_ws<8, 2, 4, 2>(a, lda, b, ldb, bias, c, ldc, M, N, st);
-        else e = launch_tall_ws<24, 1, 2, 2>(a, lda, b, ldb, bias, c, ldc, M, N, st);
-        if (e) return e;
-        mpf::prof_end("tall_gemm_bf16_kernel", st, 2.0 * ((double)M * K + (double)N * K + (double)M * N), 2.0 * M * (double)N * K);
-        return mpf::check(hipGetLastError(), "mpf_tall_gemm_bf16");
-    }
+    int e = 0;
     mpf::prof_begin(st);
-    mpf::set_kernel("tall_gemm_bf16_kernel");
-    if (bias)
-        hipLaunchKernelGGL((tall_gemm_bf16_kernel<true>), grid, dim3(256), 0, st, (const __bf16*)a, lda, (const __bf16*)b, ldb,
-                           (const __bf16*)bias, (__bf16*)c, ldc, M, N, K);
-    else
-        hipLaunchKernelGGL((tall_gemm_bf16_kernel<false>), grid, dim3(256), 0, st, (const __bf16*)a, lda, (const __bf16*)b, ldb,
-                           (const __bf16*)bias, (__bf16*)c, ldc, M, N, K);
-    mpf::prof_end("tall_gemm_bf16_kernel", st, 2.0 * ((double)M * K + (double)N * K + (double)M * N), 2.0 * M * (double)N * K);
+    mpf::set_kernel(r.ws ? "tall_ws_bf16_kernel" : "tall_gemm_bf16_kernel");
+    mpf::with_bool(bias != nullptr, [&](auto BIAS) {
+        constexpr bool kBias = decltype(BIAS)::value;
+        if (r.ws) mpf::with_int_of<8, 24>(r.KS, [&](auto KS) { e = tall_ws_launch<decltype(KS)::value, kBias>(p, r, st); });
+        else tall_launch(tall_gemm_bf16_kernel<kBias>, p, r, p.K, st);
+    });
+    if (e) return e;
+    mpf::prof_end("tall_gemm_bf16_kernel", st, p.bytes(), p.flops());
     return mpf::check(hipGetLastError(), "mpf_tall_gemm_bf16");
 }
