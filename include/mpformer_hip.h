@@ -1811,6 +1811,41 @@ int mpf_label_window_counts(const MpfLabelRecord* recs_host, const MpfLabelRecor
 int mpf_label_bits(const int32_t* map, int64_t row_stride, int H, int W, const int32_t* ids_host, int T, int64_t* bits,
                    int32_t* areas, void* stream);
 
+/*
+ * Video training input (csrc/clip_input.hip): the target half of the reference's YTVISDatasetMapper (mask2former_video/data_video/
+ * dataset_mapper.py:239-267: mask_util.decode, ResizeTransform.apply_segmentation = PIL's NEAREST on a uint8 mask, the flip,
+ * BitMasks) and of VideoMaskFormer.prepare_targets (video_maskformer_model.py:227-253: the copy into a zeroed [G, F, H_pad, W_pad]
+ * tensor), from PACKED masks: one launch for every (tube, frame) plane of a batch of clips, no dense intermediate.
+ *
+ * One record per plane, all int32 but the pointer:
+ *   src                the plane's packed words on the device, int64 in the layout of mpf_seg_pack_masks (position p = x src_h + y,
+ *                      64 positions per word; what mpf_seg_toggles_fill leaves of an RLE or a polygon), 8-byte aligned.  NULL: an
+ *                      empty plane (the instance is absent from the frame); no other field but dst is read then
+ *   src_h, src_w       the size the words were packed at
+ *   valid_h, valid_w   the frame's size after the resize: the rectangle of the canvas the mask covers
+ *   flip_out           1: valid column x of the result is valid column valid_w - 1 - x (the mapper flips after the resize)
+ *   xt_off, yt_off     offsets, in int32 elements, into the table buffer: the SOURCE column / row of every valid column / row
+ *                      (valid_w / valid_h entries; the host makes them by PIL's nearest rule).  -1: the identity map, which needs
+ *                      src == valid on that axis (the polygon route: rasterised at the resized size already)
+ *   dst                the plane's index in the output; the P records name every plane 0 .. P-1 once, in any order
+ * recs_host / tab_host are the host copies of the device buffers (tab_len int32 elements): every record and table entry is checked
+ * against the source size before the launch, so nothing read on the device can leave a source mask.
+ *
+ * out    uint8 [P, Hc, Wc], row-major (the memory of a bool tensor): EVERY byte is written, 0 or 1 inside the valid rectangle, 0 in
+ *        the pad at the bottom right; the caller needs no memset.  One writer per byte.
+ * areas  int32 [P] (cleared here): the set pixels of each plane, by integer sums.
+ * NULL buffer: MPF_E_NULL; an inconsistent record (a table outside the buffer, a table entry outside 0 .. src-1, an identity record
+ * whose sizes differ, valid larger than the canvas, a repeated or missing dst): MPF_E_SHAPE; P > 65535, a canvas or a source of
+ * 2^31 elements or more: MPF_E_TOO_LARGE.  P == 0 launches nothing.  Bitwise reproducible.
+ */
+typedef struct MpfMaskBitsRecord {
+    const void* src;
+    int32_t src_h, src_w, valid_h, valid_w;
+    int32_t flip_out, xt_off, yt_off, dst;
+} MpfMaskBitsRecord;
+int mpf_mask_bits_resample(const MpfMaskBitsRecord* recs_host, const MpfMaskBitsRecord* recs_dev, const int32_t* tab_host,
+                           const int32_t* tab_dev, int64_t tab_len, int P, uint8_t* out, int32_t* areas, int Hc, int Wc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,6 +271,7 @@ SIGNATURES = {
     "mpf_label_window_counts": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp,
                                          _c_vp]),
     "mpf_label_bits": (_c_int, [_c_vp, ctypes.c_int64, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "mpf_mask_bits_resample": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp]),
 }
 
 

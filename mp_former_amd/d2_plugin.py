@@ -997,3 +997,124 @@ def install_native_semantic_input(model, mapper=None, *, num_classes=None, ignor
     ignore = mapper.ignore_label if ignore_label is None else ignore_label
     area = (mapper.single_category_max_area if mapper is not None else 1.0) if single_category_max_area is None else single_category_max_area
     return _install_inputs(model, lambda batch: native_semantic_inputs(batch, model.device, K, ignore, area))
+
+
+# ---- video training input (clip_input.py) -----------------------------------------------------------------------------------------------
+class YTVISClipDeviceMapper:
+    """The worker side of the reference's ``YTVISDatasetMapper`` (mask2former_video/data_video/dataset_mapper.py:114-269) when the
+    clip is formed on the device (clip_input.py): it SAMPLES the frames (``random.randrange`` and ``numpy.random.choice``, in the
+    reference's order), reads them, DRAWS the geometry (``clip_input.draw_clip``: per frame the size, then the flip, from
+    ``numpy.random``) and returns the dict with ``"image_raw"`` (a list of uint8 [H, W, 3]), ``"clip"`` (the frames'
+    ``augment.SemSegParams``), the selected frames' non-crowd ``"annotations"`` as the json holds them, ``"file_names"`` and
+    ``"num_classes"``.  No resize and no mask decode on the worker: ``install_native_video_input`` forms the batch on the model's
+    device.  ``cls(cfg, is_train)`` reads the ``cfg.INPUT`` / ``cfg.MODEL`` keys the reference's ``from_config`` and
+    ``build_augmentation`` read.  Not built, and refused by name: ``INPUT.CROP.ENABLED`` and every entry of ``INPUT.AUGMENTATIONS``
+    (brightness, contrast and saturation are float blends whose rounding depends on the numpy version, rotation is an OpenCV warp),
+    a vertical flip, and evaluation (the eval branch reads whole videos through the reference's own mapper)."""
+
+    @_configurable
+    def __init__(self, is_train=True, *, min_size, max_size, sampling, random_flip, image_format, sampling_frame_num,
+                 sampling_frame_range, sampling_frame_shuffle, num_classes, size_divisibility, crop_enabled=False, augmentations=(),
+                 read_image=None):
+        from .clip_input import FLIP_MODES, SAMPLE_STYLES
+        who = "YTVISClipDeviceMapper"
+        if not is_train:
+            raise ValueError(f"{who}: only training; evaluation reads whole videos through the reference's mapper")
+        if crop_enabled:
+            raise NotImplementedError("INPUT.CROP.ENABLED: the random crop of a clip is not implemented on the device path")
+        for name in augmentations:
+            raise NotImplementedError(f"INPUT.AUGMENTATIONS {name!r}: not implemented on the device path (brightness, contrast and "
+                                      f"saturation are float blends whose rounding depends on the numpy version, rotation is an "
+                                      f"OpenCV warp)")
+        if random_flip == "vertical":
+            raise ValueError(f"{who}: INPUT.RANDOM_FLIP 'vertical': only the horizontal flip is implemented on the device path")
+        if random_flip not in FLIP_MODES:
+            raise ValueError(f"{who}: random_flip must be one of {FLIP_MODES}, got {random_flip!r}")
+        if sampling not in SAMPLE_STYLES:
+            raise ValueError(f"{who}: sampling must be one of {SAMPLE_STYLES}, got {sampling!r}")
+        self.is_train = True
+        self.min_size = (min_size,) if isinstance(min_size, int) else tuple(min_size)
+        self.max_size, self.sampling, self.random_flip, self.image_format = int(max_size), sampling, random_flip, image_format
+        self.sampling_frame_num, self.sampling_frame_range = int(sampling_frame_num), int(sampling_frame_range)
+        self.sampling_frame_shuffle, self.num_classes = bool(sampling_frame_shuffle), int(num_classes)
+        self.size_divisibility = int(size_divisibility)
+        self.read_image = read_image or _read_image_default()
+
+    @classmethod
+    def from_config(cls, cfg, is_train=True):
+        return {"is_train": is_train, "min_size": cfg.INPUT.MIN_SIZE_TRAIN, "max_size": cfg.INPUT.MAX_SIZE_TRAIN,
+                "sampling": cfg.INPUT.MIN_SIZE_TRAIN_SAMPLING, "random_flip": cfg.INPUT.RANDOM_FLIP, "image_format": cfg.INPUT.FORMAT,
+                "sampling_frame_num": cfg.INPUT.SAMPLING_FRAME_NUM, "sampling_frame_range": cfg.INPUT.SAMPLING_FRAME_RANGE,
+                "sampling_frame_shuffle": cfg.INPUT.SAMPLING_FRAME_SHUFFLE, "num_classes": cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES,
+                "size_divisibility": cfg.MODEL.MASK_FORMER.SIZE_DIVISIBILITY, "crop_enabled": cfg.INPUT.CROP.ENABLED,
+                "augmentations": tuple(cfg.INPUT.AUGMENTATIONS)}
+
+    def __call__(self, dataset_dict):
+        import random
+        import numpy as np
+        import torch
+        from .clip_input import draw_clip, sample_clip_frames
+        who = "YTVISClipDeviceMapper"
+        d = {k: v for k, v in dataset_dict.items() if k not in ("annotations", "file_names")}
+        selected = sample_clip_frames(dataset_dict["length"], self.sampling_frame_num, self.sampling_frame_range,
+                                      self.sampling_frame_shuffle, py_rng=random, np_rng=np.random)
+        file_names, video_annos = dataset_dict["file_names"], dataset_dict.get("annotations")
+        d["file_names"] = [file_names[i] for i in selected]
+        images = []
+        for name in d["file_names"]:
+            image = np.ascontiguousarray(self.read_image(name, format=self.image_format))
+            if image.ndim != 3 or image.shape[2] != 3 or image.dtype != np.uint8:
+                raise ValueError(f"{who}: expected a uint8 [H, W, 3] image, got {image.dtype} {image.shape}")
+            for key, n in (("height", image.shape[0]), ("width", image.shape[1])):
+                if key in dataset_dict and dataset_dict[key] != n:
+                    raise ValueError(f"{who}: {name} has {key} {n}, the dataset says {dataset_dict[key]}")
+            if images and tuple(images[0].shape) != image.shape:
+                raise ValueError(f"{who}: {name} is {image.shape[:2]}, the clip's first frame {tuple(images[0].shape[:2])}")
+            images.append(torch.from_numpy(image))
+        d["image_raw"] = images
+        d["clip"] = draw_clip(images[0].shape[0], images[0].shape[1], len(images), self.min_size, self.max_size, self.sampling,
+                              self.random_flip, self.size_divisibility, rng=np.random)
+        d["num_classes"] = self.num_classes
+        if video_annos is not None:
+            d["annotations"] = [[{k: v for k, v in a.items() if k != "keypoints"} for a in video_annos[i] if a.get("iscrowd", 0) == 0]
+                                for i in selected]
+        return d
+
+
+def native_video_inputs(batched_inputs, device):
+    """The dicts of ``YTVISClipDeviceMapper`` -> copies with ``"image"`` (a list of uint8 [3, h, w] views, on ``device``) and
+    ``"instances"`` (per frame ``gt_classes``, ``gt_ids``, ``gt_masks`` (``BitMasks`` of bool [G, h, w] views of the padded tube
+    store), ``gt_boxes`` and ``image_size``), as the reference's mapper would have left them: one image launch, one RLE and one
+    polygon pass per distinct size and one mask launch for the batch (clip_input.clip_batch_instances)."""
+    from .clip_input import clip_batch_instances
+    from .inference import _BitMasks, _structures
+    Boxes, Instances = _structures()
+    try:
+        from detectron2.structures import BitMasks
+    except ImportError:
+        BitMasks = _BitMasks
+    frames, targets = clip_batch_instances(batched_inputs, device=device)
+    out = []
+    for x, t in zip(batched_inputs, targets):
+        d = {k: v for k, v in x.items() if k not in ("image_raw", "annotations")}
+        first = t["frames"][0]
+        d["image"], d["instances"] = [], []
+        for f, p in enumerate(x["clip"]):
+            h, w = p.resized
+            d["image"].append(frames[first + f][:, :h, :w])
+            inst = Instances((h, w))
+            inst.gt_boxes = Boxes(t["gt_boxes"][f])
+            inst.gt_classes = t["gt_classes"][f]
+            inst.gt_ids = t["gt_ids"][f]
+            inst.gt_masks = BitMasks(t["masks"][:, f, :h, :w])
+            d["instances"].append(inst)
+        out.append(d)
+    return out
+
+
+def install_native_video_input(model):
+    """As ``install_native_lsj`` for a ``VideoMaskFormer`` fed by ``YTVISClipDeviceMapper``: the training branch gets the usual dicts
+    ("image": the clip's frames, "instances": one per frame) formed on the model's device, so the model's own normalisation and
+    its ``prepare_targets`` (the reference's, or ``install_native_video_training``'s) run unchanged; eval mode is passed through
+    untouched.  Works without detectron2 (the ``Instances`` stand-in of inference.py)."""
+    return _install_inputs(model, lambda batch: native_video_inputs(batch, model.device))

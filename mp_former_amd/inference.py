@@ -97,6 +97,13 @@ class _Boxes:
     def __len__(self):
         return self.tensor.shape[0]
 
+    def to(self, *args, **kwargs):
+        return type(self)(self.tensor.to(*args, **kwargs))
+
+
+class _BitMasks(_Boxes):
+    """Stand-in for detectron2.structures.BitMasks (``tensor`` bool [N, H, W], ``to``, ``len``)."""
+
 
 class _Instances:
     """Stand-in for detectron2.structures.Instances: ``image_size`` and the attributes set on it."""
@@ -128,6 +135,9 @@ class _Instances:
 
     def get_fields(self):
         return dict(self._fields)
+
+    def to(self, *args, **kwargs):
+        return type(self)(self._image_size, **{k: v.to(*args, **kwargs) if hasattr(v, "to") else v for k, v in self._fields.items()})
 
     def __len__(self):
         for v in self._fields.values():
